@@ -7,6 +7,12 @@ reject, history push, controller bookkeeping (incl. the 200-step proposal adapta
 falls inside the timed region).  Inputs are resident in HBM before the timed region.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5|poly7|c1|c2expr|c2written|g23]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints one JSON line; --full adds the
+measurements that stand beside the headline (other walks of the same data, the CPU baseline).
+--dump-outputs DIR writes the state the timed walk ends in; the inputs are seeded, so two builds
+run with the same arguments can be compared array for array.
 
 N > 1 runs either way, chains sharded by contiguous global id ranges (weak scaling: --chains per
 GPU), datasets replicated, no data-path collective in the reference's per-walker adaptation mode;
@@ -198,6 +204,30 @@ def effective_cores():
     return n, info
 
 
+DUMP_LIMIT_BYTES = 60 * 10 ** 6  # (--dump-outputs: under 64 MB in all, .npy headers included)
+
+
+def dump_outputs(fleet, out_dir):
+    """--dump-outputs: what a caller of the timed path reads back after its last step - every
+    chain's state (walker-get: theta, log-posterior, best point, length, age), its proposal factor
+    and its temperature - as float64 DIR/<name>.npy.  Past DUMP_LIMIT_BYTES in all, a fixed seeded
+    sample of the chains, whose ids go to chain_index.npy.  Returns the names written."""
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in fleet.obj.state().items()}
+    arrays["lmatrix"] = np.concatenate([e.lmatrix() for e in fleet.engines])
+    arrays["temperature"] = np.concatenate([e.temperature() for e in fleet.engines])
+    n = len(arrays["logpost"])
+    per_chain = sum(a[0].nbytes for a in arrays.values()) + 8  # (+ its entry in chain_index)
+    if n * per_chain > DUMP_LIMIT_BYTES:
+        keep = max(1, DUMP_LIMIT_BYTES // per_chain)
+        idx = np.sort(np.random.Generator(np.random.Philox(key=0x5EED0006)).choice(n, keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["chain_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
+    return sorted(arrays)
+
+
 def kernel_label(name):
     """which stepping kernel serves an engine of that mhx_kernel_name"""
     if "persistent tsplit" in name:
@@ -259,8 +289,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--workload", default="c2")
     ap.add_argument("--chains", type=int, default=0, help="chains per GPU (default: the workload's)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: length of the CPU baseline")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--adapt", default="auto", choices=["auto", "faithful", "pooled"],
                     help="auto: the reference's per-walker rule on 1 GPU, pooled covariance "
                          "(one RCCL all-reduce per 200 iterations) on several")
@@ -272,8 +302,15 @@ def main():
                     help="one-process runs: the device of each of the --gpus engines, comma separated "
                          "(default 0..N-1).  Naming a device twice rehearses the N-GPU code path on "
                          "fewer GPUs (with MHX_GROUP_FORCE_RCCL=1 and a stand-in librccl: tests/stub_rccl)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what stands beside the headline (1 GPU, one process): the "
+                         "direct-form, piecewise-grid, early-rejection and small-batch walks and the "
+                         "CPU baseline.  Without it a run times the headline walk only")
     ap.add_argument("--no-direct", action="store_true",
-                    help="skip the second, short measurement with the uniform-grid recurrence off")
+                    help="--full: skip the direct-form, piecewise-grid, early-rejection and small-batch walks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the state the timed walk ends in as DIR/<name>.npy "
+                         "(float64; under 64 MB in all, a fixed sample of the chains beyond that)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -491,6 +528,10 @@ def main():
         total_steps = float(chain_steps)
     assert not fleet.trapped(), "a chain trapped during the benchmark"
     assert chain_steps == n_local * args.steps, (chain_steps, n_local, args.steps)
+    dumped = None
+    if args.dump_outputs:  # (one process per GPU: each rank its own chains, in rank<r>/)
+        dumped = dump_outputs(fleet, args.dump_outputs if not per_rank else
+                              os.path.join(args.dump_outputs, "rank%d" % rank))
 
     n_points = int(sum(len(d[0]) for d in spec.data))
     bytes_step = b_alg(spec, b_pt)
@@ -578,11 +619,16 @@ def main():
         "build": {"id": build_id},
         "roofline": roof,
     }
+    if dumped is not None:
+        out["outputs"] = {"dir": args.dump_outputs, "names": dumped}
+    # --full: the walks and the CPU baseline below stand beside the headline (one GPU, one
+    # process); a plain run ends with the headline's line.
+    beside = args.full and rank == 0 and not per_rank and n_gpus == 1
     # The headline's Gaussians advance by the uniform-grid recurrence (x is a linspace: 3
     # instructions per point and peak instead of 14).  The same walk on the same data with the
     # recurrence switched off - what a dataset that is NOT a grid gets - measured the same way
     # beside it, so that nobody has to guess the factor.
-    if (rank == 0 and not per_rank and n_gpus == 1 and not args.no_direct
+    if (beside and not args.no_direct
             and args.workload in ("c2", "c5", "c3", "g23")):
         os.environ["MHX_NO_RECURRENCE"] = "1"  # (read when the dataset is set)
         try:
@@ -623,7 +669,7 @@ def main():
     # what an instrument file often looks like): since round 4 every 2048-point window on a grid
     # takes the recurrence with its own step and only the junction / jittered windows the direct
     # form; until then the whole dataset took the direct form (value_direct_form).
-    if (rank == 0 and not per_rank and n_gpus == 1 and not args.no_direct and args.workload == "c2"):
+    if (beside and not args.no_direct and args.workload == "c2"):
         import copy
         import problems as pb
         pspec = copy.copy(spec)
@@ -661,7 +707,7 @@ def main():
     # time of iterations that reject - all of a walk's first dozens (T = 10, diag(theta) steps),
     # hardly any of a settled walk's.  Opt-in and reported BESIDE the headline, whose sweeps are
     # complete: this figure counts rejections, not sweeps.
-    if (rank == 0 and not per_rank and n_gpus == 1 and not args.no_direct and args.workload == "c2"):
+    if (beside and not args.no_direct and args.workload == "c2"):
         os.environ["MHX_EARLY_REJECT"] = "1"
         try:
             er = make()
@@ -692,7 +738,7 @@ def main():
     # workgroups and a whole portion of iterations runs as one persistent launch (k_persist_ts;
     # two launches per iteration until round 3).  Microseconds per iteration of a 1024-iteration
     # stretch after 256 of warm-up, host clock around synchronised calls.
-    if (rank == 0 and not per_rank and n_gpus == 1 and not args.no_direct and args.workload == "c2"):
+    if (beside and not args.no_direct and args.workload == "c2"):
         sb = {"what": "the same data walked by 1 and by 64 walkers (walker-adaptive-steps from theta*(1 + 1 %), "
                       "T = 10): us per iteration over 1024 iterations after 256"}
         for c in (1, 64):
@@ -710,7 +756,7 @@ def main():
                                     "kernel": small.kernel_name(), "trapped": bool(small.trapped())}
             small.close()
         out["small_batches"] = sb
-    if rank == 0 and not per_rank and n_gpus == 1 and not args.no_cpu:
+    if beside and not args.no_cpu:
         ncpu, cinfo = effective_cores()
         one = cpu_baseline(spec, th0, args.cpu_seconds * 0.4, n_adapt, 1, l0)
         allc = cpu_baseline(spec, th0, args.cpu_seconds * 0.6, n_adapt, ncpu, l0) if ncpu > 1 else one

@@ -1,3 +1,4 @@
+"""prints the early-rejection, piecewise and direct-form figures of bench lines (python bench.py --full ... > file)"""
 import json, sys
 for f in sys.argv[1:]:
     d = json.loads(open(f).read().strip().splitlines()[-1])

@@ -1,4 +1,4 @@
-"""prints the fields of a bench line that the round's notes quote (python bench.py ... > file)"""
+"""prints the fields of a bench line that the round's notes quote (python bench.py --full ... > file)"""
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 sb = d.get("small_batches", {})

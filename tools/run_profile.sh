@@ -9,7 +9,7 @@ NAME=${TAG}_${WL}_s${ST}_w${WU}
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT/gpurun_out/prof_$NAME
 rm -rf $R && mkdir -p $R
-ARGS="--no-cpu --workload $WL --steps $ST --warmup $WU $*"
+ARGS="--full --no-cpu --workload $WL --steps $ST --warmup $WU $*"
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/stats -- python3 /root/repo/bench.py $ARGS > $R/bench_stats.json 2> $R/stats.err
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $R/fetch -- python3 /root/repo/bench.py $ARGS > /dev/null 2> $R/fetch.err
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $R/write -- python3 /root/repo/bench.py $ARGS > /dev/null 2> $R/write.err
