@@ -20,6 +20,7 @@
 #include <memory>
 
 #include "mhx_launch.hpp"
+#include "mhx_plan.hpp"
 #include "mhx_rtc.hpp"
 #include "mhx_types.hpp"
 
@@ -223,6 +224,11 @@ struct mhx_engine {
   std::string kernel_name;  // mhx_kernel_name
   std::string rtc_note;     // why run-time specialisation was not possible (first line)
   const Family* fam = &family_w8();  // kernel family (workgroup shape) of the current problem
+  int cus = 256;                     // compute units of the device (mhx_create)
+  // the environment switches (mhx_plan.hpp): read when the problem is finalised, and again at the
+  // start of every run (the run-time ones: compaction, graphs, re-slicing)
+  EngineKnobs knobs;
+  ProblemShape shape;                // what the mode rules read of the finalised problem
 
   ChainState S{};
   DevBuf<double> theta, prob, best_theta, best_prob, hist_prob, hist_theta, L, temperature,
@@ -332,161 +338,6 @@ std::string builtin_model_type(const FnDesc& f) {
   }
 }
 
-// May this engine use the persistent kernels at all (MHX_NO_PERSIST=1: never; persist_off: a
-// launch of theirs once lost its sweep workgroups; their handshake blocks carry 60 parameters)
-static bool persist_allowed(const mhx_engine* e) {
-  const char* np_ = getenv("MHX_NO_PERSIST");
-  return !e->persist_off && !(np_ && atoi(np_) != 0) && e->P.d <= 60;
-}
-// MHX_PERSIST_TS: 1 = the tile-sliced persistent form wherever two slices of it fit, 0 = never,
-// unset (-1) = where it fits with at least three quarters of the default slicing
-static int persist_ts_wanted() {
-  const char* s = getenv("MHX_PERSIST_TS");
-  return s ? (atoi(s) != 0 ? 1 : 0) : -1;
-}
-int64_t persist_capacity(const mhx_engine* e, bool ts);
-// nwin windows cut into ts slices are ceil(nwin / ts) windows per slice - which may fill fewer
-// slices than ts: 49 windows in 16 slices are 13 slices of 4 (the last one of 1) and three empty
-// ones, whose workgroups would be launched (or, persistent, sit on a CU and poll) for nothing.
-// The sums are the same bits either way: an empty slice's partial sum is +0.
-static int64_t trim_slices(int64_t nwin, int64_t ts) {
-  if (ts <= 0 || nwin <= 0) return ts;
-  const int64_t per = (nwin + ts - 1) / ts;
-  return (nwin + per - 1) / per;
-}
-
-// Split mode (mhx_kernels.hpp): how many workgroups share one chain's likelihood sums, or 0 for
-// the batch kernels.  Worth it when the batch launch would leave most CUs without a workgroup
-// and every (slice, wave) slot still gets at least 512 points of the longest dataset.
-// MHX_SPLIT=0 switches it off, MHX_SPLIT=<n> forces n slices.
-// cap_pc > 0: the per-chain persistent form (k_persist: one launch per portion of iterations) is
-// allowed and the GPU holds that many of its workgroups at once - where C (1 + slices) of them
-// fit, split mode costs 7.6 us per iteration instead of the two launches' 14 and pays off on
-// shorter datasets (4096 points: 13.4 us in the batch kernel).
-int choose_split(const mhx_engine* e, const Family& fam, bool capable, int64_t cap_pc) {
-  if (!capable || e->cfg.adapt_mode == MHX_ADAPT_POOLED) return 0;
-  int64_t longest = 0;
-  for (int k = 0; k < e->P.K; ++k) longest = std::max<int64_t>(longest, e->P.fn[k].n);
-  const int64_t C = e->cfg.n_chains;
-  const int W = fam.waves_per_group;
-  const int64_t by_data = longest / (512 * (int64_t)W);
-  if (const char* s = getenv("MHX_SPLIT")) {
-    const int v = atoi(s);
-    return v <= 0 ? 0 : (int)std::min<int64_t>(std::max<int64_t>(by_data, 1), v);
-  }
-  // measured (tools/debug/split_sweep.sh, round 2; chain-steps/s batch | best split):
-  //   config 2's problem   64 chains 6.6e5 | 2.4e6 (x4)    256: 2.6e6 | 4.5e6 (x4)
-  //                        512: 5.3e6 | 5.4e6 (x2)         1024: 1.05e7 | 5.9e6    2048: 2.1e7 | 6.3e6
-  //   config 3's problem   16: 4.2e3 | 1.5e5 (x24)    256: 6.7e4 | 2.9e5 (x8)    1024: 2.7e5 | 3.1e5
-  // (round 2, with the recurrence in the split sweep as well:  config 3  16: 2.3e5 (x24)
-  //  256: 4.6e5 (x4)    1024: 2.7e5 | 5.4e5 (x4);  config 2 unchanged: its split sweep is bound by
-  //  the L2, every chain reading the dataset for itself)
-  // The batch kernels (peak skipping, LDS tiles shared by 8 chains) win from about 128
-  // workgroups on when a point is cheap; a point that costs 40 instructions and more (a log per
-  // point, a pseudo-Voigt, an expression compiled as written) keeps the whole GPU busy in split
-  // mode until the batch kernels have a workgroup for every CU.  Below that about 1024
-  // workgroups in the sweep launch are best.
-  bool heavy = false;
-  for (int k = 0; k < e->P.K; ++k) {
-    const FnDesc& fd = e->P.fn[k];
-    heavy = heavy || fd.lik == MHX_LIK_POISSON || fd.lik == MHX_LIK_EXPR ||
-            fd.model == MHX_MODEL_PVOIGT2 || fd.model == MHX_MODEL_EXPR;
-  }
-  const int64_t batch_groups = (C + W - 1) / W;
-  if (batch_groups >= (heavy ? 256 : 128)) return 0;
-  // two launches cost about 14 us per iteration: the fused batch kernel is quicker than that up
-  // to roughly a dozen 1024-point tiles; one persistent launch is quicker from one slice's worth
-  // of points on (the batch kernel: 13.4 us on 4096 points)
-  if (by_data < 4) {
-    if (by_data >= 1 && !heavy && C * (1 + by_data) <= cap_pc) return (int)by_data;
-    return 0;
-  }
-  // (cheap points: beyond 8 slices the partial sums and the extra blocks cost more than they
-  // bring once there are 32 chains and more - 64 chains: x16 2.2e6, x8 2.4e6, x4 2.4e6)
-  const int64_t want = heavy ? std::max<int64_t>(4, 2048 / C)
-                             : std::max<int64_t>(2, std::min<int64_t>(1024 / C, C < 32 ? 24 : 8));
-  const int64_t slices = std::min<int64_t>(std::min<int64_t>(want, 24), by_data);
-  return slices >= 2 ? (int)slices : 0;
-}
-
-// Tile-sliced split mode (k_split_tsweep): into how many slices of whole windows every function is
-// cut, each walked by the workgroups of ALL chain groups, or 0.  For batches too small to give
-// every CU a workgroup of the batch kernels and big enough to fill workgroups of their own:
-// about two workgroups per CU in the sweep launch.  MHX_TSPLIT=0 switches it off (the per-chain
-// split mode or the batch kernels then), MHX_TSPLIT=<n> asks for n slices; MHX_SPLIT=0 means the
-// batch kernels here too, MHX_SPLIT=<n> alone the per-chain split mode.
-// cap_pc, cap_ts > 0: the persistent forms are allowed (workgroups of k_persist / k_persist_ts the
-// GPU holds at once).  One persistent launch costs about 10.3 us per iteration where the two
-// launches cost 20 (measured round 4, two-peak problem, us per iteration, persistent | default
-// of round 3):  8192 points  32 chains 12.4 | 18.2 (batch kernel)    256: 12.4 | 18.5
-//   20000 points  128: 11.1 | 22.1 (per-chain split)    256: 13.2 | 28.9
-//   50000 points  8: 10.4 | 20.4 (two launches)    128: 11.9 | 23.5
-// so it serves from 4 windows on - unless the per-chain persistent form fits, which is quicker
-// still on short datasets (20000 points, 8 ... 64 chains: 7.7 ... 8.7 us).
-int choose_tsplit(const mhx_engine* e, const Family& fam, bool capable, int64_t cap_pc, int64_t cap_ts) {
-  if (!capable || e->cfg.adapt_mode == MHX_ADAPT_POOLED) return 0;
-  int64_t longest = 0;
-  for (int k = 0; k < e->P.K; ++k) longest = std::max<int64_t>(longest, e->P.fn[k].n);
-  const int64_t nwin = (longest + kPadPoints - 1) / kPadPoints;
-  const int64_t C = e->cfg.n_chains;
-  const int W = fam.waves_per_group;
-  const int64_t groups = (C + W - 1) / W;
-  int64_t want = 0;
-  // (MHX_SPLIT set: the caller has decided - the batch kernels, or the per-chain split mode)
-  if (getenv("MHX_SPLIT") && !getenv("MHX_TSPLIT")) return 0;
-  if (const char* s0 = getenv("MHX_SPLIT"))
-    if (atoi(s0) <= 0) return 0;
-  if (const char* s = getenv("MHX_TSPLIT")) {
-    want = atoi(s);
-    if (want <= 0) return 0;
-  } else {
-    // two launches and the step kernel cost about 17 us per iteration (64 chains of config 2's
-    // problem: 20.7 us with one window per workgroup): the fused batch kernel, 0.6-0.8 us per
-    // 1024-point tile when points are cheap, is quicker than that up to about two dozen tiles
-    bool heavy = false;
-    for (int k = 0; k < e->P.K; ++k) {
-      const FnDesc& fd = e->P.fn[k];
-      heavy = heavy || fd.lik == MHX_LIK_POISSON || fd.lik == MHX_LIK_EXPR ||
-              fd.model == MHX_MODEL_PVOIGT2 || fd.model == MHX_MODEL_EXPR;
-    }
-    if (groups >= 256) return 0;
-    // fewer walkers than a workgroup has waves: the per-chain split mode - unless the persistent
-    // form is allowed, whose sweep workgroups walk LDS tiles with peak skipping and the
-    // recurrence, one window per wave however long the dataset (a single walker on 1e5 points
-    // 7.6 -> 6.4 us per step, on 1e6 points 25.4 -> 11.1; 20000 points: 6.2 against 6.7, left alone)
-    if (C < W && (cap_ts <= 0 || nwin < 12)) return 0;
-    if (nwin < (heavy ? 4 : 12)) {
-      // too short for two launches per iteration: as one persistent launch, or not at all
-      // (a window per slice, or fewer slices of up to 4 windows where the GPU does not hold that
-      // many workgroups at once: 20000 points, 512 walkers x7 instead of the per-chain split
-      // mode's two launches)
-      const int64_t fit = std::min<int64_t>(nwin, cap_ts / groups - 1);
-      if (nwin < (heavy ? 2 : 4) || fit < 2 || (nwin + fit - 1) / fit > 4) return 0;
-      const int pc = choose_split(e, fam, capable, cap_pc);
-      if (pc > 0 && C * (1 + pc) <= cap_pc) return 0;  // (the per-chain persistent form)
-      return (int)trim_slices(nwin, fit);
-    }
-    // measured (config 2's problem, chain-steps/s; slices 4 | 8 | 16 | 32 | 49):
-    //   64 chains 1.5e6 | 2.1e6 | 2.6e6 | 3.1e6 | 3.1e6     256: 6.0e6 | 7.9e6 | 8.0e6 | 7.0e6 | 6.3e6
-    //   1024: 1.47e7 | 1.33e7 | 1.13e7 | 9.2e6 | 8.8e6       (per-chain split mode: 2.4e6, 4.7e6; batch
-    //   kernels at 1024: 1.31e7) - about 512 workgroups in the sweep launch
-    want = 512 / groups;
-  }
-  want = std::min<int64_t>(want, nwin);
-  if (!getenv("MHX_TSPLIT")) {
-    want = trim_slices(nwin, want);
-    // two or three slices as TWO LAUNCHES per iteration lose to the batch kernels on datasets
-    // that are not long (measured round 4, us per iteration, two launches | batch kernels:
-    //   1536 walkers x2: 5e4 points 76.5 | 56.7, 1e5: 102 | 90.8, 1e6: 690 | 846;
-    //   1100 walkers x3: 5e4 points 58.6 | 55.2, 1e5: 75.9 | 89.9) - unless the persistent
-    // form will take them (1024 walkers x3, 5e4 points: 35.5 | 49.1)
-    const int64_t pfit = cap_ts > 0 ? std::min<int64_t>(want, cap_ts / groups - 1) : 0;
-    const bool persistable = pfit >= std::max<int64_t>(2, (3 * want + 3) / 4) && persist_ts_wanted() != 0;
-    if (!persistable && ((want == 2 && nwin < 128) || (want == 3 && nwin < 32))) return 0;
-  }
-  return want >= 2 ? (int)want : 0;
-}
-
 // The slice table of the tile-sliced split mode: function k, slice s = windows [s per_k,
 // (s + 1) per_k) of its dataset, as a FnDesc of its own (what k_split_tsweep hands to sweep()).
 int build_ts_table(mhx_engine* e, int ts) {
@@ -522,8 +373,7 @@ int build_ts_table(mhx_engine* e, int ts) {
       tab[(size_t)k * ts + sl] = g;
     }
   }
-  const char* nr = getenv("MHX_NO_RESIDENT_SLICES");
-  if (resident && !(nr && atoi(nr) != 0))
+  if (resident && !e->knobs.no_resident_slices)
     for (FnDesc& g : tab) g.solo = g.n_tiles > 0 ? 1 : 0;
   if (e->ts_table.n < tab.size() && e->ts_table.alloc(tab.size(), false) != hipSuccess)
     return fail(MHX_ENOMEM, "hipMalloc of the slice table failed");
@@ -531,43 +381,10 @@ int build_ts_table(mhx_engine* e, int ts) {
   return MHX_OK;
 }
 
-// Which workgroup shape serves this problem (mhx_types.hpp).  16 chains per workgroup and
-// 2048-point tiles pay off when the datasets are long (>= 4 such tiles) and there are enough
-// chains to give every CU its one workgroup; otherwise 8 chains per workgroup (more, smaller
-// workgroups; less barrier and pad overhead on short datasets).  MHX_FAMILY_WPG=8|16 pins it.
-const Family& choose_family(const mhx_engine* e) {
-  if (const char* s = getenv("MHX_FAMILY_WPG")) {
-    if (atoi(s) == 16) return family_w16();
-    if (atoi(s) == 8) return family_w8();
-  }
-  int64_t longest = 0;
-  for (int k = 0; k < e->P.K; ++k) longest = std::max<int64_t>(longest, e->P.fn[k].n);
-  const bool big = longest >= 4 * (int64_t)family_w16().tile_points &&
-                   e->cfg.n_chains >= 16 * 256;
-  return big ? family_w16() : family_w8();
-}
-
-// Workgroups of a persistent launch (k_persist, k_persist_ts: they wait for one another) the GPU
-// holds at once: CUs times what the occupancy calculator gives the COMPILED kernel (registers,
-// LDS and waves - an assumed "two per CU" was wrong for a kernel of 132 VGPRs and cost half the
-// speed, see k_persist_ts).  Every slot: what the calculator promises is what the dispatcher
-// gives - 128 groups x (1 + 3) = 512 workgroups on 256 CUs ran in one shift, 55.9 us per
-// iteration against 72.0 of two launches - and a workgroup that finds its slot taken for a
-// while by another kernel of the process arrives late, within the masters' patience
-// (MHX_PERSIST_FILL=<per cent>: measurements).
-int64_t persist_capacity(const mhx_engine* e, bool ts) {
-  int cus = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device) != hipSuccess || cus <= 0)
-    cus = 256;
-  const int per_cu = e->spec == SPEC_USER ? rtc_persist_per_cu(*e->user_prog, ts ? 1 : 0)
-                                          : e->fam->persist_per_cu(e->spec, ts ? 1 : 0);
-  int fill = 100;
-  if (const char* f = getenv("MHX_PERSIST_FILL")) fill = std::max(10, std::min(100, atoi(f)));
-  return (int64_t)cus * per_cu * fill / 100;
-}
-
 int finalize_problem(mhx_engine* e) {
   if (!e->problem_dirty) return MHX_OK;
+  e->knobs = read_knobs();
+  const EngineKnobs& kn = e->knobs;
   drop_split_graph(e);
   // a new problem may run in another mode and family: slot s is chain s until the next deal
   e->S.slot_chain = nullptr;
@@ -581,7 +398,19 @@ int finalize_problem(mhx_engine* e) {
   // tile-level peak skipping tests against (PeaksModel::tile_mask) are those of WINDOWS of
   // kPadPoints points, pads included, whatever the family (sweep: one mask and one seeding of the
   // Gaussian recurrence per window)
-  e->fam = &choose_family(e);
+  ProblemShape& sh = e->shape;
+  sh = ProblemShape{};
+  for (int k = 0; k < e->P.K; ++k) sh.longest = std::max<int64_t>(sh.longest, e->P.fn[k].n);
+  sh.nwin = ceil_div(sh.longest, kPadPoints);
+  sh.K = e->P.K;
+  sh.d = e->P.d;
+  sh.chains = e->cfg.n_chains;
+  sh.pooled = e->cfg.adapt_mode == MHX_ADAPT_POOLED;
+  sh.persist_off = e->persist_off;
+  sh.cus = e->cus;
+  e->fam = choose_family(sh, kn) == 16 ? &family_w16() : &family_w8();
+  sh.waves_per_group = e->fam->waves_per_group;
+  sh.tile_points = e->fam->tile_points;
   const size_t tp = (size_t)e->fam->tile_points;
   const size_t wp = (size_t)kPadPoints;
   for (int k = 0; k < e->P.K; ++k) {
@@ -616,37 +445,34 @@ int finalize_problem(mhx_engine* e) {
     // with its own h = (x_last - x_first) / (points - 1) - and 0 otherwise (direct form there).
     // MHX_NO_WINDOW_GRIDS=1: off (round 3's rule: one grid or none).
     f.tgh = nullptr;
-    {
-      const char* nwg = getenv("MHX_NO_WINDOW_GRIDS");
-      if (f.grid_H == 0.0 && !D.no_rec && !(nwg && atoi(nwg) != 0) && D.n >= 2) {
-        std::vector<double> gh(ntp, 0.0);
-        double h_prev = 0.0;
-        bool any = false;
-        for (size_t t = 0; t < ntp; ++t) {
-          const size_t i0 = t * wp, cnt = std::min(wp, D.n > i0 ? D.n - i0 : 0);
-          if (cnt < 2) continue;
-          const double* xw = &D.hx[i0];
-          if (!std::isfinite(xw[0]) || !std::isfinite(xw[cnt - 1])) continue;
-          const double tol = 8.0 * 0x1p-52 * std::max(std::fabs(xw[0]), std::fabs(xw[cnt - 1]));
-          auto fits = [&](double h) {
-            if (h == 0.0 || !std::isfinite(h)) return false;
-            for (size_t i = 0; i < cnt; ++i)
-              if (!(std::fabs(xw[i] - (xw[0] + (double)i * h)) <= tol)) return false;
-            return true;
-          };
-          double h = h_prev;
-          if (!fits(h)) h = (xw[cnt - 1] - xw[0]) / (double)(cnt - 1);
-          if (!fits(h)) continue;
-          gh[t] = 64.0 * h;
-          h_prev = h;
-          any = true;
-        }
-        if (any) {
-          if (D.tgh.alloc(ntp, false) != hipSuccess)
-            return fail(MHX_ENOMEM, "hipMalloc of dataset %d's window grids failed", k);
-          HIP_TRY(hipMemcpy(D.tgh.p, gh.data(), ntp * sizeof(double), hipMemcpyHostToDevice));
-          f.tgh = D.tgh.p;
-        }
+    if (f.grid_H == 0.0 && !D.no_rec && !kn.no_window_grids && D.n >= 2) {
+      std::vector<double> gh(ntp, 0.0);
+      double h_prev = 0.0;
+      bool any = false;
+      for (size_t t = 0; t < ntp; ++t) {
+        const size_t i0 = t * wp, cnt = std::min(wp, D.n > i0 ? D.n - i0 : 0);
+        if (cnt < 2) continue;
+        const double* xw = &D.hx[i0];
+        if (!std::isfinite(xw[0]) || !std::isfinite(xw[cnt - 1])) continue;
+        const double tol = 8.0 * 0x1p-52 * std::max(std::fabs(xw[0]), std::fabs(xw[cnt - 1]));
+        auto fits = [&](double h) {
+          if (h == 0.0 || !std::isfinite(h)) return false;
+          for (size_t i = 0; i < cnt; ++i)
+            if (!(std::fabs(xw[i] - (xw[0] + (double)i * h)) <= tol)) return false;
+          return true;
+        };
+        double h = h_prev;
+        if (!fits(h)) h = (xw[cnt - 1] - xw[0]) / (double)(cnt - 1);
+        if (!fits(h)) continue;
+        gh[t] = 64.0 * h;
+        h_prev = h;
+        any = true;
+      }
+      if (any) {
+        if (D.tgh.alloc(ntp, false) != hipSuccess)
+          return fail(MHX_ENOMEM, "hipMalloc of dataset %d's window grids failed", k);
+        HIP_TRY(hipMemcpy(D.tgh.p, gh.data(), ntp * sizeof(double), hipMemcpyHostToDevice));
+        f.tgh = D.tgh.p;
       }
     }
     // the one tile stays in LDS (sweep).  Measured (tools/ab_tree.sh, test.lisp's shape): +9 %
@@ -656,12 +482,10 @@ int finalize_problem(mhx_engine* e) {
   }
   // MHX_NO_TILE_SKIP=1: evaluate every Gaussian peak at every point (the skipping is exact, so
   // this only exists to show that the results do not change)
-  const char* nts = getenv("MHX_NO_TILE_SKIP");
-  const int tile_skip = (nts && atoi(nts) != 0) ? 0 : 1;
+  const int tile_skip = kn.no_tile_skip ? 0 : 1;
   bool any_expr = false;
   // MHX_NO_RECOGNISE=1: every expression compiled as written (A/B runs; bench.py --workload c2expr)
-  const char* nrec = getenv("MHX_NO_RECOGNISE");
-  const bool recognise = e->recognise && !(nrec && atoi(nrec) != 0);
+  const bool recognise = e->recognise && !kn.no_recognise;
   for (int k = 0; k < e->P.K; ++k) {
     FnDesc& f = e->P.fn[k];
     f.user_slot = f.prior_slot = -1;
@@ -687,10 +511,8 @@ int finalize_problem(mhx_engine* e) {
         f.shape[0] = f.shape[1] = 0;
       }
     }
-    {  // MHX_NO_YW=1: the shared-tile layout with x for every step (A/B runs; same bits either way)
-      const char* ny = getenv("MHX_NO_YW");
-      f.no_yw = (ny && atoi(ny) != 0) ? 1 : 0;
-    }
+    // MHX_NO_YW=1: the shared-tile layout with x for every step (A/B runs; same bits either way)
+    f.no_yw = kn.no_yw ? 1 : 0;
     if (f.lik == MHX_LIK_EXPR) {
       if (e->lik_expr[k].empty())
         return fail(MHX_ESTATE, "dataset %d uses MHX_LIK_EXPR but mhx_set_likelihood_expr was "
@@ -703,6 +525,8 @@ int finalize_problem(mhx_engine* e) {
       return fail(MHX_ESTATE, "function %d reads xcol1 but dataset %d has one column of x "
                               "(mhx_set_dataset_cols)", k, k);
     any_expr = any_expr || f.model == MHX_MODEL_EXPR || !e->prior_expr[k].expr.empty();
+    sh.heavy = sh.heavy || f.lik == MHX_LIK_POISSON || f.lik == MHX_LIK_EXPR ||
+               f.model == MHX_MODEL_PVOIGT2 || f.model == MHX_MODEL_EXPR;
   }
   // Which kernels: an ahead-of-time specialisation if the problem matches one; otherwise kernels
   // compiled at run time (hiprtc) in which EVERY function - expression or enumerated model - gets
@@ -710,19 +534,14 @@ int finalize_problem(mhx_engine* e) {
   // skipping): 2.4-2.8x the run-time-dispatched generic kernels on configs 2 and 3.  The generic
   // kernels remain for MHX_FORCE_GENERIC=1 / MHX_NO_RTC_SPECIALISE=1 and for machines without
   // hiprtc.
-  {  // MHX_NO_DEAL=1: every wave judges its own chain's proposal (A/B runs; same bits either way)
-    const char* nd = getenv("MHX_NO_DEAL");
-    e->P.no_deal = (nd && atoi(nd) != 0) ? 1 : 0;
-    e->P.test_lose_sweepers = 0;
+  // MHX_NO_DEAL=1: every wave judges its own chain's proposal (A/B runs; same bits either way)
+  e->P.no_deal = kn.no_deal ? 1 : 0;
+  e->P.test_lose_sweepers = 0;
 #ifdef MHX_DEBUG_HOOKS  // (tests/hooks/libmhx_hooks.so: a persistent launch whose sweepers never come)
-    const char* tl = getenv("MHX_TEST_LOSE_SWEEPERS");
-    e->P.test_lose_sweepers = (tl && atoi(tl) != 0) ? 1 : 0;
+  e->P.test_lose_sweepers = kn.test_lose_sweepers ? 1 : 0;
 #endif
-  }
-  const char* fg = getenv("MHX_FORCE_GENERIC");
-  const char* ns = getenv("MHX_NO_RTC_SPECIALISE");
-  const bool force_generic = fg && atoi(fg) != 0;
-  const bool specialise = !(ns && atoi(ns) != 0) && !force_generic;
+  const bool force_generic = kn.force_generic;
+  const bool specialise = !kn.no_rtc_specialise && !force_generic;
   // a function with a per-window grid table needs the kernel instance that follows it
   // (FixedSpec<Model, LIK, true>, mhx_kernels.hpp): compiled at run time, like every problem
   // without an ahead-of-time kernel - the ahead-of-time ones stay what they were
@@ -740,16 +559,12 @@ int finalize_problem(mhx_engine* e) {
   // finite parameters) with the weighted normal likelihood and no prior body - compiled at run
   // time too, so that the ahead-of-time kernels do not carry the test (4-5 % in a walk's first
   // iterations even when it never fires)
-  bool any_er = false;
-  {
-    const char* er = getenv("MHX_EARLY_REJECT");
-    const FnDesc& f0 = e->P.fn[0];
-    any_er = er && atoi(er) != 0 && specialise && e->P.K == 1 && f0.lik == MHX_LIK_NORMAL &&
-             (f0.model == MHX_MODEL_GAUSS_PEAKS || f0.model == MHX_MODEL_LORENTZ_PEAKS ||
-              f0.model == MHX_MODEL_POLY) &&
-             e->prior_expr[0].expr.empty() && !builtin_model_type(f0).empty() &&
-             e->cfg.adapt_mode != MHX_ADAPT_POOLED;
-  }
+  const FnDesc& f0 = e->P.fn[0];
+  const bool any_er = kn.early_reject && specialise && e->P.K == 1 && f0.lik == MHX_LIK_NORMAL &&
+                      (f0.model == MHX_MODEL_GAUSS_PEAKS || f0.model == MHX_MODEL_LORENTZ_PEAKS ||
+                       f0.model == MHX_MODEL_POLY) &&
+                      e->prior_expr[0].expr.empty() && !builtin_model_type(f0).empty() &&
+                      e->cfg.adapt_mode != MHX_ADAPT_POOLED;
   const int aot = (any_expr || any_wgrid || any_er) ? SPEC_GENERIC : select_spec(e->P);
   e->rtc_note.clear();
   HIP_TRY(hipMemcpy(e->dP.p, &e->P, sizeof(ProblemDesc), hipMemcpyHostToDevice));
@@ -787,12 +602,8 @@ int finalize_problem(mhx_engine* e) {
     }
     HIP_TRY(hipMemcpy(e->dP.p, &e->P, sizeof(ProblemDesc), hipMemcpyHostToDevice));
     std::string err;
-    // (before the kernels exist their occupancy is not known: the most they could have)
-    const int64_t cap_guess = persist_allowed(e) ? 2 * 256 : 0;
-    const bool want_split = choose_split(e, *e->fam, !builtin, cap_guess) > 0 ||
-                            choose_tsplit(e, *e->fam, !builtin, cap_guess, cap_guess) > 0;
     std::shared_ptr<UserProgram> prog =
-        rtc_get(models, priors, builtin, want_split, *e->fam, &err);
+        rtc_get(models, priors, builtin, want_split(sh, kn, !builtin), *e->fam, &err);
     if (prog) {
       e->user_prog = prog;
       e->spec = SPEC_USER;
@@ -806,100 +617,44 @@ int finalize_problem(mhx_engine* e) {
       e->spec = SPEC_GENERIC;
     }
   }
-  // split mode for small batches on long datasets
-  {
-    const bool capable = e->spec == SPEC_USER ? e->user_prog->has_split
-                                              : e->fam->split_capable(e->spec);
-    const bool pa = capable && persist_allowed(e);
-    const int64_t cap_pc = pa ? persist_capacity(e, false) : 0;
-    const int64_t cap_ts = pa && persist_ts_wanted() != 0 ? persist_capacity(e, true) : 0;
-    const int ts = choose_tsplit(e, *e->fam, capable, cap_pc, cap_ts);
-    e->tsplit = ts > 0;
-    e->split_slices = e->tsplit ? ts : choose_split(e, *e->fam, capable, cap_pc);
-    e->S.split_slots = e->tsplit ? e->split_slices : e->split_slices * e->fam->waves_per_group;
-    e->S.split_part = nullptr;
-    e->ts_initial = e->tsplit ? ts : 0;
-    if (e->tsplit) {
-      const int rc = build_ts_table(e, ts);
-      if (rc != MHX_OK) return rc;
-    }
-    if (e->split_slices > 0) {
-      // (tile-sliced: room for the most slices a later re-slicing may take - compact_slots)
-      int64_t nwin_max = 1;
-      for (int k = 0; k < e->P.K; ++k)
-        nwin_max = std::max<int64_t>(nwin_max, (e->P.fn[k].n + kPadPoints - 1) / kPadPoints);
-      const size_t slots_max =
-          e->tsplit ? (size_t)std::max<int64_t>(e->S.split_slots, std::min<int64_t>(nwin_max, 512))
-                    : (size_t)e->S.split_slots;
-      const size_t np = (size_t)e->cfg.n_chains * e->P.K * slots_max;
-      if (e->split_part.alloc(np) != hipSuccess)
-        return fail(MHX_ENOMEM, "hipMalloc of the split-mode partial sums failed");
-      e->S.split_part = e->split_part.p;
-    }
-    HIP_TRY(hipMemset(e->split_pending.p, 0, (size_t)e->cfg.n_chains * sizeof(int32_t)));
-    // the per-chain split mode as ONE launch per portion of iterations (k_persist): the chain's
-    // master wave and its sweep workgroups hand each other the proposal and the partial sums
-    // through memory, which needs every workgroup of the launch on the GPU at once
-    // (MHX_NO_PERSIST=1: the two launches per iteration of rounds 1-3)
-    e->persist = false;
-    if (e->split_slices > 0) {
-      const int64_t W = e->fam->waves_per_group;
-      // tile-sliced: (1 + slices) workgroups per chain GROUP - with fewer slices, down to 2,
-      // where the default slicing would not fit the GPU at once (a run's repacking keeps to the
-      // same bound: compact_tsplit)
-      const int64_t units = e->tsplit ? (e->cfg.n_chains + W - 1) / W : e->cfg.n_chains;
-      const int64_t cap = persist_capacity(e, e->tsplit);
-      int64_t slices = e->split_slices;
-      // The tile-sliced form runs with fewer slices where the default slicing does not fit the
-      // GPU at once - down to three quarters of it (MHX_PERSIST_TS=1: down to 2; =0: never the
-      // persistent form).  Measured round 4 (two-peak problem, 1e5 points, us per iteration,
-      // persistent | two launches):  8 chains x49 10.1 | 20.0    64: x49 12.2 | 23.0
-      //   128: x27 14.3 | x32 26.5    256: x13 19.6 | x16 33.6    512: x6 31.2 | x8 46.6
-      //   1024: x2 68.9 | x4 71.7;   1e6 points  8: 15.4 | 23.8    64: 34.5 | 45.8
-      //   256: 120 | 121    1024: x2 611 | x4 429 (half the slices: not taken).
-      // (Round 3 had measured the persistent form no faster and left it behind a switch: its
-      // kernel took 132 VGPRs, one workgroup fitted a CU, and the launch ran in two shifts.)
-      const int wanted = persist_ts_wanted();
-      if (e->tsplit && !getenv("MHX_TSPLIT")) {
-        int64_t nwin_all = 1;
-        for (int k = 0; k < e->P.K; ++k)
-          nwin_all = std::max<int64_t>(nwin_all, (e->P.fn[k].n + kPadPoints - 1) / kPadPoints);
-        const int64_t fit = trim_slices(nwin_all, std::min<int64_t>(slices, cap / units - 1));
-        const int64_t least = wanted > 0 ? 2 : std::max<int64_t>(2, (3 * slices + 3) / 4);
-        // (fewer slices only where an iteration is short enough for the saved launches to
-        // matter: up to 48 windows per slice - 1e6 points, 1024 walkers: x3, 163 windows each,
-        // 500 us against the two launches' x4 424; 512: x7, 70 each, 226 against x8 223;
-        // 256: x15, 33 each, 106 against x16 121; 1e5 points, 1024 walkers: x3 55.9 against x4 72.0)
-        const bool short_rounds = fit > 0 && (nwin_all + fit - 1) / fit <= 48;
-        slices = fit >= least && (fit == slices || short_rounds || wanted > 0) ? fit : 0;
-      }
-      const bool want = e->tsplit ? wanted != 0 : true;
-      e->persist = want && persist_allowed(e) && slices >= (e->tsplit ? 2 : 1) &&
-                   units * (1 + slices) <= cap;
-      if (e->persist && e->tsplit) {  // (the table of the persistent form: fewer slices, resident windows)
-        const int rc = build_ts_table(e, (int)slices);
-        if (rc != MHX_OK) return rc;
-        e->split_slices = (int)slices;
-        e->S.split_slots = (int)slices;
-        e->ts_initial = (int)slices;
-      }
-      if (e->persist) {
-        const size_t nm = 64 * (size_t)e->cfg.n_chains;
-        int64_t nwin_all = 1;
-        for (int k = 0; k < e->P.K; ++k)
-          nwin_all = std::max<int64_t>(nwin_all, (e->P.fn[k].n + kPadPoints - 1) / kPadPoints);
-        const size_t slots_cap = e->tsplit ? (size_t)std::max<int64_t>(e->S.split_slots, std::min<int64_t>(nwin_all, 512))
-                                           : (size_t)e->S.split_slots;
-        const size_t npb = 16 * (size_t)e->cfg.n_chains * e->P.K * slots_cap;
-        if ((e->persist_msg.n < nm && e->persist_msg.alloc(nm) != hipSuccess) ||
-            (e->persist_part.n < npb && e->persist_part.alloc(npb) != hipSuccess))
-          return fail(MHX_ENOMEM, "hipMalloc of the persistent kernel's handshake buffers failed");
-        if (!e->persist_error.p && e->persist_error.alloc(1) != hipSuccess)
-          return fail(MHX_ENOMEM, "hipMalloc of the persistent kernel's error word failed");
-        e->S.persist_msg = e->persist_msg.p;
-        e->S.persist_part = e->persist_part.p;
-        e->S.persist_error = e->persist_error.p;
-      }
+  // the launch form (mhx_plan.hpp), then its tables and buffers
+  sh.capable = e->spec == SPEC_USER ? e->user_prog->has_split : e->fam->split_capable(e->spec);
+  if (sh.capable) {
+    for (int ts = 0; ts < 2; ++ts)
+      (ts ? sh.per_cu_ts : sh.per_cu) = e->spec == SPEC_USER ? rtc_persist_per_cu(*e->user_prog, ts)
+                                                             : e->fam->persist_per_cu(e->spec, ts);
+  }
+  const LaunchPlan plan = plan_modes(sh, kn);
+  e->tsplit = plan.tsplit;
+  e->split_slices = plan.split_slices;
+  e->persist = plan.persist;
+  e->ts_initial = plan.ts_initial;
+  e->S.split_slots = e->tsplit ? e->split_slices : e->split_slices * e->fam->waves_per_group;
+  e->S.split_part = nullptr;
+  if (e->tsplit) {
+    const int rc = build_ts_table(e, e->split_slices);
+    if (rc != MHX_OK) return rc;
+  }
+  HIP_TRY(hipMemset(e->split_pending.p, 0, (size_t)e->cfg.n_chains * sizeof(int32_t)));
+  if (e->split_slices > 0) {
+    // (tile-sliced: room for the most slices a later re-slicing may take - compact_tsplit)
+    const size_t slots_max = e->tsplit ? (size_t)std::max<int64_t>(e->S.split_slots, std::min<int64_t>(sh.nwin, 512))
+                                       : (size_t)e->S.split_slots;
+    const size_t np = (size_t)e->cfg.n_chains * e->P.K * slots_max;
+    if (e->split_part.alloc(np) != hipSuccess)
+      return fail(MHX_ENOMEM, "hipMalloc of the split-mode partial sums failed");
+    e->S.split_part = e->split_part.p;
+    if (e->persist) {  // (the handshake blocks of the persistent kernels: mhx_types.hpp)
+      const size_t nm = 64 * (size_t)e->cfg.n_chains;
+      const size_t npb = 16 * np;
+      if ((e->persist_msg.n < nm && e->persist_msg.alloc(nm) != hipSuccess) ||
+          (e->persist_part.n < npb && e->persist_part.alloc(npb) != hipSuccess))
+        return fail(MHX_ENOMEM, "hipMalloc of the persistent kernel's handshake buffers failed");
+      if (!e->persist_error.p && e->persist_error.alloc(1) != hipSuccess)
+        return fail(MHX_ENOMEM, "hipMalloc of the persistent kernel's error word failed");
+      e->S.persist_msg = e->persist_msg.p;
+      e->S.persist_part = e->persist_part.p;
+      e->S.persist_error = e->persist_error.p;
     }
   }
   // a name for what was chosen (mhx_kernel_name)
@@ -1147,8 +902,8 @@ int put_slot_map(mhx_engine* e, const std::vector<int32_t>& map) {
 int compact_tsplit(mhx_engine* e, const std::vector<int32_t>& st, int64_t running) {
   const int64_t W = e->fam->waves_per_group;
   const int64_t mapped = e->slots_mapped > 0 ? e->slots_mapped : e->cfg.n_chains;
-  if (running <= 0 || running * 4 > mapped * 3) return MHX_OK;
-  const int64_t groups = (running + W - 1) / W;
+  if (!repack_due(running, mapped)) return MHX_OK;
+  const int64_t groups = ceil_div(running, W);
   std::vector<int32_t> map((size_t)(groups * W), -1);
   size_t j = 0;
   for (size_t c = 0; c < st.size(); ++c)
@@ -1158,16 +913,7 @@ int compact_tsplit(mhx_engine* e, const std::vector<int32_t>& st, int64_t runnin
     if (rc != MHX_OK) return rc;
   }
   e->slots_mapped = running;
-  int64_t nwin = 1;
-  for (int k = 0; k < e->P.K; ++k)
-    nwin = std::max<int64_t>(nwin, (e->P.fn[k].n + kPadPoints - 1) / kPadPoints);
-  const char* forced = getenv("MHX_TSPLIT");
-  int64_t ts = forced ? e->split_slices
-                      : std::max<int64_t>(e->split_slices,
-                                          std::min<int64_t>(std::min<int64_t>(512 / groups, nwin), 512));
-  if (e->persist && !forced)  // (every workgroup of a persistent launch on the GPU at once)
-    ts = std::max<int64_t>(2, std::min<int64_t>(ts, persist_capacity(e, true) / groups - 1));
-  if (!forced) ts = std::max<int64_t>(2, trim_slices(nwin, ts));
+  const int64_t ts = reslice_tsplit(e->shape, e->knobs, e->split_slices, e->persist, groups);
   if (ts != e->split_slices) {
     const int rc = build_ts_table(e, (int)ts);
     if (rc != MHX_OK) return rc;
@@ -1189,8 +935,7 @@ int reset_tsplit(mhx_engine* e) {
 }
 
 int compact_slots(mhx_engine* e, const std::vector<int32_t>& st, int64_t running) {
-  const char* nc = getenv("MHX_NO_COMPACT");
-  if ((nc && atoi(nc) != 0) || !e->fam) return MHX_OK;
+  if (e->knobs.no_compact || !e->fam) return MHX_OK;
   if (e->tsplit) {
     if (!e->ts_repack_due) return MHX_OK;
     e->ts_repack_due = false;
@@ -1199,20 +944,12 @@ int compact_slots(mhx_engine* e, const std::vector<int32_t>& st, int64_t running
   if (e->split_slices > 0) return MHX_OK;
   const int64_t W = e->fam->waves_per_group;
   const int64_t in_use = e->S.slot_chain ? e->S.n_slots : e->cfg.n_chains;
-  const int64_t groups = (in_use + W - 1) / W;
-  int cus = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device) != hipSuccess || cus <= 0)
-    cus = 256;
-  const int64_t resident = (int64_t)cus * (W <= 8 ? 2 : 1);  // workgroups the GPU holds at once
-  const char* force = getenv("MHX_COMPACT_ALWAYS");          // (tests: repack small launches too)
-  const int64_t floor_groups = (force && atoi(force) != 0) ? 1 : resident;
   // chains mapped at the last deal (all of them before the first): a new deal when a quarter of
   // them has finished since.  With no more workgroups than the GPU holds their number stays, and
   // the deal only evens out how many waves each CU and SIMD still has to run.
   const int64_t mapped = e->slots_mapped > 0 ? e->slots_mapped : e->cfg.n_chains;
-  if (running <= 0 || running * 4 > mapped * 3) return MHX_OK;
-  const int64_t target =
-      std::max<int64_t>((running + W - 1) / W, std::min<int64_t>(groups, floor_groups));
+  if (!repack_due(running, mapped)) return MHX_OK;
+  const int64_t target = deal_target(e->cus, W, in_use, running, e->knobs.compact_always);
   std::vector<int32_t> map((size_t)(target * W), -1);
   int64_t j = 0;
   for (size_t c = 0; c < st.size(); ++c)
@@ -1230,25 +967,33 @@ int compact_slots(mhx_engine* e, const std::vector<int32_t>& st, int64_t running
 // workgroups of 8 - two waves on every SIMD of half the CUs, the other half idle; dealt over 256
 // workgroups of 4 every wave has a SIMD to itself.
 int deal_initial(mhx_engine* e) {
-  const char* nc = getenv("MHX_NO_COMPACT");
-  if ((nc && atoi(nc) != 0) || e->split_slices > 0 || !e->fam) return MHX_OK;
+  if (e->knobs.no_compact || e->split_slices > 0 || !e->fam) return MHX_OK;
   const int64_t W = e->fam->waves_per_group, C = e->cfg.n_chains;
-  const int64_t groups = (C + W - 1) / W;
-  int cus = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device) != hipSuccess || cus <= 0)
-    cus = 256;
-  // up to one workgroup per CU: workgroups of 4; between one and two per CU (8-wave family):
-  // two on EVERY CU instead of two on some and one on the others
-  const int64_t resident = (int64_t)cus * (W <= 8 ? 2 : 1);
-  const int64_t target = groups <= cus ? std::min<int64_t>(cus, std::max<int64_t>(groups, (C + 3) / 4))
-                                       : (groups < resident ? resident : groups);
-  if (target <= groups || C <= W) return MHX_OK;
+  const int64_t target = deal_initial_target(e->cus, W, C);
+  if (target == 0) return MHX_OK;
   std::vector<int32_t> map((size_t)(target * W), -1);
   for (int64_t c = 0; c < C; ++c) map[(size_t)((c % target) * W + c / target)] = (int32_t)c;
   const int rc = put_slot_map(e, map);
   if (rc != MHX_OK) return rc;
   e->slots_mapped = C;
   return MHX_OK;
+}
+
+// the start of a run (mhx_adaptive_begin, plain steps): the run-time switches read again, the
+// problem finalised, every chain walking again in slot s = chain s and the slices the problem was
+// finalised with; the run description is an argument frozen into the captured launches
+int begin_run(mhx_engine* e) {
+  int rc = use_device(e);
+  if (rc != MHX_OK) return rc;
+  e->knobs = read_knobs();
+  if ((rc = finalize_problem(e)) != MHX_OK) return rc;
+  drop_split_graph(e);
+  e->S.slot_chain = nullptr;
+  e->S.n_slots = e->cfg.n_chains;
+  e->slots_mapped = 0;
+  e->split_iter = 0;
+  e->ts_repack_due = false;
+  return reset_tsplit(e);
 }
 
 int count_running(mhx_engine* e, int64_t* n_running) {
@@ -1366,9 +1111,8 @@ int launch_steps_enqueue(mhx_engine* e, int64_t iters, int plain) {
         }
         return he;
       };
-      const char* ng = getenv("MHX_NO_GRAPH");
       // (only whole portions: a remainder of another length would mean capturing again)
-      const bool use_graph = !(ng && atoi(ng) != 0) && now == e->split_portion && !e->persist;
+      const bool use_graph = !e->knobs.no_graph && now == e->split_portion && !e->persist;
       bool done = false;
       if (e->persist) {  // tile-sliced, persistent: the portion is ONE launch (k_persist_ts)
         HIP_TRY(hipMemsetAsync(e->persist_msg.p, 0, e->persist_msg.n * sizeof(unsigned long long), e->stream));
@@ -1584,6 +1328,9 @@ int mhx_create(const mhx_config* cfg, mhx_engine** out) {
                 e->device, prop.gcnArchName);
       break;
     }
+    if (hipDeviceGetAttribute(&e->cus, hipDeviceAttributeMultiprocessorCount, e->device) != hipSuccess ||
+        e->cus <= 0)
+      e->cus = 256;
     if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess ||
         hipStreamCreateWithFlags(&e->stop_stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreate(&e->ev0) != hipSuccess || hipEventCreate(&e->ev1) != hipSuccess) {
@@ -2009,16 +1756,8 @@ static int adaptive_begin_enqueue(mhx_engine* e, const mhx_run_opts* o) {
     return fail(MHX_EUNSUPPORTED, ":slope-settle is outside the accelerated path");
   if (!(o->temperature > 0.0) || !std::isfinite(o->temperature))
     return fail(MHX_EINVAL, "temperature must be finite and > 0");
-  int rc = use_device(e);
+  int rc = begin_run(e);
   if (rc != MHX_OK) return rc;
-  if ((rc = finalize_problem(e)) != MHX_OK) return rc;
-  drop_split_graph(e);  // the run description is an argument frozen into the captured launches
-  e->S.slot_chain = nullptr;  // every chain walks again: slot s is chain s (compact_slots)
-  e->S.n_slots = e->cfg.n_chains;
-  e->slots_mapped = 0;
-  e->split_iter = 0;
-  e->ts_repack_due = false;
-  if ((rc = reset_tsplit(e)) != MHX_OK) return rc;
   if ((rc = deal_initial(e)) != MHX_OK) return rc;
   const int d = e->P.d;
   RunDesc& R = e->R;
@@ -2153,16 +1892,8 @@ static int plain_steps(mhx_engine* e, int64_t n, const double* L, int per_chain_
                             "formed by the host shims from mhx_get_trace)");
   if (!e->chains_ready) return fail(MHX_ESTATE, "mhx_init_chains has not been called");
   if (n < 0) return fail(MHX_EINVAL, "n < 0");
-  int rc = use_device(e);
+  int rc = begin_run(e);
   if (rc != MHX_OK) return rc;
-  if ((rc = finalize_problem(e)) != MHX_OK) return rc;
-  drop_split_graph(e);
-  e->S.slot_chain = nullptr;
-  e->S.n_slots = e->cfg.n_chains;
-  e->slots_mapped = 0;
-  e->split_iter = 0;
-  e->ts_repack_due = false;
-  if ((rc = reset_tsplit(e)) != MHX_OK) return rc;
   const size_t C = (size_t)e->cfg.n_chains, dd = (size_t)e->P.d * e->P.d;
   if (per_chain_l) {
     HIP_TRY(hipMemcpy(e->L.p, L, C * dd * sizeof(double), hipMemcpyHostToDevice));
