@@ -207,9 +207,15 @@ int mhx_set_bounds(mhx_engine* e, int k, const int32_t* idx, const double* lo,
  * arithmetic expression over `x` (with a vector-valued x, mhx_set_dataset_cols: `xcol0`, `xcol1`), the
  * identifiers in param_names (local parameter j =
  * theta[param_index[j]]), numeric literals, + - * / ?: < <= > >= == != && || !, and the
- * functions exp log sqrt sin cos tan atan tanh abs pow min max.  It is compiled for gfx950
+ * functions exp log sqrt sin cos tan atan tanh abs pow min max floor, and ipow(u, n) (n an
+ * integer: SBCL's order of multiplications for (expt u n)).  It is compiled for gfx950
  * with hiprtc into the same fused kernels when the problem is finalised (first
- * mhx_init_chains / mhx_logpost), and evaluated without contraction.
+ * mhx_init_chains / mhx_logpost), and evaluated without contraction.  Accuracy: exp and log
+ * < 1 ulp (exp: inf above ln(DBL_MAX), 0 below the underflow, NaN for NaN and +-inf; log:
+ * finite on positive subnormals, NaN for x <= 0, +inf and NaN); sqrt abs floor min max exact; a
+ * quotient by a divisor that does not depend on x is a * (1/b), within 1.5 ulp - inf where 1/b
+ * overflows (|b| < 2^-1024), fewer bits where 1/b is subnormal (|b| > 2^1022) - unless
+ * MHX_EXPR_EXACT_DIV=1, which keeps IEEE divisions.
  * A body that IS one of the enumerated models - a polynomial background c0 + c1 x + ... plus
  * Gaussian peaks a * exp(-ipow((x - mu) / w, 2)) or Lorentzian peaks a / (1 + ipow((x - mu) / w,
  * 2)) over distinct parameters (pow(u, 2.0), u * u and -1 * S are understood; csrc/mhx_expr.cpp) -

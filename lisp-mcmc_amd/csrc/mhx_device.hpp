@@ -404,23 +404,25 @@ __device__ __forceinline__ double mexp2_negsq_safe(double t) {
   s = s < -1100.0 ? -1100.0 : s;
   return mexp2(s);
 }
-// log(x) for the Poisson term k*log(lambda) (M:383): the fdlibm recipe (x = 2^k (1+f),
-// s = f/(2+f), log(1+f) = f - (f^2/2 - s (f^2/2 + R(s^2)))) with the quotient formed from
-// v_rcp_f64 + two Newton steps instead of an IEEE division.  < 1 ulp on normal positive x.
-// x <= 0, subnormal, inf or NaN -> NaN: a rate outside (0, inf) is where the reference errors
-// (log of a negative number is complex, log 0 traps), and a NaN log-posterior freezes the chain.
+// log(x): the fdlibm recipe (x = 2^k (1+f), s = f/(2+f), log(1+f) = f - (f^2/2 - s (f^2/2 +
+// R(s^2)))) with the quotient formed from v_rcp_f64 + two Newton steps instead of an IEEE
+// division.  < 1 ulp on positive finite x, subnormals included: those are scaled by 2^54 first
+// and k lowered by 54, as fdlibm does - the reference's (log x) is libm's, finite there.
+// x <= 0, +inf or NaN -> NaN: an argument outside (0, inf) is where the reference errors (log of
+// a negative number is complex, log 0 traps), and a NaN log-posterior freezes the chain.
 // (out of line like dexp: it only serves the logs of user expressions within 1/16 of 1 and the
-// arguments that end in NaN)
+// arguments outside the normal range - tlog() sends them here, its hot path stays the table's)
 __device__ __attribute__((noinline)) double mlog(double x) {
   const double ln2_hi = 6.93147180369123816490e-01, ln2_lo = 1.90821492927058770002e-10,
                Lg1 = 6.666666666666735130e-01, Lg2 = 3.999999999940941908e-01,
                Lg3 = 2.857142874366239149e-01, Lg4 = 2.222219843214978396e-01,
                Lg5 = 1.818357216161805012e-01, Lg6 = 1.531383769920937332e-01,
                Lg7 = 1.479819860511658591e-01;
-  const unsigned long long b = (unsigned long long)__double_as_longlong(x);
+  const bool sub = x > 0.0 && x < 0x1p-1022;  // positive subnormal: exact scaling to a normal
+  const unsigned long long b = (unsigned long long)__double_as_longlong(sub ? x * 0x1p54 : x);
   const int hx0 = (int)(b >> 32);
   const unsigned int lx = (unsigned int)b;
-  int k = (hx0 >> 20) - 1023;
+  int k = (hx0 >> 20) - (sub ? 1023 + 54 : 1023);
   int hx = hx0 & 0x000fffff;
   const int i = (hx + 0x95f64) & 0x100000;
   hx |= (i ^ 0x3ff00000);
@@ -440,7 +442,8 @@ __device__ __attribute__((noinline)) double mlog(double x) {
   const double R = t2 + t1;
   const double hfsq = (0.5 * f) * f;
   const double r = __builtin_fma(dk, ln2_hi, -((hfsq - __builtin_fma(s, hfsq + R, dk * ln2_lo)) - f));
-  // valid iff 2^-1022 <= x < inf: one unsigned compare on the high word (sign bit fails it)
+  // valid iff 2^-1022 <= x < inf after the scaling: one unsigned compare on the high word (the
+  // sign bit fails it, and so do +0 and -0)
   const bool ok = (unsigned int)(hx0 - 0x00100000) < (unsigned int)(0x7ff00000 - 0x00100000);
   return ok ? r : __builtin_nan("");
 }
@@ -455,7 +458,8 @@ __device__ __attribute__((noinline)) double mlog(double x) {
 //                 k log(lambda) - lambda near lambda = 1 is of size 1: 2^-56 is nothing to it);
 //                 x <= 0, subnormal, inf or NaN -> NaN.  18 VALU instructions + one ds_read_b128.
 //   tlog(x)       (log x) of a user expression: within 1/16 of 1 through mlog() (< 1 ulp there
-//                 too), and so is everything mlog() answers with NaN.
+//                 too), and so is every argument that is not a positive normal number: positive
+//                 subnormals get mlog()'s finite log, x <= 0, +inf and NaN its NaN.
 // In instructions: the table is indexed by the mantissa bits of x itself (the LDS copy is rotated
 // by OFF's 48 entries: lds_tables_begin), -k comes out of one subtraction and one shift, z out of
 // one v_ldexp_f64 (the same bits as subtracting k from the exponent field, which took an and, a

@@ -192,8 +192,10 @@ static std::string generate(const std::vector<UserExpr>& models,
     << "; }\n";
   // Divisions by expressions that do not depend on x (1/w, 1/tau ...) are loop invariant; with
   // reciprocal math the compiler forms the reciprocal once per step instead of dividing per
-  // data point (<= 1 ulp per quotient, inside the stated tolerance).  MHX_EXPR_EXACT_DIV=1
-  // keeps IEEE divisions.
+  // data point.  a * RN(1/b) is within 1.5 ulp of RN(a/b), not 1 (inside the stated tolerance),
+  // and it is inf where 1/b overflows (|b| < 2^-1024) and loses bits where 1/b is subnormal
+  // (|b| > 2^1022) even when a/b is an ordinary number (tests/test_gpu_expr_math.py).
+  // MHX_EXPR_EXACT_DIV=1 keeps IEEE divisions.
   const bool recip = !(getenv("MHX_EXPR_EXACT_DIV") && atoi(getenv("MHX_EXPR_EXACT_DIV")) != 0);
   for (size_t m = 0; m < models.size(); ++m) {
     const UserExpr& u = models[m];

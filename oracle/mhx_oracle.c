@@ -553,6 +553,32 @@ static double mir_tlog(double x, int* plain) {
   return ordinary ? res : NAN;
 }
 
+/* The two table routines of user expressions (csrc/mhx_device.hpp, called through mhx_rtc.cpp's
+ * mhx_ux_exp / mhx_ux_log), exported for tests/test_gpu_expr_math.py: the device's values must
+ * equal these bit for bit.
+ * gexp: x log2 e = k + j/256 + r (low dword of kd = 256 k + j), 2^(j/256) from the exp2 table,
+ * 2^r - 1 by its cubic, the scale by ldexp; |x| > 1000 decided outright (inf / 0 / NaN). */
+double orc_mirror_gexp(double x) {
+  const double MAGIC = 0x1.8p44, L2E_HI = 0x1.71547652b82fep+0, L2E_LO = 0x1.777d0ffda0d24p-56;
+  const double q3 = 0x1.3b2ab83eadfb0p-7, q2 = 0x1.c6b0902b5a0abp-5, q1 = 0x1.ebfbdff82c585p-3,
+               q0 = 0x1.62e42fefa39d9p-1;
+  const double kd = fma(x, L2E_HI, MAGIC);
+  const double kf = kd - MAGIC;
+  const double r = fma(x, L2E_LO, fma(x, L2E_HI, -kf));
+  const int32_t lo = (int32_t)(uint32_t)to_bits(kd);
+  const double th = mir_exp2_tab[lo & 255][0], rho = mir_exp2_tab[lo & 255][1];
+  double a = fma(r, q3, q2);
+  a = fma(r, a, q1);
+  a = fma(r, a, q0);
+  const double ee = fma(r, a, rho);
+  double v = ldexp(fma(th, ee, th), (int)(lo >> 8));
+  if (!(fabs(x) <= 1000.0)) v = fabs(x) < INFINITY ? (x > 0.0 ? INFINITY : 0.0) : NAN;
+  return v;
+}
+/* tlog's table branch (= tlog_rate): what the device answers for every positive normal x
+ * outside [0.9375, 1.0625); NaN for everything that is not a positive normal number */
+double orc_mirror_tlog(double x) { return mir_tlog(x, NULL); }
+
 /* csrc/mhx_engine.cpp, mhx_set_dataset: x is a uniform grid x_0 + i h to 8 ulp of max |x| ->
  * 64 h (the step between two successive points of one lane), else 0 */
 static int mir_no_recurrence = 0; /* orc_mirror_set_recurrence(0): MHX_NO_RECURRENCE=1's twin */

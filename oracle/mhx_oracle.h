@@ -88,6 +88,10 @@ void orc_mirror_set_recurrence(int on);
  * datasets whose x are ONE grid; default 1: window by window, csrc/mhx_engine.cpp) */
 void orc_mirror_set_window_grids(int on);
 double orc_logpost_mirror(const orc_problem* p, const double* theta, double* parts);
+/* MIRROR of the exp / log of user expressions (csrc/mhx_device.hpp gexp, and tlog's table branch:
+ * positive normals outside [0.9375, 1.0625), NaN for what is not a positive normal number) */
+double orc_mirror_gexp(double x);
+double orc_mirror_tlog(double x);
 /* sum_i |term_i| over all likelihood points: the scale of the stated tolerance */
 double orc_logpost_abs_terms(const orc_problem* p, const double* theta);
 

@@ -73,6 +73,8 @@ def lib():
         "orc_walker_create2": (vp, [vp, f64p, i]),
         "orc_logpost_mirror": (d, [vp, f64p, f64p]),
         "orc_mirror_set_recurrence": (None, [i]),
+        "orc_mirror_gexp": (d, [d]),
+        "orc_mirror_tlog": (d, [d]),
         "orc_mirror_set_window_grids": (None, [i]),
         "orc_walker_destroy": (None, [vp]),
         "orc_walker_take_step_injected": (i, [vp, f64p, f64p, d, d]),
@@ -307,3 +309,18 @@ def philox(ctr, key):
     o = (C.c_uint32 * 4)()
     lib().orc_philox4x32_10(c, k, o)
     return list(o)
+
+
+def mirror_gexp(x):
+    """the exp of user expressions (csrc/mhx_device.hpp gexp) restated, elementwise"""
+    f = lib().orc_mirror_gexp
+    x = np.asarray(x, dtype=np.float64)
+    return np.array([f(v) for v in x.ravel().tolist()]).reshape(x.shape)
+
+
+def mirror_tlog(x):
+    """tlog's table branch restated, elementwise (positive normals outside [0.9375, 1.0625) are
+    the device's own values; NaN for what is not a positive normal number)"""
+    f = lib().orc_mirror_tlog
+    x = np.asarray(x, dtype=np.float64)
+    return np.array([f(v) for v in x.ravel().tolist()]).reshape(x.shape)

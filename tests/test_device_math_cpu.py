@@ -1,12 +1,14 @@
 """CPU checks of device math that has no oracle twin: the table-driven logarithm of the Poisson
 sweep (tlog, csrc/mhx_device.hpp).  The table is parsed out of the header, its two defining
 properties are verified with mpmath, and a C restatement of the algorithm (same operations, C99
-fma) is measured against the 80-bit logl."""
+fma) is measured against the 80-bit logl.  mlog (v_rcp_f64, hardware only) and the compiled
+routines themselves are measured on the device: tests/test_gpu_expr_math.py."""
 import os
 import re
 import subprocess
 import tempfile
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -245,3 +247,39 @@ def test_table_exp2_stays_near_half_an_ulp():
     worst, ok = subprocess.check_output([exe]).decode().split()
     # 0.5 ulp from the final fma's rounding + the cubic's 0.04 + the roundings inside e
     assert float(worst) < 0.56 and ok == "1", (worst, ok)
+
+
+# ---- the oracle's exports of the expression exp / log (tests/test_gpu_expr_math.py's mirrors) ----
+
+
+def test_oracle_mirror_gexp_below_one_ulp(orc):
+    """orc_mirror_gexp (the device's gexp restated, which the GPU test holds the device to bit for
+    bit): < 1 ulp of the 80-bit expl on a sample, the documented values beyond |x| = 1000"""
+    rng = np.random.default_rng(5)
+    x = np.concatenate([rng.uniform(-r, r, 30000) for r in (1.0, 30.0, 708.0)])
+    got = orc.mirror_gexp(x)
+    ref = np.exp(x.astype(np.longdouble))
+    _, e = np.frexp(ref)
+    u = np.abs(got.astype(np.longdouble) - ref) / np.ldexp(np.longdouble(1), e - 53)
+    assert float(u.max()) < 1.0, float(u.max())
+    # (the same code as GEXP_SRC's restatement above)
+    edge = orc.mirror_gexp(np.array([0.0, 710.0, -746.0, 1e300, -1e300, 1000.5, -1000.5]))
+    assert edge.tolist() == [1.0, np.inf, 0.0, np.inf, 0.0, np.inf, 0.0]
+    assert np.all(np.isnan(orc.mirror_gexp(np.array([np.nan, np.inf, -np.inf]))))
+
+
+def test_oracle_mirror_tlog_table_branch(orc):
+    """orc_mirror_tlog: < 0.75 ulp on positive normals outside [0.9375, 1.0625); NaN for what is
+    not a positive normal number"""
+    rng = np.random.default_rng(6)
+    bits = (rng.integers(1, 2047, 60000).astype(np.uint64) << np.uint64(52)) | \
+        rng.integers(0, 1 << 52, 60000, dtype=np.uint64)
+    x = bits.view(np.float64)
+    x = x[(x < 0.9375) | (x >= 1.0625)]
+    got = orc.mirror_tlog(x)
+    ref = np.log(x.astype(np.longdouble))
+    _, e = np.frexp(np.abs(ref))
+    u = np.abs(got.astype(np.longdouble) - ref) / np.ldexp(np.longdouble(1), e - 53)
+    assert float(u.max()) < 0.75, float(u.max())
+    bad = orc.mirror_tlog(np.array([0.0, -1.0, 2.0 ** -1074, np.inf, -np.inf, np.nan]))
+    assert np.all(np.isnan(bad))
