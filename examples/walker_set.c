@@ -108,6 +108,25 @@ int main(int argc, char** argv) {
     ok = ok && fabs(mean[j] / star[j] - 1.0) < 0.05;
   }
   for (long c = 0; c < chains; ++c) ok = ok && isfinite(best_lp[c]) && age[c] > 2000;
+  /* (walker-set-get walkers :get :median-params :take 1024) and the 2.5 / 97.5 percentiles
+   * (`95cr`, mcmc-fitting.lisp:1508) of every walker in ONE launch per device: no history
+   * crosses to the host */
+  enum { NP = 3, SHOW = 3, TAKE = 1024 };
+  static const char* names[D] = {"b0", "b1", "a1", "mu1", "w1", "a2", "mu2", "w2"};
+  const int32_t num[NP] = {50, 5, 195}, den[NP] = {1, 2, 2};
+  double* pct = malloc(sizeof(double) * (size_t)chains * NP * D);
+  int32_t* used = malloc(sizeof(int32_t) * (size_t)chains);
+  TRY(mhx_group_get_percentiles(g, TAKE, num, den, NP, pct, used));
+  printf("median and 95cr of the newest %d steps of the first walkers:\n", (int)TAKE);
+  for (long c = 0; c < chains && c < SHOW; ++c)
+    for (int j = 0; j < D; ++j) {
+      const double* p = pct + (size_t)c * NP * D;
+      printf("  walker %ld %s median %.6f 95cr [%.6f, %.6f] over %d steps\n", c, names[j],
+             p[0 * D + j], p[1 * D + j], p[2 * D + j], (int)used[c]);
+      ok = ok && p[1 * D + j] <= p[0 * D + j] && p[0 * D + j] <= p[2 * D + j];
+    }
+  free(pct);
+  free(used);
   mhx_group_destroy(g);
   free(th0);
   free(best);

@@ -20,6 +20,10 @@
  *   walker-many-steps          M:849-853     -> mhx_many_steps
  *   walker-get                 M:487-543     -> mhx_get_state / _acceptance / _lmatrix /
  *                                               _trace / _proposal_factor
+ *   walker-set-get             M:1029-1030   -> mhx_get_percentiles / _covariances /
+ *                                               _proposal_factors / _window_best (every
+ *                                               chain in one launch), mhx_group_get_*
+ *   nth-percentile             M:1495-1506   -> mhx_percentile_rank (the position rule)
  *   walker-modify              M:547-580     -> mhx_walker_modify (+ mhx_set_history)
  *   create-log-liklihood-function M:402-416  -> mhx_set_likelihood_expr
  *   prior-bounds-let           M:346-369     -> mhx_set_bounds (+ mhx_set_prior_expr)
@@ -61,6 +65,7 @@ extern "C" {
 #define MHX_MAX_FUNCTIONS 16 /* K: functions / datasets of one (global) fit         */
 #define MHX_MAX_FN_PARAMS 32 /* parameters one function gathers from the vector      */
 #define MHX_MAX_BOUNDS 64    /* bounds in one prior-bounds-let block                */
+#define MHX_MAX_PERCENTILES 16 /* percentiles one mhx_get_percentiles call may ask for */
 
 /* ---- status codes ------------------------------------------------------ */
 enum {
@@ -371,6 +376,67 @@ int mhx_get_trace(mhx_engine* e, int64_t chain, int take, double* prob, double* 
  * M:891-894), 2 uncaught invalid-operation.  n_forward = (length :forward-steps). */
 int mhx_get_proposal_factor(mhx_engine* e, int64_t chain, int take, double* L_out,
                             int* status, int* n_forward);
+
+/* ---- walker-set-get (M:1029-1030): summaries of EVERY chain in one launch ----
+ * What (mapcar (lambda (w) (walker-get w :get ... :take take)) walkers) computes, on the
+ * device ring, without moving any history to the host.  n_chains = the engine's chains; take in
+ * [1, history_capacity] as for mhx_get_proposal_factor; every chain's window is its newest
+ * min(take, walker-length, steps the ring holds) steps; any output pointer may be NULL;
+ * MHX_ESTATE before mhx_init_chains.  The chains are worked through in portions whose device
+ * scratch stays below 64 MiB whatever n_chains and take are.  A chain in MHX_CHAIN_FP_TRAP is
+ * summarised from the history it has. */
+
+/* The position rule of nth-percentile (M:1495-1506) for the n = num/den per cent point of len
+ * sorted values: q = num (len-1) / (100 den) as an exact rational, *pos = floor(q), *between =
+ * 1 when q has a fractional part (the percentile is then the mean of elements pos and pos+1).
+ * For integer n (the median's 50) this is the reference's own arithmetic; for 2.5 / 84.1 / 97.5
+ * the reference multiplies single-floats, and the rational reading is this project's
+ * definition.  Host only: needs no engine and no device.  MHX_EINVAL unless len >= 1,
+ * den >= 1, 0 <= num <= 100 den. */
+int mhx_percentile_rank(int64_t len, int32_t num, int32_t den, int64_t* pos, int32_t* between);
+/* out[n_chains][n_pct][d]: for percentile q = pct_num[q]/pct_den[q] per cent and parameter p the
+ * value nth-percentile gives on parameter p's column of the chain's window: the element at pos
+ * of the ascending sort, or (e[pos] + e[pos+1]) / 2 (IEEE) when between.  :median-params is
+ * 50/1, `95cr` 5/2 and 195/2, `iqr` 25/1 and 75/1, `standard-deviation-normal` 841/10.  Exact
+ * for any take (selection on the device; no sort, no window size limit).  -0 sorts before +0
+ * (they compare equal: either may be returned); a NaN sorts last, whatever its sign.
+ * n_used[n_chains]: steps the window held (< min(take, walker-length): the ring had wrapped).
+ * 0 <= n_pct <= MHX_MAX_PERCENTILES; n_pct = 0 writes nothing. */
+int mhx_get_percentiles(mhx_engine* e, int take, const int32_t* pct_num, const int32_t* pct_den,
+                        int n_pct, double* out, int32_t* n_used);
+/* (walker-get w :get :covariance-matrix :take take) M:541 = lplist-covariance (M:614-643) of
+ * :unique-steps (M:492-496): cov[n_chains][d][d].  Unique steps: those whose prob differs IN
+ * BITS from the next older step's, the oldest of the window always kept (n_unique[n_chains]).
+ * Averages (/ (reduce #'+ x) n), then every entry the serial sum over the unique steps, newest
+ * first, of (x_i - avg_i)(x_j - avg_j) / n, the division inside the sum, no fused multiply-add.
+ * status[n_chains]: 0 ok, 1 an average or an entry is not finite (a trapped overflow in the
+ * reference). */
+int mhx_get_covariances(mhx_engine* e, int take, double* cov, int32_t* n_unique, int32_t* status);
+/* mhx_get_proposal_factor for every chain (:l-matrix M:543; :stddev-params M:525-539 is its
+ * diagonal): L[n_chains][d][d], status[n_chains] (0 ok, 1 caught, 2 invalid operation, 3 a
+ * single forward step: the reference's empty matrix), n_forward[n_chains] - the same device
+ * code, the same bits. */
+int mhx_get_proposal_factors(mhx_engine* e, int take, double* L, int32_t* status,
+                             int32_t* n_forward);
+/* (walker-get w :get :most-likely-step :take take) M:503-505: the step of greatest prob in the
+ * window, among equal greatest probs the OLDEST (the reduce keeps the older unless the newer
+ * is strictly greater): prob[n_chains], theta[n_chains][d]. */
+int mhx_get_window_best(mhx_engine* e, int take, double* prob, double* theta);
+/* Steps the device history ring of every chain holds: the greatest `take` (the power of two
+ * not below mhx_config.history_capacity and the adaptation window). */
+int mhx_get_history_capacity(mhx_engine* e, int32_t* capacity);
+/* HIP-event milliseconds the kernels of the engine's last mhx_get_percentiles / _covariances /
+ * _proposal_factors / _window_best call ran (all portions; copies excluded). */
+int mhx_get_summary_timing(mhx_engine* e, double* kernel_ms);
+/* The same for a group, gathered in global chain order like mhx_group_get_state; every
+ * device's launch is enqueued before any is waited for. */
+int mhx_group_get_percentiles(mhx_group* g, int take, const int32_t* pct_num,
+                              const int32_t* pct_den, int n_pct, double* out, int32_t* n_used);
+int mhx_group_get_covariances(mhx_group* g, int take, double* cov, int32_t* n_unique,
+                              int32_t* status);
+int mhx_group_get_proposal_factors(mhx_group* g, int take, double* L, int32_t* status,
+                                   int32_t* n_forward);
+int mhx_group_get_window_best(mhx_group* g, int take, double* prob, double* theta);
 
 /* Restore a saved walk (walker-load, sketched in the comments M:987-1001): prob[n], theta[n][d]
  * NEWEST FIRST, as walker-save would have written them.  Sets the ring (newest

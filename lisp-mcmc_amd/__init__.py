@@ -20,11 +20,11 @@ from .ingest import read_file_to_data, create_walker_data  # noqa: F401
 from .saveload import walker_save, walker_load  # noqa: F401
 from .walker import (  # noqa: F401
     Walker, WalkerStep, walker_create, mcmc_fit, walker_adaptive_steps,
-    walker_adaptive_steps_full, walker_many_steps, walker_take_step, walker_get,
+    walker_adaptive_steps_full, walker_many_steps, walker_take_step, walker_get, walker_set_get,
     walker_modify, prior_bounds, log_prior_flat, request_stop, create_log_liklihood_function,
 )
 
 __all__ = ["capi", "MhxError", "Engine", "Group", "comm_unique_id", "partition", "models", "Walker", "WalkerStep", "walker_create",
            "mcmc_fit", "walker_adaptive_steps", "walker_adaptive_steps_full",
-           "walker_many_steps", "walker_take_step", "walker_get", "walker_modify",
+           "walker_many_steps", "walker_take_step", "walker_get", "walker_set_get", "walker_modify",
            "prior_bounds", "log_prior_flat", "request_stop", "create_log_liklihood_function"]

@@ -114,6 +114,17 @@ SIGNATURES = {
     "mhx_group_request_stop": (C.c_int, [C.c_void_p]),
     "mhx_group_get_state": (C.c_int, [C.c_void_p, f64p, f64p, f64p, f64p, i64p, i64p]),
     "mhx_group_get_counters": (C.c_int, [C.c_void_p, u64p, u64p]),
+    "mhx_percentile_rank": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, i64p, i32p]),
+    "mhx_get_percentiles": (C.c_int, [C.c_void_p, C.c_int, i32p, i32p, C.c_int, f64p, i32p]),
+    "mhx_get_covariances": (C.c_int, [C.c_void_p, C.c_int, f64p, i32p, i32p]),
+    "mhx_get_proposal_factors": (C.c_int, [C.c_void_p, C.c_int, f64p, i32p, i32p]),
+    "mhx_get_window_best": (C.c_int, [C.c_void_p, C.c_int, f64p, f64p]),
+    "mhx_get_history_capacity": (C.c_int, [C.c_void_p, i32p]),
+    "mhx_get_summary_timing": (C.c_int, [C.c_void_p, f64p]),
+    "mhx_group_get_percentiles": (C.c_int, [C.c_void_p, C.c_int, i32p, i32p, C.c_int, f64p, i32p]),
+    "mhx_group_get_covariances": (C.c_int, [C.c_void_p, C.c_int, f64p, i32p, i32p]),
+    "mhx_group_get_proposal_factors": (C.c_int, [C.c_void_p, C.c_int, f64p, i32p, i32p]),
+    "mhx_group_get_window_best": (C.c_int, [C.c_void_p, C.c_int, f64p, f64p]),
 }
 
 _lib = None

@@ -300,6 +300,7 @@ struct mhx_engine {
   uint64_t launches = 0;
   double kernel_ms = 0.0;
   uint64_t timed_launches = 0;
+  double summary_ms = 0.0;  // kernels of the last batched summary call (mhx_get_summary_timing)
 };
 
 namespace {
@@ -1337,7 +1338,8 @@ int mhx_create(const mhx_config* cfg, mhx_engine** out) {
       rc = fail(MHX_EDEVICE, "stream/event creation failed");
       break;
     }
-    if (family_w8().configure() != hipSuccess || family_w16().configure() != hipSuccess) {
+    if (family_w8().configure() != hipSuccess || family_w16().configure() != hipSuccess ||
+        summary_configure() != hipSuccess) {
       rc = fail(MHX_EDEVICE, "hipFuncSetAttribute(max dynamic LDS = %zu / %zu) failed",
                 family_w8().lds_bytes, family_w16().lds_bytes);
       break;
@@ -2109,6 +2111,218 @@ int mhx_get_proposal_factor(mhx_engine* e, int64_t chain, int take, double* L_ou
   return MHX_OK;
 }
 
+// ---- walker-set-get: every chain's summary in one launch (k_percentiles, k_covariances,
+// k_l_matrices, k_window_best).  The chains are worked through in portions: results and scratch
+// (an index list of `take` ints and up to two d x d matrices per chain) live in the engine's
+// stage buffer, at most kSummaryStageBytes of it whatever n_chains x take is.
+static constexpr size_t kSummaryStageBytes = (size_t)64 << 20;
+enum { SUM_PERCENTILES = 0, SUM_COVARIANCES = 1, SUM_FACTORS = 2, SUM_BEST = 3 };
+struct SummaryCall {
+  int kind = 0, take = 0;
+  PctList pc{};
+  // host destinations of the engine's chain 0 (any may be NULL), in the order of the pieces below
+  double* hd[2] = {nullptr, nullptr};
+  int32_t* hi[2] = {nullptr, nullptr};
+};
+// a portion's pieces in the stage buffer: two double arrays [n][nd], two int arrays [n], the
+// index scratch [n][take]; copied[] says which of the double pieces is a result
+struct SummaryLayout {
+  size_t nd[2] = {0, 0};
+  bool copied[2] = {false, false};
+  int ni = 0;
+  bool scratch = false;
+  size_t per_chain = 0;
+};
+static SummaryLayout summary_layout(const mhx_engine* e, const SummaryCall& q) {
+  const size_t d = (size_t)e->P.d, dd = d * d;
+  SummaryLayout y;
+  switch (q.kind) {
+    case SUM_PERCENTILES: y.nd[0] = (size_t)q.pc.n * d; y.copied[0] = true; y.ni = 1; break;
+    case SUM_COVARIANCES: y.nd[0] = dd; y.copied[0] = true; y.ni = 2; y.scratch = true; break;
+    case SUM_FACTORS: y.nd[0] = dd; y.copied[0] = true; y.nd[1] = dd; y.ni = 2; y.scratch = true; break;
+    default: y.nd[0] = 1; y.nd[1] = d; y.copied[0] = y.copied[1] = true; break;
+  }
+  y.per_chain = (y.nd[0] + y.nd[1]) * sizeof(double) + (size_t)y.ni * sizeof(int32_t) +
+                (y.scratch ? (size_t)q.take * sizeof(int32_t) : 0);
+  return y;
+}
+struct SummaryPieces {
+  double* dv[2];
+  int32_t* iv[2];
+  int32_t* scratch;
+  size_t bytes;
+};
+static SummaryPieces summary_pieces(mhx_engine* e, const SummaryLayout& y, const SummaryCall& q,
+                                    int64_t n) {
+  SummaryPieces s{};
+  size_t o = 0;
+  for (int k = 0; k < 2; ++k) {
+    s.dv[k] = reinterpret_cast<double*>(e->stage.p + o);
+    o += align256((size_t)n * y.nd[k] * sizeof(double));
+  }
+  for (int k = 0; k < 2; ++k) {
+    s.iv[k] = reinterpret_cast<int32_t*>(e->stage.p + o);
+    o += align256((size_t)n * sizeof(int32_t));
+  }
+  s.scratch = reinterpret_cast<int32_t*>(e->stage.p + o);
+  o += align256(y.scratch ? (size_t)n * q.take * sizeof(int32_t) : 0);
+  s.bytes = o;
+  return s;
+}
+static int64_t summary_portion(const SummaryLayout& y) {
+  return std::max<int64_t>(1, (int64_t)((kSummaryStageBytes - 5 * 256) / y.per_chain));
+}
+static int summary_check(mhx_engine* e, const SummaryCall& q) {
+  if (!e) return fail(MHX_EINVAL, "engine is NULL");
+  if (!e->chains_ready) return fail(MHX_ESTATE, "mhx_init_chains has not been called");
+  if (q.take < 1 || q.take > e->S.R)
+    return fail(MHX_EINVAL, "take must be in [1, history_capacity = %d]", e->S.R);
+  return MHX_OK;
+}
+static int summary_fill_pcts(SummaryCall* q, const int32_t* num, const int32_t* den, int n_pct) {
+  if (n_pct < 0 || n_pct > MHX_MAX_PERCENTILES)
+    return fail(MHX_EINVAL, "n_pct must be in [0,%d]", MHX_MAX_PERCENTILES);
+  if (n_pct > 0 && (!num || !den)) return fail(MHX_EINVAL, "NULL percentile list");
+  q->pc.n = n_pct;
+  for (int k = 0; k < n_pct; ++k) {
+    if (den[k] < 1 || num[k] < 0 || (int64_t)num[k] > (int64_t)100 * den[k])
+      return fail(MHX_EINVAL, "percentile %d: %d/%d is outside [0, 100]", k, num[k], den[k]);
+    q->pc.num[k] = num[k];
+    q->pc.den[k] = den[k];
+  }
+  return MHX_OK;
+}
+// the launch of the n chains from c0 on, into the stage buffer (nothing is waited for)
+static int summary_enqueue(mhx_engine* e, const SummaryCall& q, int64_t c0, int64_t n) {
+  int rc = use_device(e);
+  if (rc != MHX_OK) return rc;
+  const SummaryLayout y = summary_layout(e, q);
+  if ((rc = ensure_stage(e, summary_pieces(e, y, q, n).bytes)) != MHX_OK) return rc;
+  const SummaryPieces s = summary_pieces(e, y, q, n);
+  // (the factor kernel leaves what it does not reach untouched, as k_l_matrix does: zeros)
+  HIP_TRY(hipMemsetAsync(e->stage.p, 0, s.bytes, e->stream));
+  HIP_TRY(hipEventRecord(e->ev0, e->stream));
+  switch (q.kind) {
+    case SUM_PERCENTILES: {
+      const bool lds = !e->knobs.summary_no_lds && pct_lds_bytes(q.take, e->P.d) <= kPctLdsBudget;
+      HIP_TRY(launch_percentiles(e->stream, e->S, c0, n, q.take, q.pc, lds, s.dv[0], s.iv[0]));
+      break;
+    }
+    case SUM_COVARIANCES:
+      HIP_TRY(launch_covariances(e->stream, e->S, c0, n, q.take, s.scratch, s.dv[0], s.iv[0], s.iv[1]));
+      break;
+    case SUM_FACTORS:
+      HIP_TRY(launch_l_matrices(e->stream, e->S, c0, n, q.take, s.scratch, s.dv[1], s.dv[0], s.iv[0],
+                                s.iv[1]));
+      break;
+    default:
+      HIP_TRY(launch_window_best(e->stream, e->S, c0, n, q.take, s.dv[0], s.dv[1]));
+      break;
+  }
+  HIP_TRY(hipEventRecord(e->ev1, e->stream));
+  return MHX_OK;
+}
+// ... and its results, to the caller's arrays (of this engine's chains) at chain c0
+static int summary_collect(mhx_engine* e, const SummaryCall& q, int64_t c0, int64_t n) {
+  int rc = use_device(e);
+  if (rc != MHX_OK) return rc;
+  const SummaryLayout y = summary_layout(e, q);
+  const SummaryPieces s = summary_pieces(e, y, q, n);
+  HIP_TRY(hipEventSynchronize(e->ev1));
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
+  e->summary_ms += (double)ms;
+  for (int k = 0; k < 2; ++k)
+    if (y.copied[k] && q.hd[k] && y.nd[k] > 0)
+      HIP_TRY(hipMemcpy(q.hd[k] + (size_t)c0 * y.nd[k], s.dv[k],
+                        (size_t)n * y.nd[k] * sizeof(double), hipMemcpyDeviceToHost));
+  for (int k = 0; k < y.ni; ++k)
+    if (q.hi[k])
+      HIP_TRY(hipMemcpy(q.hi[k] + c0, s.iv[k], (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return MHX_OK;
+}
+// calls[i] on engs[i]: round by round, every engine's portion enqueued before any is waited for
+static int summary_run(const std::vector<mhx_engine*>& engs, const std::vector<SummaryCall>& calls) {
+  int rc = MHX_OK;
+  for (size_t i = 0; i < engs.size(); ++i)
+    if ((rc = summary_check(engs[i], calls[i])) != MHX_OK) return rc;
+  std::vector<int64_t> at(engs.size(), 0), now(engs.size(), 0);
+  for (mhx_engine* e : engs) e->summary_ms = 0.0;
+  for (;;) {
+    bool any = false;
+    for (size_t i = 0; i < engs.size(); ++i) {
+      const int64_t left = engs[i]->cfg.n_chains - at[i];
+      now[i] = std::min<int64_t>(left, summary_portion(summary_layout(engs[i], calls[i])));
+      if (now[i] <= 0) continue;
+      any = true;
+      if ((rc = summary_enqueue(engs[i], calls[i], at[i], now[i])) != MHX_OK) {
+        for (mhx_engine* e : engs) drain(e);
+        return rc;
+      }
+    }
+    if (!any) return MHX_OK;
+    for (size_t i = 0; i < engs.size(); ++i) {
+      if (now[i] <= 0) continue;
+      if ((rc = summary_collect(engs[i], calls[i], at[i], now[i])) != MHX_OK) {
+        for (mhx_engine* e : engs) drain(e);
+        return rc;
+      }
+      at[i] += now[i];
+    }
+  }
+}
+static SummaryCall summary_call(int kind, int take, double* d0, double* d1, int32_t* i0, int32_t* i1) {
+  SummaryCall q;
+  q.kind = kind;
+  q.take = take;
+  q.hd[0] = d0;
+  q.hd[1] = d1;
+  q.hi[0] = i0;
+  q.hi[1] = i1;
+  return q;
+}
+
+int mhx_percentile_rank(int64_t len, int32_t num, int32_t den, int64_t* pos, int32_t* between) {
+  if (len < 1) return fail(MHX_EINVAL, "len must be >= 1");
+  if (den < 1 || num < 0 || (int64_t)num > (int64_t)100 * den)
+    return fail(MHX_EINVAL, "the percentile %d/%d is outside [0, 100]", num, den);
+  int64_t p = 0;
+  int32_t b = 0;
+  percentile_rank_of(len, num, den, &p, &b);
+  if (pos) *pos = p;
+  if (between) *between = b;
+  return MHX_OK;
+}
+
+int mhx_get_percentiles(mhx_engine* e, int take, const int32_t* pct_num, const int32_t* pct_den,
+                        int n_pct, double* out, int32_t* n_used) {
+  SummaryCall q = summary_call(SUM_PERCENTILES, take, out, nullptr, n_used, nullptr);
+  int rc = summary_check(e, q);
+  if (rc != MHX_OK || (rc = summary_fill_pcts(&q, pct_num, pct_den, n_pct)) != MHX_OK) return rc;
+  if (n_pct == 0) return MHX_OK;
+  return summary_run({e}, {q});
+}
+int mhx_get_covariances(mhx_engine* e, int take, double* cov, int32_t* n_unique, int32_t* status) {
+  return summary_run({e}, {summary_call(SUM_COVARIANCES, take, cov, nullptr, n_unique, status)});
+}
+int mhx_get_proposal_factors(mhx_engine* e, int take, double* L, int32_t* status,
+                             int32_t* n_forward) {
+  return summary_run({e}, {summary_call(SUM_FACTORS, take, L, nullptr, status, n_forward)});
+}
+int mhx_get_window_best(mhx_engine* e, int take, double* prob, double* theta) {
+  return summary_run({e}, {summary_call(SUM_BEST, take, prob, theta, nullptr, nullptr)});
+}
+int mhx_get_history_capacity(mhx_engine* e, int32_t* capacity) {
+  if (!e) return fail(MHX_EINVAL, "engine is NULL");
+  if (capacity) *capacity = e->S.R;
+  return MHX_OK;
+}
+int mhx_get_summary_timing(mhx_engine* e, double* kernel_ms) {
+  if (!e) return fail(MHX_EINVAL, "engine is NULL");
+  if (kernel_ms) *kernel_ms = e->summary_ms;
+  return MHX_OK;
+}
+
 int mhx_set_history(mhx_engine* e, int64_t chain, const double* prob, const double* theta, int n) {
   if (!e || !prob || !theta) return fail(MHX_EINVAL, "NULL argument");
   if (!e->chains_ready) return fail(MHX_ESTATE, "mhx_init_chains has not been called");
@@ -2597,6 +2811,45 @@ int mhx_group_get_counters(mhx_group* g, uint64_t* chain_steps, uint64_t* kernel
   if (chain_steps) *chain_steps = cs;
   if (kernel_launches) *kernel_launches = kl;
   return MHX_OK;
+}
+
+// walker-set-get over a group: engine i's results land at its first global chain
+static int group_summary(mhx_group* g, SummaryCall q) {
+  if (!g) return fail(MHX_EINVAL, "group is NULL");
+  std::vector<SummaryCall> calls;
+  for (size_t i = 0; i < g->eng.size(); ++i) {
+    const SummaryLayout y = summary_layout(g->eng[i], q);
+    SummaryCall c = q;
+    const size_t f = (size_t)g->first[i];
+    for (int k = 0; k < 2; ++k) {
+      if (c.hd[k]) c.hd[k] += f * y.nd[k];
+      if (c.hi[k]) c.hi[k] += f;
+    }
+    calls.push_back(c);
+  }
+  return summary_run(g->eng, calls);
+}
+int mhx_group_get_percentiles(mhx_group* g, int take, const int32_t* pct_num,
+                              const int32_t* pct_den, int n_pct, double* out, int32_t* n_used) {
+  if (!g) return fail(MHX_EINVAL, "group is NULL");
+  SummaryCall q = summary_call(SUM_PERCENTILES, take, out, nullptr, n_used, nullptr);
+  int rc = MHX_OK;
+  for (mhx_engine* e : g->eng)
+    if ((rc = summary_check(e, q)) != MHX_OK) return rc;
+  if ((rc = summary_fill_pcts(&q, pct_num, pct_den, n_pct)) != MHX_OK) return rc;
+  if (n_pct == 0) return MHX_OK;
+  return group_summary(g, q);
+}
+int mhx_group_get_covariances(mhx_group* g, int take, double* cov, int32_t* n_unique,
+                              int32_t* status) {
+  return group_summary(g, summary_call(SUM_COVARIANCES, take, cov, nullptr, n_unique, status));
+}
+int mhx_group_get_proposal_factors(mhx_group* g, int take, double* L, int32_t* status,
+                                   int32_t* n_forward) {
+  return group_summary(g, summary_call(SUM_FACTORS, take, L, nullptr, status, n_forward));
+}
+int mhx_group_get_window_best(mhx_group* g, int take, double* prob, double* theta) {
+  return group_summary(g, summary_call(SUM_BEST, take, prob, theta, nullptr, nullptr));
 }
 
 }  // extern "C"

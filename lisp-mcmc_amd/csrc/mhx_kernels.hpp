@@ -2827,6 +2827,272 @@ __global__ __launch_bounds__(kThreads) void k_acceptance(ChainState S, int take,
   if (l == 0) out[c] = (double)num / (double)den;
 }
 
+// ------------------------------------------------------------------------------------------
+// walker-set-get (M:1029-1030): the summarising selectors of walker-get for EVERY chain in one
+// launch, on the device ring.  No model Spec is involved: compiled once (the primary family's
+// unit), never through hiprtc.  Each launch covers the `n` chains from `c0` on (the host works
+// through the chains in portions so that the scratch stays bounded); outputs and scratch are
+// indexed by the chain's place in the portion.
+// ------------------------------------------------------------------------------------------
+#if defined(MHX_FAMILY_PRIMARY) && !defined(__HIPCC_RTC__)
+__device__ __forceinline__ Ring ring_of(const ChainState& S, int64_t c) {
+  Ring r;
+  r.prob = S.hist_prob + c * S.R;
+  r.theta = S.hist_theta + c * S.R * S.d;
+  r.mask = S.R - 1;
+  r.d = S.d;
+  r.nh = uniform_i64(S.n_hist[c]);
+  r.length = uniform_i64(S.length[c]);
+  return r;
+}
+// steps a window of `take` (<= R) holds: what mhx_get_trace would deliver
+__device__ __forceinline__ int ring_held(const Ring& r, int take) {
+  int64_t t = r.length < r.nh ? r.length : r.nh;
+  if (t > (int64_t)take) t = take;
+  return (int)(t < 0 ? 0 : t);
+}
+
+// order-preserving 64-bit key of a double: all bits of a negative flipped, the sign bit of the
+// others set.  -0 < +0 as keys (they compare equal as numbers: either may stand for the other);
+// every NaN gets the greatest key, so it sorts last whatever its sign.
+__device__ __forceinline__ unsigned long long order_key(double v) {
+  const unsigned long long b = bits_of(v);
+  if (v != v) return ~0ULL;
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ULL);
+}
+__device__ __forceinline__ double key_value(unsigned long long k) {
+  const unsigned long long b = (k >> 63) ? (k ^ 0x8000000000000000ULL) : ~k;
+  return __longlong_as_double((long long)b);
+}
+__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    const unsigned long long o = (unsigned long long)__shfl_xor((long long)v, m, 64);
+    v = o < v ? o : v;
+  }
+  return v;
+}
+
+// nth-percentile (M:1495-1506) of the n keys key_at(0 .. n-1) by one wavefront: the key of rank
+// `pos` of the ascending order by most-significant-bit-first radix selection (one bit a pass:
+// count the still-candidate keys whose bit is 0; the rank falls among them or among the others),
+// 64 passes whatever n is, nothing sorted, nothing stored.  `between`: the mean with the next
+// element - the same key when the rank is not the last of its run of equal keys, else the
+// smallest key above it (one masked min-reduction).  All lanes return the same value.
+template <class KeyAt>
+__device__ __forceinline__ double select_percentile(KeyAt key_at, int n, int pos, bool between) {
+  const int l = lane_id();
+  unsigned long long prefix = 0, mask = 0;
+  int k = pos, cand = n;
+  for (int b = 63; b >= 0; --b) {
+    const unsigned long long bit = 1ULL << b;
+    int cnt = 0;
+    for (int s = l; s < n; s += kWave) {
+      const unsigned long long key = key_at(s);
+      cnt += ((key & mask) == prefix && (key & bit) == 0) ? 1 : 0;
+    }
+    const int c0 = __builtin_amdgcn_readfirstlane(wave_sum_i(cnt));
+    if (k < c0) {
+      cand = c0;
+    } else {
+      k -= c0;
+      cand -= c0;
+      prefix |= bit;
+    }
+    mask |= bit;
+  }
+  const double lo = key_value(prefix);
+  if (!between) return lo;
+  unsigned long long up = prefix;
+  if (k + 1 >= cand) {
+    unsigned long long m = ~0ULL;
+    for (int s = l; s < n; s += kWave) {
+      const unsigned long long key = key_at(s);
+      if (key > prefix && key < m) m = key;
+    }
+    up = wave_min_u64(m);
+  }
+  return (lo + key_value(up)) / 2.0;
+}
+
+// mhx_get_percentiles.  One workgroup of kPctWaves wavefronts per chain; wave w serves the
+// parameters w, w + kPctWaves, ...; every percentile reruns the selection (64 cheap passes over
+// a column that is already in LDS, against one pass to bring it there).
+//   use_lds = 1: the window's rows - t x d contiguous doubles, two runs when the ring has
+//     wrapped - are read ONCE, coalesced, by the whole workgroup and laid down as keys, one
+//     column of `tpad` slots per parameter (tpad staggers the columns over the banks for the
+//     transposing store; the selection reads a column with unit stride, conflict-free)
+//   use_lds = 0: a window that does not fit (d * tpad * 8 bytes of LDS): every pass reads the
+//     column from global memory / L2 with stride d
+constexpr int kPctWaves = 4;
+constexpr int kPctThreads = kWave * kPctWaves;
+__global__ __launch_bounds__(kPctThreads) void k_percentiles(ChainState S, int64_t c0, int take,
+                                                            PctList pc, int use_lds, int tpad,
+                                                            double* __restrict__ out,
+                                                            int32_t* __restrict__ n_used) {
+  unsigned long long* col = reinterpret_cast<unsigned long long*>(mhx_lds_raw);
+  const int w = wave_in_group(), l = lane_id(), d = S.d;
+  const int64_t i = blockIdx.x;
+  const Ring ring = ring_of(S, c0 + i);
+  const int t = ring_held(ring, take);
+  if (threadIdx.x == 0) n_used[i] = t;
+  if (use_lds) {
+    const int64_t oldest = ring.nh - t;
+    for (int f = threadIdx.x; f < t * d; f += kPctThreads) {
+      const int s = f / d, p = f - s * d;
+      const int64_t slot = (oldest + s) & (int64_t)ring.mask;
+      col[(size_t)p * tpad + s] = order_key(ring.theta[slot * d + p]);
+    }
+    __syncthreads();
+  }
+  for (int p = w; p < d; p += kPctWaves)
+    for (int q = 0; q < pc.n; ++q) {
+      double v = 0.0;
+      if (t > 0) {
+        int64_t pos;
+        int32_t between;
+        percentile_rank_of(t, pc.num[q], pc.den[q], &pos, &between);
+        if (use_lds) {
+          const unsigned long long* cp = col + (size_t)p * tpad;
+          v = select_percentile([&](int s) { return cp[s]; }, t, (int)pos, between != 0);
+        } else {
+          v = select_percentile(
+              [&](int s) { return order_key(ring.theta[(int64_t)ring.slot(s) * d + p]); }, t,
+              (int)pos, between != 0);
+        }
+      }
+      if (l == 0) out[(i * pc.n + q) * d + p] = v;
+    }
+}
+
+// mhx_get_covariances: :covariance-matrix M:541 = lplist-covariance (M:614-643) of :unique-steps
+// (M:492-496), one wavefront per chain.  uniq: [n][take] ring slots of the unique steps, newest
+// first (compacted in order like ring_forward_list); cov [n][d][d].
+__global__ __launch_bounds__(kThreads) void k_covariances(ChainState S, int64_t c0, int64_t n,
+                                                         int take, int* __restrict__ uniq_all,
+                                                         double* __restrict__ cov_all,
+                                                         int32_t* __restrict__ n_unique,
+                                                         int32_t* __restrict__ status) {
+  __shared__ double avg_all[kWavesPerGroup][MHX_MAX_PARAMS + 1];
+  const int w = wave_in_group(), l = lane_id(), d = S.d;
+  const int64_t i = (int64_t)blockIdx.x * kWavesPerGroup + w;
+  if (i >= n) return;
+  const Ring r = ring_of(S, c0 + i);
+  const int t = ring_held(r, take);
+  int* uniq = uniq_all + i * take;
+  double* cov = cov_all + i * d * d;
+  double* avg = avg_all[w];
+  int nu = 0;
+  for (int base = 0; base < t; base += kWave) {
+    const int s = base + l;
+    bool f = false;
+    if (s < t) {
+      const bool last = s == t - 1;
+      const double a = r.prob[r.slot(s)];
+      const double b = last ? 0.0 : r.prob[r.slot(s + 1)];
+      f = last || bits_of(a) != bits_of(b);
+    }
+    const unsigned long long m = __ballot(f);
+    const int pos = nu + __popcll(m & ((1ULL << l) - 1ULL));
+    if (f) uniq[pos] = r.slot(s);
+    nu += __popcll(m);
+  }
+  __threadfence();
+  int st = L_OK;
+  if (nu == 0) {  // (no history at all: nothing the reference could be asked about)
+    for (int e = l; e < d * d; e += kWave) cov[e] = 0.0;
+    st = L_CAUGHT;
+  } else {
+    const double dn = (double)nu;
+    auto x = [&](int k, int p) -> double { return r.theta[(int64_t)uniq[k] * d + p]; };
+    // averages M:626: (/ (reduce #'+ x) n)
+    if (l < d) {
+      double s = x(0, l);
+      for (int k = 1; k < nu; ++k) s = s + x(k, l);
+      const double a = s / dn;
+      avg[l] = a;
+      st = trap_of(a);
+    }
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    // covariance M:636-643 (the /n sits inside the accumulation; multiply, divide, add)
+    for (int e = l; e < d * d; e += kWave) {
+      const int a = e / d, b = e - a * d;
+      const double aa = avg[a], ab = avg[b];
+      double mini = 0.0;
+      for (int k = 0; k < nu; ++k) {
+        const double u = x(k, a) - aa, v = x(k, b) - ab;
+        mini = mini + (u * v) / dn;
+      }
+      cov[e] = mini;
+      if (st == L_OK) st = trap_of(mini);
+    }
+  }
+  const bool bad = __ballot(st != L_OK) != 0ULL;
+  if (l == 0) {
+    n_unique[i] = nu;
+    status[i] = bad ? L_CAUGHT : L_OK;
+  }
+}
+
+// mhx_get_proposal_factors: ring_l_matrix - the code k_l_matrix and the controller run - for
+// every chain.  fwd [n][take], cov / out [n][d][d] (zeroed by the host, as for k_l_matrix).
+__global__ __launch_bounds__(kThreads) void k_l_matrices(ChainState S, int64_t c0, int64_t n,
+                                                        int take, int* __restrict__ fwd,
+                                                        double* __restrict__ cov,
+                                                        double* __restrict__ out,
+                                                        int32_t* __restrict__ status,
+                                                        int32_t* __restrict__ n_forward) {
+  __shared__ double avg_all[kWavesPerGroup][MHX_MAX_PARAMS + 1];
+  const int w = wave_in_group(), d = S.d;
+  const int64_t i = (int64_t)blockIdx.x * kWavesPerGroup + w;
+  if (i >= n) return;
+  const Ring ring = ring_of(S, c0 + i);
+  int nf = 0;
+  const int st = ring_l_matrix(ring, take, fwd + i * take, cov + i * d * d, out + i * d * d,
+                               (lds_dptr_t)avg_all[w], &nf);
+  if (lane_id() == 0) {
+    status[i] = st;
+    n_forward[i] = nf;
+  }
+}
+
+// mhx_get_window_best: :most-likely-step M:503-505 over the window.  The reference's reduce goes
+// from the newest step to the oldest and keeps the step it holds only while that one is STRICTLY
+// greater: of equal greatest probs the oldest wins.  Per lane over its strided share in that
+// order, then a butterfly that carries the step index.
+__global__ __launch_bounds__(kThreads) void k_window_best(ChainState S, int64_t c0, int64_t n,
+                                                         int take, double* __restrict__ prob,
+                                                         double* __restrict__ theta) {
+  const int w = wave_in_group(), l = lane_id(), d = S.d;
+  const int64_t i = (int64_t)blockIdx.x * kWavesPerGroup + w;
+  if (i >= n) return;
+  const Ring r = ring_of(S, c0 + i);
+  const int t = ring_held(r, take);
+  double bv = 0.0;
+  int bs = -1;
+  for (int s = l; s < t; s += kWave) {
+    const double v = r.prob[r.slot(s)];
+    if (bs < 0 || !(bv > v)) {
+      bv = v;
+      bs = s;
+    }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    const double ov = __shfl_xor(bv, m, 64);
+    const int os = __shfl_xor(bs, m, 64);
+    const bool take_other = os >= 0 && (bs < 0 || ov > bv || (ov == bv && os > bs));
+    if (take_other) {
+      bv = ov;
+      bs = os;
+    }
+  }
+  if (l == 0) prob[i] = bv;
+  if (l < d) theta[i * d + l] = bs < 0 ? 0.0 : r.theta[(int64_t)r.slot(bs) * d + l];
+}
+#endif  // MHX_FAMILY_PRIMARY
+
 }  // inline namespace MHX_FAMILY
 }  // namespace mhx
 

@@ -81,4 +81,26 @@ struct Family {
 const Family& family_w8();
 const Family& family_w16();
 
+// walker-set-get: summaries of the `n` chains from `c0` on (mhx_kernels.hpp; family-independent,
+// compiled once).  Outputs and scratch are indexed by the chain's place in [c0, c0 + n).
+// The LDS a percentile workgroup needs for a window of `take` steps of d parameters, and the
+// column pitch that goes with it; above kPctLdsBudget the kernel reads its columns from memory.
+constexpr size_t kPctLdsBudget = 80 * 1024;  // two workgroups per CU (160 KiB)
+inline int pct_column_pitch(int take, int d) {
+  return ((take + 15) & ~15) + (d >= 16 ? 1 : 16 / d);
+}
+inline size_t pct_lds_bytes(int take, int d) {
+  return (size_t)d * pct_column_pitch(take, d) * sizeof(double);
+}
+hipError_t summary_configure();
+hipError_t launch_percentiles(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
+                              const PctList& pc, bool use_lds, double* out, int32_t* n_used);
+hipError_t launch_covariances(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
+                              int* uniq, double* cov, int32_t* n_unique, int32_t* status);
+hipError_t launch_l_matrices(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
+                             int* fwd, double* cov, double* out, int32_t* status,
+                             int32_t* n_forward);
+hipError_t launch_window_best(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
+                              double* prob, double* theta);
+
 }  // namespace mhx

@@ -258,6 +258,40 @@ const Family& MHX_CAT(family_, MHX_FAMILY)() {
 }
 
 #ifdef MHX_FAMILY_PRIMARY  // family-independent helpers: defined by one unit only
+hipError_t summary_configure() {
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_percentiles),
+                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPctLdsBudget);
+}
+hipError_t launch_percentiles(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
+                              const PctList& pc, bool use_lds, double* out, int32_t* n_used) {
+  if (n <= 0) return hipSuccess;
+  const size_t lds = use_lds ? pct_lds_bytes(take, S.d) : 0;
+  if (lds > kPctLdsBudget) return hipErrorInvalidValue;
+  k_percentiles<<<dim3((unsigned)n), dim3(kPctThreads), lds, st>>>(
+      S, c0, take, pc, use_lds ? 1 : 0, pct_column_pitch(take, S.d), out, n_used);
+  return hipGetLastError();
+}
+hipError_t launch_covariances(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
+                              int* uniq, double* cov, int32_t* n_unique, int32_t* status) {
+  if (n <= 0) return hipSuccess;
+  k_covariances<<<grid_for(n), dim3(kThreads), 0, st>>>(S, c0, n, take, uniq, cov, n_unique, status);
+  return hipGetLastError();
+}
+hipError_t launch_l_matrices(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
+                             int* fwd, double* cov, double* out, int32_t* status,
+                             int32_t* n_forward) {
+  if (n <= 0) return hipSuccess;
+  k_l_matrices<<<grid_for(n), dim3(kThreads), 0, st>>>(S, c0, n, take, fwd, cov, out, status,
+                                                      n_forward);
+  return hipGetLastError();
+}
+hipError_t launch_window_best(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
+                              double* prob, double* theta) {
+  if (n <= 0) return hipSuccess;
+  k_window_best<<<grid_for(n), dim3(kThreads), 0, st>>>(S, c0, n, take, prob, theta);
+  return hipGetLastError();
+}
+
 const char* spec_name(int spec) {
   static const char* names[] = {"generic",      "gauss22_normal", "gauss15_poisson",
                                            "pvoigt2_normal", "poly2_normal",   "poly8_normal",

@@ -133,6 +133,28 @@ struct ChainState {
   int32_t* persist_error;
 };
 
+// nth-percentile's position rule (M:1495-1506, include/mhx.h: mhx_percentile_rank) for the
+// n = num/den per cent point of `len` sorted values: q = num (len-1) / (100 den) exactly;
+// pos = floor(q), between = q has a fractional part.  The caller has checked len >= 1,
+// den >= 1, 0 <= num <= 100 den (all products then fit 64 bits).
+#ifndef __HIPCC_RTC__
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+inline void percentile_rank_of(int64_t len, int32_t num, int32_t den,
+                        int64_t* pos, int32_t* between) {
+  const int64_t a = (int64_t)num * (len - 1), b = (int64_t)100 * den;
+  *pos = a / b;
+  *between = a % b != 0 ? 1 : 0;
+}
+#endif
+
+// the percentiles one mhx_get_percentiles call asks for (a kernel argument)
+struct PctList {
+  int32_t n;
+  int32_t num[MHX_MAX_PERCENTILES], den[MHX_MAX_PERCENTILES];
+};
+
 struct RunDesc {
   int64_t n, sts, temp_steps, mwl, tail;
   int32_t auto_mode, has_mwl, adapt_mode;

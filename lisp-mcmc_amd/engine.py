@@ -7,7 +7,65 @@ import numpy as np
 from . import _capi as capi
 
 
-class Engine:
+def percentile_ratio(p):
+    """a percentile as the (num, den) the ABI takes: the rational walker._percentile uses"""
+    from fractions import Fraction
+    f = Fraction(p).limit_denominator(1000)
+    return f.numerator, f.denominator
+
+
+class _Summaries:
+    """walker-set-get's batched read-backs (include/mhx.h): every chain in one launch.  Shared by
+    Engine (mhx_get_*) and Group (mhx_group_get_*)."""
+    _summary_prefix = "mhx_get_"
+
+    def _summary(self, name):
+        return getattr(capi.lib(), self._summary_prefix + name)
+
+    def percentiles(self, take, pcts):
+        """[n_chains, len(pcts), d] nth-percentile of every parameter over the newest `take`
+        steps, and n_used [n_chains]; pcts: numbers (50, 2.5, ...) or (num, den) pairs"""
+        rat = [p if isinstance(p, tuple) else percentile_ratio(p) for p in pcts]
+        num, nump = capi.as_i32([r[0] for r in rat] or [0])
+        den, denp = capi.as_i32([r[1] for r in rat] or [1])
+        out = np.zeros((self.n_chains, len(rat), self.d))
+        used = np.zeros(self.n_chains, dtype=np.int32)
+        capi.check(self._summary("percentiles")(self._h, int(take), nump, denp, len(rat),
+                                                out.ctypes.data_as(capi.f64p),
+                                                used.ctypes.data_as(capi.i32p)))
+        return out, used
+
+    def covariances(self, take):
+        """:covariance-matrix of every chain: cov [n_chains, d, d], n_unique, status"""
+        cov = np.zeros((self.n_chains, self.d, self.d))
+        nu = np.zeros(self.n_chains, dtype=np.int32)
+        st = np.zeros(self.n_chains, dtype=np.int32)
+        capi.check(self._summary("covariances")(self._h, int(take), cov.ctypes.data_as(capi.f64p),
+                                                nu.ctypes.data_as(capi.i32p),
+                                                st.ctypes.data_as(capi.i32p)))
+        return cov, nu, st
+
+    def proposal_factors(self, take):
+        """:l-matrix of every chain: status [n_chains], L [n_chains, d, d], n_forward"""
+        L = np.zeros((self.n_chains, self.d, self.d))
+        st = np.zeros(self.n_chains, dtype=np.int32)
+        nf = np.zeros(self.n_chains, dtype=np.int32)
+        capi.check(self._summary("proposal_factors")(self._h, int(take),
+                                                     L.ctypes.data_as(capi.f64p),
+                                                     st.ctypes.data_as(capi.i32p),
+                                                     nf.ctypes.data_as(capi.i32p)))
+        return st, L, nf
+
+    def window_best(self, take):
+        """:most-likely-step over the window, every chain: prob [n_chains], theta [n_chains, d]"""
+        pr = np.zeros(self.n_chains)
+        th = np.zeros((self.n_chains, self.d))
+        capi.check(self._summary("window_best")(self._h, int(take), pr.ctypes.data_as(capi.f64p),
+                                                th.ctypes.data_as(capi.f64p)))
+        return pr, th
+
+
+class Engine(_Summaries):
     def __init__(self, n_chains, n_params, n_functions=1, device=0, seed=0, chain_offset=0,
                  adapt_mode=capi.ADAPT_FAITHFUL, history_capacity=0, poisson_logfact_double=False):
         cfg = capi.Config()
@@ -259,6 +317,18 @@ class Engine:
                                                       C.byref(nf)))
         return st.value, L, nf.value
 
+    def history_capacity(self):
+        """steps the device ring of every chain holds: the greatest `take`"""
+        n = C.c_int32(0)
+        capi.check(capi.lib().mhx_get_history_capacity(self._h, C.byref(n)))
+        return n.value
+
+    def summary_timing(self):
+        """HIP-event milliseconds of the kernels of the last batched summary call"""
+        ms = C.c_double(0)
+        capi.check(capi.lib().mhx_get_summary_timing(self._h, C.byref(ms)))
+        return ms.value
+
     def set_history(self, chain, prob, theta):
         """restore a walk, newest first (walker-load)"""
         pa, pp = capi.as_f64(prob)
@@ -326,10 +396,11 @@ class _GroupEngine(Engine):
         self._h = C.c_void_p()
 
 
-class Group:
+class Group(_Summaries):
     """ONE host process, several GPUs (include/mhx.h, mhx_group_*): n_chains walkers in all,
     contiguous global id ranges per device, launches enqueued on every device before any is
     waited for, the pooled tick's all-reduce through RCCL."""
+    _summary_prefix = "mhx_group_get_"
 
     def __init__(self, n_chains, n_params, n_functions=1, devices=(0,), seed=0, chain_offset=0,
                  adapt_mode=capi.ADAPT_FAITHFUL, history_capacity=0, poisson_logfact_double=False):
@@ -417,6 +488,9 @@ class Group:
             bt.ctypes.data_as(capi.f64p), bl.ctypes.data_as(capi.f64p),
             ln.ctypes.data_as(capi.i64p), ag.ctypes.data_as(capi.i64p)))
         return dict(theta=th, logpost=lp, best_theta=bt, best_logpost=bl, length=ln, age=ag)
+
+    def history_capacity(self):
+        return self.engines[0].history_capacity()
 
     def counters(self):
         a, b = C.c_uint64(0), C.c_uint64(0)

@@ -166,6 +166,31 @@ library, or without a gfx950 device, walker-create signals MHX-ERROR."
   (length :pointer) (age :pointer))
 (cffi:defcfun ("mhx_group_get_counters" %mhx-group-get-counters) :int
   (g :pointer) (chain-steps :pointer) (kernel-launches :pointer))
+;; walker-set-get: summaries of every chain in one launch
+(cffi:defcfun ("mhx_percentile_rank" %mhx-percentile-rank) :int
+  (len :int64) (num :int32) (den :int32) (pos :pointer) (between :pointer))
+(cffi:defcfun ("mhx_get_percentiles" %mhx-get-percentiles) :int
+  (e :pointer) (take :int) (pct-num :pointer) (pct-den :pointer) (n-pct :int) (out :pointer)
+  (n-used :pointer))
+(cffi:defcfun ("mhx_get_covariances" %mhx-get-covariances) :int
+  (e :pointer) (take :int) (cov :pointer) (n-unique :pointer) (status :pointer))
+(cffi:defcfun ("mhx_get_proposal_factors" %mhx-get-proposal-factors) :int
+  (e :pointer) (take :int) (l-out :pointer) (status :pointer) (n-forward :pointer))
+(cffi:defcfun ("mhx_get_window_best" %mhx-get-window-best) :int
+  (e :pointer) (take :int) (prob :pointer) (theta :pointer))
+(cffi:defcfun ("mhx_get_history_capacity" %mhx-get-history-capacity) :int
+  (e :pointer) (capacity :pointer))
+(cffi:defcfun ("mhx_get_summary_timing" %mhx-get-summary-timing) :int
+  (e :pointer) (kernel-ms :pointer))
+(cffi:defcfun ("mhx_group_get_percentiles" %mhx-group-get-percentiles) :int
+  (g :pointer) (take :int) (pct-num :pointer) (pct-den :pointer) (n-pct :int) (out :pointer)
+  (n-used :pointer))
+(cffi:defcfun ("mhx_group_get_covariances" %mhx-group-get-covariances) :int
+  (g :pointer) (take :int) (cov :pointer) (n-unique :pointer) (status :pointer))
+(cffi:defcfun ("mhx_group_get_proposal_factors" %mhx-group-get-proposal-factors) :int
+  (g :pointer) (take :int) (l-out :pointer) (status :pointer) (n-forward :pointer))
+(cffi:defcfun ("mhx_group_get_window_best" %mhx-group-get-window-best) :int
+  (g :pointer) (take :int) (prob :pointer) (theta :pointer))
 
 (defmacro with-c-call (&body body)
   "HIP/RCCL runtime code may raise inexact/invalid flags that SBCL turns into conditions;

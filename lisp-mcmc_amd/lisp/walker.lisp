@@ -587,6 +587,104 @@ vectors of (x_i - mean_i)(x_j - mean_j) / n, the division inside the sum."
                                 keys))
         (t (error "walker-get: unknown :get ~s" get))))))
 
+;;; ------------------------------------------------------------------ walker-set-get M:1029-1030
+;;; walker-get mapped over the set.  The summarising selectors are ONE batched device call for all
+;;; chains (mhx_get_percentiles / _covariances / _proposal_factors / _window_best, or their
+;;; mhx_group_get_* forms): no history crosses to the host.
+(defun %set-call (walker engine-fn group-fn &rest args)
+  "ENGINE-FN on the walker's engine or GROUP-FN on its group, ARGS after the handle"
+  (with-c-call
+    (check (if (grouped-p walker)
+               (apply group-fn (walker-group walker) args)
+               (apply engine-fn (engine-of walker) args)))))
+
+(defun %set-lengths (walker)
+  "(walker-length w) of every chain, read once"
+  (let ((n (walker-n-chains walker))
+        (none (cffi:null-pointer)))
+    (cffi:with-foreign-object (ln :int64 n)
+      (%set-call walker #'%mhx-get-state #'%mhx-group-get-state none none none none ln none)
+      (loop for c below n collect (cffi:mem-aref ln :int64 c)))))
+
+(defun %l-matrix-value (status matrix)
+  "what (walker-get :get :l-matrix) makes of the device's status"
+  (case status
+    (0 matrix)
+    (1 (error 'division-by-zero :operation 'cholesky-decomp :operands nil))
+    (2 (error 'floating-point-invalid-operation :operation 'cholesky-decomp :operands nil))
+    (t (make-array '(0 0) :element-type 'double-float))))
+
+(defun walker-set-get (walker &key (get :steps) take param)
+  "(walker-set-get the-walker-set &key get take param) M:1029-1030 over a batched walker: a list
+with one entry per chain, each what (walker-get walker :get get :take take :chain c) returns.  A
+condition is signalled for the first chain walker-get would signal it for, as mapcar would."
+  (let* ((n (walker-n-chains walker))
+         (d (walker-n-params walker))
+         (keys (walker-param-keys walker))
+         (lengths (%set-lengths walker))
+         (longest (reduce #'max lengths))
+         (wanted (max 1 (if take (min take longest) longest)))
+         (ring (cffi:with-foreign-object (cap :int32)
+                 (with-c-call
+                   (check (%mhx-get-history-capacity (first (all-engines walker)) cap)))
+                 (cffi:mem-ref cap :int32)))
+         (window (min wanted ring))
+         (none (cffi:null-pointer)))
+    (flet ((per-chain ()
+             (loop for c below n
+                   collect (walker-get walker :get get :take take :param param :chain c)))
+           (note-truncation ()
+             (when (> wanted ring)
+               (warn "walker-set-get ~s :take ~d: the device history ring holds the newest ~d steps of a walk; create the walker with :history-capacity >= the walks' length to keep them all"
+                     get wanted ring)))
+           (plist-at (ptr offset)
+             (%plist walker (read-doubles (cffi:inc-pointer ptr (* 8 offset)) d)))
+           (matrix-at (ptr offset)
+             (let ((a (make-array (list d d) :element-type 'double-float)))
+               (dotimes (i d a)
+                 (dotimes (j d)
+                   (setf (aref a i j) (cffi:mem-aref ptr :double (+ offset (* i d) j))))))))
+      (case get
+        (:median-params                 ; nth-percentile 50 of every parameter, M:516-523
+         (cffi:with-foreign-objects ((num :int32) (den :int32) (out :double (* n d)))
+           (setf (cffi:mem-ref num :int32) 50
+                 (cffi:mem-ref den :int32) 1)
+           (%set-call walker #'%mhx-get-percentiles #'%mhx-group-get-percentiles
+                      window num den 1 out none)
+           (note-truncation)
+           (loop for c below n collect (plist-at out (* c d)))))
+        (:covariance-matrix             ; M:541
+         (cffi:with-foreign-object (cov :double (* n d d))
+           (%set-call walker #'%mhx-get-covariances #'%mhx-group-get-covariances
+                      window cov none none)
+           (note-truncation)
+           (loop for c below n collect (matrix-at cov (* c d d)))))
+        (:most-likely-step              ; M:503-505 over the window
+         (cffi:with-foreign-objects ((pr :double n) (th :double (* n d)))
+           (%set-call walker #'%mhx-get-window-best #'%mhx-group-get-window-best window pr th)
+           (note-truncation)
+           (loop for c below n
+                 collect (make-walker-step :prob (cffi:mem-aref pr :double c)
+                                           :params (plist-at th (* c d))))))
+        ((:l-matrix :stddev-params)     ; M:543, M:525-539
+         (if (> wanted ring)
+             (per-chain)        ; walker-get signals what the device says of such a window
+             (cffi:with-foreign-objects ((lm :double (* n d d)) (st :int32 n))
+               (%set-call walker #'%mhx-get-proposal-factors #'%mhx-group-get-proposal-factors
+                          window lm st none)
+               (loop for c below n
+                     for len in lengths
+                     collect (if (and (eq get :stddev-params) (< len 10))
+                                 (loop for k in keys append (list k 0d0))
+                                 (let ((l (%l-matrix-value (cffi:mem-aref st :int32 c)
+                                                           (matrix-at lm (* c d d)))))
+                                   (if (eq get :l-matrix)
+                                       l
+                                       (loop for k in keys
+                                             for i from 0
+                                             append (list k (aref l i i))))))))))
+        (t (per-chain))))))
+
 ;;; ------------------------------------------------------------------ save / load M:971-1001
 ;;; The plist the reference's (commented) walker-construct-print-list builds, written and read
 ;;; under with-standard-io-syntax; functions are only NAMED in the file, so walker-load wants

@@ -10,6 +10,7 @@ walker-adaptive-steps path (M: = mcmc-fitting.lisp):
     walker-many-steps            M:849-853     walker_many_steps
     walker-take-step             M:1072-1095   walker_take_step
     walker-get                   M:487-543     walker_get
+    walker-set-get               M:1029-1030   walker_set_get
     walker-modify                M:547-580     walker_modify
     prior-bounds-let             M:346-369     prior_bounds
     mfit-walker-estop            M:860-861     request_stop
@@ -389,6 +390,38 @@ def lplist_covariance(v):
     return cov
 
 
+def _l_matrix_value(st, L):
+    """the value or condition of (walker-get :l-matrix) for a status of the device's ring_l_matrix"""
+    if st == capi.L_CAUGHT:
+        raise ArithmeticError("(walker-get :l-matrix): type-error / division-by-zero / "
+                              "floating-point-overflow (the conditions M:891-894 handles)")
+    if st == capi.L_INVALID:
+        raise FloatingPointError("(walker-get :l-matrix): floating-point-invalid-operation")
+    return L if st == capi.L_OK else np.zeros((0, 0))
+
+
+_LIST_SELECTORS = ("steps", "log-liklihoods", "params", "param", "unique-steps", "forward-steps")
+
+
+def _list_selector(g, steps, prob, param):
+    """the list-valued selectors of M:487-543 over a window's newest-first steps"""
+    if g == "steps":
+        return steps
+    if g == "log-liklihoods":  # M:540
+        return [s.prob for s in steps]
+    if g == "params":
+        return [s.params for s in steps]
+    if g == "param":
+        return [s.params[_key(param)] for s in steps]
+    if g == "unique-steps":  # M:492-496: `equal` on two double-floats is eql - the same BITS
+        bits = np.asarray(prob, dtype=np.float64).view(np.uint64)  # (0.0 / -0.0 differ, NaN = NaN)
+        return [steps[i].params for i in range(len(steps))
+                if i + 1 >= len(steps) or bits[i] != bits[i + 1]]
+    # "forward-steps", M:497-502
+    return [steps[i].params for i in range(len(steps) - 1)
+            if not steps[i].prob <= steps[i + 1].prob]
+
+
 def walker_get(walker, get=":steps", take=None, param=None, chain=0):
     """(walker-get walker &key get take param) M:487-543, served from the device trace."""
     e = walker.engine
@@ -403,12 +436,7 @@ def walker_get(walker, get=":steps", take=None, param=None, chain=0):
         return Fraction(int(round(a * t)), t)
     if g == "l-matrix":  # M:543
         st, L, _ = e.proposal_factor(chain, max(t, 1))
-        if st == capi.L_CAUGHT:
-            raise ArithmeticError("(walker-get :l-matrix): type-error / division-by-zero / "
-                                  "floating-point-overflow (the conditions M:891-894 handles)")
-        if st == capi.L_INVALID:
-            raise FloatingPointError("(walker-get :l-matrix): floating-point-invalid-operation")
-        return L if st == capi.L_OK else np.zeros((0, 0))
+        return _l_matrix_value(st, L)
     prob, th = e.trace(chain, t)
     if len(prob) < t:
         # the reference keeps every step of a walk (M:549); the engine keeps the newest
@@ -419,21 +447,8 @@ def walker_get(walker, get=":steps", take=None, param=None, chain=0):
             "steps; create the walker with history_capacity >= the walk's length to keep them all"
             % (get, t, len(prob), cap)), stacklevel=2)
     steps = [walker._step(th[i], prob[i]) for i in range(len(prob))]
-    if g == "steps":
-        return steps
-    if g == "log-liklihoods":  # M:540
-        return [s.prob for s in steps]
-    if g == "params":
-        return [s.params for s in steps]
-    if g == "param":
-        return [s.params[_key(param)] for s in steps]
-    if g == "unique-steps":  # M:492-496: `equal` on two double-floats is eql - the same BITS
-        bits = np.asarray(prob, dtype=np.float64).view(np.uint64)  # (0.0 / -0.0 differ, NaN = NaN)
-        return [steps[i].params for i in range(len(steps))
-                if i + 1 >= len(steps) or bits[i] != bits[i + 1]]
-    if g == "forward-steps":  # M:497-502
-        return [steps[i].params for i in range(len(steps) - 1)
-                if not steps[i].prob <= steps[i + 1].prob]
+    if g in _LIST_SELECTORS:
+        return _list_selector(g, steps, prob, param)
     if g == "most-likely-step":  # M:503-505 over the window; ties keep the later element
         best = steps[0]
         for s in steps[1:]:
@@ -450,6 +465,86 @@ def walker_get(walker, get=":steps", take=None, param=None, chain=0):
         L = walker_get(walker, ":l-matrix", take, chain=chain)
         return {k: float(L[j, j]) for j, k in enumerate(keys)}
     raise ValueError("unknown :get %r" % (get,))
+
+
+_SUMMARY_SELECTORS = ("median-params", "stddev-params", "l-matrix", "covariance-matrix",
+                      "most-likely-step", "most-likely-params", "acceptance")
+
+
+def walker_set_get(walker, get=":steps", take=None, param=None):
+    """(walker-set-get the-walker-set &key get take param) M:1029-1030: walker-get mapped over
+    the set - a list with one entry per chain, each what walker_get(..., chain=c) returns.
+
+    The summarising selectors (:median-params :stddev-params :l-matrix :covariance-matrix
+    :most-likely-step :most-likely-params :acceptance) are served by ONE batched device call for
+    all chains (include/mhx.h, mhx_get_percentiles and its kin): no history crosses to the host.
+    The list-valued selectors read one trace per chain, the lengths once.  A condition is raised
+    for the first chain (in chain order) that walker_get would raise it for, as mapcar would;
+    HistoryTruncated is warned once per call when any chain's window reached past its ring."""
+    e = walker.engine
+    g = str(get).lstrip(":").lower()
+    if g not in _SUMMARY_SELECTORS and g not in _LIST_SELECTORS:
+        raise ValueError("unknown :get %r" % (get,))
+    keys = walker.param_keys
+    n = e.n_chains
+    state = e.state()  # every chain's length (and most likely step): read ONCE
+    cap = state["length"].astype(np.int64)
+    t = cap.copy() if take is None else np.minimum(int(take), cap)
+    if g == "most-likely-params":  # M:511-515 (struct slot, not windowed)
+        return [dict(zip(keys, (float(v) for v in state["best_theta"][c]))) for c in range(n)]
+    ring = e.history_capacity()
+    widest = max(int(t.max()), 1)
+
+    def truncated(held, wanted, count):
+        warnings.warn(HistoryTruncated(
+            "walker-set-get %s :take %s: the device history ring holds the newest %d steps of a "
+            "walk and %d of the set's %d windows reach past it (the widest asks for %d); create the "
+            "walker with history_capacity >= the walks' length to keep them all"
+            % (get, take, held, count, n, wanted)), stacklevel=3)
+
+    if g in ("acceptance", "l-matrix", "stddev-params"):
+        if widest > ring:
+            # walker_get hands such a window to the device, which refuses it: the chain that
+            # asks for it raises (unless an earlier chain raises first) - in walker_get's words
+            return [walker_get(walker, get, take, param, chain=c) for c in range(n)]
+        if g == "acceptance":  # M:506-508
+            a = e.acceptance(widest)
+            return [Fraction(int(round(a[c] * int(t[c]))), int(t[c])) for c in range(n)]
+        st, L, _ = e.proposal_factors(widest)
+        out = []
+        for c in range(n):
+            if g == "stddev-params" and cap[c] < 10:  # M:528-529
+                out.append({k: 0.0 for k in keys})
+                continue
+            Lc = _l_matrix_value(int(st[c]), L[c].copy())
+            out.append(Lc if g == "l-matrix" else {k: float(Lc[j, j]) for j, k in enumerate(keys)})
+        return out
+    past = int((t > ring).sum())
+    window = min(widest, ring)
+    if g == "median-params":  # M:516-523
+        med, _ = e.percentiles(window, [(50, 1)])
+        if past:
+            truncated(ring, widest, past)
+        return [{k: float(med[c, 0, j]) for j, k in enumerate(keys)} for c in range(n)]
+    if g == "covariance-matrix":  # M:541
+        cov, _, _ = e.covariances(window)
+        if past:
+            truncated(ring, widest, past)
+        return [cov[c].copy() for c in range(n)]
+    if g == "most-likely-step":  # M:503-505 over the window
+        pr, th = e.window_best(window)
+        if past:
+            truncated(ring, widest, past)
+        return [walker._step(th[c], pr[c]) for c in range(n)]
+    out, short = [], 0
+    for c in range(n):
+        prob, th = e.trace(c, int(t[c]))
+        short += len(prob) < t[c]
+        steps = [walker._step(th[i], prob[i]) for i in range(len(prob))]
+        out.append(_list_selector(g, steps, prob, param))
+    if short:
+        truncated(ring, widest, short)
+    return out
 
 
 def walker_modify(walker, modify=None, **kw):
