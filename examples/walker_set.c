@@ -127,6 +127,28 @@ int main(int argc, char** argv) {
     }
   free(pct);
   free(used);
+  /* the band of walker-get-data-and-fit (mcmc-fitting.lisp:1249-1253) of every walker: greatest
+   * and smallest model value over the ceiling(0.66 take) most probable steps, at a few x; and
+   * the fit itself at walker 0's most likely parameters */
+  enum { MX = 5 };
+  const double xs[MX] = {0.1, 0.3, 0.5, 0.7, 0.9};
+  double* ymax = malloc(sizeof(double) * (size_t)chains * MX);
+  double* ymin = malloc(sizeof(double) * (size_t)chains * MX);
+  int32_t* nsel = malloc(sizeof(int32_t) * (size_t)chains);
+  int32_t* flag = malloc(sizeof(int32_t) * (size_t)chains);
+  double yfit[MX];
+  TRY(mhx_group_get_fit_bands(g, 0, 1000, xs, 1, MX, ymax, ymin, nsel, flag));
+  TRY(mhx_eval_function(mhx_group_engine(g, 0), 0, best, 1, xs, 1, MX, yfit));
+  printf("fit and band of walker 0 over its %d most probable steps:\n", (int)nsel[0]);
+  for (int i = 0; i < MX; ++i) {
+    printf("  x %.1f fit %.6f band [%.6f, %.6f]\n", xs[i], yfit[i], ymin[i], ymax[i]);
+    ok = ok && ymin[i] <= ymax[i];
+  }
+  for (long c = 0; c < chains; ++c) ok = ok && flag[c] == 0 && nsel[c] > 0;
+  free(ymax);
+  free(ymin);
+  free(nsel);
+  free(flag);
   mhx_group_destroy(g);
   free(th0);
   free(best);

@@ -24,6 +24,8 @@
  *                                               _proposal_factors / _window_best (every
  *                                               chain in one launch), mhx_group_get_*
  *   nth-percentile             M:1495-1506   -> mhx_percentile_rank (the position rule)
+ *   walker-get-data-and-fit    M:1230-1255   -> mhx_eval_function, mhx_get_fit_bands,
+ *                                               mhx_band_count, mhx_group_get_fit_bands
  *   walker-modify              M:547-580     -> mhx_walker_modify (+ mhx_set_history)
  *   create-log-liklihood-function M:402-416  -> mhx_set_likelihood_expr
  *   prior-bounds-let           M:346-369     -> mhx_set_bounds (+ mhx_set_prior_expr)
@@ -437,6 +439,44 @@ int mhx_group_get_covariances(mhx_group* g, int take, double* cov, int32_t* n_un
 int mhx_group_get_proposal_factors(mhx_group* g, int take, double* L, int32_t* status,
                                    int32_t* n_forward);
 int mhx_group_get_window_best(mhx_group* g, int take, double* prob, double* theta);
+
+/* ---- walker-get-data-and-fit (M:1230-1255), its -no-stddev sibling (M:1208-1227) and
+ * walker-plot-residuals (M:1271-1283) without the plotting: the model's VALUES and the envelope
+ * of the model over the most probable two thirds of the walk, computed on the device. */
+
+/* (ceiling (* 0.66 take)) M:1250, the steps the envelope is taken over.  0.66 is read as a
+ * SINGLE float and the integer is coerced to single: the product is rounded to binary32 before
+ * the ceiling (150 -> 100, 300 -> 199, 1000 -> 660).  Host only: needs no engine and no device.
+ * MHX_EINVAL unless take >= 1. */
+int mhx_band_count(int64_t take, int64_t* k);
+/* out[n][m]: function fn of the finalised problem at the m points xcols[0 .. n_cols)[m] (column
+ * after column) for each of the n FULL parameter vectors theta[n][d]; the function's gather map
+ * is applied as in the sweep.  n_cols must be the columns of x the function reads (2 for an
+ * expression model that names xcol1, else 1).  xcols == NULL: the function's own dataset x, which
+ * is on the device already; m must then be its point count (pads are not included).  Every value
+ * is the model's direct form at that x: no likelihood, no prior, no recurrence, no tile
+ * skipping.  Serves every model the engine can walk (ahead-of-time kernels, the generic one,
+ * run-time compiled expression and specialised problems).  Worked through in portions whose
+ * device scratch stays below 64 MiB whatever n and m are.  mhx_get_summary_timing covers it. */
+int mhx_eval_function(mhx_engine* e, int fn, const double* theta, int64_t n, const double* xcols,
+                      int n_cols, int64_t m, double* out);
+/* For every chain c, ymax[n_chains][m] and ymin[n_chains][m]: M:1249-1253 on the device ring, no
+ * history crossing to the host.  take_c = min(take, walker-length_c); the candidates are ALL the
+ * steps the ring holds (the reference sorts the whole walk - only the COUNT comes from take);
+ * k_c = min(mhx_band_count(take_c), steps held) of them are selected: those of greatest prob,
+ * among equal probs (-0 = +0) the newer first, a NaN prob last.  ymax / ymin are the greatest /
+ * smallest model value over the selected steps at each x: the very bits mhx_eval_function
+ * returns for those parameter vectors.  n_selected[c] = k_c; status[c] = 1 when a selected value
+ * is not finite (the reference would have trapped; that chain's band is unspecified), else 0.
+ * xcols, n_cols, m as for mhx_eval_function.  take in [1, history_capacity]; any output may be
+ * NULL; MHX_ESTATE before mhx_init_chains. */
+int mhx_get_fit_bands(mhx_engine* e, int fn, int take, const double* xcols, int n_cols, int64_t m,
+                      double* ymax, double* ymin, int32_t* n_selected, int32_t* status);
+/* The same for a group, in global chain order; every device's launch is enqueued before any is
+ * waited for. */
+int mhx_group_get_fit_bands(mhx_group* g, int fn, int take, const double* xcols, int n_cols,
+                            int64_t m, double* ymax, double* ymin, int32_t* n_selected,
+                            int32_t* status);
 
 /* Restore a saved walk (walker-load, sketched in the comments M:987-1001): prob[n], theta[n][d]
  * NEWEST FIRST, as walker-save would have written them.  Sets the ring (newest

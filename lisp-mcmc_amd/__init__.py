@@ -11,7 +11,7 @@ importlib.import_module("lisp-mcmc_amd").
 """
 from . import _capi as capi  # noqa: F401
 from ._capi import MhxError  # noqa: F401
-from .engine import Engine, Group, comm_unique_id, partition  # noqa: F401
+from .engine import Engine, Group, band_count, comm_unique_id, partition  # noqa: F401
 from . import models  # noqa: F401
 from . import sexpr  # noqa: F401
 from . import distributed  # noqa: F401
@@ -22,9 +22,13 @@ from .walker import (  # noqa: F401
     Walker, WalkerStep, walker_create, mcmc_fit, walker_adaptive_steps,
     walker_adaptive_steps_full, walker_many_steps, walker_take_step, walker_get, walker_set_get,
     walker_modify, prior_bounds, log_prior_flat, request_stop, create_log_liklihood_function,
+    walker_get_data_and_fit, walker_get_data_and_fit_no_stddev, walker_get_residuals,
+    walker_set_get_data_and_fit, fit_linspace,
 )
 
 __all__ = ["capi", "MhxError", "Engine", "Group", "comm_unique_id", "partition", "models", "Walker", "WalkerStep", "walker_create",
            "mcmc_fit", "walker_adaptive_steps", "walker_adaptive_steps_full",
            "walker_many_steps", "walker_take_step", "walker_get", "walker_set_get", "walker_modify",
-           "prior_bounds", "log_prior_flat", "request_stop", "create_log_liklihood_function"]
+           "prior_bounds", "log_prior_flat", "request_stop", "create_log_liklihood_function",
+           "band_count", "walker_get_data_and_fit", "walker_get_data_and_fit_no_stddev",
+           "walker_get_residuals", "walker_set_get_data_and_fit", "fit_linspace"]

@@ -125,6 +125,13 @@ SIGNATURES = {
     "mhx_group_get_covariances": (C.c_int, [C.c_void_p, C.c_int, f64p, i32p, i32p]),
     "mhx_group_get_proposal_factors": (C.c_int, [C.c_void_p, C.c_int, f64p, i32p, i32p]),
     "mhx_group_get_window_best": (C.c_int, [C.c_void_p, C.c_int, f64p, f64p]),
+    "mhx_band_count": (C.c_int, [C.c_int64, i64p]),
+    "mhx_eval_function": (C.c_int, [C.c_void_p, C.c_int, f64p, C.c_int64, f64p, C.c_int, C.c_int64,
+                                    f64p]),
+    "mhx_get_fit_bands": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f64p, C.c_int, C.c_int64, f64p,
+                                    f64p, i32p, i32p]),
+    "mhx_group_get_fit_bands": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f64p, C.c_int, C.c_int64,
+                                          f64p, f64p, i32p, i32p]),
 }
 
 _lib = None

@@ -1339,7 +1339,7 @@ int mhx_create(const mhx_config* cfg, mhx_engine** out) {
       break;
     }
     if (family_w8().configure() != hipSuccess || family_w16().configure() != hipSuccess ||
-        summary_configure() != hipSuccess) {
+        summary_configure() != hipSuccess || fit_configure() != hipSuccess) {
       rc = fail(MHX_EDEVICE, "hipFuncSetAttribute(max dynamic LDS = %zu / %zu) failed",
                 family_w8().lds_bytes, family_w16().lds_bytes);
       break;
@@ -2323,6 +2323,229 @@ int mhx_get_summary_timing(mhx_engine* e, double* kernel_ms) {
   return MHX_OK;
 }
 
+// ---- walker-get-data-and-fit (M:1230-1255): model values and credible bands on the device
+// (k_band_select, k_fit).  An ITEM is a parameter vector (mhx_eval_function) or a chain
+// (mhx_get_fit_bands).  Items and points are worked through in portions: at most
+// kFitChunkPoints points of x at a time, and as many items as keep the stage buffer - x, the
+// parameter vectors or the selected steps' slots, the results - below kSummaryStageBytes.
+static constexpr int64_t kFitChunkPoints = (int64_t)1 << 17;
+struct FitCall {
+  int fn = 0, take = 0;  // take 0: parameter vectors, else bands of the engine's chains
+  int64_t n = 0, m = 0;
+  const double* theta = nullptr;  // [n][d] on the host (parameter vectors)
+  const double* xcols = nullptr;  // [n_cols][m] on the host, or NULL: the function's dataset
+  int n_cols = 1;
+  // host destinations of the engine's item 0 (any may be NULL)
+  double *ymax = nullptr, *ymin = nullptr;
+  int32_t *n_sel = nullptr, *status = nullptr;
+};
+struct FitPieces {
+  int32_t *sel, *n_sel, *status;
+  double *theta, *x0, *x1, *ymax, *ymin;
+  size_t bytes;
+};
+static int64_t fit_items(const mhx_engine* e, const FitCall& q) {
+  return q.take > 0 ? e->cfg.n_chains : q.n;
+}
+static int64_t fit_portion(const mhx_engine* e, const FitCall& q) {
+  const size_t mc = (size_t)std::min<int64_t>(q.m, kFitChunkPoints);
+  const size_t per = 2 * mc * sizeof(double) + (size_t)e->P.d * sizeof(double) +
+                     (size_t)q.take * sizeof(int32_t) + 2 * sizeof(int32_t);
+  const size_t fixed = 2 * mc * sizeof(double) + 8 * 256;
+  return std::max<int64_t>(1, (int64_t)((kSummaryStageBytes - fixed) / per));
+}
+// (the pieces whose size depends on the items alone come first: they keep their place from one
+// chunk of points to the next)
+static FitPieces fit_pieces(mhx_engine* e, const FitCall& q, int64_t n, int64_t m) {
+  FitPieces s{};
+  size_t o = 0;
+  auto take_piece = [&](size_t bytes) {
+    unsigned char* p = e->stage.p + o;
+    o += align256(bytes);
+    return p;
+  };
+  s.sel = reinterpret_cast<int32_t*>(take_piece((size_t)n * q.take * sizeof(int32_t)));
+  s.n_sel = reinterpret_cast<int32_t*>(take_piece((size_t)n * sizeof(int32_t)));
+  s.status = reinterpret_cast<int32_t*>(take_piece((size_t)n * sizeof(int32_t)));
+  s.theta = reinterpret_cast<double*>(take_piece(q.take > 0 ? 0 : (size_t)n * e->P.d * sizeof(double)));
+  s.x0 = reinterpret_cast<double*>(take_piece((size_t)m * sizeof(double)));
+  s.x1 = reinterpret_cast<double*>(take_piece((size_t)m * sizeof(double)));
+  s.ymax = reinterpret_cast<double*>(take_piece((size_t)n * m * sizeof(double)));
+  s.ymin = reinterpret_cast<double*>(take_piece((size_t)n * m * sizeof(double)));
+  s.bytes = o;
+  return s;
+}
+// x columns the model of function fn reads
+static int fit_fn_cols(const mhx_engine* e, int fn) {
+  return e->P.fn[fn].model == MHX_MODEL_EXPR ? std::max(1, e->fn_expr[fn].xcols) : 1;
+}
+static int fit_check(mhx_engine* e, FitCall* q) {
+  if (!e) return fail(MHX_EINVAL, "engine is NULL");
+  if (q->take != 0 || q->n < 0) {
+    if (!e->chains_ready) return fail(MHX_ESTATE, "mhx_init_chains has not been called");
+    if (q->take < 1 || q->take > e->S.R)
+      return fail(MHX_EINVAL, "take must be in [1, history_capacity = %d]", e->S.R);
+  }
+  int rc = use_device(e);
+  if (rc != MHX_OK || (rc = finalize_problem(e)) != MHX_OK) return rc;
+  if (q->fn < 0 || q->fn >= e->P.K) return fail(MHX_EINVAL, "function %d out of range", q->fn);
+  if (q->n_cols != fit_fn_cols(e, q->fn))
+    return fail(MHX_EINVAL, "function %d reads %d column(s) of x, n_cols is %d", q->fn,
+                fit_fn_cols(e, q->fn), q->n_cols);
+  if (!q->xcols && q->m != e->P.fn[q->fn].n)
+    return fail(MHX_EINVAL, "xcols is NULL: m must be the dataset's %lld points",
+                (long long)e->P.fn[q->fn].n);
+  if (q->m < 1) return fail(MHX_EINVAL, "m must be >= 1");
+  if (q->take == 0 && q->n > 0 && !q->theta) return fail(MHX_EINVAL, "theta is NULL");
+  return MHX_OK;
+}
+// items [i0, i0 + n) at points [m0, m0 + m): enqueued, nothing waited for
+static int fit_enqueue(mhx_engine* e, const FitCall& q, int64_t i0, int64_t n, int64_t m0, int64_t m) {
+  int rc = use_device(e);
+  if (rc != MHX_OK) return rc;
+  if ((rc = ensure_stage(e, fit_pieces(e, q, n, m).bytes)) != MHX_OK) return rc;
+  const FitPieces s = fit_pieces(e, q, n, m);
+  const FnDesc& f = e->P.fn[q.fn];
+  const int d = e->P.d;
+  FitArgs A{};
+  A.fn = q.fn;
+  A.n = n;
+  A.m = m;
+  A.n_chunks = fit_chunks(m);
+  if (q.xcols) {
+    HIP_TRY(hipMemcpyAsync(s.x0, q.xcols + m0, (size_t)m * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    if (q.n_cols > 1)
+      HIP_TRY(hipMemcpyAsync(s.x1, q.xcols + q.m + m0, (size_t)m * sizeof(double), hipMemcpyHostToDevice,
+                             e->stream));
+    A.x0 = s.x0;
+    A.x1 = q.n_cols > 1 ? s.x1 : nullptr;
+  } else {
+    A.x0 = f.x + m0;
+    A.x1 = f.n_xcols > 1 ? f.c + m0 : nullptr;
+  }
+  A.ymax = s.ymax;
+  if (q.take > 0) {
+    A.theta = e->S.hist_theta;
+    A.sel = s.sel;
+    A.n_sel = s.n_sel;
+    A.sel_pitch = q.take;
+    A.rows_per_item = e->S.R;
+    A.row0 = i0 * e->S.R;
+    A.ymin = s.ymin;
+    A.status = s.status;
+    if (m0 == 0) HIP_TRY(hipMemsetAsync(s.status, 0, (size_t)n * sizeof(int32_t), e->stream));
+  } else {
+    if (m0 == 0)
+      HIP_TRY(hipMemcpyAsync(s.theta, q.theta + (size_t)i0 * d, (size_t)n * d * sizeof(double),
+                             hipMemcpyHostToDevice, e->stream));
+    A.theta = s.theta;
+    A.rows_per_item = 1;
+  }
+  HIP_TRY(hipEventRecord(e->ev0, e->stream));
+  if (q.take > 0 && m0 == 0) HIP_TRY(launch_band_select(e->stream, e->S, i0, n, q.take, s.sel, s.n_sel));
+  HIP_TRY(e->spec == SPEC_USER ? rtc_launch_fit(*e->user_prog, e->stream, e->dP.p, A)
+                               : launch_fit(e->spec, e->stream, e->dP.p, A));
+  HIP_TRY(hipEventRecord(e->ev1, e->stream));
+  e->launches++;
+  return MHX_OK;
+}
+static int fit_collect(mhx_engine* e, const FitCall& q, int64_t i0, int64_t n, int64_t m0, int64_t m) {
+  int rc = use_device(e);
+  if (rc != MHX_OK) return rc;
+  const FitPieces s = fit_pieces(e, q, n, m);
+  HIP_TRY(hipEventSynchronize(e->ev1));
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
+  e->summary_ms += (double)ms;
+  double* const hd[2] = {q.ymax, q.take > 0 ? q.ymin : nullptr};
+  const double* const dv[2] = {s.ymax, s.ymin};
+  for (int k = 0; k < 2; ++k)
+    if (hd[k])
+      HIP_TRY(hipMemcpy2D(hd[k] + (size_t)i0 * q.m + m0, (size_t)q.m * sizeof(double), dv[k],
+                          (size_t)m * sizeof(double), (size_t)m * sizeof(double), (size_t)n,
+                          hipMemcpyDeviceToHost));
+  if (q.take > 0 && m0 + m >= q.m) {  // (the status gathers over the chunks of points)
+    if (q.n_sel)
+      HIP_TRY(hipMemcpy(q.n_sel + i0, s.n_sel, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (q.status)
+      HIP_TRY(hipMemcpy(q.status + i0, s.status, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  }
+  return MHX_OK;
+}
+// calls[i] on engs[i]: round by round, every engine's portion enqueued before any is waited for
+static int fit_run(const std::vector<mhx_engine*>& engs, std::vector<FitCall> calls) {
+  int rc = MHX_OK;
+  for (size_t i = 0; i < engs.size(); ++i)
+    if ((rc = fit_check(engs[i], &calls[i])) != MHX_OK) return rc;
+  const size_t E = engs.size();
+  std::vector<int64_t> i0(E, 0), m0(E, 0), n(E, 0), m(E, 0);
+  for (mhx_engine* e : engs) e->summary_ms = 0.0;
+  for (;;) {
+    bool any = false;
+    for (size_t i = 0; i < E; ++i) {
+      n[i] = std::min<int64_t>(fit_items(engs[i], calls[i]) - i0[i], fit_portion(engs[i], calls[i]));
+      m[i] = std::min<int64_t>(calls[i].m - m0[i], kFitChunkPoints);
+      if (n[i] <= 0) continue;
+      any = true;
+      if ((rc = fit_enqueue(engs[i], calls[i], i0[i], n[i], m0[i], m[i])) != MHX_OK) {
+        for (mhx_engine* e : engs) drain(e);
+        return rc;
+      }
+    }
+    if (!any) return MHX_OK;
+    for (size_t i = 0; i < E; ++i) {
+      if (n[i] <= 0) continue;
+      if ((rc = fit_collect(engs[i], calls[i], i0[i], n[i], m0[i], m[i])) != MHX_OK) {
+        for (mhx_engine* e : engs) drain(e);
+        return rc;
+      }
+      m0[i] += m[i];
+      if (m0[i] >= calls[i].m) {
+        m0[i] = 0;
+        i0[i] += n[i];
+      }
+    }
+  }
+}
+
+int mhx_band_count(int64_t take, int64_t* k) {
+  if (take < 1) return fail(MHX_EINVAL, "take must be >= 1");
+  if (k) *k = band_count_of(take);
+  return MHX_OK;
+}
+int mhx_eval_function(mhx_engine* e, int fn, const double* theta, int64_t n, const double* xcols,
+                      int n_cols, int64_t m, double* out) {
+  if (n < 0) return fail(MHX_EINVAL, "n < 0");
+  FitCall q;
+  q.fn = fn;
+  q.n = n;
+  q.m = m;
+  q.theta = theta;
+  q.xcols = xcols;
+  q.n_cols = n_cols;
+  q.ymax = out;
+  return fit_run({e}, {q});
+}
+static FitCall band_call(int fn, int take, const double* xcols, int n_cols, int64_t m, double* ymax,
+                         double* ymin, int32_t* n_selected, int32_t* status) {
+  FitCall q;
+  q.fn = fn;
+  q.take = take;
+  q.n = -1;  // (bands, whatever take is: fit_check)
+  q.m = m;
+  q.xcols = xcols;
+  q.n_cols = n_cols;
+  q.ymax = ymax;
+  q.ymin = ymin;
+  q.n_sel = n_selected;
+  q.status = status;
+  return q;
+}
+int mhx_get_fit_bands(mhx_engine* e, int fn, int take, const double* xcols, int n_cols, int64_t m,
+                      double* ymax, double* ymin, int32_t* n_selected, int32_t* status) {
+  return fit_run({e}, {band_call(fn, take, xcols, n_cols, m, ymax, ymin, n_selected, status)});
+}
+
 int mhx_set_history(mhx_engine* e, int64_t chain, const double* prob, const double* theta, int n) {
   if (!e || !prob || !theta) return fail(MHX_EINVAL, "NULL argument");
   if (!e->chains_ready) return fail(MHX_ESTATE, "mhx_init_chains has not been called");
@@ -2850,6 +3073,21 @@ int mhx_group_get_proposal_factors(mhx_group* g, int take, double* L, int32_t* s
 }
 int mhx_group_get_window_best(mhx_group* g, int take, double* prob, double* theta) {
   return group_summary(g, summary_call(SUM_BEST, take, prob, theta, nullptr, nullptr));
+}
+
+int mhx_group_get_fit_bands(mhx_group* g, int fn, int take, const double* xcols, int n_cols,
+                            int64_t m, double* ymax, double* ymin, int32_t* n_selected,
+                            int32_t* status) {
+  if (!g) return fail(MHX_EINVAL, "group is NULL");
+  if (m < 1) return fail(MHX_EINVAL, "m must be >= 1");
+  std::vector<FitCall> calls;
+  for (size_t i = 0; i < g->eng.size(); ++i) {
+    const size_t f = (size_t)g->first[i];
+    calls.push_back(band_call(fn, take, xcols, n_cols, m, ymax ? ymax + f * (size_t)m : nullptr,
+                              ymin ? ymin + f * (size_t)m : nullptr,
+                              n_selected ? n_selected + f : nullptr, status ? status + f : nullptr));
+  }
+  return fit_run(g->eng, calls);
 }
 
 }  // extern "C"

@@ -960,6 +960,27 @@ __device__ __forceinline__ double sweep_direct_rec(const FnDesc& f,
   return wave_sum(acc0 + acc1);
 }
 
+// The model VALUE at PTS points of a lane for one parameter vector (k_fit: mhx_eval_function,
+// mhx_get_fit_bands): one prepare, then the guarded direct form at every x - no fast path (its
+// precondition is about the dataset's x, and x is the caller's here), no recurrence, no tile
+// skipping.  DYN: the run-time shaped models, whose parameters stay in the wave's scratch.
+template <class Model, int PTS, bool DYN = false, class PF>
+__device__ __forceinline__ void model_values(const FnDesc& f, PF pf, double* scratch,
+                                             const double (&x0)[PTS], const double (&x1)[PTS],
+                                             double (&v)[PTS]) {
+  auto run = [&](const typename Model::Prep& prep) {
+    __builtin_amdgcn_wave_barrier();  // (the wave's own writes to its scratch in prepare)
+#pragma unroll
+    for (int j = 0; j < PTS; ++j) {
+      if constexpr (model_xcols<Model>::value > 1) v[j] = Model::eval2(prep, x0[j], x1[j]);
+      else v[j] = model_eval<Model, false>(prep, x0[j]);
+    }
+    __builtin_amdgcn_wave_barrier();  // (... which the next vector's prepare overwrites)
+  };
+  if constexpr (DYN) run(Model::prepare(pf, f, scratch));
+  else run(model_prepare<Model>(pf, f, scratch));
+}
+
 // A problem whose K functions all use one compiled model and likelihood
 template <class Model, int LIK, bool WG = false>
 struct FixedSpec {
@@ -1021,6 +1042,12 @@ struct FixedSpec {
   }
   static __device__ __forceinline__ double logprior(const FnDesc&, const double*, double bt) {
     return bt;
+  }
+  template <int PTS, class PF>
+  static __device__ __forceinline__ void values(const FnDesc& f, PF pf, double* scratch,
+                                                const double (&x0)[PTS], const double (&x1)[PTS],
+                                                double (&v)[PTS]) {
+    model_values<Model, PTS>(f, pf, scratch, x0, x1, v);
   }
 };
 
@@ -1090,6 +1117,27 @@ struct GenericSpec {
         return by_lik<SinusoidModel>(f, pf, active, lds);
       default:
         return by_lik<PVoigt2Model>(f, pf, active, lds);
+    }
+  }
+  template <int PTS, class PF>
+  static __device__ __forceinline__ void values(const FnDesc& f, PF pf, double* scratch,
+                                                const double (&x0)[PTS], const double (&x1)[PTS],
+                                                double (&v)[PTS]) {
+    switch (f.model) {
+      case MHX_MODEL_POLY:
+        return model_values<PolyModelDyn, PTS, true>(f, pf, scratch, x0, x1, v);
+      case MHX_MODEL_GAUSS_PEAKS:
+        return model_values<PeaksModelDyn<false>, PTS, true>(f, pf, scratch, x0, x1, v);
+      case MHX_MODEL_LORENTZ_PEAKS:
+        return model_values<PeaksModelDyn<true>, PTS, true>(f, pf, scratch, x0, x1, v);
+      case MHX_MODEL_LORDER_MIXED:
+        return model_values<LorderModel, PTS>(f, pf, scratch, x0, x1, v);
+      case MHX_MODEL_EXP_DECAY:
+        return model_values<ExpDecayModel, PTS>(f, pf, scratch, x0, x1, v);
+      case MHX_MODEL_SINUSOID:
+        return model_values<SinusoidModel, PTS>(f, pf, scratch, x0, x1, v);
+      default:
+        return model_values<PVoigt2Model, PTS>(f, pf, scratch, x0, x1, v);
     }
   }
 };
@@ -3091,7 +3139,143 @@ __global__ __launch_bounds__(kThreads) void k_window_best(ChainState S, int64_t 
   if (l == 0) prob[i] = bv;
   if (l < d) theta[i * d + l] = bs < 0 ? 0.0 : r.theta[(int64_t)r.slot(bs) * d + l];
 }
+
+// mhx_get_fit_bands, first half: which steps walker-get-data-and-fit envelopes (M:1249-1251).
+// One wavefront per chain.  Candidates: ALL the steps the ring holds (the reference sorts the
+// whole walk); k = min(ceiling(0.66 take_c), held) of them, take_c = min(take, walker-length),
+// are selected - those of greatest prob, among equal probs the newer first, a NaN last.  A rank
+// problem on the prob column: the radix selection of select_percentile on the descending key
+// gives the threshold and how many steps AT the threshold belong, then one pass newest first
+// compacts the slots of the selected steps into sel[i][0 .. k) (ballot + prefix count, the
+// ties counted off as they come).  No sort.
+__device__ __forceinline__ unsigned long long band_key(double v) {
+  if (v != v) return ~0ULL;
+  if (v == 0.0) v = 0.0;  // (-0 and +0 are one prob)
+  return ~order_key(v);
+}
+__global__ __launch_bounds__(kThreads) void k_band_select(ChainState S, int64_t c0, int64_t n,
+                                                         int take, int32_t* __restrict__ sel_all,
+                                                         int32_t* __restrict__ n_sel) {
+  const int w = wave_in_group(), l = lane_id();
+  const int64_t i = (int64_t)blockIdx.x * kWavesPerGroup + w;
+  if (i >= n) return;
+  const Ring r = ring_of(S, c0 + i);
+  const int held = ring_held(r, S.R);
+  const int64_t take_c = r.length < (int64_t)take ? r.length : (int64_t)take;
+  int64_t want = take_c >= 1 ? band_count_of(take_c) : 0;
+  const int k = (int)(want < (int64_t)held ? want : (int64_t)held);
+  if (l == 0) n_sel[i] = k;
+  if (k <= 0) return;
+  int32_t* sel = sel_all + i * take;
+  auto key_at = [&](int s) { return band_key(r.prob[r.slot(s)]); };
+  // the key of rank k - 1 and that rank's place among the steps that share it
+  unsigned long long prefix = 0, mask = 0;
+  int rank = k - 1;
+  for (int b = 63; b >= 0; --b) {
+    const unsigned long long bit = 1ULL << b;
+    int cnt = 0;
+    for (int s = l; s < held; s += kWave) {
+      const unsigned long long key = key_at(s);
+      cnt += ((key & mask) == prefix && (key & bit) == 0) ? 1 : 0;
+    }
+    const int z = __builtin_amdgcn_readfirstlane(wave_sum_i(cnt));
+    if (rank >= z) {
+      rank -= z;
+      prefix |= bit;
+    }
+    mask |= bit;
+  }
+  const int ties = rank + 1;  // steps at the threshold that belong: the newest `ties` of them
+  int pos = 0, seen = 0;
+  for (int base = 0; base < held; base += kWave) {
+    const int s = base + l;
+    const unsigned long long key = s < held ? key_at(s) : ~0ULL;
+    const bool in = s < held;
+    const bool eq = in && key == prefix;
+    const unsigned long long me = __ballot(eq);
+    const unsigned long long below = (1ULL << l) - 1ULL;
+    const bool f = in && (key < prefix || (eq && seen + __popcll(me & below) < ties));
+    const unsigned long long mf = __ballot(f);
+    if (f) sel[pos + __popcll(mf & below)] = r.slot(s);
+    pos += __popcll(mf);
+    seen += __popcll(me);
+  }
+}
 #endif  // MHX_FAMILY_PRIMARY
+
+// mhx_eval_function and the second half of mhx_get_fit_bands: ONE kernel, so that a band is made
+// of the very bits mhx_eval_function returns.  Wave g serves item g / n_chunks (a parameter
+// vector, or a chain and its selected steps: FitArgs, mhx_types.hpp) and chunk g % n_chunks of
+// the m points: kFitPts x per lane, kept in registers with a running max and min each.  Per step:
+// the parameter vector goes to the wave's LDS row (the next step's is on its way from memory
+// meanwhile), ONE Model::prepare with the parameters in scalar registers, then the model's
+// guarded direct form at the lane's x (Spec::values).  max / min do not depend on the order of
+// the steps.  Dynamic LDS only (the math tables lead it).
+struct FitLds {
+  LdsHead head;
+  double th[kWavesPerGroup][MHX_MAX_PARAMS + 1];
+  double scr[kWavesPerGroup][MHX_MAX_FN_PARAMS + 4];  // (model_wants_scratch, the DYN models)
+};
+static_assert(sizeof(FitLds) == fit_lds_bytes(kWavesPerGroup), "fit_lds_bytes (mhx_types.hpp)");
+static_assert(__builtin_offsetof(FitLds, head) == 0, "the tables must lead the dynamic LDS");
+template <class Spec>
+__device__ __forceinline__ void k_fit_body(const ProblemDesc* __restrict__ Pp, FitArgs A) {
+  FitLds& lds = *reinterpret_cast<FitLds*>(mhx_lds_raw);
+  lds_tables_begin();
+  __syncthreads();  // (the only barrier: waves without work leave behind it)
+  const int w = wave_in_group(), l = lane_id();
+  const int64_t g = (int64_t)blockIdx.x * kWavesPerGroup + w;
+  if (g >= A.n * A.n_chunks) return;
+  const int64_t i = g / A.n_chunks;
+  const int64_t p0 = (g - i * A.n_chunks) * (int64_t)(kWave * kFitPts) + l;
+  const FnDesc& f = Pp->fn[A.fn];
+  const int d = Pp->d;
+  double x0[kFitPts], x1[kFitPts], mx[kFitPts], mn[kFitPts];
+#pragma unroll
+  for (int j = 0; j < kFitPts; ++j) {
+    const int64_t p = p0 + (int64_t)j * kWave;
+    const int64_t q = p < A.m ? p : A.m - 1;  // (beyond m: the last point once more, never stored)
+    x0[j] = A.x0[q];
+    x1[j] = A.x1 ? A.x1[q] : 0.0;
+    mx[j] = mn[j] = 0.0;
+  }
+  const int ns = A.sel ? __builtin_amdgcn_readfirstlane(A.n_sel[i]) : 1;
+  const int32_t* sl = A.sel ? A.sel + i * A.sel_pitch : nullptr;
+  const int64_t base = A.row0 + i * A.rows_per_item;
+  double* th = lds.th[w];
+  double thn = 0.0;
+  if (ns > 0 && l < d) thn = A.theta[(base + (sl ? (int64_t)sl[0] : 0)) * d + l];
+  bool bad = false;
+  for (int k = 0; k < ns; ++k) {
+    if (l < d) th[l] = thn;
+    __builtin_amdgcn_wave_barrier();
+    if (k + 1 < ns && l < d) thn = A.theta[(base + (int64_t)sl[k + 1]) * d + l];
+    auto pf = [&](int j) -> double { return th[f.idx[j]]; };
+    double v[kFitPts];
+    Spec::template values<kFitPts>(f, pf, lds.scr[w], x0, x1, v);
+#pragma unroll
+    for (int j = 0; j < kFitPts; ++j) {
+      bad = bad || !finite_f64(v[j]);
+      mx[j] = (k == 0 || v[j] > mx[j]) ? v[j] : mx[j];
+      mn[j] = (k == 0 || v[j] < mn[j]) ? v[j] : mn[j];
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < kFitPts; ++j) {
+    const int64_t p = p0 + (int64_t)j * kWave;
+    if (p < A.m) {
+      A.ymax[i * A.m + p] = mx[j];
+      if (A.ymin) A.ymin[i * A.m + p] = mn[j];
+    }
+  }
+  if (A.status && __ballot(bad) != 0ULL && l == 0) A.status[i] = 1;
+}
+#ifndef __HIPCC_RTC__
+template <class Spec>
+__global__ __launch_bounds__(kThreads) void k_fit(const ProblemDesc* __restrict__ Pp, FitArgs A) {
+  k_fit_body<Spec>(Pp, A);
+}
+#endif
 
 }  // inline namespace MHX_FAMILY
 }  // namespace mhx

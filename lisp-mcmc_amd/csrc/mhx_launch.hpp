@@ -103,4 +103,13 @@ hipError_t launch_l_matrices(hipStream_t st, const ChainState& S, int64_t c0, in
 hipError_t launch_window_best(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
                               double* prob, double* theta);
 
+// mhx_eval_function / mhx_get_fit_bands: the steps every chain's band envelopes (sel [n][take]
+// ring slots, n_sel [n]), and the model values / envelopes themselves (FitArgs, mhx_types.hpp)
+// for the ahead-of-time specs; run-time compiled problems go through rtc_launch_fit.
+inline int fit_chunks(int64_t m) { return (int)((m + kWave * kFitPts - 1) / (kWave * kFitPts)); }
+hipError_t fit_configure();
+hipError_t launch_band_select(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
+                              int32_t* sel, int32_t* n_sel);
+hipError_t launch_fit(int spec, hipStream_t st, const ProblemDesc* P, const FitArgs& A);
+
 }  // namespace mhx

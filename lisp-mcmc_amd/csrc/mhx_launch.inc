@@ -292,6 +292,32 @@ hipError_t launch_window_best(hipStream_t st, const ChainState& S, int64_t c0, i
   return hipGetLastError();
 }
 
+// mhx_eval_function / mhx_get_fit_bands (k_band_select, k_fit): compiled in this family only,
+// whichever family steps the problem - a wave is an item and a chunk of x in either
+hipError_t fit_configure() {
+  hipError_t e = hipSuccess;
+  for (int s = 0; s < SPEC__COUNT; ++s)
+    for_spec(s, [&](auto sp) {
+      using SpecT = decltype(sp);
+      if (e == hipSuccess) e = no_static_lds(&k_fit<SpecT>);
+    });
+  return e;
+}
+hipError_t launch_band_select(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
+                              int32_t* sel, int32_t* n_sel) {
+  if (n <= 0) return hipSuccess;
+  k_band_select<<<grid_for(n), dim3(kThreads), 0, st>>>(S, c0, n, take, sel, n_sel);
+  return hipGetLastError();
+}
+hipError_t launch_fit(int spec, hipStream_t st, const ProblemDesc* P, const FitArgs& A) {
+  if (A.n <= 0 || A.m <= 0) return hipSuccess;
+  for_spec(spec, [&](auto sp) {
+    using SpecT = decltype(sp);
+    k_fit<SpecT><<<grid_for(A.n * A.n_chunks), dim3(kThreads), fit_lds_bytes(kWavesPerGroup), st>>>(P, A);
+  });
+  return hipGetLastError();
+}
+
 const char* spec_name(int spec) {
   static const char* names[] = {"generic",      "gauss22_normal", "gauss15_poisson",
                                            "pvoigt2_normal", "poly2_normal",   "poly8_normal",

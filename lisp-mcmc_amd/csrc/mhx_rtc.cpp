@@ -284,6 +284,17 @@ static std::string generate(const std::vector<UserExpr>& models,
         << ">::loglik_part(f, pf, p0, p1, scratch);\n";
   }
   s << "      default: (void)scratch; return 0.0;\n    }\n  }\n"
+       "  template <int PTS, class PF>\n"
+       "  static __device__ __forceinline__ void values(const FnDesc& f, PF pf, double* scratch,\n"
+       "      const double (&x0)[PTS], const double (&x1)[PTS], double (&v)[PTS]) {\n"
+       "    switch (f.user_slot) {\n";
+  for (size_t m = 0; m < models.size(); ++m)
+    s << "      case " << m << ": return model_values<UserModel" << m
+      << ", PTS>(f, pf, scratch, x0, x1, v);\n";
+  s << (builtin_fallback
+            ? "      default: return GenericSpec::values<PTS>(f, pf, scratch, x0, x1, v);\n"
+            : "      default: (void)scratch; return;  // every function has a slot\n")
+    << "    }\n  }\n"
        "  static __device__ __forceinline__ double logprior(const FnDesc& f, const double* th,\n"
        "                                                    double bounds_total) {\n"
        "    switch (f.prior_slot) {\n";
@@ -305,6 +316,9 @@ static std::string generate(const std::vector<UserExpr>& models,
        "extern \"C\" __global__ __launch_bounds__(MHX_USER_THREADS) void mhx_user_logpost(\n"
        "    const ProblemDesc* P, const double* theta, int64_t n, double* out, double* parts) {\n"
        "  k_logpost_body<UserSpec>(P, theta, n, out, parts);\n}\n"
+       "extern \"C\" __global__ __launch_bounds__(MHX_USER_THREADS) void mhx_user_fit(\n"
+       "    const ProblemDesc* P, FitArgs A) {\n"
+       "  k_fit_body<UserSpec>(P, A);\n}\n"
        "extern \"C\" __global__ __launch_bounds__(MHX_USER_THREADS) void mhx_user_init(const ProblemDesc* P,\n"
        "                                                              ChainState S) {\n"
        "  k_init_body<UserSpec>(P, S);\n}\n"
@@ -527,6 +541,12 @@ static int build_once(const std::vector<UserExpr>& models, const std::vector<Use
       *err = std::string("module function ") + x.n + " has static LDS";
       return -1;
     }
+  he = hipModuleGetFunction(&prog->f_fit, prog->module, "mhx_user_fit");
+  if (he != hipSuccess || static_lds(prog->f_fit) != 0) {
+    *err = he != hipSuccess ? std::string("module function mhx_user_fit: ") + hipGetErrorString(he)
+                            : std::string("module function mhx_user_fit has static LDS");
+    return -1;
+  }
   prog->has_split = false;
   if (with_split) {
     he = hipModuleGetFunction(&prog->f_split_sweep, prog->module, "mhx_user_split_sweep");
@@ -633,6 +653,14 @@ hipError_t rtc_launch_logpost(const UserProgram& p, hipStream_t st, const Proble
   void* args[] = {(void*)&P, (void*)&theta, (void*)&n, (void*)&out, (void*)&parts};
   return hipModuleLaunchKernel(p.f_logpost, grid_for(p, n), 1, 1, (unsigned)p.fam->threads, 1, 1,
                                (unsigned)p.fam->lds_bytes, st, args, nullptr);
+}
+hipError_t rtc_launch_fit(const UserProgram& p, hipStream_t st, const ProblemDesc* P,
+                          const FitArgs& A) {
+  if (A.n <= 0 || A.m <= 0) return hipSuccess;
+  FitArgs a = A;
+  void* args[] = {(void*)&P, (void*)&a};
+  return hipModuleLaunchKernel(p.f_fit, grid_for(p, A.n * A.n_chunks), 1, 1, (unsigned)p.fam->threads,
+                               1, 1, fit_lds_bytes(p.fam->waves_per_group), st, args, nullptr);
 }
 hipError_t rtc_launch_init(const UserProgram& p, hipStream_t st, const ProblemDesc* P,
                            const ChainState& S) {

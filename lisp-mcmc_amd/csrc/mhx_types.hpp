@@ -155,6 +155,43 @@ struct PctList {
   int32_t num[MHX_MAX_PERCENTILES], den[MHX_MAX_PERCENTILES];
 };
 
+// walker-get-data-and-fit's count of enveloped steps, (ceiling (* 0.66 take)) M:1250
+// (include/mhx.h: mhx_band_count): 0.66 is a single float and so is the product.
+#ifndef __HIPCC_RTC__
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+inline int64_t band_count_of(int64_t take) {
+  const float p = 0.66f * (float)take;
+  return (int64_t)__builtin_ceilf(p);
+}
+#endif
+
+// k_fit (mhx_eval_function, mhx_get_fit_bands): the model of function `fn` at m points for n
+// items.  An item is ONE parameter vector (sel == nullptr: row row0 + i of theta; ymax receives
+// the values) or a chain's selected steps (rows row0 + i rows_per_item + sel[i sel_pitch + k],
+// k < n_sel[i]; ymax / ymin receive the envelope).  A wave serves one item and one chunk of
+// kWave x kFitPts points; n_chunks chunks cover m.
+constexpr int kFitPts = 8;  // x a lane keeps in registers, with a running max and min each
+struct FitArgs {
+  const double* theta;
+  const int32_t* sel;
+  const int32_t* n_sel;
+  int64_t row0, n;
+  int32_t rows_per_item, sel_pitch, fn, n_chunks;
+  const double* x0;  // [m]
+  const double* x1;  // [m] the second column of x, or nullptr
+  int64_t m;
+  double* ymax;      // [n][m]
+  double* ymin;      // [n][m] or nullptr
+  int32_t* status;   // [n] set to 1 where a value is not finite (zeroed by the host), or nullptr
+};
+// dynamic LDS of k_fit for a family of `wpg` waves per workgroup: the math tables, then per wave
+// the parameter vector and the model's scratch (FitLds, mhx_kernels.hpp)
+constexpr unsigned fit_lds_bytes(int wpg) {
+  return 6144u + (unsigned)wpg * (MHX_MAX_PARAMS + 1 + MHX_MAX_FN_PARAMS + 4) * 8u;
+}
+
 struct RunDesc {
   int64_t n, sts, temp_steps, mwl, tail;
   int32_t auto_mode, has_mwl, adapt_mode;

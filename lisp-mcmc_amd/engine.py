@@ -65,6 +65,43 @@ class _Summaries:
         return pr, th
 
 
+    def fit_bands(self, fn, take, x=None, m=None):
+        """walker-get-data-and-fit's envelopes for every chain (mhx_get_fit_bands): the greatest
+        and smallest value of function `fn` over each chain's band_count(take) most probable
+        steps, at the points x ([m] or [n_cols, m]; None: the function's own dataset x, `m` its
+        point count).  Returns ymax [n_chains, m], ymin [n_chains, m], n_selected, status."""
+        xa, xp, n_cols, m = _x_columns(self, fn, x, m)
+        ymax = np.zeros((self.n_chains, m))
+        ymin = np.zeros((self.n_chains, m))
+        nsel = np.zeros(self.n_chains, dtype=np.int32)
+        st = np.zeros(self.n_chains, dtype=np.int32)
+        capi.check(self._summary("fit_bands")(self._h, int(fn), int(take), xp, n_cols, m,
+                                              ymax.ctypes.data_as(capi.f64p),
+                                              ymin.ctypes.data_as(capi.f64p),
+                                              nsel.ctypes.data_as(capi.i32p),
+                                              st.ctypes.data_as(capi.i32p)))
+        return ymax, ymin, nsel, st
+
+
+def band_count(take):
+    """(ceiling (* 0.66 take)) M:1250 in the reference's single-float arithmetic (mhx_band_count)"""
+    k = C.c_int64(0)
+    capi.check(capi.lib().mhx_band_count(int(take), C.byref(k)))
+    return k.value
+
+
+def _x_columns(owner, fn, x, m):
+    """(array, pointer, n_cols, m) of the x argument of eval_function / fit_bands; x None: the
+    dataset of function fn as set_dataset saw it"""
+    if x is None:
+        pts, cols = getattr(owner, "_datasets", {}).get(int(fn), (0, 1))
+        return None, None, cols, int(pts if m is None else m)
+    xa = np.ascontiguousarray(x, dtype=np.float64)
+    if xa.ndim == 1:
+        xa = xa[None, :]
+    return xa, xa.ctypes.data_as(capi.f64p), int(xa.shape[0]), int(xa.shape[1])
+
+
 class Engine(_Summaries):
     def __init__(self, n_chains, n_params, n_functions=1, device=0, seed=0, chain_offset=0,
                  adapt_mode=capi.ADAPT_FAITHFUL, history_capacity=0, poisson_logfact_double=False):
@@ -128,6 +165,8 @@ class Engine(_Summaries):
         it (mcmc-fitting.lisp:1136-1137): mhx_set_dataset_cols"""
         xa, xp = capi.as_f64(x)
         ya, yp = capi.as_f64(y)
+        # (points, columns of x): what eval_function / fit_bands take for x=None
+        self.__dict__.setdefault("_datasets", {})[int(k)] = (int(ya.size), xa.shape[1] if xa.ndim == 2 else 1)
         if xa.ndim == 2 and xa.shape[0] == ya.shape[0] and ya.ndim == 1:
             cols = [np.ascontiguousarray(xa[:, j]) for j in range(xa.shape[1])]
             ptrs = (capi.f64p * len(cols))(*[c.ctypes.data_as(capi.f64p) for c in cols])
@@ -317,6 +356,20 @@ class Engine(_Summaries):
                                                       C.byref(nf)))
         return st.value, L, nf.value
 
+    def eval_function(self, fn, theta, x=None, m=None, n_cols=None):
+        """function `fn` of the problem at the points x ([m] or [n_cols, m]; None: the function's
+        own dataset x, `m` its point count) for the full parameter vectors theta [n, d] or [d]:
+        [n, m] (or [m]) model values (mhx_eval_function)"""
+        th = np.ascontiguousarray(theta, dtype=np.float64)
+        one = th.ndim == 1
+        th = th.reshape(-1, self.d)
+        xa, xp, nc, m = _x_columns(self, fn, x, m)
+        out = np.zeros((th.shape[0], m))
+        capi.check(capi.lib().mhx_eval_function(self._h, int(fn), th.ctypes.data_as(capi.f64p),
+                                                th.shape[0], xp, nc if n_cols is None else n_cols,
+                                                m, out.ctypes.data_as(capi.f64p)))
+        return out[0] if one else out
+
     def history_capacity(self):
         """steps the device ring of every chain holds: the greatest `take`"""
         n = C.c_int32(0)
@@ -444,6 +497,7 @@ class Group(_Summaries):
     def set_dataset(self, k, x, y, sigma=None, likelihood=capi.LIK_NORMAL):
         xa, xp = capi.as_f64(x)
         ya, yp = capi.as_f64(y)
+        self.__dict__.setdefault("_datasets", {})[int(k)] = (int(ya.size), 1)
         sp = None
         if sigma is not None:
             sa, sp = capi.as_f64(np.broadcast_to(np.asarray(sigma, dtype=np.float64), xa.shape))

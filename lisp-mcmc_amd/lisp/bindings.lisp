@@ -191,6 +191,16 @@ library, or without a gfx950 device, walker-create signals MHX-ERROR."
   (g :pointer) (take :int) (l-out :pointer) (status :pointer) (n-forward :pointer))
 (cffi:defcfun ("mhx_group_get_window_best" %mhx-group-get-window-best) :int
   (g :pointer) (take :int) (prob :pointer) (theta :pointer))
+(cffi:defcfun ("mhx_band_count" %mhx-band-count) :int (take :int64) (k :pointer))
+(cffi:defcfun ("mhx_eval_function" %mhx-eval-function) :int
+  (e :pointer) (fn :int) (theta :pointer) (n :int64) (xcols :pointer) (n-cols :int) (m :int64)
+  (out :pointer))
+(cffi:defcfun ("mhx_get_fit_bands" %mhx-get-fit-bands) :int
+  (e :pointer) (fn :int) (take :int) (xcols :pointer) (n-cols :int) (m :int64) (ymax :pointer)
+  (ymin :pointer) (n-selected :pointer) (status :pointer))
+(cffi:defcfun ("mhx_group_get_fit_bands" %mhx-group-get-fit-bands) :int
+  (g :pointer) (fn :int) (take :int) (xcols :pointer) (n-cols :int) (m :int64) (ymax :pointer)
+  (ymin :pointer) (n-selected :pointer) (status :pointer))
 
 (defmacro with-c-call (&body body)
   "HIP/RCCL runtime code may raise inexact/invalid flags that SBCL turns into conditions;

@@ -17,6 +17,7 @@
    #:walker-adaptive-steps #:walker-adaptive-steps-full #:walker-many-steps
    #:walker-take-step #:walker-take-step-injected #:walker-get #:walker-set-get #:walker-modify
    #:walker-destroy
+   #:walker-get-data-and-fit #:walker-get-data-and-fit-no-stddev #:walker-get-residuals
    #:walker-save #:walker-load #:diagonal-covariance
    #:mfit-walker-estop #:request-stop
    ;; likelihood / prior designators

@@ -685,6 +685,121 @@ condition is signalled for the first chain walker-get would signal it for, as ma
                                              append (list k (aref l i i))))))))))
         (t (per-chain))))))
 
+;;; ------------------------------------------------------------------ data and fit M:1208-1283
+;;; The numbers behind the reference's plots.  The :function lives on the device, so the fit
+;;; curve is mhx_eval_function and the envelope of the model over the most probable two thirds of
+;;; the walk is mhx_get_fit_bands: no history crosses to the host.  :chain selects a member of a
+;;; batched walker.
+(defun %even-grid (low high count)
+  "COUNT doubles from LOW to HIGH inclusive: exact rationals, made doubles at the end"
+  (let ((step (/ (cl:rational (- high low)) (1- count)))
+        (origin (cl:rational low)))
+    (loop for i below count
+          collect (coerce (+ origin (* i step)) 'double-float))))
+
+(defun %parameter-vector (walker plist)
+  (loop for k in (walker-param-keys walker) collect (getf plist k)))
+
+(defun %model-values (walker fn-number plist xs)
+  "function FN-NUMBER at the parameters PLIST: at the list XS, or at its own dataset's x (XS nil)"
+  (let* ((d (walker-n-params walker))
+         (m (if xs
+                (length xs)
+                (length (first (elt (walker-data walker) fn-number))))))
+    (cffi:with-foreign-objects ((th :double d) (xp :double m) (out :double m))
+      (fill-doubles th (%parameter-vector walker plist))
+      (when xs (fill-doubles xp xs))
+      (with-c-call
+        (check (%mhx-eval-function (first (all-engines walker)) fn-number th 1
+                                   (if xs xp (cffi:null-pointer)) 1 m out)))
+      (coerce (read-doubles out m) 'list))))
+
+(defun %clamped-take (walker take chain)
+  (let ((len (walker-length walker chain)))
+    (if (or (null take) (> take len)) len take)))
+
+(defun %solution (walker which-solution take chain)
+  (case which-solution
+    (:most-likely (walker-step-params
+                   (walker-get walker :get :most-likely-step :take take :chain chain)))
+    (t (walker-get walker :get :median-params :take take :chain chain))))
+
+(defun %shifted (values shift)
+  (if shift (mapcar (lambda (v) (+ shift v)) values) values))
+
+(defun walker-get-data-and-fit-no-stddev (walker &key (take 1000) (x-column 0) (y-column 1)
+                                                   (fn-number 0)
+                                                   (which-solution (or :most-likely :median))
+                                                   x-shift y-shift (chain 0))
+  "-> (x-fit y-fit x-data y-data params): the fit on 1000 points between the data's least and
+greatest x at the chosen solution"
+  (let* ((take (%clamped-take walker take chain))
+         (data (elt (walker-data walker) fn-number))
+         (x-data (elt data x-column))
+         (y-data (elt data y-column))
+         (x-fit (%even-grid (reduce #'min x-data) (reduce #'max x-data) 1000))
+         (params (%solution walker which-solution take chain))
+         (y-fit (%model-values walker fn-number params x-fit)))
+    (list (%shifted x-fit x-shift) (%shifted y-fit y-shift)
+          (%shifted x-data x-shift) (%shifted y-data y-shift) params)))
+
+(defun walker-get-data-and-fit (walker &key (take 1000) (x-column 0) (y-column 1) (fn-number 0)
+                                         (which-solution (or :most-likely :median))
+                                         x-shift y-shift (chain 0))
+  "-> (x-fit max-ys min-ys y-fit x-data y-data params): as above, with the greatest and smallest
+model value at every x-fit over the (ceiling (* 0.66 take)) most probable steps of the walk"
+  (destructuring-bind (x-fit-shifted y-fit-shifted x-data-shifted y-data-shifted params)
+      (walker-get-data-and-fit-no-stddev walker :take take :x-column x-column :y-column y-column
+                                                :fn-number fn-number
+                                                :which-solution which-solution
+                                                :x-shift x-shift :y-shift y-shift :chain chain)
+    (let* ((n (walker-n-chains walker))
+           (m 1000)
+           (x-data (elt (elt (walker-data walker) fn-number) x-column))
+           (x-fit (%even-grid (reduce #'min x-data) (reduce #'max x-data) m))
+           (ring (cffi:with-foreign-object (cap :int32)
+                   (with-c-call
+                     (check (%mhx-get-history-capacity (first (all-engines walker)) cap)))
+                   (cffi:mem-ref cap :int32)))
+           (take (%clamped-take walker take chain))
+           (ymax (cffi:foreign-alloc :double :count (* n m)))
+           (ymin (cffi:foreign-alloc :double :count (* n m))))
+      (when (> (walker-length walker chain) ring)
+        (warn "walker-get-data-and-fit :take ~d: the device history ring holds the newest ~d steps of a walk; create the walker with :history-capacity >= the walk's length to keep them all"
+              take ring))
+      (unwind-protect
+           (cffi:with-foreign-objects ((xp :double m) (st :int32 n))
+             (fill-doubles xp x-fit)
+             (%set-call walker #'%mhx-get-fit-bands #'%mhx-group-get-fit-bands
+                        fn-number (max 1 (min take ring)) xp 1 m ymax ymin (cffi:null-pointer) st)
+             (unless (zerop (cffi:mem-aref st :int32 chain))
+               (error 'floating-point-invalid-operation
+                      :operation 'walker-get-data-and-fit :operands (list :chain chain)))
+             (flet ((row (ptr)
+                      (loop for i below m
+                            collect (+ (if y-shift y-shift 0)
+                                       (cffi:mem-aref ptr :double (+ (* chain m) i))))))
+               (list x-fit-shifted (row ymax) (row ymin) y-fit-shifted x-data-shifted
+                     y-data-shifted params)))
+        (cffi:foreign-free ymax)
+        (cffi:foreign-free ymin)))))
+
+(defun walker-get-residuals (walker &key (take 1000) (x-column 0) (y-column 1) (fn-number 0)
+                                      (chain 0))
+  "-> (x-data residuals stddev): the model at the median parameters minus the data, at the
+data's own x - what walker-plot-residuals draws"
+  (let* ((take (%clamped-take walker take chain))
+         (data (elt (walker-data walker) fn-number))
+         (x-data (elt data x-column))
+         (y-data (elt data y-column))
+         (stddev (elt (walker-data-error walker) fn-number))
+         (stddev (if (= 1 (length stddev))
+                     (make-list (length x-data) :initial-element (elt stddev 0))
+                     stddev))
+         (params (walker-get walker :get :median-params :take take :chain chain))
+         (y-fit (%model-values walker fn-number params nil)))
+    (list x-data (mapcar #'- y-fit y-data) stddev)))
+
 ;;; ------------------------------------------------------------------ save / load M:971-1001
 ;;; The plist the reference's (commented) walker-construct-print-list builds, written and read
 ;;; under with-standard-io-syntax; functions are only NAMED in the file, so walker-load wants

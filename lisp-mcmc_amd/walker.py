@@ -11,6 +11,9 @@ walker-adaptive-steps path (M: = mcmc-fitting.lisp):
     walker-take-step             M:1072-1095   walker_take_step
     walker-get                   M:487-543     walker_get
     walker-set-get               M:1029-1030   walker_set_get
+    walker-get-data-and-fit      M:1230-1255   walker_get_data_and_fit (+ _no_stddev M:1208-1227,
+                                               walker_get_residuals M:1271-1283,
+                                               walker_set_get_data_and_fit)
     walker-modify                M:547-580     walker_modify
     prior-bounds-let             M:346-369     prior_bounds
     mfit-walker-estop            M:860-861     request_stop
@@ -545,6 +548,134 @@ def walker_set_get(walker, get=":steps", take=None, param=None):
     if short:
         truncated(ring, widest, short)
     return out
+
+
+def fit_linspace(lo, hi, n=1000):
+    """(linspace lo hi :len n) M:235-248: exact rationals from the double `hi - lo`, coerced to
+    double at the end"""
+    lo, hi = float(lo), float(hi)
+    step = Fraction(hi - lo) / (n - 1)
+    start = Fraction(lo)
+    return np.array([float(start + i * step) for i in range(n)])
+
+
+def _fit_inputs(walker, take, x_column, y_column, fn_number):
+    """what M:1232-1241 binds: the data columns and x-fit of one function"""
+    data = walker.data[fn_number]
+    x_data = np.asarray(data[x_column], dtype=np.float64)
+    y_data = np.asarray(data[y_column], dtype=np.float64)
+    if x_data.ndim != 1:
+        raise capi.MhxError(capi.EUNSUPPORTED, "walker-get-data-and-fit draws one column of x: "
+                            "a vector-valued x has no min and max (use Engine.eval_function)")
+    return x_data, y_data, fit_linspace(x_data.min(), x_data.max())
+
+
+def _fit_solution(walker, which_solution, take, chains=None):
+    """M:1243-1246 for every chain (chains None) or one: the parameter plists and their vectors"""
+    get = ":most-likely-step" if str(which_solution).lstrip(":").lower() == "most-likely" \
+        else ":median-params"
+    if chains is None:
+        sol = walker_set_get(walker, get, take)
+    else:
+        sol = [walker_get(walker, get, take, chain=chains)]
+    plists = [dict(s.params) if isinstance(s, WalkerStep) else s for s in sol]
+    th = np.array([[p[k] for k in walker.param_keys] for p in plists], dtype=np.float64)
+    return plists, th
+
+
+def _shift(v, by):
+    return list(v) if by is None else [by + float(a) for a in v]
+
+
+def _band_take(walker, take, lengths, who):
+    """the window the ring can serve, with walker_get's warning when the walk is longer"""
+    ring = walker.engine.history_capacity()
+    if int(lengths.max()) > ring:
+        warnings.warn(HistoryTruncated(
+            "%s :take %s: the device history ring holds the newest %d of the walk's %d steps; "
+            "create the walker with history_capacity >= the walk's length to keep them all"
+            % (who, take, ring, int(lengths.max()))), stacklevel=3)
+    return min(max(int(take), 1), ring)
+
+
+def walker_get_data_and_fit_no_stddev(walker, take=1000, x_column=0, y_column=1, fn_number=0,
+                                      which_solution=":most-likely", x_shift=None, y_shift=None,
+                                      chain=0):
+    """(walker-get-data-and-fit-no-stddev walker &key take x-column y-column fn-number
+    which-solution x-shift y-shift) M:1208-1227 -> [x_fit, y_fit, x_data, y_data, params]; the
+    model is evaluated by the device's own code (mhx_eval_function)."""
+    cap = walker.length(chain)
+    take = cap if take is None or take > cap else int(take)
+    x_data, y_data, x_fit = _fit_inputs(walker, take, x_column, y_column, fn_number)
+    plists, th = _fit_solution(walker, which_solution, take, chain)
+    y_fit = walker.engine.eval_function(fn_number, th[0], x_fit)
+    return [_shift(x_fit, x_shift), _shift(y_fit, y_shift), _shift(x_data, x_shift),
+            _shift(y_data, y_shift), plists[0]]
+
+
+def _data_and_fit(walker, take, x_column, y_column, fn_number, which_solution, x_shift, y_shift,
+                  chains, who):
+    e = walker.engine
+    lengths = e.state()["length"].astype(np.int64)
+    x_data, y_data, x_fit = _fit_inputs(walker, take, x_column, y_column, fn_number)
+    big = int(lengths.max()) if take is None else int(take)
+    # (every chain clamps `take` to its own length, M:1232-1234: on the device for the band, in
+    # walker_get / walker_set_get for the solution)
+    which = range(e.n_chains) if chains is None else [chains]
+    ymax, ymin, _, status = e.fit_bands(
+        fn_number, _band_take(walker, big, lengths[list(which)], who), x_fit)
+    bad = [c for c in which if status[c]]
+    if bad:
+        raise FloatingPointError(
+            "%s: the model is not finite at a step of walker(s) %s: the reference would have "
+            "signalled a floating-point trap here" % (who, bad[:8]))
+    plists, th = _fit_solution(walker, which_solution, take, chains)
+    y_fit = e.eval_function(fn_number, th, x_fit)
+    ys = 0 if y_shift is None else y_shift  # (+ (if y-shift y-shift 0) ...) M:1252-1253
+    out = []
+    for i, c in enumerate(which):
+        out.append([_shift(x_fit, x_shift), [ys + float(v) for v in ymax[c]],
+                    [ys + float(v) for v in ymin[c]], _shift(y_fit[i], y_shift),
+                    _shift(x_data, x_shift), _shift(y_data, y_shift), plists[i]])
+    return out
+
+
+def walker_get_data_and_fit(walker, take=1000, x_column=0, y_column=1, fn_number=0,
+                            which_solution=":most-likely", x_shift=None, y_shift=None, chain=0):
+    """(walker-get-data-and-fit walker &key take x-column y-column fn-number which-solution
+    x-shift y-shift) M:1230-1255 -> [x_fit, max_ys, min_ys, y_fit, x_data, y_data, params]:
+    the fit on 1000 points between the data's least and greatest x and the envelope of the model
+    over the ceiling(0.66 take) most probable steps of the walk, both computed on the device
+    (mhx_get_fit_bands, mhx_eval_function).  Raises FloatingPointError where the reference would
+    have trapped on a non-finite model value."""
+    return _data_and_fit(walker, take, x_column, y_column, fn_number, which_solution, x_shift,
+                         y_shift, int(chain), "walker-get-data-and-fit")[0]
+
+
+def walker_set_get_data_and_fit(walker, take=1000, x_column=0, y_column=1, fn_number=0,
+                                which_solution=":most-likely", x_shift=None, y_shift=None):
+    """walker-get-data-and-fit mapped over the set: entry c is what
+    walker_get_data_and_fit(..., chain=c) returns, from ONE fit_bands call, one eval_function
+    call and one walker_set_get."""
+    return _data_and_fit(walker, take, x_column, y_column, fn_number, which_solution, x_shift,
+                         y_shift, None, "walker-set-get-data-and-fit")
+
+
+def walker_get_residuals(walker, take=1000, x_column=0, y_column=1, fn_number=0, chain=0):
+    """the data of walker-plot-residuals M:1271-1283 without the plot: [x_data, y_fit - y_data,
+    stddev] at the median parameters over `take`; y_fit at the dataset's own x, which is on the
+    device already; a stddev of one number is spread over the points (M:1280)."""
+    cap = walker.length(chain)
+    take = cap if take is None or take > cap else int(take)
+    data = walker.data[fn_number]
+    x_data = np.asarray(data[x_column], dtype=np.float64)
+    y_data = np.asarray(data[y_column], dtype=np.float64)
+    sd = np.asarray(walker.data_error[fn_number], dtype=np.float64).reshape(-1)
+    if sd.size == 1:
+        sd = np.full(len(y_data), sd[0])
+    _, th = _fit_solution(walker, ":median", take, chain)
+    y_fit = walker.engine.eval_function(fn_number, th[0])
+    return [list(x_data), [float(a - b) for a, b in zip(y_fit, y_data)], list(sd)]
 
 
 def walker_modify(walker, modify=None, **kw):
