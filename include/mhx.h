@@ -26,6 +26,8 @@
  *   nth-percentile             M:1495-1506   -> mhx_percentile_rank (the position rule)
  *   walker-get-data-and-fit    M:1230-1255   -> mhx_eval_function, mhx_get_fit_bands,
  *                                               mhx_band_count, mhx_group_get_fit_bands
+ *   walker-with-exp            M:1052-1064   -> mhx_get_derived, mhx_group_get_derived (the
+ *                                               expression at every step, and its posterior)
  *   walker-modify              M:547-580     -> mhx_walker_modify (+ mhx_set_history)
  *   create-log-liklihood-function M:402-416  -> mhx_set_likelihood_expr
  *   prior-bounds-let           M:346-369     -> mhx_set_bounds (+ mhx_set_prior_expr)
@@ -68,6 +70,7 @@ extern "C" {
 #define MHX_MAX_FN_PARAMS 32 /* parameters one function gathers from the vector      */
 #define MHX_MAX_BOUNDS 64    /* bounds in one prior-bounds-let block                */
 #define MHX_MAX_PERCENTILES 16 /* percentiles one mhx_get_percentiles call may ask for */
+#define MHX_MAX_DERIVED 16   /* expressions one mhx_get_derived call may evaluate        */
 
 /* ---- status codes ------------------------------------------------------ */
 enum {
@@ -428,7 +431,7 @@ int mhx_get_window_best(mhx_engine* e, int take, double* prob, double* theta);
  * not below mhx_config.history_capacity and the adaptation window). */
 int mhx_get_history_capacity(mhx_engine* e, int32_t* capacity);
 /* HIP-event milliseconds the kernels of the engine's last mhx_get_percentiles / _covariances /
- * _proposal_factors / _window_best call ran (all portions; copies excluded). */
+ * _proposal_factors / _window_best / _fit_bands / _derived or mhx_eval_function call ran (all portions; copies excluded). */
 int mhx_get_summary_timing(mhx_engine* e, double* kernel_ms);
 /* The same for a group, gathered in global chain order like mhx_group_get_state; every
  * device's launch is enqueued before any is waited for. */
@@ -477,6 +480,53 @@ int mhx_get_fit_bands(mhx_engine* e, int fn, int take, const double* xcols, int 
 int mhx_group_get_fit_bands(mhx_group* g, int fn, int take, const double* xcols, int n_cols,
                             int64_t m, double* ymax, double* ymin, int32_t* n_selected,
                             int32_t* status);
+
+/* ---- walker-with-exp (M:1052-1064) and the posterior of the expression -----------------------
+ * The reference substitutes a walker's most-likely parameters into an expression and evaluates
+ * it: a peak area, a width, a ratio.  Here the n_expr expressions g_q are evaluated at EVERY step
+ * of every chain's window, on the device ring, and summarised there, so the quantity comes with
+ * its error bar.  exprs[q]: C syntax, the grammar of mhx_set_prior_expr - the identifiers in
+ * names (names[i] = theta[index[i]]), literals, the operators and functions listed at
+ * mhx_set_function_expr - plus `prob`, the step's log-posterior.  x, xcol0, xcol1, bounds_total
+ * and any unknown identifier: MHX_EINVAL, mhx_last_error names the identifier.  Evaluated without
+ * contraction with the engine's exp / log (< 1 ulp; MHX_EXPR_OCML_MATH=1: ocml's); every division
+ * is IEEE (a step is evaluated once: there is no reciprocal to hoist, MHX_EXPR_EXACT_DIV plays no
+ * part).  The expressions are compiled with hiprtc into a module of their own, kept - per process
+ * and on disk, as the expression models are - under the prepared texts and names: the same texts
+ * a second time compile nothing.
+ * The window is mhx_get_percentiles': the newest min(take, walker-length, steps held) steps,
+ * n_used[n_chains] as there; take in [1, history_capacity]; n_expr in [1, MHX_MAX_DERIVED];
+ * 0 <= n_pct <= MHX_MAX_PERCENTILES; any output may be NULL; MHX_ESTATE before mhx_init_chains; a
+ * chain in MHX_CHAIN_FP_TRAP is summarised from the history it has.
+ *   values[n_chains][n_expr][take]  values[c][q][s] = g_q at the step s-th from newest; entries
+ *                                   with s >= n_used[c] are not written
+ *   at_most_likely[n_chains][n_expr] g_q at the chain's most-likely step, the walker's own
+ *                                   (:most-likely-params M:511-515; mhx_get_state's best_theta,
+ *                                   `prob` = best_logpost) whatever take is: walker-with-exp
+ *   pct[n_chains][n_pct][n_expr]    nth-percentile (M:1495-1506) of the window's values: the rank
+ *                                   rule of mhx_percentile_rank, the order of mhx_get_percentiles
+ *                                   (a NaN last, -0 / +0 interchangeable); an element of the
+ *                                   ascending order or the IEEE mean of two neighbours
+ *   mean[n_chains][n_expr]          M:1518-1519: the serial sum newest first, one division
+ *   stddev[n_chains][n_expr]        standard-deviation M:1521-1527: the serial sum newest first of
+ *                                   (v - mean) * (v - mean), / (n - 1), sqrt.  With ONE step this
+ *                                   is the IEEE 0/0: a NaN (the reference divides by zero)
+ *   status[n_chains][n_expr]        1: a value of the window is not finite (the reference would
+ *                                   have trapped), else 0
+ * Worked through in portions whose device scratch stays below 64 MiB; mhx_get_summary_timing
+ * covers the call. */
+int mhx_get_derived(mhx_engine* e, const char* const* exprs, int n_expr, const char* const* names,
+                    const int32_t* index, int n_names, int take, const int32_t* pct_num,
+                    const int32_t* pct_den, int n_pct, double* at_most_likely, double* pct,
+                    double* mean, double* stddev, double* values, int32_t* n_used,
+                    int32_t* status);
+/* The same for a group, in global chain order; every device's work is enqueued before any is
+ * waited for. */
+int mhx_group_get_derived(mhx_group* g, const char* const* exprs, int n_expr,
+                          const char* const* names, const int32_t* index, int n_names, int take,
+                          const int32_t* pct_num, const int32_t* pct_den, int n_pct,
+                          double* at_most_likely, double* pct, double* mean, double* stddev,
+                          double* values, int32_t* n_used, int32_t* status);
 
 /* Restore a saved walk (walker-load, sketched in the comments M:987-1001): prob[n], theta[n][d]
  * NEWEST FIRST, as walker-save would have written them.  Sets the ring (newest

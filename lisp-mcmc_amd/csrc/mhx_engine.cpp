@@ -2546,6 +2546,225 @@ int mhx_get_fit_bands(mhx_engine* e, int fn, int take, const double* xcols, int 
   return fit_run({e}, {band_call(fn, take, xcols, n_cols, m, ymax, ymin, n_selected, status)});
 }
 
+// ---- walker-with-exp (M:1052-1064) and the posterior of the expression: derived quantities of
+// every chain on the device (mhx_user_derived, run-time compiled: mhx_derived.hpp; then
+// k_derived_summary).  A portion's pieces in the stage buffer: the values [n][ne][take], the
+// results, n_used; as many chains at a time as keep them below kSummaryStageBytes.
+struct DerivedCall {
+  int ne = 0, take = 0, n_names = 0;
+  std::vector<std::string> exprs, names;  // prepared texts; names as given
+  int32_t idx[MHX_MAX_PARAMS + 1] = {0};
+  PctList pc{};
+  std::shared_ptr<DerivedProgram> prog;  // of this call's engine's device
+  // host destinations of the engine's chain 0 (any may be NULL)
+  double *at_best = nullptr, *pct = nullptr, *mean = nullptr, *stddev = nullptr, *values = nullptr;
+  int32_t *n_used = nullptr, *status = nullptr;
+};
+struct DerivedPieces {
+  double *values, *at_best, *pct, *mean, *stddev;
+  int32_t *n_used, *status;
+  size_t bytes;
+};
+static size_t derived_per_chain(const DerivedCall& q) {
+  return ((size_t)q.ne * q.take + (size_t)q.ne * (3 + q.pc.n)) * sizeof(double) +
+         (size_t)(1 + q.ne) * sizeof(int32_t);
+}
+static int64_t derived_portion(const DerivedCall& q) {
+  return std::max<int64_t>(1, (int64_t)((kSummaryStageBytes - 7 * 256) / derived_per_chain(q)));
+}
+static DerivedPieces derived_pieces(mhx_engine* e, const DerivedCall& q, int64_t n) {
+  DerivedPieces s{};
+  size_t o = 0;
+  auto take_piece = [&](size_t bytes) {
+    unsigned char* p = e->stage.p + o;
+    o += align256(bytes);
+    return p;
+  };
+  const size_t ne = (size_t)q.ne;
+  s.values = reinterpret_cast<double*>(take_piece((size_t)n * ne * q.take * sizeof(double)));
+  s.at_best = reinterpret_cast<double*>(take_piece((size_t)n * ne * sizeof(double)));
+  s.pct = reinterpret_cast<double*>(take_piece((size_t)n * ne * q.pc.n * sizeof(double)));
+  s.mean = reinterpret_cast<double*>(take_piece((size_t)n * ne * sizeof(double)));
+  s.stddev = reinterpret_cast<double*>(take_piece((size_t)n * ne * sizeof(double)));
+  s.n_used = reinterpret_cast<int32_t*>(take_piece((size_t)n * sizeof(int32_t)));
+  s.status = reinterpret_cast<int32_t*>(take_piece((size_t)n * ne * sizeof(int32_t)));
+  s.bytes = o;
+  return s;
+}
+// the part of the arguments that needs no engine: texts and names
+static int derived_prepare(DerivedCall* q, const char* const* exprs, int n_expr,
+                           const char* const* names, const int32_t* index, int n_names, int take,
+                           const int32_t* pct_num, const int32_t* pct_den, int n_pct) {
+  if (n_expr < 1 || n_expr > MHX_MAX_DERIVED || !exprs)
+    return fail(MHX_EINVAL, "n_expr must be in [1,%d]", MHX_MAX_DERIVED);
+  if (n_names < 0 || n_names > MHX_MAX_PARAMS || (n_names > 0 && (!names || !index)))
+    return fail(MHX_EINVAL, "n_names must be in [0,%d]", MHX_MAX_PARAMS);
+  q->ne = n_expr;
+  q->take = take;
+  q->n_names = n_names;
+  for (int j = 0; j < n_names; ++j) {
+    if (!valid_ident(names[j]) || !strcmp(names[j], "prob"))
+      return fail(MHX_EINVAL, "name %d is not an identifier (or is x / bounds_total / prob)", j);
+    q->names.push_back(names[j]);
+    q->idx[j] = index[j];
+  }
+  for (int k = 0; k < n_expr; ++k) {
+    if (!exprs[k] || !*exprs[k]) return fail(MHX_EINVAL, "expression %d is empty", k);
+    std::string out, err;
+    if (rtc_prepare_expr(exprs[k], q->names, "prob", &out, &err) != 0)
+      return fail(MHX_EINVAL, "expression %d: %s", k, err.c_str());
+    q->exprs.push_back(out);
+  }
+  SummaryCall pcs;
+  const int rc = summary_fill_pcts(&pcs, pct_num, pct_den, n_pct);
+  q->pc = pcs.pc;
+  return rc;
+}
+static int derived_check(mhx_engine* e, DerivedCall* q) {
+  if (!e) return fail(MHX_EINVAL, "engine is NULL");
+  if (!e->chains_ready) return fail(MHX_ESTATE, "mhx_init_chains has not been called");
+  if (q->take < 1 || q->take > e->S.R)
+    return fail(MHX_EINVAL, "take must be in [1, history_capacity = %d]", e->S.R);
+  for (int j = 0; j < q->n_names; ++j)
+    if (q->idx[j] < 0 || q->idx[j] >= e->P.d)
+      return fail(MHX_EINVAL, "index[%d] = %d outside [0,%d)", j, q->idx[j], e->P.d);
+  const int rc = use_device(e);
+  if (rc != MHX_OK) return rc;
+  std::string err;
+  q->prog = rtc_get_derived(q->exprs, q->names, &err);
+  if (!q->prog) return fail(MHX_EINVAL, "%s", err.c_str());
+  return MHX_OK;
+}
+static int derived_enqueue(mhx_engine* e, const DerivedCall& q, int64_t c0, int64_t n) {
+  int rc = use_device(e);
+  if (rc != MHX_OK) return rc;
+  if ((rc = ensure_stage(e, derived_pieces(e, q, n).bytes)) != MHX_OK) return rc;
+  const DerivedPieces s = derived_pieces(e, q, n);
+  DerivedArgs A{};
+  A.c0 = c0;
+  A.n = n;
+  A.take = q.take;
+  A.pitch = q.take;
+  for (int j = 0; j < q.n_names; ++j) A.idx[j] = q.idx[j];
+  A.values = s.values;
+  A.at_best = s.at_best;
+  const bool lds = !e->knobs.summary_no_lds && pct_lds_bytes(q.take, q.ne) <= kPctLdsBudget;
+  HIP_TRY(hipEventRecord(e->ev0, e->stream));
+  HIP_TRY(rtc_launch_derived(*q.prog, e->stream, e->S, A));
+  HIP_TRY(launch_derived_summary(e->stream, e->S, c0, n, q.take, q.ne, q.pc, lds, s.values, s.pct,
+                                 s.mean, s.stddev, s.n_used, s.status));
+  HIP_TRY(hipEventRecord(e->ev1, e->stream));
+  e->launches += 2;
+  return MHX_OK;
+}
+static int derived_collect(mhx_engine* e, const DerivedCall& q, int64_t c0, int64_t n) {
+  int rc = use_device(e);
+  if (rc != MHX_OK) return rc;
+  const DerivedPieces s = derived_pieces(e, q, n);
+  HIP_TRY(hipEventSynchronize(e->ev1));
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
+  e->summary_ms += (double)ms;
+  const size_t ne = (size_t)q.ne;
+  auto back = [&](double* host, const double* dev, size_t per) -> hipError_t {
+    if (!host || per == 0) return hipSuccess;
+    return hipMemcpy(host + (size_t)c0 * per, dev, (size_t)n * per * sizeof(double), hipMemcpyDeviceToHost);
+  };
+  HIP_TRY(back(q.at_best, s.at_best, ne));
+  HIP_TRY(back(q.pct, s.pct, ne * q.pc.n));
+  HIP_TRY(back(q.mean, s.mean, ne));
+  HIP_TRY(back(q.stddev, s.stddev, ne));
+  if (q.status)
+    HIP_TRY(hipMemcpy(q.status + (size_t)c0 * ne, s.status, (size_t)n * ne * sizeof(int32_t),
+                      hipMemcpyDeviceToHost));
+  std::vector<int32_t> used;
+  if (q.n_used || q.values) {
+    used.resize((size_t)n);
+    HIP_TRY(hipMemcpy(used.data(), s.n_used, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (q.n_used) memcpy(q.n_used + c0, used.data(), (size_t)n * sizeof(int32_t));
+  }
+  if (q.values) {
+    // entries at and beyond n_used are not the caller's to lose: whole runs of full windows in
+    // one copy, a chain with a shorter window row by row
+    const size_t per = ne * (size_t)q.take;
+    int64_t a = 0;
+    while (a < n) {
+      int64_t b = a;
+      while (b < n && used[(size_t)b] == q.take) ++b;
+      if (b > a)
+        HIP_TRY(hipMemcpy(q.values + (size_t)(c0 + a) * per, s.values + (size_t)a * per,
+                          (size_t)(b - a) * per * sizeof(double), hipMemcpyDeviceToHost));
+      if (b < n) {
+        if (used[(size_t)b] > 0)
+          HIP_TRY(hipMemcpy2D(q.values + (size_t)(c0 + b) * per, (size_t)q.take * sizeof(double),
+                              s.values + (size_t)b * per, (size_t)q.take * sizeof(double),
+                              (size_t)used[(size_t)b] * sizeof(double), ne, hipMemcpyDeviceToHost));
+        ++b;
+      }
+      a = b;
+    }
+  }
+  return MHX_OK;
+}
+// calls[i] on engs[i]: round by round, every engine's portion enqueued before any is waited for
+static int derived_run(const std::vector<mhx_engine*>& engs, std::vector<DerivedCall>& calls) {
+  int rc = MHX_OK;
+  for (size_t i = 0; i < engs.size(); ++i)
+    if ((rc = derived_check(engs[i], &calls[i])) != MHX_OK) return rc;
+  std::vector<int64_t> at(engs.size(), 0), now(engs.size(), 0);
+  for (mhx_engine* e : engs) e->summary_ms = 0.0;
+  for (;;) {
+    bool any = false;
+    for (size_t i = 0; i < engs.size(); ++i) {
+      now[i] = std::min<int64_t>(engs[i]->cfg.n_chains - at[i], derived_portion(calls[i]));
+      if (now[i] <= 0) continue;
+      any = true;
+      if ((rc = derived_enqueue(engs[i], calls[i], at[i], now[i])) != MHX_OK) {
+        for (mhx_engine* e : engs) drain(e);
+        return rc;
+      }
+    }
+    if (!any) return MHX_OK;
+    for (size_t i = 0; i < engs.size(); ++i) {
+      if (now[i] <= 0) continue;
+      if ((rc = derived_collect(engs[i], calls[i], at[i], now[i])) != MHX_OK) {
+        for (mhx_engine* e : engs) drain(e);
+        return rc;
+      }
+      at[i] += now[i];
+    }
+  }
+}
+// the call of an engine whose chain 0 is the caller's chain `first`
+static DerivedCall derived_at(const DerivedCall& q0, size_t first, double* at_most_likely,
+                              double* pct, double* mean, double* stddev, double* values,
+                              int32_t* n_used, int32_t* status) {
+  DerivedCall q = q0;
+  const size_t ne = (size_t)q.ne;
+  q.at_best = at_most_likely ? at_most_likely + first * ne : nullptr;
+  q.pct = pct ? pct + first * ne * q.pc.n : nullptr;
+  q.mean = mean ? mean + first * ne : nullptr;
+  q.stddev = stddev ? stddev + first * ne : nullptr;
+  q.values = values ? values + first * ne * (size_t)q.take : nullptr;
+  q.n_used = n_used ? n_used + first : nullptr;
+  q.status = status ? status + first * ne : nullptr;
+  return q;
+}
+
+int mhx_get_derived(mhx_engine* e, const char* const* exprs, int n_expr, const char* const* names,
+                    const int32_t* index, int n_names, int take, const int32_t* pct_num,
+                    const int32_t* pct_den, int n_pct, double* at_most_likely, double* pct,
+                    double* mean, double* stddev, double* values, int32_t* n_used,
+                    int32_t* status) {
+  if (!e) return fail(MHX_EINVAL, "engine is NULL");
+  DerivedCall q0;
+  const int rc = derived_prepare(&q0, exprs, n_expr, names, index, n_names, take, pct_num, pct_den, n_pct);
+  if (rc != MHX_OK) return rc;
+  std::vector<DerivedCall> calls{
+      derived_at(q0, 0, at_most_likely, pct, mean, stddev, values, n_used, status)};
+  return derived_run({e}, calls);
+}
+
 int mhx_set_history(mhx_engine* e, int64_t chain, const double* prob, const double* theta, int n) {
   if (!e || !prob || !theta) return fail(MHX_EINVAL, "NULL argument");
   if (!e->chains_ready) return fail(MHX_ESTATE, "mhx_init_chains has not been called");
@@ -3088,6 +3307,22 @@ int mhx_group_get_fit_bands(mhx_group* g, int fn, int take, const double* xcols,
                               n_selected ? n_selected + f : nullptr, status ? status + f : nullptr));
   }
   return fit_run(g->eng, calls);
+}
+
+int mhx_group_get_derived(mhx_group* g, const char* const* exprs, int n_expr,
+                          const char* const* names, const int32_t* index, int n_names, int take,
+                          const int32_t* pct_num, const int32_t* pct_den, int n_pct,
+                          double* at_most_likely, double* pct, double* mean, double* stddev,
+                          double* values, int32_t* n_used, int32_t* status) {
+  if (!g) return fail(MHX_EINVAL, "group is NULL");
+  DerivedCall q0;
+  const int rc = derived_prepare(&q0, exprs, n_expr, names, index, n_names, take, pct_num, pct_den, n_pct);
+  if (rc != MHX_OK) return rc;
+  std::vector<DerivedCall> calls;
+  for (size_t i = 0; i < g->eng.size(); ++i)
+    calls.push_back(derived_at(q0, (size_t)g->first[i], at_most_likely, pct, mean, stddev, values,
+                               n_used, status));
+  return derived_run(g->eng, calls);
 }
 
 }  // extern "C"

@@ -3013,6 +3013,79 @@ __global__ __launch_bounds__(kPctThreads) void k_percentiles(ChainState S, int64
     }
 }
 
+// mhx_get_derived, second half: the posterior summaries of the values mhx_user_derived left in
+// the portion's staging buffer, vals [n][ne][pitch] newest first.  One workgroup of kPctWaves
+// wavefronts per chain, as k_percentiles, the expressions in the parameters' place.
+//   use_lds = 1: the t values of every expression are laid down as keys, one column of `tpad`
+//     slots each (read once, unit stride); the selections and the sums run from there
+//   use_lds = 0 (ne * tpad * 8 bytes do not fit): both read the staging buffer
+// mean M:1518-1519 and standard-deviation M:1521-1527: lane q of the LAST wave walks expression
+// q's column newest first - the serial sum, one division; then the serial sum of
+// (v - mean) * (v - mean), / (n - 1), sqrt (n = 1: 0/0, a NaN) - and notes a value that is not
+// finite (status).  A NaN read back from a key is the canonical one: any NaN makes both sums NaN.
+// pct [n][n_pct][ne], mean / stddev / status [n][ne], n_used [n].
+__global__ __launch_bounds__(kPctThreads) void k_derived_summary(
+    ChainState S, int64_t c0, int take, int ne, int pitch, PctList pc, int use_lds, int tpad,
+    const double* __restrict__ vals, double* __restrict__ pct, double* __restrict__ mean,
+    double* __restrict__ stddev, int32_t* __restrict__ n_used, int32_t* __restrict__ status) {
+  unsigned long long* col = reinterpret_cast<unsigned long long*>(mhx_lds_raw);
+  const int w = wave_in_group(), l = lane_id();
+  const int64_t i = blockIdx.x;
+  const Ring ring = ring_of(S, c0 + i);
+  const int t = ring_held(ring, take);
+  const double* v = vals + i * (int64_t)ne * pitch;
+  if (threadIdx.x == 0) n_used[i] = t;
+  if (use_lds) {
+    for (int q = 0; q < ne; ++q)
+      for (int s = threadIdx.x; s < t; s += kPctThreads)
+        col[(size_t)q * tpad + s] = order_key(v[(int64_t)q * pitch + s]);
+    __syncthreads();
+  }
+  if (w == kPctWaves - 1 && l < ne) {
+    const unsigned long long* cp = col + (size_t)l * tpad;
+    const double* vp = v + (int64_t)l * pitch;
+    auto at = [&](int s) -> double { return use_lds ? key_value(cp[s]) : vp[s]; };
+    double m = 0.0, sd = 0.0;
+    bool bad = false;
+    if (t > 0) {
+      double sum = at(0);
+      bad = !finite_f64(sum);
+      for (int s = 1; s < t; ++s) {
+        const double x = at(s);
+        bad = bad || !finite_f64(x);
+        sum = sum + x;
+      }
+      m = sum / (double)t;
+      double sq = (at(0) - m) * (at(0) - m);
+      for (int s = 1; s < t; ++s) {
+        const double u = at(s) - m;
+        sq = sq + u * u;
+      }
+      sd = __builtin_sqrt(sq / (double)(t - 1));
+    }
+    mean[i * ne + l] = m;
+    stddev[i * ne + l] = sd;
+    status[i * ne + l] = bad ? 1 : 0;
+  }
+  for (int q = w; q < ne; q += kPctWaves)
+    for (int k = 0; k < pc.n; ++k) {
+      double r = 0.0;
+      if (t > 0) {
+        int64_t pos;
+        int32_t between;
+        percentile_rank_of(t, pc.num[k], pc.den[k], &pos, &between);
+        if (use_lds) {
+          const unsigned long long* cp = col + (size_t)q * tpad;
+          r = select_percentile([&](int s) { return cp[s]; }, t, (int)pos, between != 0);
+        } else {
+          const double* vp = v + (int64_t)q * pitch;
+          r = select_percentile([&](int s) { return order_key(vp[s]); }, t, (int)pos, between != 0);
+        }
+      }
+      if (l == 0) pct[(i * pc.n + k) * ne + q] = r;
+    }
+}
+
 // mhx_get_covariances: :covariance-matrix M:541 = lplist-covariance (M:614-643) of :unique-steps
 // (M:492-496), one wavefront per chain.  uniq: [n][take] ring slots of the unique steps, newest
 // first (compacted in order like ring_forward_list); cov [n][d][d].

@@ -95,6 +95,12 @@ inline size_t pct_lds_bytes(int take, int d) {
 hipError_t summary_configure();
 hipError_t launch_percentiles(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
                               const PctList& pc, bool use_lds, double* out, int32_t* n_used);
+// mhx_get_derived, the summaries (k_derived_summary): vals [n][ne][take] as mhx_user_derived
+// left them; the keys of a chain go to LDS where pct_lds_bytes(take, ne) fits kPctLdsBudget
+hipError_t launch_derived_summary(hipStream_t st, const ChainState& S, int64_t c0, int64_t n,
+                                  int take, int ne, const PctList& pc, bool use_lds,
+                                  const double* vals, double* pct, double* mean, double* stddev,
+                                  int32_t* n_used, int32_t* status);
 hipError_t launch_covariances(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
                               int* uniq, double* cov, int32_t* n_unique, int32_t* status);
 hipError_t launch_l_matrices(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,

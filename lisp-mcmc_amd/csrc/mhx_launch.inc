@@ -259,8 +259,12 @@ const Family& MHX_CAT(family_, MHX_FAMILY)() {
 
 #ifdef MHX_FAMILY_PRIMARY  // family-independent helpers: defined by one unit only
 hipError_t summary_configure() {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_percentiles),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPctLdsBudget);
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_percentiles),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPctLdsBudget);
+  if (e == hipSuccess)
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_derived_summary),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPctLdsBudget);
+  return e;
 }
 hipError_t launch_percentiles(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
                               const PctList& pc, bool use_lds, double* out, int32_t* n_used) {
@@ -269,6 +273,18 @@ hipError_t launch_percentiles(hipStream_t st, const ChainState& S, int64_t c0, i
   if (lds > kPctLdsBudget) return hipErrorInvalidValue;
   k_percentiles<<<dim3((unsigned)n), dim3(kPctThreads), lds, st>>>(
       S, c0, take, pc, use_lds ? 1 : 0, pct_column_pitch(take, S.d), out, n_used);
+  return hipGetLastError();
+}
+hipError_t launch_derived_summary(hipStream_t st, const ChainState& S, int64_t c0, int64_t n,
+                                  int take, int ne, const PctList& pc, bool use_lds,
+                                  const double* vals, double* pct, double* mean, double* stddev,
+                                  int32_t* n_used, int32_t* status) {
+  if (n <= 0) return hipSuccess;
+  const size_t lds = use_lds ? pct_lds_bytes(take, ne) : 0;
+  if (lds > kPctLdsBudget) return hipErrorInvalidValue;
+  k_derived_summary<<<dim3((unsigned)n), dim3(kPctThreads), lds, st>>>(
+      S, c0, take, ne, take, pc, use_lds ? 1 : 0, pct_column_pitch(take, ne), vals, pct, mean,
+      stddev, n_used, status);
   return hipGetLastError();
 }
 hipError_t launch_covariances(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,

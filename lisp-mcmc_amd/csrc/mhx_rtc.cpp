@@ -424,6 +424,94 @@ static void cache_store(const std::string& key, const std::vector<char>& code) {
   if (!ok || rename(tmp.c_str(), path.c_str()) != 0) (void)remove(tmp.c_str());
 }
 
+// ---- source -> loaded module, through the on-disk cache ------------------------------------------
+struct EmbeddedHeader {
+  const char* src;
+  const char* name;
+};
+// what the stepping programs include (their cache keys hash exactly these, in this order)
+static const std::vector<EmbeddedHeader> kStepHeaders = {
+    {kSrc_mhx_kernels_hpp, "mhx_kernels.hpp"}, {kSrc_mhx_device_hpp, "mhx_device.hpp"},
+    {kSrc_mhx_types_hpp, "mhx_types.hpp"},     {kSrc_mhx_h, "../../include/mhx.h"},
+    {kSrc_mhx_exp2_table_inc, "mhx_exp2_table.inc"}, {kSrc_mhx_log_table_inc, "mhx_log_table.inc"}};
+// `defines`: the options after the fixed ones (MHX_RTC_FLAGS comes last).  *module is replaced.
+static int compile_module(const std::string& source, const std::vector<EmbeddedHeader>& headers,
+                          const std::vector<std::string>& defines, hipModule_t* module,
+                          std::string* log, std::string* err) {
+  Hiprtc& r = rtc();
+  std::vector<const char*> hdr_src, hdr_name;
+  for (const EmbeddedHeader& h : headers) {
+    hdr_src.push_back(h.src);
+    hdr_name.push_back(h.name);
+  }
+  // MHX_RTC_FLAGS: extra compiler options, blank separated (tuning experiments: -DMHX_PPI_MASKED=2 ...)
+  std::vector<std::string> extra;
+  if (const char* xf = getenv("MHX_RTC_FLAGS")) {
+    std::istringstream is(xf);
+    std::string w;
+    while (is >> w) extra.push_back(w);
+  }
+  std::vector<const char*> opts = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off"};
+  for (const std::string& x : defines) opts.push_back(x.c_str());
+  for (const std::string& x : extra) opts.push_back(x.c_str());
+  int vmaj = 0, vmin = 0;
+  if (r.Version) (void)r.Version(&vmaj, &vmin);
+  std::string key = "mhx-rtc-1|hiprtc " + std::to_string(vmaj) + "." + std::to_string(vmin) + "|";
+  for (const char* o : opts) key += std::string(o) + " ";
+  for (const char* h : hdr_src)
+    key += "|" + std::to_string((unsigned long long)fnv1a(h, 14695981039346656037ULL));
+  key += "|" + source;
+  std::vector<char> code;
+  bool from_cache = cache_load(key, &code);
+  if (from_cache) {  // a file that does not load (truncated, other driver) is dropped and rebuilt
+    if (*module) {
+      (void)hipModuleUnload(*module);
+      *module = nullptr;
+    }
+    if (hipModuleLoadData(module, code.data()) != hipSuccess) {
+      *module = nullptr;
+      (void)remove(cache_path(key).c_str());
+      from_cache = false;
+    }
+  }
+  if (!from_cache) {
+    hiprtcProgram p = nullptr;
+    int rc = r.CreateProgram(&p, source.c_str(), "mhx_user.hip", (int)hdr_src.size(), hdr_src.data(),
+                             hdr_name.data());
+    if (rc != 0) {
+      *err = std::string("hiprtcCreateProgram: ") + (r.GetErrorString ? r.GetErrorString(rc) : "?");
+      return -1;
+    }
+    rc = r.CompileProgram(p, (int)opts.size(), opts.data());
+    size_t ls = 0;
+    if (r.GetProgramLogSize(p, &ls) == 0 && ls > 1) {
+      log->resize(ls);
+      r.GetProgramLog(p, &(*log)[0]);
+    }
+    if (rc != 0) {
+      *err = "hiprtc compilation of the expression failed:\n" + log->substr(0, 3000);
+      r.DestroyProgram(&p);
+      return -1;
+    }
+    size_t cs = 0;
+    r.GetCodeSize(p, &cs);
+    code.resize(cs);
+    r.GetCode(p, code.data());
+    r.DestroyProgram(&p);
+    if (*module) {
+      (void)hipModuleUnload(*module);
+      *module = nullptr;
+    }
+    const hipError_t le = hipModuleLoadData(module, code.data());
+    if (le != hipSuccess) {
+      *err = std::string("hipModuleLoadData: ") + hipGetErrorString(le);
+      return -1;
+    }
+    cache_store(key, code);
+  }
+  return 0;
+}
+
 static int build_once(const std::vector<UserExpr>& models, const std::vector<UserExpr>& priors,
                       bool builtin_fallback, bool with_split, const Family& fam, int min_waves,
                       UserProgram* prog, std::string* err) {
@@ -439,82 +527,17 @@ static int build_once(const std::vector<UserExpr>& models, const std::vector<Use
       fclose(fp);
     }
   }
-  const char* hdr_src[] = {kSrc_mhx_kernels_hpp, kSrc_mhx_device_hpp, kSrc_mhx_types_hpp,
-                           kSrc_mhx_h, kSrc_mhx_exp2_table_inc, kSrc_mhx_log_table_inc};
-  const char* hdr_name[] = {"mhx_kernels.hpp", "mhx_device.hpp", "mhx_types.hpp",
-                            "../../include/mhx.h", "mhx_exp2_table.inc", "mhx_log_table.inc"};
   // the same family defines the ahead-of-time build of this workgroup shape gets (Makefile)
   const std::string wpg = "-DMHX_WPG=" + std::to_string(fam.waves_per_group);
   const std::string famns = "-DMHX_FAMILY=w" + std::to_string(fam.waves_per_group);
-  // MHX_RTC_FLAGS: extra compiler options, blank separated (tuning experiments: -DMHX_PPI_MASKED=2 ...)
-  std::vector<std::string> extra;
-  if (const char* xf = getenv("MHX_RTC_FLAGS")) {
-    std::istringstream is(xf);
-    std::string w;
-    while (is >> w) extra.push_back(w);
-  }
   // -DMHX_PPI_MASKED=2: the run-time-masked tile loops (more than two peaks) with 2 points per
   // iteration instead of the ahead-of-time build's 4.  Half the loop body: kernels loaded with
   // hipModuleLoadData lose far more than ahead-of-time ones once their hot loop outgrows the
   // instruction cache (bench.py --workload g23: 4.5e6 chain-steps/s with 4 points, 1.28e7 with 2;
   // the same kernel built ahead of time: 1.48e7 / 1.41e7).
-  std::vector<const char*> opts = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
-                                   wpg.c_str(), famns.c_str(), "-DMHX_PPI_MASKED=2"};
-  for (const std::string& x : extra) opts.push_back(x.c_str());
-  int vmaj = 0, vmin = 0;
-  if (r.Version) (void)r.Version(&vmaj, &vmin);
-  std::string key = "mhx-rtc-1|hiprtc " + std::to_string(vmaj) + "." + std::to_string(vmin) + "|";
-  for (const char* o : opts) key += std::string(o) + " ";
-  for (const char* h : hdr_src)
-    key += "|" + std::to_string((unsigned long long)fnv1a(h, 14695981039346656037ULL));
-  key += "|" + prog->source;
-  std::vector<char> code;
-  bool from_cache = cache_load(key, &code);
-  if (from_cache) {  // a file that does not load (truncated, other driver) is dropped and rebuilt
-    if (prog->module) {
-      (void)hipModuleUnload(prog->module);
-      prog->module = nullptr;
-    }
-    if (hipModuleLoadData(&prog->module, code.data()) != hipSuccess) {
-      prog->module = nullptr;
-      (void)remove(cache_path(key).c_str());
-      from_cache = false;
-    }
-  }
-  if (!from_cache) {
-    hiprtcProgram p = nullptr;
-    int rc = r.CreateProgram(&p, prog->source.c_str(), "mhx_user.hip", 6, hdr_src, hdr_name);
-    if (rc != 0) {
-      *err = std::string("hiprtcCreateProgram: ") + (r.GetErrorString ? r.GetErrorString(rc) : "?");
-      return -1;
-    }
-    rc = r.CompileProgram(p, (int)opts.size(), opts.data());
-    size_t ls = 0;
-    if (r.GetProgramLogSize(p, &ls) == 0 && ls > 1) {
-      prog->log.resize(ls);
-      r.GetProgramLog(p, &prog->log[0]);
-    }
-    if (rc != 0) {
-      *err = "hiprtc compilation of the expression failed:\n" + prog->log.substr(0, 3000);
-      r.DestroyProgram(&p);
-      return -1;
-    }
-    size_t cs = 0;
-    r.GetCodeSize(p, &cs);
-    code.resize(cs);
-    r.GetCode(p, code.data());
-    r.DestroyProgram(&p);
-    if (prog->module) {
-      (void)hipModuleUnload(prog->module);
-      prog->module = nullptr;
-    }
-    const hipError_t le = hipModuleLoadData(&prog->module, code.data());
-    if (le != hipSuccess) {
-      *err = std::string("hipModuleLoadData: ") + hipGetErrorString(le);
-      return -1;
-    }
-    cache_store(key, code);
-  }
+  if (compile_module(prog->source, kStepHeaders, {wpg, famns, "-DMHX_PPI_MASKED=2"}, &prog->module,
+                     &prog->log, err) != 0)
+    return -1;
   hipError_t he = hipSuccess;
   struct { hipFunction_t* f; const char* n; } fs[] = {{&prog->f_logpost, "mhx_user_logpost"},
                                                       {&prog->f_init, "mhx_user_init"},
@@ -743,6 +766,107 @@ hipError_t rtc_launch_adaptive(const UserProgram& p, hipStream_t st, const Probl
   return hipModuleLaunchKernel(p.f_adaptive, grid_for(p, S.slot_chain ? S.n_slots : S.n_chains), 1, 1,
                                (unsigned)p.fam->threads, 1, 1,
                                (unsigned)p.fam->lds_bytes, st, args, nullptr);
+}
+
+// ---- mhx_get_derived: walker-with-exp for every step of every chain (mhx_derived.hpp) ---------
+// A module of its own, one kernel: the stepping programs above neither contain it nor change
+// with it.  The source - and so both cache keys - is made of the prepared expression texts and
+// the names, in the caller's order; WHERE a name sits in theta is a kernel argument.
+DerivedProgram::~DerivedProgram() {
+  if (module) (void)hipModuleUnload(module);
+}
+static std::string generate_derived(const std::vector<std::string>& exprs,
+                                    const std::vector<std::string>& names) {
+  std::ostringstream s;
+  const bool ocml = getenv("MHX_EXPR_OCML_MATH") && atoi(getenv("MHX_EXPR_OCML_MATH")) != 0;
+  s << "#include \"mhx_derived.hpp\"\n"
+       "namespace mhx {\n"
+       "__device__ __forceinline__ double mhx_ux_min(double a, double b) { return a < b ? a : b; }\n"
+       "__device__ __forceinline__ double mhx_ux_max(double a, double b) { return a > b ? a : b; }\n"
+       "__device__ __forceinline__ double mhx_ux_ipow(double base, double pw) {\n"
+       "  int power = (int)pw; const bool neg = power < 0; if (neg) power = -power;\n"
+       "  int nextn = power >> 1; double total = (power & 1) ? base : 1.0;\n"
+       "  while (nextn != 0) { base = base * base; if (nextn & 1) total = base * total; nextn >>= 1; }\n"
+       "  return neg ? 1.0 / total : total;\n}\n"
+    << "__device__ __forceinline__ double mhx_ux_exp(double a) { return "
+    << (ocml ? "exp(a)" : "gexp(a)") << "; }\n"
+    << "__device__ __forceinline__ double mhx_ux_log(double a) { return "
+    << (ocml ? "(a > 0.0 ? log(a) : __builtin_nan(\"\"))" : "tlog(a)") << "; }\n"
+    // every division is IEEE: a step is evaluated once, there is no loop to hoist 1/b out of
+    << "struct DerivedExprs {\n"
+    << "  static constexpr int kN = " << exprs.size() << ", kP = " << names.size() << ";\n"
+    << "  static __device__ __forceinline__ void eval(const double* p, double prob, double* g) {\n"
+    << "    (void)p; (void)prob;\n";
+  for (size_t j = 0; j < names.size(); ++j)
+    s << "    const double p_" << names[j] << " = p[" << j << "]; (void)p_" << names[j] << ";\n";
+  for (size_t q = 0; q < exprs.size(); ++q)
+    s << "    g[" << q << "] = (double)(" << exprs[q] << ");\n";
+  s << "  }\n};\n}  // namespace mhx\n"
+       "using namespace mhx;\n"
+       "extern \"C\" __global__ __launch_bounds__(kDerivedThreads) void mhx_user_derived(\n"
+       "    ChainState S, DerivedArgs A) {\n"
+       "  k_derived_body<DerivedExprs>(S, A);\n}\n";
+  return s.str();
+}
+
+std::shared_ptr<DerivedProgram> rtc_get_derived(const std::vector<std::string>& exprs,
+                                                const std::vector<std::string>& names,
+                                                std::string* err) {
+  // (as rtc_get: the newest modules stay loaded for the life of the process, leaked on purpose)
+  constexpr size_t kCap = 48;
+  static std::mutex& mu = *new std::mutex;
+  static auto& cache = *new std::map<std::string, std::shared_ptr<DerivedProgram>>;
+  static auto& order = *new std::vector<std::string>;
+  if (!rtc().ok) {
+    *err = "libhiprtc.so could not be loaded: derived quantities need ROCm's hiprtc";
+    return nullptr;
+  }
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  const std::string source = generate_derived(exprs, names);
+  const std::string key = "dev" + std::to_string(dev) + "|" + source;
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = cache.find(key);
+  if (it != cache.end()) return it->second;
+  if (const char* dump = getenv("MHX_RTC_DUMP_DERIVED")) {  // the generated unit, for study
+    if (FILE* fp = fopen(dump, "w")) {
+      fputs(source.c_str(), fp);
+      fclose(fp);
+    }
+  }
+  std::shared_ptr<DerivedProgram> prog(new DerivedProgram());
+  std::vector<EmbeddedHeader> headers = kStepHeaders;
+  headers.push_back({kSrc_mhx_derived_hpp, "mhx_derived.hpp"});
+  // (the primary family's names: the kernel is one workgroup per chain whatever steps the problem)
+  if (compile_module(source, headers, {"-DMHX_WPG=8", "-DMHX_FAMILY=w8"}, &prog->module, &prog->log,
+                     err) != 0)
+    return nullptr;
+  hipError_t he = hipModuleGetFunction(&prog->f_derived, prog->module, "mhx_user_derived");
+  int lds = -1;
+  if (he == hipSuccess)
+    he = hipFuncGetAttribute(&lds, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, prog->f_derived);
+  if (he != hipSuccess || lds != 0) {
+    *err = he != hipSuccess ? std::string("module function mhx_user_derived: ") + hipGetErrorString(he)
+                            : std::string("module function mhx_user_derived has static LDS");
+    return nullptr;
+  }
+  if (order.size() >= kCap) {
+    cache.erase(order.front());
+    order.erase(order.begin());
+  }
+  cache[key] = prog;
+  order.push_back(key);
+  return prog;
+}
+
+hipError_t rtc_launch_derived(const DerivedProgram& p, hipStream_t st, const ChainState& S,
+                              const DerivedArgs& A) {
+  if (A.n <= 0) return hipSuccess;
+  ChainState s = S;
+  DerivedArgs a = A;
+  void* args[] = {(void*)&s, (void*)&a};
+  return hipModuleLaunchKernel(p.f_derived, (unsigned)A.n, 1, 1, (unsigned)kDerivedThreads, 1, 1,
+                               (unsigned)kDerivedLdsBytes, st, args, nullptr);
 }
 
 }  // namespace mhx

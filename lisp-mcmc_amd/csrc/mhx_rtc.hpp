@@ -104,4 +104,19 @@ hipError_t rtc_launch_persist_ts(const UserProgram& p, hipStream_t st, const Pro
                                  const FnDesc* slices, const ChainState& S, const RunDesc& R,
                                  int n_slices, int64_t max_iters, int plain);
 
+// mhx_get_derived: the module of one set of prepared expression texts over `names` (p_<name> in
+// the texts), kernel mhx_user_derived (mhx_derived.hpp), through the same process-wide and on-disk
+// caches as the stepping programs but never part of them.  nullptr and *err on error.
+struct DerivedProgram {
+  hipModule_t module = nullptr;
+  hipFunction_t f_derived = nullptr;
+  std::string log;
+  ~DerivedProgram();
+};
+std::shared_ptr<DerivedProgram> rtc_get_derived(const std::vector<std::string>& exprs,
+                                                const std::vector<std::string>& names,
+                                                std::string* err);
+hipError_t rtc_launch_derived(const DerivedProgram& p, hipStream_t st, const ChainState& S,
+                              const DerivedArgs& A);
+
 }  // namespace mhx

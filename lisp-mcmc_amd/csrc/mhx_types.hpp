@@ -192,6 +192,19 @@ constexpr unsigned fit_lds_bytes(int wpg) {
   return 6144u + (unsigned)wpg * (MHX_MAX_PARAMS + 1 + MHX_MAX_FN_PARAMS + 4) * 8u;
 }
 
+// mhx_user_derived (mhx_get_derived, mhx_derived.hpp): the expressions of one run-time compiled
+// module over the windows of the n chains from c0 on.  idx[j] = the place in theta of the j-th
+// name; values [n][n_expr][pitch] newest first, at_best [n][n_expr] (the most-likely step).
+struct DerivedArgs {
+  int64_t c0, n;
+  int32_t take, pitch;
+  int32_t idx[MHX_MAX_PARAMS + 1];
+  double* values;
+  double* at_best;
+};
+constexpr int kDerivedThreads = 256;  // one workgroup of four waves per chain, as k_percentiles
+constexpr unsigned kDerivedLdsBytes = 6144u;  // its dynamic LDS: LdsHead, the math tables
+
 struct RunDesc {
   int64_t n, sts, temp_steps, mwl, tail;
   int32_t auto_mode, has_mwl, adapt_mode;

@@ -82,6 +82,37 @@ class _Summaries:
                                               st.ctypes.data_as(capi.i32p)))
         return ymax, ymin, nsel, st
 
+    def derived(self, exprs, names, index, take, percentiles=(), values=False):
+        """walker-with-exp for every step of every chain, and its posterior (mhx_get_derived): the
+        C-syntax expressions `exprs` over names[i] = theta[index[i]] (and `prob`) on each chain's
+        newest `take` steps.  A dict of at_most_likely [n_chains, n_expr] (the expression at the
+        chain's most-likely step), pct [n_chains, len(percentiles), n_expr], mean and stddev
+        [n_chains, n_expr] (stddev is NaN for a one-step window), n_used [n_chains], status
+        [n_chains, n_expr] (1: a value of the window is not finite) and, with values=True, values
+        [n_chains, n_expr, take] newest first (NaN beyond n_used).  percentiles: numbers or
+        (num, den) pairs, as for percentiles()."""
+        exprs, names = list(exprs), list(names)
+        rat = [p if isinstance(p, tuple) else percentile_ratio(p) for p in percentiles]
+        num, nump = capi.as_i32([r[0] for r in rat] or [0])
+        den, denp = capi.as_i32([r[1] for r in rat] or [1])
+        idx, idxp = capi.as_i32(list(index) or [0])
+        ex = (C.c_char_p * max(len(exprs), 1))(*[t.encode() for t in exprs])
+        nm = (C.c_char_p * max(len(names), 1))(*[t.encode() for t in names])
+        n, ne = self.n_chains, len(exprs)
+        out = {"at_most_likely": np.zeros((n, ne)), "pct": np.zeros((n, len(rat), ne)),
+               "mean": np.zeros((n, ne)), "stddev": np.zeros((n, ne)),
+               "n_used": np.zeros(n, dtype=np.int32), "status": np.zeros((n, ne), dtype=np.int32)}
+        vp = None
+        if values:
+            out["values"] = np.full((n, ne, int(take)), np.nan)
+            vp = out["values"].ctypes.data_as(capi.f64p)
+        capi.check(self._summary("derived")(
+            self._h, ex, ne, nm, idxp, len(names), int(take), nump, denp, len(rat),
+            out["at_most_likely"].ctypes.data_as(capi.f64p), out["pct"].ctypes.data_as(capi.f64p),
+            out["mean"].ctypes.data_as(capi.f64p), out["stddev"].ctypes.data_as(capi.f64p), vp,
+            out["n_used"].ctypes.data_as(capi.i32p), out["status"].ctypes.data_as(capi.i32p)))
+        return out
+
 
 def band_count(take):
     """(ceiling (* 0.66 take)) M:1250 in the reference's single-float arithmetic (mhx_band_count)"""

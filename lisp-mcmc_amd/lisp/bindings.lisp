@@ -201,6 +201,16 @@ library, or without a gfx950 device, walker-create signals MHX-ERROR."
 (cffi:defcfun ("mhx_group_get_fit_bands" %mhx-group-get-fit-bands) :int
   (g :pointer) (fn :int) (take :int) (xcols :pointer) (n-cols :int) (m :int64) (ymax :pointer)
   (ymin :pointer) (n-selected :pointer) (status :pointer))
+(cffi:defcfun ("mhx_get_derived" %mhx-get-derived) :int
+  (e :pointer) (exprs :pointer) (n-expr :int) (names :pointer) (index :pointer) (n-names :int)
+  (take :int) (pct-num :pointer) (pct-den :pointer) (n-pct :int) (at-most-likely :pointer)
+  (pct :pointer) (mean :pointer) (stddev :pointer) (values :pointer) (n-used :pointer)
+  (status :pointer))
+(cffi:defcfun ("mhx_group_get_derived" %mhx-group-get-derived) :int
+  (g :pointer) (exprs :pointer) (n-expr :int) (names :pointer) (index :pointer) (n-names :int)
+  (take :int) (pct-num :pointer) (pct-den :pointer) (n-pct :int) (at-most-likely :pointer)
+  (pct :pointer) (mean :pointer) (stddev :pointer) (values :pointer) (n-used :pointer)
+  (status :pointer))
 
 (defmacro with-c-call (&body body)
   "HIP/RCCL runtime code may raise inexact/invalid flags that SBCL turns into conditions;

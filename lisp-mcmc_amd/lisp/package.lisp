@@ -18,6 +18,7 @@
    #:walker-take-step #:walker-take-step-injected #:walker-get #:walker-set-get #:walker-modify
    #:walker-destroy
    #:walker-get-data-and-fit #:walker-get-data-and-fit-no-stddev #:walker-get-residuals
+   #:walker-with-exp #:walker-exp-get #:walker-set-exp-get
    #:walker-save #:walker-load #:diagonal-covariance
    #:mfit-walker-estop #:request-stop
    ;; likelihood / prior designators

@@ -804,6 +804,106 @@ data's own x - what walker-plot-residuals draws"
 ;;; The plist the reference's (commented) walker-construct-print-list builds, written and read
 ;;; under with-standard-io-syntax; functions are only NAMED in the file, so walker-load wants
 ;;; the :function / :log-liklihood / :log-prior designators again, exactly as there.
+;;; ------------------------------------------------------------ derived quantities M:1052-1064
+;;; walker-with-exp is host work in a Lisp host: the most-likely parameters go into the form and
+;;; the form is evaluated, whatever it is.  Its posterior - the form at every step of the window,
+;;; then percentiles, mean and standard deviation - is mhx_get_derived: the form crosses as a
+;;; device expression (form->c) and no history crosses back.
+(defun %with-parameters (form plist)
+  "FORM with every keyword replaced by its value in PLIST"
+  (cond ((keywordp form) (getf plist form))
+        ((consp form) (cons (%with-parameters (car form) plist)
+                            (%with-parameters (cdr form) plist)))
+        (t form)))
+
+(defun walker-with-exp (walker exp &key (take 1000))
+  "EXP, a form whose keywords name parameters of WALKER - (* :a1 :w1 (sqrt pi)) - evaluated with
+the walker's most-likely parameters in their place"
+  (eval (%with-parameters exp (walker-get walker :get :most-likely-params :take take))))
+
+(defun %keywords-of (form)
+  "the keywords of FORM, each once, in the order they first appear"
+  (let ((seen nil))
+    (labels ((walk (f)
+               (cond ((keywordp f) (pushnew f seen))
+                     ((consp f) (walk (car f)) (walk (cdr f))))))
+      (walk form))
+    (nreverse seen)))
+
+(defun %exp-percentiles (get)
+  "the (num . den) per cent points mhx_get_derived is asked for to answer GET"
+  (cond ((consp get)
+         ;; n to the thousandth of a per cent, as an exact ratio (84.1 -> 84100 / 1000)
+         (list (cons (round (* 1000 (second get))) 1000)))
+        (t (case get
+             (:median '((50 . 1)))
+             (:95cr '((5 . 2) (195 . 2)))
+             (:iqr '((25 . 1) (75 . 1)))
+             (:stddev-normal '((50 . 1) (841 . 10)))
+             (t nil)))))
+
+(defun walker-set-exp-get (walker exp &key (get :median) (take 1000))
+  "For every chain of WALKER, GET of the values EXP takes over the chain's newest TAKE steps: one
+device call (mhx_get_derived), a list with one entry per chain.  GET: :most-likely (EXP at the
+most-likely step), :median, :95cr (a list low high), :iqr, :mean, :stddev (a NaN for a one-step
+window), :stddev-normal (the 84.1 point minus the median), :values (newest first) or
+(:percentile n).  Besides keywords EXP may name PROB, the step's log-posterior."
+  (let* ((n (walker-n-chains walker))
+         (keys (walker-param-keys walker))
+         (used (%keywords-of exp))
+         (index (loop for k in used
+                      collect (or (position k keys)
+                                  (error 'mhx-error :code -1
+                                                    :message (format nil "~s is no parameter of the walker" k)))))
+         (names (mapcar #'mangle-symbol used))
+         (text (form->c exp))
+         (points (%exp-percentiles get))
+         (n-pct (length points))
+         (selector (if (consp get) (first get) get))
+         (ring (cffi:with-foreign-object (cap :int32)
+                 (with-c-call
+                   (check (%mhx-get-history-capacity (first (all-engines walker)) cap)))
+                 (cffi:mem-ref cap :int32)))
+         (window (max 1 (min take ring)))
+         (none (cffi:null-pointer))
+         (vals (if (eq selector :values)
+                   (cffi:foreign-alloc :double :count (* n window))
+                   none)))
+    (unless (member selector '(:most-likely :median :95cr :iqr :mean :stddev :stddev-normal
+                               :values :percentile))
+      (error 'mhx-error :code -1 :message (format nil "unknown :get ~s" get)))
+    (unwind-protect
+         (with-c-strings (exprs (list text))
+           (with-c-strings (name-ptrs names)
+             (cffi:with-foreign-objects ((idx :int32 (max 1 (length index)))
+                                         (num :int32 (max 1 n-pct)) (den :int32 (max 1 n-pct))
+                                         (best :double n) (pct :double (* n (max 1 n-pct)))
+                                         (mean :double n) (sd :double n) (held :int32 n))
+               (fill-int32s idx index)
+               (fill-int32s num (mapcar #'car points))
+               (fill-int32s den (mapcar #'cdr points))
+               (%set-call walker #'%mhx-get-derived #'%mhx-group-get-derived
+                          exprs 1 name-ptrs idx (length index) window num den n-pct
+                          best pct mean sd vals held none)
+               (flet ((point (c q) (cffi:mem-aref pct :double (+ (* c n-pct) q))))
+                 (loop for c below n
+                       collect (ecase selector
+                                 (:most-likely (cffi:mem-aref best :double c))
+                                 ((:median :percentile) (point c 0))
+                                 (:95cr (list (point c 0) (point c 1)))
+                                 ((:iqr :stddev-normal) (- (point c 1) (point c 0)))
+                                 (:mean (cffi:mem-aref mean :double c))
+                                 (:stddev (cffi:mem-aref sd :double c))
+                                 (:values
+                                  (loop for s below (cffi:mem-aref held :int32 c)
+                                        collect (cffi:mem-aref vals :double (+ (* c window) s))))))))))
+      (unless (cffi:null-pointer-p vals)
+        (cffi:foreign-free vals)))))
+
+(defun walker-exp-get (walker exp &key (get :median) (take 1000) (chain 0))
+  "walker-set-exp-get's answer for one chain of WALKER"
+  (elt (walker-set-exp-get walker exp :get get :take take) chain))
+
 (defun %designator-name (x)
   (cond ((null x) nil)
         ((symbolp x) x)

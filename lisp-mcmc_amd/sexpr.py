@@ -256,6 +256,32 @@ def prior_body_to_expr(text):
     return to_c(parse(text), {"bounds-total": "bounds_total"})
 
 
+def keyword_exp_to_expr(text):
+    """The form given to walker-with-exp (M:1052-1064), e.g. '(* :a1 :w1 (sqrt pi))': its
+    keywords stand for the walker's parameters.  -> (names, C expression): the mangled keys in
+    the order they first appear, and the text mhx_get_derived takes.  `prob` (the step's
+    log-posterior), pi, t and nil are the only symbols that are not keywords."""
+    form = parse(text)
+    if isinstance(form, list) and len(form) == 2 and form[0] == "quote":
+        form = form[1]
+    names = []
+
+    def walk(f, head):
+        if isinstance(f, str):
+            if head or number(f) is not None:
+                return
+            if f.startswith(":"):
+                if mangle(f) not in names:
+                    names.append(mangle(f))
+            elif f.lower() not in ("pi", "t", "nil", "prob"):
+                raise SexprError("symbol %r is neither a parameter keyword nor prob / pi" % (f,))
+        else:
+            for i, v in enumerate(f):
+                walk(v, i == 0 and isinstance(v, str))
+    walk(form, False)
+    return names, to_c(form)
+
+
 def symbols_of(form, acc=None):
     acc = set() if acc is None else acc
     if isinstance(form, str):

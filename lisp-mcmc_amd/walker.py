@@ -14,6 +14,8 @@ walker-adaptive-steps path (M: = mcmc-fitting.lisp):
     walker-get-data-and-fit      M:1230-1255   walker_get_data_and_fit (+ _no_stddev M:1208-1227,
                                                walker_get_residuals M:1271-1283,
                                                walker_set_get_data_and_fit)
+    walker-with-exp              M:1052-1064   walker_with_exp, walker_set_with_exp; its posterior
+                                               walker_exp_get, walker_set_exp_get
     walker-modify                M:547-580     walker_modify
     prior-bounds-let             M:346-369     prior_bounds
     mfit-walker-estop            M:860-861     request_stop
@@ -676,6 +678,104 @@ def walker_get_residuals(walker, take=1000, x_column=0, y_column=1, fn_number=0,
     _, th = _fit_solution(walker, ":median", take, chain)
     y_fit = walker.engine.eval_function(fn_number, th[0])
     return [list(x_data), [float(a - b) for a, b in zip(y_fit, y_data)], list(sd)]
+
+
+_EXP_PERCENTILES = {"median": (50,), "95cr": (2.5, 97.5), "iqr": (25, 75),
+                    "stddev-normal": (50, 84.1)}
+_EXP_SELECTORS = ("most-likely", "median", "95cr", "iqr", "mean", "stddev", "stddev-normal",
+                  "values", "percentile")
+
+
+def exp_selector(get):
+    """(selector, percentiles the device is asked for) of walker_exp_get's `get`: ':median',
+    ':95cr', ... or (':percentile', n)"""
+    arg = None
+    if isinstance(get, (tuple, list)):
+        if len(get) != 2:
+            raise ValueError("unknown :get %r" % (get,))
+        get, arg = get
+    g = str(get).lstrip(":").lower()
+    if g not in _EXP_SELECTORS or (g == "percentile") != (arg is not None):
+        raise ValueError("unknown :get %r" % (get,))
+    if g == "percentile":
+        if not 0 <= float(arg) <= 100:
+            raise ValueError("a percentile lies in [0, 100], not %r" % (arg,))
+        return g, (arg,)
+    return g, _EXP_PERCENTILES.get(g, ())
+
+
+def _exp_call(walker, exp):
+    """(names, places in theta, C text) of a walker-with-exp form; KeyError for a keyword that
+    is no parameter key of the walker"""
+    from . import sexpr
+    names, text = sexpr.keyword_exp_to_expr(exp)
+    keys = list(walker.param_keys)
+    for k in names:
+        if k not in keys:
+            raise KeyError(":" + k)
+    return names, [keys.index(k) for k in names], text
+
+
+def _exp_window(walker, take):
+    e = walker.engine
+    return max(1, min(int(take), e.history_capacity()))
+
+
+def _exp_results(g, pcts, r, values):
+    """what walker_exp_get returns, chain by chain, from Engine.derived's arrays"""
+    out = []
+    for c in range(r["n_used"].shape[0]):
+        p = [float(v) for v in r["pct"][c, :, 0]]
+        if g == "most-likely":
+            out.append(float(r["at_most_likely"][c, 0]))
+        elif g in ("median", "percentile"):
+            out.append(p[0])
+        elif g == "95cr":  # M:1508-1509
+            out.append([p[0], p[1]])
+        elif g == "iqr":  # M:1511-1513
+            out.append(p[1] - p[0])
+        elif g == "stddev-normal":  # M:1529-1535: the 84.1 point minus the median
+            out.append(p[1] - p[0])
+        elif g == "mean":
+            out.append(float(r["mean"][c, 0]))
+        elif g == "stddev":
+            out.append(float(r["stddev"][c, 0]))
+        else:  # values, newest first
+            out.append(values[c, 0, :int(r["n_used"][c])].copy())
+    return out
+
+
+def walker_set_exp_get(walker, exp, get=":median", take=1000):
+    """walker_exp_get for every chain of the set from ONE device call (mhx_get_derived): a list
+    with, chain by chain, exactly what walker_exp_get(..., chain=c) returns."""
+    g, pcts = exp_selector(get)
+    names, index, text = _exp_call(walker, exp)
+    r = walker.engine.derived([text], names, index, _exp_window(walker, take), pcts,
+                              values=g == "values")
+    return _exp_results(g, pcts, r, r.get("values"))
+
+
+def walker_exp_get(walker, exp, get=":median", take=1000, chain=0):
+    """The posterior of walker-with-exp's expression over the walker's newest `take` steps: the
+    form is evaluated at every step of the window on the device (mhx_get_derived) and summarised
+    there.  get: :most-likely (walker_with_exp), :median, :95cr (a [lo, hi] pair), :iqr, :mean,
+    :stddev (NaN for a one-step window), :stddev-normal (the 84.1 point minus the median,
+    M:1529-1535), :values (newest first) or (":percentile", n)."""
+    return walker_set_exp_get(walker, exp, get, take)[chain]
+
+
+def walker_set_with_exp(walker, exp, take=1000):
+    """walker_with_exp for every chain of the set from one device call"""
+    return walker_set_exp_get(walker, exp, ":most-likely", take)
+
+
+def walker_with_exp(walker, exp, take=1000, chain=0):
+    """(walker-with-exp walker exp &key take) M:1052-1064: the form `exp` (Lisp text) with every
+    keyword replaced by that parameter of the walker's most-likely step, evaluated - on the
+    device, in binary64, in the form's own order of operations.  `take` is accepted as in the
+    reference, where :most-likely-params ignores it too (M:511-515).  KeyError for a keyword
+    that is no parameter key, SexprError for an operator the device grammar lacks."""
+    return walker_set_with_exp(walker, exp, take)[chain]
 
 
 def walker_modify(walker, modify=None, **kw):
