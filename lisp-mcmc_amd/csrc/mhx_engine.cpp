@@ -22,6 +22,7 @@
 #include "mhx_launch.hpp"
 #include "mhx_plan.hpp"
 #include "mhx_rtc.hpp"
+#include "mhx_stage.hpp"
 #include "mhx_types.hpp"
 
 using namespace mhx;
@@ -864,7 +865,6 @@ int ensure_stage(mhx_engine* e, size_t bytes) {
     return fail(MHX_ENOMEM, "hipMalloc of %zu staging bytes failed", want);
   return MHX_OK;
 }
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // The slot -> chain map on the device (ChainState::slot_chain).  Grown whenever a deal needs more
 // entries than it holds: which of compact_tsplit / compact_slots / deal_initial runs first depends
@@ -2111,176 +2111,201 @@ int mhx_get_proposal_factor(mhx_engine* e, int64_t chain, int take, double* L_ou
   return MHX_OK;
 }
 
-// ---- walker-set-get: every chain's summary in one launch (k_percentiles, k_covariances,
-// k_l_matrices, k_window_best).  The chains are worked through in portions: results and scratch
-// (an index list of `take` ints and up to two d x d matrices per chain) live in the engine's
-// stage buffer, at most kSummaryStageBytes of it whatever n_chains x take is.
-static constexpr size_t kSummaryStageBytes = (size_t)64 << 20;
-enum { SUM_PERCENTILES = 0, SUM_COVARIANCES = 1, SUM_FACTORS = 2, SUM_BEST = 3 };
-struct SummaryCall {
-  int kind = 0, take = 0;
-  PctList pc{};
-  // host destinations of the engine's chain 0 (any may be NULL), in the order of the pieces below
-  double* hd[2] = {nullptr, nullptr};
-  int32_t* hi[2] = {nullptr, nullptr};
+extern "C++" {
+// ---- the batched read-outs of the history ring: walker-set-get, fit curves and bands, derived
+// quantities.  Each works through its items - chains, or parameter vectors - in portions whose
+// pieces (mhx_stage.hpp) stay below kStageBudget of the engine's stage buffer whatever the call's
+// size.  A read-out is a call struct with
+//   check(e)           the arguments against engine e, before anything is launched
+//   items(e), points() what there is to work through (points: 1 unless x goes in chunks)
+//   carve(e, c, n, m)  the pieces of n items at m points, taken from carver c
+//   upload(e, p)       the copies and clears ahead of portion p's kernels (not timed)
+//   launch(e, p)       ... its kernels
+//   collect(e, p)      ... and its results, copied to the caller's arrays
+// and dst[], its host destinations; run_portions() does the rest.
+
+// a host destination: the caller's array at the engine's item 0 (may be NULL), bytes per item
+struct HostDst {
+  void* p = nullptr;
+  size_t item_bytes = 0;
+  void* at(int64_t item) const { return static_cast<unsigned char*>(p) + (size_t)item * item_bytes; }
 };
-// a portion's pieces in the stage buffer: two double arrays [n][nd], two int arrays [n], the
-// index scratch [n][take]; copied[] says which of the double pieces is a result
-struct SummaryLayout {
-  size_t nd[2] = {0, 0};
-  bool copied[2] = {false, false};
-  int ni = 0;
-  bool scratch = false;
-  size_t per_chain = 0;
-};
-static SummaryLayout summary_layout(const mhx_engine* e, const SummaryCall& q) {
-  const size_t d = (size_t)e->P.d, dd = d * d;
-  SummaryLayout y;
-  switch (q.kind) {
-    case SUM_PERCENTILES: y.nd[0] = (size_t)q.pc.n * d; y.copied[0] = true; y.ni = 1; break;
-    case SUM_COVARIANCES: y.nd[0] = dd; y.copied[0] = true; y.ni = 2; y.scratch = true; break;
-    case SUM_FACTORS: y.nd[0] = dd; y.copied[0] = true; y.nd[1] = dd; y.ni = 2; y.scratch = true; break;
-    default: y.nd[0] = 1; y.nd[1] = d; y.copied[0] = y.copied[1] = true; break;
-  }
-  y.per_chain = (y.nd[0] + y.nd[1]) * sizeof(double) + (size_t)y.ni * sizeof(int32_t) +
-                (y.scratch ? (size_t)q.take * sizeof(int32_t) : 0);
-  return y;
+template <class T>
+static T* stage_at(const mhx_engine* e, size_t offset) {
+  return reinterpret_cast<T*>(e->stage.p + offset);
 }
-struct SummaryPieces {
-  double* dv[2];
-  int32_t* iv[2];
-  int32_t* scratch;
-  size_t bytes;
-};
-static SummaryPieces summary_pieces(mhx_engine* e, const SummaryLayout& y, const SummaryCall& q,
-                                    int64_t n) {
-  SummaryPieces s{};
-  size_t o = 0;
-  for (int k = 0; k < 2; ++k) {
-    s.dv[k] = reinterpret_cast<double*>(e->stage.p + o);
-    o += align256((size_t)n * y.nd[k] * sizeof(double));
-  }
-  for (int k = 0; k < 2; ++k) {
-    s.iv[k] = reinterpret_cast<int32_t*>(e->stage.p + o);
-    o += align256((size_t)n * sizeof(int32_t));
-  }
-  s.scratch = reinterpret_cast<int32_t*>(e->stage.p + o);
-  o += align256(y.scratch ? (size_t)n * q.take * sizeof(int32_t) : 0);
-  s.bytes = o;
-  return s;
+// n items from item i0 on: from the stage buffer to a destination
+static int copy_back(const HostDst& h, int64_t i0, int64_t n, const void* dev) {
+  if (h.p && h.item_bytes > 0)
+    HIP_TRY(hipMemcpy(h.at(i0), dev, (size_t)n * h.item_bytes, hipMemcpyDeviceToHost));
+  return MHX_OK;
 }
-static int64_t summary_portion(const SummaryLayout& y) {
-  return std::max<int64_t>(1, (int64_t)((kSummaryStageBytes - 5 * 256) / y.per_chain));
-}
-static int summary_check(mhx_engine* e, const SummaryCall& q) {
+// the window of a read-out of the chains' histories
+static int window_check(const mhx_engine* e, int take) {
   if (!e) return fail(MHX_EINVAL, "engine is NULL");
   if (!e->chains_ready) return fail(MHX_ESTATE, "mhx_init_chains has not been called");
-  if (q.take < 1 || q.take > e->S.R)
+  if (take < 1 || take > e->S.R)
     return fail(MHX_EINVAL, "take must be in [1, history_capacity = %d]", e->S.R);
   return MHX_OK;
 }
-static int summary_fill_pcts(SummaryCall* q, const int32_t* num, const int32_t* den, int n_pct) {
+static int fill_pcts(PctList* pc, const int32_t* num, const int32_t* den, int n_pct) {
   if (n_pct < 0 || n_pct > MHX_MAX_PERCENTILES)
     return fail(MHX_EINVAL, "n_pct must be in [0,%d]", MHX_MAX_PERCENTILES);
   if (n_pct > 0 && (!num || !den)) return fail(MHX_EINVAL, "NULL percentile list");
-  q->pc.n = n_pct;
+  pc->n = n_pct;
   for (int k = 0; k < n_pct; ++k) {
     if (den[k] < 1 || num[k] < 0 || (int64_t)num[k] > (int64_t)100 * den[k])
       return fail(MHX_EINVAL, "percentile %d: %d/%d is outside [0, 100]", k, num[k], den[k]);
-    q->pc.num[k] = num[k];
-    q->pc.den[k] = den[k];
+    pc->num[k] = num[k];
+    pc->den[k] = den[k];
   }
   return MHX_OK;
 }
-// the launch of the n chains from c0 on, into the stage buffer (nothing is waited for)
-static int summary_enqueue(mhx_engine* e, const SummaryCall& q, int64_t c0, int64_t n) {
-  int rc = use_device(e);
-  if (rc != MHX_OK) return rc;
-  const SummaryLayout y = summary_layout(e, q);
-  if ((rc = ensure_stage(e, summary_pieces(e, y, q, n).bytes)) != MHX_OK) return rc;
-  const SummaryPieces s = summary_pieces(e, y, q, n);
-  // (the factor kernel leaves what it does not reach untouched, as k_l_matrix does: zeros)
-  HIP_TRY(hipMemsetAsync(e->stage.p, 0, s.bytes, e->stream));
-  HIP_TRY(hipEventRecord(e->ev0, e->stream));
-  switch (q.kind) {
-    case SUM_PERCENTILES: {
-      const bool lds = !e->knobs.summary_no_lds && pct_lds_bytes(q.take, e->P.d) <= kPctLdsBudget;
-      HIP_TRY(launch_percentiles(e->stream, e->S, c0, n, q.take, q.pc, lds, s.dv[0], s.iv[0]));
-      break;
-    }
-    case SUM_COVARIANCES:
-      HIP_TRY(launch_covariances(e->stream, e->S, c0, n, q.take, s.scratch, s.dv[0], s.iv[0], s.iv[1]));
-      break;
-    case SUM_FACTORS:
-      HIP_TRY(launch_l_matrices(e->stream, e->S, c0, n, q.take, s.scratch, s.dv[1], s.dv[0], s.iv[0],
-                                s.iv[1]));
-      break;
-    default:
-      HIP_TRY(launch_window_best(e->stream, e->S, c0, n, q.take, s.dv[0], s.dv[1]));
-      break;
-  }
-  HIP_TRY(hipEventRecord(e->ev1, e->stream));
-  return MHX_OK;
-}
-// ... and its results, to the caller's arrays (of this engine's chains) at chain c0
-static int summary_collect(mhx_engine* e, const SummaryCall& q, int64_t c0, int64_t n) {
-  int rc = use_device(e);
-  if (rc != MHX_OK) return rc;
-  const SummaryLayout y = summary_layout(e, q);
-  const SummaryPieces s = summary_pieces(e, y, q, n);
-  HIP_TRY(hipEventSynchronize(e->ev1));
-  float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
-  e->summary_ms += (double)ms;
-  for (int k = 0; k < 2; ++k)
-    if (y.copied[k] && q.hd[k] && y.nd[k] > 0)
-      HIP_TRY(hipMemcpy(q.hd[k] + (size_t)c0 * y.nd[k], s.dv[k],
-                        (size_t)n * y.nd[k] * sizeof(double), hipMemcpyDeviceToHost));
-  for (int k = 0; k < y.ni; ++k)
-    if (q.hi[k])
-      HIP_TRY(hipMemcpy(q.hi[k] + c0, s.iv[k], (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-  return MHX_OK;
-}
-// calls[i] on engs[i]: round by round, every engine's portion enqueued before any is waited for
-static int summary_run(const std::vector<mhx_engine*>& engs, const std::vector<SummaryCall>& calls) {
+
+// Call q on every engine of engs, engine i's results landing at item first[i] of the caller's
+// arrays (first NULL: one engine, item 0).  Round by round, every engine's portion is enqueued
+// before any is waited for; summary_ms gathers the kernels' time over the portions.
+template <class Q>
+static int run_portions(const std::vector<mhx_engine*>& engs, const int64_t* first, const Q& q) {
+  const size_t E = engs.size();
+  std::vector<Q> calls(E, q);
   int rc = MHX_OK;
-  for (size_t i = 0; i < engs.size(); ++i)
-    if ((rc = summary_check(engs[i], calls[i])) != MHX_OK) return rc;
-  std::vector<int64_t> at(engs.size(), 0), now(engs.size(), 0);
-  for (mhx_engine* e : engs) e->summary_ms = 0.0;
+  for (size_t i = 0; i < E; ++i)
+    if ((rc = calls[i].check(engs[i])) != MHX_OK) return rc;
+  std::vector<PortionCursor> at(E);
+  for (size_t i = 0; i < E; ++i) {
+    mhx_engine* e = engs[i];
+    Q& c = calls[i];
+    for (HostDst& h : c.dst)
+      if (h.p && first) h.p = h.at(first[i]);
+    e->summary_ms = 0.0;
+    at[i] = portion_cursor(c.items(e), c.points(),
+                           [&](Carver& cv, int64_t n, int64_t m) { c.carve(e, cv, n, m); });
+  }
+  auto give_up = [&](int code) {
+    for (mhx_engine* e : engs) drain(e);
+    return code;
+  };
+  // The stage buffer is sized once per engine, for the call's largest portion - its first, in
+  // items and in points - and before the first launch: no piece moves while the call runs, so
+  // what one chunk of points leaves in the buffer (the fit's selection and status) is there for
+  // the next, and every carve() below sees the final e->stage.p.
+  for (size_t i = 0; i < E; ++i) {
+    if (at[i].done()) continue;
+    const Portion p = at[i].now();
+    Carver cv;
+    calls[i].carve(engs[i], cv, p.n, p.m);
+    if ((rc = use_device(engs[i])) != MHX_OK || (rc = ensure_stage(engs[i], cv.bytes())) != MHX_OK)
+      return give_up(rc);
+  }
+  auto enqueue = [&](mhx_engine* e, const Q& c, const Portion& p) {
+    int r = use_device(e);
+    if (r != MHX_OK || (r = c.upload(e, p)) != MHX_OK) return r;
+    HIP_TRY(hipEventRecord(e->ev0, e->stream));
+    if ((r = c.launch(e, p)) != MHX_OK) return r;
+    HIP_TRY(hipEventRecord(e->ev1, e->stream));
+    return (int)MHX_OK;
+  };
+  auto collect = [&](mhx_engine* e, const Q& c, const Portion& p) {
+    const int r = use_device(e);
+    if (r != MHX_OK) return r;
+    HIP_TRY(hipEventSynchronize(e->ev1));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
+    e->summary_ms += (double)ms;
+    return c.collect(e, p);
+  };
   for (;;) {
     bool any = false;
-    for (size_t i = 0; i < engs.size(); ++i) {
-      const int64_t left = engs[i]->cfg.n_chains - at[i];
-      now[i] = std::min<int64_t>(left, summary_portion(summary_layout(engs[i], calls[i])));
-      if (now[i] <= 0) continue;
+    for (size_t i = 0; i < E; ++i) {
+      if (at[i].done()) continue;
       any = true;
-      if ((rc = summary_enqueue(engs[i], calls[i], at[i], now[i])) != MHX_OK) {
-        for (mhx_engine* e : engs) drain(e);
-        return rc;
-      }
+      if ((rc = enqueue(engs[i], calls[i], at[i].now())) != MHX_OK) return give_up(rc);
     }
     if (!any) return MHX_OK;
-    for (size_t i = 0; i < engs.size(); ++i) {
-      if (now[i] <= 0) continue;
-      if ((rc = summary_collect(engs[i], calls[i], at[i], now[i])) != MHX_OK) {
-        for (mhx_engine* e : engs) drain(e);
-        return rc;
-      }
-      at[i] += now[i];
+    for (size_t i = 0; i < E; ++i) {
+      if (at[i].done()) continue;
+      if ((rc = collect(engs[i], calls[i], at[i].now())) != MHX_OK) return give_up(rc);
+      at[i].advance();
     }
   }
 }
-static SummaryCall summary_call(int kind, int take, double* d0, double* d1, int32_t* i0, int32_t* i1) {
-  SummaryCall q;
-  q.kind = kind;
-  q.take = take;
-  q.hd[0] = d0;
-  q.hd[1] = d1;
-  q.hi[0] = i0;
-  q.hi[1] = i1;
-  return q;
+template <class Q>
+static int run_portions(mhx_engine* e, const Q& q) {
+  return run_portions({e}, nullptr, q);
 }
+}  // extern "C++"
+
+// ---- walker-set-get: every chain's summary in one launch (k_percentiles, k_covariances,
+// k_l_matrices, k_window_best).  Results and scratch (an index list of `take` ints and up to two
+// d x d matrices per chain) are a portion's pieces.
+struct SummaryCall {
+  int kind = 0, take = 0;
+  PctList pc{};
+  SummaryShape y{};
+  HostDst dst[4];  // of the pieces dv[0], dv[1], iv[0], iv[1]; NULL where a piece is no result
+
+  SummaryCall(int kind_, int take_, double* d0, double* d1, int32_t* i0, int32_t* i1)
+      : kind(kind_), take(take_) {
+    dst[0].p = d0, dst[1].p = d1, dst[2].p = i0, dst[3].p = i1;
+  }
+  int check(mhx_engine* e) {
+    const int rc = window_check(e, take);
+    if (rc != MHX_OK) return rc;
+    y = summary_shape(kind, e->P.d, pc.n, take);
+    for (int k = 0; k < 2; ++k) {
+      dst[k].item_bytes = y.nd[k] * sizeof(double);
+      dst[2 + k].item_bytes = sizeof(int32_t);
+    }
+    return MHX_OK;
+  }
+  int64_t items(const mhx_engine* e) const { return e->cfg.n_chains; }
+  int64_t points() const { return 1; }
+  SummaryPieces carve(const mhx_engine*, Carver& c, int64_t n, int64_t) const {
+    return carve_summary(c, y, n);
+  }
+  int upload(mhx_engine* e, const Portion& p) const {
+    Carver c;
+    carve(e, c, p.n, p.m);
+    // (the factor kernel leaves what it does not reach untouched, as k_l_matrix does: zeros)
+    HIP_TRY(hipMemsetAsync(e->stage.p, 0, c.bytes(), e->stream));
+    return MHX_OK;
+  }
+  int launch(mhx_engine* e, const Portion& p) const {
+    Carver c;
+    const SummaryPieces s = carve(e, c, p.n, p.m);
+    double* const dv[2] = {stage_at<double>(e, s.dv[0]), stage_at<double>(e, s.dv[1])};
+    int32_t* const iv[2] = {stage_at<int32_t>(e, s.iv[0]), stage_at<int32_t>(e, s.iv[1])};
+    int32_t* const scratch = stage_at<int32_t>(e, s.scratch);
+    switch (kind) {
+      case SUM_PERCENTILES: {
+        const bool lds = !e->knobs.summary_no_lds && pct_lds_bytes(take, e->P.d) <= kPctLdsBudget;
+        HIP_TRY(launch_percentiles(e->stream, e->S, p.i0, p.n, take, pc, lds, dv[0], iv[0]));
+        break;
+      }
+      case SUM_COVARIANCES:
+        HIP_TRY(launch_covariances(e->stream, e->S, p.i0, p.n, take, scratch, dv[0], iv[0], iv[1]));
+        break;
+      case SUM_FACTORS:
+        HIP_TRY(launch_l_matrices(e->stream, e->S, p.i0, p.n, take, scratch, dv[1], dv[0], iv[0], iv[1]));
+        break;
+      default:
+        HIP_TRY(launch_window_best(e->stream, e->S, p.i0, p.n, take, dv[0], dv[1]));
+        break;
+    }
+    return MHX_OK;
+  }
+  int collect(mhx_engine* e, const Portion& p) const {
+    Carver c;
+    const SummaryPieces s = carve(e, c, p.n, p.m);
+    const size_t off[4] = {s.dv[0], s.dv[1], s.iv[0], s.iv[1]};
+    for (int k = 0; k < 4; ++k) {
+      const int rc = copy_back(dst[k], p.i0, p.n, e->stage.p + off[k]);
+      if (rc != MHX_OK) return rc;
+    }
+    return MHX_OK;
+  }
+};
 
 int mhx_percentile_rank(int64_t len, int32_t num, int32_t den, int64_t* pos, int32_t* between) {
   if (len < 1) return fail(MHX_EINVAL, "len must be >= 1");
@@ -2296,21 +2321,21 @@ int mhx_percentile_rank(int64_t len, int32_t num, int32_t den, int64_t* pos, int
 
 int mhx_get_percentiles(mhx_engine* e, int take, const int32_t* pct_num, const int32_t* pct_den,
                         int n_pct, double* out, int32_t* n_used) {
-  SummaryCall q = summary_call(SUM_PERCENTILES, take, out, nullptr, n_used, nullptr);
-  int rc = summary_check(e, q);
-  if (rc != MHX_OK || (rc = summary_fill_pcts(&q, pct_num, pct_den, n_pct)) != MHX_OK) return rc;
+  SummaryCall q(SUM_PERCENTILES, take, out, nullptr, n_used, nullptr);
+  int rc = window_check(e, take);
+  if (rc != MHX_OK || (rc = fill_pcts(&q.pc, pct_num, pct_den, n_pct)) != MHX_OK) return rc;
   if (n_pct == 0) return MHX_OK;
-  return summary_run({e}, {q});
+  return run_portions(e, q);
 }
 int mhx_get_covariances(mhx_engine* e, int take, double* cov, int32_t* n_unique, int32_t* status) {
-  return summary_run({e}, {summary_call(SUM_COVARIANCES, take, cov, nullptr, n_unique, status)});
+  return run_portions(e, SummaryCall(SUM_COVARIANCES, take, cov, nullptr, n_unique, status));
 }
 int mhx_get_proposal_factors(mhx_engine* e, int take, double* L, int32_t* status,
                              int32_t* n_forward) {
-  return summary_run({e}, {summary_call(SUM_FACTORS, take, L, nullptr, status, n_forward)});
+  return run_portions(e, SummaryCall(SUM_FACTORS, take, L, nullptr, status, n_forward));
 }
 int mhx_get_window_best(mhx_engine* e, int take, double* prob, double* theta) {
-  return summary_run({e}, {summary_call(SUM_BEST, take, prob, theta, nullptr, nullptr)});
+  return run_portions(e, SummaryCall(SUM_BEST, take, prob, theta, nullptr, nullptr));
 }
 int mhx_get_history_capacity(mhx_engine* e, int32_t* capacity) {
   if (!e) return fail(MHX_EINVAL, "engine is NULL");
@@ -2326,187 +2351,119 @@ int mhx_get_summary_timing(mhx_engine* e, double* kernel_ms) {
 // ---- walker-get-data-and-fit (M:1230-1255): model values and credible bands on the device
 // (k_band_select, k_fit).  An ITEM is a parameter vector (mhx_eval_function) or a chain
 // (mhx_get_fit_bands).  Items and points are worked through in portions: at most
-// kFitChunkPoints points of x at a time, and as many items as keep the stage buffer - x, the
-// parameter vectors or the selected steps' slots, the results - below kSummaryStageBytes.
-static constexpr int64_t kFitChunkPoints = (int64_t)1 << 17;
+// kFitChunkPoints points of x at a time, and as many items as keep the pieces - x, the
+// parameter vectors or the selected steps' slots, the results - below kStageBudget.
 struct FitCall {
   int fn = 0, take = 0;  // take 0: parameter vectors, else bands of the engine's chains
-  int64_t n = 0, m = 0;
+  int64_t n = 0, m = 0;  // (n < 0: bands, whatever take is: check)
   const double* theta = nullptr;  // [n][d] on the host (parameter vectors)
   const double* xcols = nullptr;  // [n_cols][m] on the host, or NULL: the function's dataset
   int n_cols = 1;
-  // host destinations of the engine's item 0 (any may be NULL)
-  double *ymax = nullptr, *ymin = nullptr;
-  int32_t *n_sel = nullptr, *status = nullptr;
-};
-struct FitPieces {
-  int32_t *sel, *n_sel, *status;
-  double *theta, *x0, *x1, *ymax, *ymin;
-  size_t bytes;
-};
-static int64_t fit_items(const mhx_engine* e, const FitCall& q) {
-  return q.take > 0 ? e->cfg.n_chains : q.n;
-}
-static int64_t fit_portion(const mhx_engine* e, const FitCall& q) {
-  const size_t mc = (size_t)std::min<int64_t>(q.m, kFitChunkPoints);
-  const size_t per = 2 * mc * sizeof(double) + (size_t)e->P.d * sizeof(double) +
-                     (size_t)q.take * sizeof(int32_t) + 2 * sizeof(int32_t);
-  const size_t fixed = 2 * mc * sizeof(double) + 8 * 256;
-  return std::max<int64_t>(1, (int64_t)((kSummaryStageBytes - fixed) / per));
-}
-// (the pieces whose size depends on the items alone come first: they keep their place from one
-// chunk of points to the next)
-static FitPieces fit_pieces(mhx_engine* e, const FitCall& q, int64_t n, int64_t m) {
-  FitPieces s{};
-  size_t o = 0;
-  auto take_piece = [&](size_t bytes) {
-    unsigned char* p = e->stage.p + o;
-    o += align256(bytes);
-    return p;
-  };
-  s.sel = reinterpret_cast<int32_t*>(take_piece((size_t)n * q.take * sizeof(int32_t)));
-  s.n_sel = reinterpret_cast<int32_t*>(take_piece((size_t)n * sizeof(int32_t)));
-  s.status = reinterpret_cast<int32_t*>(take_piece((size_t)n * sizeof(int32_t)));
-  s.theta = reinterpret_cast<double*>(take_piece(q.take > 0 ? 0 : (size_t)n * e->P.d * sizeof(double)));
-  s.x0 = reinterpret_cast<double*>(take_piece((size_t)m * sizeof(double)));
-  s.x1 = reinterpret_cast<double*>(take_piece((size_t)m * sizeof(double)));
-  s.ymax = reinterpret_cast<double*>(take_piece((size_t)n * m * sizeof(double)));
-  s.ymin = reinterpret_cast<double*>(take_piece((size_t)n * m * sizeof(double)));
-  s.bytes = o;
-  return s;
-}
-// x columns the model of function fn reads
-static int fit_fn_cols(const mhx_engine* e, int fn) {
-  return e->P.fn[fn].model == MHX_MODEL_EXPR ? std::max(1, e->fn_expr[fn].xcols) : 1;
-}
-static int fit_check(mhx_engine* e, FitCall* q) {
-  if (!e) return fail(MHX_EINVAL, "engine is NULL");
-  if (q->take != 0 || q->n < 0) {
-    if (!e->chains_ready) return fail(MHX_ESTATE, "mhx_init_chains has not been called");
-    if (q->take < 1 || q->take > e->S.R)
-      return fail(MHX_EINVAL, "take must be in [1, history_capacity = %d]", e->S.R);
+  enum { YMAX, YMIN, N_SEL, STATUS };
+  HostDst dst[4];
+
+  FitCall(int fn_, int take_, int64_t n_, const double* theta_, const double* xcols_, int n_cols_,
+          int64_t m_, double* ymax, double* ymin, int32_t* n_sel, int32_t* status)
+      : fn(fn_), take(take_), n(n_), m(m_), theta(theta_), xcols(xcols_), n_cols(n_cols_) {
+    const size_t row = (size_t)std::max<int64_t>(m, 0) * sizeof(double);
+    dst[YMAX] = {ymax, row}, dst[YMIN] = {ymin, row};
+    dst[N_SEL] = {n_sel, sizeof(int32_t)}, dst[STATUS] = {status, sizeof(int32_t)};
   }
-  int rc = use_device(e);
-  if (rc != MHX_OK || (rc = finalize_problem(e)) != MHX_OK) return rc;
-  if (q->fn < 0 || q->fn >= e->P.K) return fail(MHX_EINVAL, "function %d out of range", q->fn);
-  if (q->n_cols != fit_fn_cols(e, q->fn))
-    return fail(MHX_EINVAL, "function %d reads %d column(s) of x, n_cols is %d", q->fn,
-                fit_fn_cols(e, q->fn), q->n_cols);
-  if (!q->xcols && q->m != e->P.fn[q->fn].n)
-    return fail(MHX_EINVAL, "xcols is NULL: m must be the dataset's %lld points",
-                (long long)e->P.fn[q->fn].n);
-  if (q->m < 1) return fail(MHX_EINVAL, "m must be >= 1");
-  if (q->take == 0 && q->n > 0 && !q->theta) return fail(MHX_EINVAL, "theta is NULL");
-  return MHX_OK;
-}
-// items [i0, i0 + n) at points [m0, m0 + m): enqueued, nothing waited for
-static int fit_enqueue(mhx_engine* e, const FitCall& q, int64_t i0, int64_t n, int64_t m0, int64_t m) {
-  int rc = use_device(e);
-  if (rc != MHX_OK) return rc;
-  if ((rc = ensure_stage(e, fit_pieces(e, q, n, m).bytes)) != MHX_OK) return rc;
-  const FitPieces s = fit_pieces(e, q, n, m);
-  const FnDesc& f = e->P.fn[q.fn];
-  const int d = e->P.d;
-  FitArgs A{};
-  A.fn = q.fn;
-  A.n = n;
-  A.m = m;
-  A.n_chunks = fit_chunks(m);
-  if (q.xcols) {
-    HIP_TRY(hipMemcpyAsync(s.x0, q.xcols + m0, (size_t)m * sizeof(double), hipMemcpyHostToDevice, e->stream));
-    if (q.n_cols > 1)
-      HIP_TRY(hipMemcpyAsync(s.x1, q.xcols + q.m + m0, (size_t)m * sizeof(double), hipMemcpyHostToDevice,
-                             e->stream));
-    A.x0 = s.x0;
-    A.x1 = q.n_cols > 1 ? s.x1 : nullptr;
-  } else {
-    A.x0 = f.x + m0;
-    A.x1 = f.n_xcols > 1 ? f.c + m0 : nullptr;
+  // x columns the model of function fn reads
+  static int fn_cols(const mhx_engine* e, int fn) {
+    return e->P.fn[fn].model == MHX_MODEL_EXPR ? std::max(1, e->fn_expr[fn].xcols) : 1;
   }
-  A.ymax = s.ymax;
-  if (q.take > 0) {
-    A.theta = e->S.hist_theta;
-    A.sel = s.sel;
-    A.n_sel = s.n_sel;
-    A.sel_pitch = q.take;
-    A.rows_per_item = e->S.R;
-    A.row0 = i0 * e->S.R;
-    A.ymin = s.ymin;
-    A.status = s.status;
-    if (m0 == 0) HIP_TRY(hipMemsetAsync(s.status, 0, (size_t)n * sizeof(int32_t), e->stream));
-  } else {
-    if (m0 == 0)
-      HIP_TRY(hipMemcpyAsync(s.theta, q.theta + (size_t)i0 * d, (size_t)n * d * sizeof(double),
-                             hipMemcpyHostToDevice, e->stream));
-    A.theta = s.theta;
-    A.rows_per_item = 1;
+  int check(mhx_engine* e) {
+    if (!e) return fail(MHX_EINVAL, "engine is NULL");
+    int rc = take != 0 || n < 0 ? window_check(e, take) : MHX_OK;
+    if (rc != MHX_OK || (rc = use_device(e)) != MHX_OK || (rc = finalize_problem(e)) != MHX_OK) return rc;
+    if (fn < 0 || fn >= e->P.K) return fail(MHX_EINVAL, "function %d out of range", fn);
+    if (n_cols != fn_cols(e, fn))
+      return fail(MHX_EINVAL, "function %d reads %d column(s) of x, n_cols is %d", fn, fn_cols(e, fn), n_cols);
+    if (!xcols && m != e->P.fn[fn].n)
+      return fail(MHX_EINVAL, "xcols is NULL: m must be the dataset's %lld points", (long long)e->P.fn[fn].n);
+    if (m < 1) return fail(MHX_EINVAL, "m must be >= 1");
+    if (take == 0 && n > 0 && !theta) return fail(MHX_EINVAL, "theta is NULL");
+    return MHX_OK;
   }
-  HIP_TRY(hipEventRecord(e->ev0, e->stream));
-  if (q.take > 0 && m0 == 0) HIP_TRY(launch_band_select(e->stream, e->S, i0, n, q.take, s.sel, s.n_sel));
-  HIP_TRY(e->spec == SPEC_USER ? rtc_launch_fit(*e->user_prog, e->stream, e->dP.p, A)
-                               : launch_fit(e->spec, e->stream, e->dP.p, A));
-  HIP_TRY(hipEventRecord(e->ev1, e->stream));
-  e->launches++;
-  return MHX_OK;
-}
-static int fit_collect(mhx_engine* e, const FitCall& q, int64_t i0, int64_t n, int64_t m0, int64_t m) {
-  int rc = use_device(e);
-  if (rc != MHX_OK) return rc;
-  const FitPieces s = fit_pieces(e, q, n, m);
-  HIP_TRY(hipEventSynchronize(e->ev1));
-  float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
-  e->summary_ms += (double)ms;
-  double* const hd[2] = {q.ymax, q.take > 0 ? q.ymin : nullptr};
-  const double* const dv[2] = {s.ymax, s.ymin};
-  for (int k = 0; k < 2; ++k)
-    if (hd[k])
-      HIP_TRY(hipMemcpy2D(hd[k] + (size_t)i0 * q.m + m0, (size_t)q.m * sizeof(double), dv[k],
-                          (size_t)m * sizeof(double), (size_t)m * sizeof(double), (size_t)n,
-                          hipMemcpyDeviceToHost));
-  if (q.take > 0 && m0 + m >= q.m) {  // (the status gathers over the chunks of points)
-    if (q.n_sel)
-      HIP_TRY(hipMemcpy(q.n_sel + i0, s.n_sel, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (q.status)
-      HIP_TRY(hipMemcpy(q.status + i0, s.status, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  int64_t items(const mhx_engine* e) const { return take > 0 ? e->cfg.n_chains : n; }
+  int64_t points() const { return m; }
+  FitPieces carve(const mhx_engine* e, Carver& c, int64_t n_items, int64_t m_points) const {
+    return carve_fit(c, e->P.d, take, n_items, m_points);
   }
-  return MHX_OK;
-}
-// calls[i] on engs[i]: round by round, every engine's portion enqueued before any is waited for
-static int fit_run(const std::vector<mhx_engine*>& engs, std::vector<FitCall> calls) {
-  int rc = MHX_OK;
-  for (size_t i = 0; i < engs.size(); ++i)
-    if ((rc = fit_check(engs[i], &calls[i])) != MHX_OK) return rc;
-  const size_t E = engs.size();
-  std::vector<int64_t> i0(E, 0), m0(E, 0), n(E, 0), m(E, 0);
-  for (mhx_engine* e : engs) e->summary_ms = 0.0;
-  for (;;) {
-    bool any = false;
-    for (size_t i = 0; i < E; ++i) {
-      n[i] = std::min<int64_t>(fit_items(engs[i], calls[i]) - i0[i], fit_portion(engs[i], calls[i]));
-      m[i] = std::min<int64_t>(calls[i].m - m0[i], kFitChunkPoints);
-      if (n[i] <= 0) continue;
-      any = true;
-      if ((rc = fit_enqueue(engs[i], calls[i], i0[i], n[i], m0[i], m[i])) != MHX_OK) {
-        for (mhx_engine* e : engs) drain(e);
-        return rc;
-      }
+  // items [i0, i0 + n) at points [m0, m0 + m).  What depends on the items alone is done on the
+  // portion's first chunk of points: the status gathers over the chunks
+  int upload(mhx_engine* e, const Portion& p) const {
+    Carver c;
+    const FitPieces s = carve(e, c, p.n, p.m);
+    const size_t mb = (size_t)p.m * sizeof(double);
+    if (xcols) {
+      HIP_TRY(hipMemcpyAsync(stage_at<double>(e, s.x0), xcols + p.m0, mb, hipMemcpyHostToDevice, e->stream));
+      if (n_cols > 1)
+        HIP_TRY(hipMemcpyAsync(stage_at<double>(e, s.x1), xcols + m + p.m0, mb, hipMemcpyHostToDevice, e->stream));
     }
-    if (!any) return MHX_OK;
-    for (size_t i = 0; i < E; ++i) {
-      if (n[i] <= 0) continue;
-      if ((rc = fit_collect(engs[i], calls[i], i0[i], n[i], m0[i], m[i])) != MHX_OK) {
-        for (mhx_engine* e : engs) drain(e);
-        return rc;
-      }
-      m0[i] += m[i];
-      if (m0[i] >= calls[i].m) {
-        m0[i] = 0;
-        i0[i] += n[i];
-      }
-    }
+    if (p.m0 != 0) return MHX_OK;
+    if (take > 0)
+      HIP_TRY(hipMemsetAsync(stage_at<int32_t>(e, s.status), 0, (size_t)p.n * sizeof(int32_t), e->stream));
+    else
+      HIP_TRY(hipMemcpyAsync(stage_at<double>(e, s.theta), theta + (size_t)p.i0 * e->P.d,
+                             (size_t)p.n * e->P.d * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    return MHX_OK;
   }
-}
+  int launch(mhx_engine* e, const Portion& p) const {
+    Carver c;
+    const FitPieces s = carve(e, c, p.n, p.m);
+    const FnDesc& f = e->P.fn[fn];
+    FitArgs A{};
+    A.fn = fn;
+    A.n = p.n;
+    A.m = p.m;
+    A.n_chunks = fit_chunks(p.m);
+    if (xcols) {
+      A.x0 = stage_at<double>(e, s.x0);
+      A.x1 = n_cols > 1 ? stage_at<double>(e, s.x1) : nullptr;
+    } else {
+      A.x0 = f.x + p.m0;
+      A.x1 = f.n_xcols > 1 ? f.c + p.m0 : nullptr;
+    }
+    A.ymax = stage_at<double>(e, s.ymax);
+    if (take > 0) {
+      int32_t *const sel = stage_at<int32_t>(e, s.sel), *const n_sel = stage_at<int32_t>(e, s.n_sel);
+      A.theta = e->S.hist_theta;
+      A.sel = sel;
+      A.n_sel = n_sel;
+      A.sel_pitch = take;
+      A.rows_per_item = e->S.R;
+      A.row0 = p.i0 * e->S.R;
+      A.ymin = stage_at<double>(e, s.ymin);
+      A.status = stage_at<int32_t>(e, s.status);
+      if (p.m0 == 0) HIP_TRY(launch_band_select(e->stream, e->S, p.i0, p.n, take, sel, n_sel));
+    } else {
+      A.theta = stage_at<double>(e, s.theta);
+      A.rows_per_item = 1;
+    }
+    HIP_TRY(e->spec == SPEC_USER ? rtc_launch_fit(*e->user_prog, e->stream, e->dP.p, A)
+                                 : launch_fit(e->spec, e->stream, e->dP.p, A));
+    e->launches++;
+    return MHX_OK;
+  }
+  int collect(mhx_engine* e, const Portion& p) const {
+    Carver c;
+    const FitPieces s = carve(e, c, p.n, p.m);
+    const size_t dv[2] = {s.ymax, s.ymin};
+    for (int k = 0; k < (take > 0 ? 2 : 1); ++k)
+      if (dst[k].p)
+        HIP_TRY(hipMemcpy2D(static_cast<double*>(dst[k].at(p.i0)) + p.m0, (size_t)m * sizeof(double),
+                            stage_at<double>(e, dv[k]), (size_t)p.m * sizeof(double),
+                            (size_t)p.m * sizeof(double), (size_t)p.n, hipMemcpyDeviceToHost));
+    if (take > 0 && p.m0 + p.m >= m) {  // (the status gathers over the chunks of points)
+      int rc = copy_back(dst[N_SEL], p.i0, p.n, stage_at<int32_t>(e, s.n_sel));
+      if (rc != MHX_OK || (rc = copy_back(dst[STATUS], p.i0, p.n, stage_at<int32_t>(e, s.status))) != MHX_OK)
+        return rc;
+    }
+    return MHX_OK;
+  }
+};
 
 int mhx_band_count(int64_t take, int64_t* k) {
   if (take < 1) return fail(MHX_EINVAL, "take must be >= 1");
@@ -2516,240 +2473,141 @@ int mhx_band_count(int64_t take, int64_t* k) {
 int mhx_eval_function(mhx_engine* e, int fn, const double* theta, int64_t n, const double* xcols,
                       int n_cols, int64_t m, double* out) {
   if (n < 0) return fail(MHX_EINVAL, "n < 0");
-  FitCall q;
-  q.fn = fn;
-  q.n = n;
-  q.m = m;
-  q.theta = theta;
-  q.xcols = xcols;
-  q.n_cols = n_cols;
-  q.ymax = out;
-  return fit_run({e}, {q});
-}
-static FitCall band_call(int fn, int take, const double* xcols, int n_cols, int64_t m, double* ymax,
-                         double* ymin, int32_t* n_selected, int32_t* status) {
-  FitCall q;
-  q.fn = fn;
-  q.take = take;
-  q.n = -1;  // (bands, whatever take is: fit_check)
-  q.m = m;
-  q.xcols = xcols;
-  q.n_cols = n_cols;
-  q.ymax = ymax;
-  q.ymin = ymin;
-  q.n_sel = n_selected;
-  q.status = status;
-  return q;
+  return run_portions(e, FitCall(fn, 0, n, theta, xcols, n_cols, m, out, nullptr, nullptr, nullptr));
 }
 int mhx_get_fit_bands(mhx_engine* e, int fn, int take, const double* xcols, int n_cols, int64_t m,
                       double* ymax, double* ymin, int32_t* n_selected, int32_t* status) {
-  return fit_run({e}, {band_call(fn, take, xcols, n_cols, m, ymax, ymin, n_selected, status)});
+  return run_portions(e, FitCall(fn, take, -1, nullptr, xcols, n_cols, m, ymax, ymin, n_selected, status));
 }
 
 // ---- walker-with-exp (M:1052-1064) and the posterior of the expression: derived quantities of
 // every chain on the device (mhx_user_derived, run-time compiled: mhx_derived.hpp; then
-// k_derived_summary).  A portion's pieces in the stage buffer: the values [n][ne][take], the
-// results, n_used; as many chains at a time as keep them below kSummaryStageBytes.
+// k_derived_summary).  A portion's pieces: the values [n][ne][take], the results, n_used.
 struct DerivedCall {
   int ne = 0, take = 0, n_names = 0;
   std::vector<std::string> exprs, names;  // prepared texts; names as given
   int32_t idx[MHX_MAX_PARAMS + 1] = {0};
   PctList pc{};
   std::shared_ptr<DerivedProgram> prog;  // of this call's engine's device
-  // host destinations of the engine's chain 0 (any may be NULL)
-  double *at_best = nullptr, *pct = nullptr, *mean = nullptr, *stddev = nullptr, *values = nullptr;
-  int32_t *n_used = nullptr, *status = nullptr;
+  enum { AT_BEST, PCT, MEAN, STDDEV, VALUES, N_USED, STATUS };
+  HostDst dst[7];
+
+  // the part of the arguments that needs no engine: texts, names, destinations
+  int prepare(const char* const* exprs_, int n_expr, const char* const* names_, const int32_t* index,
+              int n_names_, int take_, const int32_t* pct_num, const int32_t* pct_den, int n_pct,
+              double* at_most_likely, double* pct, double* mean, double* stddev, double* values,
+              int32_t* n_used, int32_t* status) {
+    if (n_expr < 1 || n_expr > MHX_MAX_DERIVED || !exprs_)
+      return fail(MHX_EINVAL, "n_expr must be in [1,%d]", MHX_MAX_DERIVED);
+    if (n_names_ < 0 || n_names_ > MHX_MAX_PARAMS || (n_names_ > 0 && (!names_ || !index)))
+      return fail(MHX_EINVAL, "n_names must be in [0,%d]", MHX_MAX_PARAMS);
+    ne = n_expr;
+    take = take_;
+    n_names = n_names_;
+    for (int j = 0; j < n_names; ++j) {
+      if (!valid_ident(names_[j]) || !strcmp(names_[j], "prob"))
+        return fail(MHX_EINVAL, "name %d is not an identifier (or is x / bounds_total / prob)", j);
+      names.push_back(names_[j]);
+      idx[j] = index[j];
+    }
+    for (int k = 0; k < n_expr; ++k) {
+      if (!exprs_[k] || !*exprs_[k]) return fail(MHX_EINVAL, "expression %d is empty", k);
+      std::string out, err;
+      if (rtc_prepare_expr(exprs_[k], names, "prob", &out, &err) != 0)
+        return fail(MHX_EINVAL, "expression %d: %s", k, err.c_str());
+      exprs.push_back(out);
+    }
+    const int rc = fill_pcts(&pc, pct_num, pct_den, n_pct);
+    if (rc != MHX_OK) return rc;
+    const size_t row = (size_t)ne * sizeof(double);
+    dst[AT_BEST] = {at_most_likely, row}, dst[MEAN] = {mean, row}, dst[STDDEV] = {stddev, row};
+    dst[PCT] = {pct, row * (size_t)pc.n};
+    dst[VALUES] = {values, row * (size_t)std::max(take, 0)};
+    dst[N_USED] = {n_used, sizeof(int32_t)};
+    dst[STATUS] = {status, (size_t)ne * sizeof(int32_t)};
+    return MHX_OK;
+  }
+  int check(mhx_engine* e) {
+    int rc = window_check(e, take);
+    if (rc != MHX_OK) return rc;
+    for (int j = 0; j < n_names; ++j)
+      if (idx[j] < 0 || idx[j] >= e->P.d)
+        return fail(MHX_EINVAL, "index[%d] = %d outside [0,%d)", j, idx[j], e->P.d);
+    if ((rc = use_device(e)) != MHX_OK) return rc;
+    std::string err;
+    prog = rtc_get_derived(exprs, names, &err);
+    if (!prog) return fail(MHX_EINVAL, "%s", err.c_str());
+    return MHX_OK;
+  }
+  int64_t items(const mhx_engine* e) const { return e->cfg.n_chains; }
+  int64_t points() const { return 1; }
+  DerivedPieces carve(const mhx_engine*, Carver& c, int64_t n, int64_t) const {
+    return carve_derived(c, ne, take, pc.n, n);
+  }
+  int upload(mhx_engine*, const Portion&) const { return MHX_OK; }
+  int launch(mhx_engine* e, const Portion& p) const {
+    Carver c;
+    const DerivedPieces s = carve(e, c, p.n, p.m);
+    DerivedArgs A{};
+    A.c0 = p.i0;
+    A.n = p.n;
+    A.take = take;
+    A.pitch = take;
+    for (int j = 0; j < n_names; ++j) A.idx[j] = idx[j];
+    A.values = stage_at<double>(e, s.values);
+    A.at_best = stage_at<double>(e, s.at_best);
+    const bool lds = !e->knobs.summary_no_lds && pct_lds_bytes(take, ne) <= kPctLdsBudget;
+    HIP_TRY(rtc_launch_derived(*prog, e->stream, e->S, A));
+    HIP_TRY(launch_derived_summary(e->stream, e->S, p.i0, p.n, take, ne, pc, lds, A.values,
+                                   stage_at<double>(e, s.pct), stage_at<double>(e, s.mean),
+                                   stage_at<double>(e, s.stddev), stage_at<int32_t>(e, s.n_used),
+                                   stage_at<int32_t>(e, s.status)));
+    e->launches += 2;
+    return MHX_OK;
+  }
+  int collect(mhx_engine* e, const Portion& p) const {
+    Carver c;
+    const DerivedPieces s = carve(e, c, p.n, p.m);
+    const int which[5] = {AT_BEST, PCT, MEAN, STDDEV, STATUS};
+    const size_t off[5] = {s.at_best, s.pct, s.mean, s.stddev, s.status};
+    for (int k = 0; k < 5; ++k) {
+      const int rc = copy_back(dst[which[k]], p.i0, p.n, e->stage.p + off[k]);
+      if (rc != MHX_OK) return rc;
+    }
+    const int64_t c0 = p.i0, n = p.n;
+    std::vector<int32_t> used;
+    if (dst[N_USED].p || dst[VALUES].p) {
+      used.resize((size_t)n);
+      HIP_TRY(hipMemcpy(used.data(), stage_at<int32_t>(e, s.n_used), (size_t)n * sizeof(int32_t),
+                        hipMemcpyDeviceToHost));
+      if (dst[N_USED].p) memcpy(dst[N_USED].at(c0), used.data(), (size_t)n * sizeof(int32_t));
+    }
+    if (dst[VALUES].p) {
+      // entries at and beyond n_used are not the caller's to lose: whole runs of full windows in
+      // one copy, a chain with a shorter window row by row
+      double* const host = static_cast<double*>(dst[VALUES].p);
+      const double* const dev = stage_at<double>(e, s.values);
+      const size_t per = (size_t)ne * (size_t)take;
+      int64_t a = 0;
+      while (a < n) {
+        int64_t b = a;
+        while (b < n && used[(size_t)b] == take) ++b;
+        if (b > a)
+          HIP_TRY(hipMemcpy(host + (size_t)(c0 + a) * per, dev + (size_t)a * per,
+                            (size_t)(b - a) * per * sizeof(double), hipMemcpyDeviceToHost));
+        if (b < n) {
+          if (used[(size_t)b] > 0)
+            HIP_TRY(hipMemcpy2D(host + (size_t)(c0 + b) * per, (size_t)take * sizeof(double),
+                                dev + (size_t)b * per, (size_t)take * sizeof(double),
+                                (size_t)used[(size_t)b] * sizeof(double), (size_t)ne, hipMemcpyDeviceToHost));
+          ++b;
+        }
+        a = b;
+      }
+    }
+    return MHX_OK;
+  }
 };
-struct DerivedPieces {
-  double *values, *at_best, *pct, *mean, *stddev;
-  int32_t *n_used, *status;
-  size_t bytes;
-};
-static size_t derived_per_chain(const DerivedCall& q) {
-  return ((size_t)q.ne * q.take + (size_t)q.ne * (3 + q.pc.n)) * sizeof(double) +
-         (size_t)(1 + q.ne) * sizeof(int32_t);
-}
-static int64_t derived_portion(const DerivedCall& q) {
-  return std::max<int64_t>(1, (int64_t)((kSummaryStageBytes - 7 * 256) / derived_per_chain(q)));
-}
-static DerivedPieces derived_pieces(mhx_engine* e, const DerivedCall& q, int64_t n) {
-  DerivedPieces s{};
-  size_t o = 0;
-  auto take_piece = [&](size_t bytes) {
-    unsigned char* p = e->stage.p + o;
-    o += align256(bytes);
-    return p;
-  };
-  const size_t ne = (size_t)q.ne;
-  s.values = reinterpret_cast<double*>(take_piece((size_t)n * ne * q.take * sizeof(double)));
-  s.at_best = reinterpret_cast<double*>(take_piece((size_t)n * ne * sizeof(double)));
-  s.pct = reinterpret_cast<double*>(take_piece((size_t)n * ne * q.pc.n * sizeof(double)));
-  s.mean = reinterpret_cast<double*>(take_piece((size_t)n * ne * sizeof(double)));
-  s.stddev = reinterpret_cast<double*>(take_piece((size_t)n * ne * sizeof(double)));
-  s.n_used = reinterpret_cast<int32_t*>(take_piece((size_t)n * sizeof(int32_t)));
-  s.status = reinterpret_cast<int32_t*>(take_piece((size_t)n * ne * sizeof(int32_t)));
-  s.bytes = o;
-  return s;
-}
-// the part of the arguments that needs no engine: texts and names
-static int derived_prepare(DerivedCall* q, const char* const* exprs, int n_expr,
-                           const char* const* names, const int32_t* index, int n_names, int take,
-                           const int32_t* pct_num, const int32_t* pct_den, int n_pct) {
-  if (n_expr < 1 || n_expr > MHX_MAX_DERIVED || !exprs)
-    return fail(MHX_EINVAL, "n_expr must be in [1,%d]", MHX_MAX_DERIVED);
-  if (n_names < 0 || n_names > MHX_MAX_PARAMS || (n_names > 0 && (!names || !index)))
-    return fail(MHX_EINVAL, "n_names must be in [0,%d]", MHX_MAX_PARAMS);
-  q->ne = n_expr;
-  q->take = take;
-  q->n_names = n_names;
-  for (int j = 0; j < n_names; ++j) {
-    if (!valid_ident(names[j]) || !strcmp(names[j], "prob"))
-      return fail(MHX_EINVAL, "name %d is not an identifier (or is x / bounds_total / prob)", j);
-    q->names.push_back(names[j]);
-    q->idx[j] = index[j];
-  }
-  for (int k = 0; k < n_expr; ++k) {
-    if (!exprs[k] || !*exprs[k]) return fail(MHX_EINVAL, "expression %d is empty", k);
-    std::string out, err;
-    if (rtc_prepare_expr(exprs[k], q->names, "prob", &out, &err) != 0)
-      return fail(MHX_EINVAL, "expression %d: %s", k, err.c_str());
-    q->exprs.push_back(out);
-  }
-  SummaryCall pcs;
-  const int rc = summary_fill_pcts(&pcs, pct_num, pct_den, n_pct);
-  q->pc = pcs.pc;
-  return rc;
-}
-static int derived_check(mhx_engine* e, DerivedCall* q) {
-  if (!e) return fail(MHX_EINVAL, "engine is NULL");
-  if (!e->chains_ready) return fail(MHX_ESTATE, "mhx_init_chains has not been called");
-  if (q->take < 1 || q->take > e->S.R)
-    return fail(MHX_EINVAL, "take must be in [1, history_capacity = %d]", e->S.R);
-  for (int j = 0; j < q->n_names; ++j)
-    if (q->idx[j] < 0 || q->idx[j] >= e->P.d)
-      return fail(MHX_EINVAL, "index[%d] = %d outside [0,%d)", j, q->idx[j], e->P.d);
-  const int rc = use_device(e);
-  if (rc != MHX_OK) return rc;
-  std::string err;
-  q->prog = rtc_get_derived(q->exprs, q->names, &err);
-  if (!q->prog) return fail(MHX_EINVAL, "%s", err.c_str());
-  return MHX_OK;
-}
-static int derived_enqueue(mhx_engine* e, const DerivedCall& q, int64_t c0, int64_t n) {
-  int rc = use_device(e);
-  if (rc != MHX_OK) return rc;
-  if ((rc = ensure_stage(e, derived_pieces(e, q, n).bytes)) != MHX_OK) return rc;
-  const DerivedPieces s = derived_pieces(e, q, n);
-  DerivedArgs A{};
-  A.c0 = c0;
-  A.n = n;
-  A.take = q.take;
-  A.pitch = q.take;
-  for (int j = 0; j < q.n_names; ++j) A.idx[j] = q.idx[j];
-  A.values = s.values;
-  A.at_best = s.at_best;
-  const bool lds = !e->knobs.summary_no_lds && pct_lds_bytes(q.take, q.ne) <= kPctLdsBudget;
-  HIP_TRY(hipEventRecord(e->ev0, e->stream));
-  HIP_TRY(rtc_launch_derived(*q.prog, e->stream, e->S, A));
-  HIP_TRY(launch_derived_summary(e->stream, e->S, c0, n, q.take, q.ne, q.pc, lds, s.values, s.pct,
-                                 s.mean, s.stddev, s.n_used, s.status));
-  HIP_TRY(hipEventRecord(e->ev1, e->stream));
-  e->launches += 2;
-  return MHX_OK;
-}
-static int derived_collect(mhx_engine* e, const DerivedCall& q, int64_t c0, int64_t n) {
-  int rc = use_device(e);
-  if (rc != MHX_OK) return rc;
-  const DerivedPieces s = derived_pieces(e, q, n);
-  HIP_TRY(hipEventSynchronize(e->ev1));
-  float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
-  e->summary_ms += (double)ms;
-  const size_t ne = (size_t)q.ne;
-  auto back = [&](double* host, const double* dev, size_t per) -> hipError_t {
-    if (!host || per == 0) return hipSuccess;
-    return hipMemcpy(host + (size_t)c0 * per, dev, (size_t)n * per * sizeof(double), hipMemcpyDeviceToHost);
-  };
-  HIP_TRY(back(q.at_best, s.at_best, ne));
-  HIP_TRY(back(q.pct, s.pct, ne * q.pc.n));
-  HIP_TRY(back(q.mean, s.mean, ne));
-  HIP_TRY(back(q.stddev, s.stddev, ne));
-  if (q.status)
-    HIP_TRY(hipMemcpy(q.status + (size_t)c0 * ne, s.status, (size_t)n * ne * sizeof(int32_t),
-                      hipMemcpyDeviceToHost));
-  std::vector<int32_t> used;
-  if (q.n_used || q.values) {
-    used.resize((size_t)n);
-    HIP_TRY(hipMemcpy(used.data(), s.n_used, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (q.n_used) memcpy(q.n_used + c0, used.data(), (size_t)n * sizeof(int32_t));
-  }
-  if (q.values) {
-    // entries at and beyond n_used are not the caller's to lose: whole runs of full windows in
-    // one copy, a chain with a shorter window row by row
-    const size_t per = ne * (size_t)q.take;
-    int64_t a = 0;
-    while (a < n) {
-      int64_t b = a;
-      while (b < n && used[(size_t)b] == q.take) ++b;
-      if (b > a)
-        HIP_TRY(hipMemcpy(q.values + (size_t)(c0 + a) * per, s.values + (size_t)a * per,
-                          (size_t)(b - a) * per * sizeof(double), hipMemcpyDeviceToHost));
-      if (b < n) {
-        if (used[(size_t)b] > 0)
-          HIP_TRY(hipMemcpy2D(q.values + (size_t)(c0 + b) * per, (size_t)q.take * sizeof(double),
-                              s.values + (size_t)b * per, (size_t)q.take * sizeof(double),
-                              (size_t)used[(size_t)b] * sizeof(double), ne, hipMemcpyDeviceToHost));
-        ++b;
-      }
-      a = b;
-    }
-  }
-  return MHX_OK;
-}
-// calls[i] on engs[i]: round by round, every engine's portion enqueued before any is waited for
-static int derived_run(const std::vector<mhx_engine*>& engs, std::vector<DerivedCall>& calls) {
-  int rc = MHX_OK;
-  for (size_t i = 0; i < engs.size(); ++i)
-    if ((rc = derived_check(engs[i], &calls[i])) != MHX_OK) return rc;
-  std::vector<int64_t> at(engs.size(), 0), now(engs.size(), 0);
-  for (mhx_engine* e : engs) e->summary_ms = 0.0;
-  for (;;) {
-    bool any = false;
-    for (size_t i = 0; i < engs.size(); ++i) {
-      now[i] = std::min<int64_t>(engs[i]->cfg.n_chains - at[i], derived_portion(calls[i]));
-      if (now[i] <= 0) continue;
-      any = true;
-      if ((rc = derived_enqueue(engs[i], calls[i], at[i], now[i])) != MHX_OK) {
-        for (mhx_engine* e : engs) drain(e);
-        return rc;
-      }
-    }
-    if (!any) return MHX_OK;
-    for (size_t i = 0; i < engs.size(); ++i) {
-      if (now[i] <= 0) continue;
-      if ((rc = derived_collect(engs[i], calls[i], at[i], now[i])) != MHX_OK) {
-        for (mhx_engine* e : engs) drain(e);
-        return rc;
-      }
-      at[i] += now[i];
-    }
-  }
-}
-// the call of an engine whose chain 0 is the caller's chain `first`
-static DerivedCall derived_at(const DerivedCall& q0, size_t first, double* at_most_likely,
-                              double* pct, double* mean, double* stddev, double* values,
-                              int32_t* n_used, int32_t* status) {
-  DerivedCall q = q0;
-  const size_t ne = (size_t)q.ne;
-  q.at_best = at_most_likely ? at_most_likely + first * ne : nullptr;
-  q.pct = pct ? pct + first * ne * q.pc.n : nullptr;
-  q.mean = mean ? mean + first * ne : nullptr;
-  q.stddev = stddev ? stddev + first * ne : nullptr;
-  q.values = values ? values + first * ne * (size_t)q.take : nullptr;
-  q.n_used = n_used ? n_used + first : nullptr;
-  q.status = status ? status + first * ne : nullptr;
-  return q;
-}
 
 int mhx_get_derived(mhx_engine* e, const char* const* exprs, int n_expr, const char* const* names,
                     const int32_t* index, int n_names, int take, const int32_t* pct_num,
@@ -2757,12 +2615,10 @@ int mhx_get_derived(mhx_engine* e, const char* const* exprs, int n_expr, const c
                     double* mean, double* stddev, double* values, int32_t* n_used,
                     int32_t* status) {
   if (!e) return fail(MHX_EINVAL, "engine is NULL");
-  DerivedCall q0;
-  const int rc = derived_prepare(&q0, exprs, n_expr, names, index, n_names, take, pct_num, pct_den, n_pct);
-  if (rc != MHX_OK) return rc;
-  std::vector<DerivedCall> calls{
-      derived_at(q0, 0, at_most_likely, pct, mean, stddev, values, n_used, status)};
-  return derived_run({e}, calls);
+  DerivedCall q;
+  const int rc = q.prepare(exprs, n_expr, names, index, n_names, take, pct_num, pct_den, n_pct,
+                           at_most_likely, pct, mean, stddev, values, n_used, status);
+  return rc != MHX_OK ? rc : run_portions(e, q);
 }
 
 int mhx_set_history(mhx_engine* e, int64_t chain, const double* prob, const double* theta, int n) {
@@ -3255,43 +3111,35 @@ int mhx_group_get_counters(mhx_group* g, uint64_t* chain_steps, uint64_t* kernel
   return MHX_OK;
 }
 
-// walker-set-get over a group: engine i's results land at its first global chain
-static int group_summary(mhx_group* g, SummaryCall q) {
+// the batched read-outs over a group: engine i's results land at its first global chain
+extern "C++" {
+template <class Q>
+static int run_portions(mhx_group* g, const Q& q) {
   if (!g) return fail(MHX_EINVAL, "group is NULL");
-  std::vector<SummaryCall> calls;
-  for (size_t i = 0; i < g->eng.size(); ++i) {
-    const SummaryLayout y = summary_layout(g->eng[i], q);
-    SummaryCall c = q;
-    const size_t f = (size_t)g->first[i];
-    for (int k = 0; k < 2; ++k) {
-      if (c.hd[k]) c.hd[k] += f * y.nd[k];
-      if (c.hi[k]) c.hi[k] += f;
-    }
-    calls.push_back(c);
-  }
-  return summary_run(g->eng, calls);
+  return run_portions(g->eng, g->first.data(), q);
+}
 }
 int mhx_group_get_percentiles(mhx_group* g, int take, const int32_t* pct_num,
                               const int32_t* pct_den, int n_pct, double* out, int32_t* n_used) {
   if (!g) return fail(MHX_EINVAL, "group is NULL");
-  SummaryCall q = summary_call(SUM_PERCENTILES, take, out, nullptr, n_used, nullptr);
+  SummaryCall q(SUM_PERCENTILES, take, out, nullptr, n_used, nullptr);
   int rc = MHX_OK;
   for (mhx_engine* e : g->eng)
-    if ((rc = summary_check(e, q)) != MHX_OK) return rc;
-  if ((rc = summary_fill_pcts(&q, pct_num, pct_den, n_pct)) != MHX_OK) return rc;
+    if ((rc = window_check(e, take)) != MHX_OK) return rc;
+  if ((rc = fill_pcts(&q.pc, pct_num, pct_den, n_pct)) != MHX_OK) return rc;
   if (n_pct == 0) return MHX_OK;
-  return group_summary(g, q);
+  return run_portions(g, q);
 }
 int mhx_group_get_covariances(mhx_group* g, int take, double* cov, int32_t* n_unique,
                               int32_t* status) {
-  return group_summary(g, summary_call(SUM_COVARIANCES, take, cov, nullptr, n_unique, status));
+  return run_portions(g, SummaryCall(SUM_COVARIANCES, take, cov, nullptr, n_unique, status));
 }
 int mhx_group_get_proposal_factors(mhx_group* g, int take, double* L, int32_t* status,
                                    int32_t* n_forward) {
-  return group_summary(g, summary_call(SUM_FACTORS, take, L, nullptr, status, n_forward));
+  return run_portions(g, SummaryCall(SUM_FACTORS, take, L, nullptr, status, n_forward));
 }
 int mhx_group_get_window_best(mhx_group* g, int take, double* prob, double* theta) {
-  return group_summary(g, summary_call(SUM_BEST, take, prob, theta, nullptr, nullptr));
+  return run_portions(g, SummaryCall(SUM_BEST, take, prob, theta, nullptr, nullptr));
 }
 
 int mhx_group_get_fit_bands(mhx_group* g, int fn, int take, const double* xcols, int n_cols,
@@ -3299,14 +3147,7 @@ int mhx_group_get_fit_bands(mhx_group* g, int fn, int take, const double* xcols,
                             int32_t* status) {
   if (!g) return fail(MHX_EINVAL, "group is NULL");
   if (m < 1) return fail(MHX_EINVAL, "m must be >= 1");
-  std::vector<FitCall> calls;
-  for (size_t i = 0; i < g->eng.size(); ++i) {
-    const size_t f = (size_t)g->first[i];
-    calls.push_back(band_call(fn, take, xcols, n_cols, m, ymax ? ymax + f * (size_t)m : nullptr,
-                              ymin ? ymin + f * (size_t)m : nullptr,
-                              n_selected ? n_selected + f : nullptr, status ? status + f : nullptr));
-  }
-  return fit_run(g->eng, calls);
+  return run_portions(g, FitCall(fn, take, -1, nullptr, xcols, n_cols, m, ymax, ymin, n_selected, status));
 }
 
 int mhx_group_get_derived(mhx_group* g, const char* const* exprs, int n_expr,
@@ -3315,14 +3156,10 @@ int mhx_group_get_derived(mhx_group* g, const char* const* exprs, int n_expr,
                           double* at_most_likely, double* pct, double* mean, double* stddev,
                           double* values, int32_t* n_used, int32_t* status) {
   if (!g) return fail(MHX_EINVAL, "group is NULL");
-  DerivedCall q0;
-  const int rc = derived_prepare(&q0, exprs, n_expr, names, index, n_names, take, pct_num, pct_den, n_pct);
-  if (rc != MHX_OK) return rc;
-  std::vector<DerivedCall> calls;
-  for (size_t i = 0; i < g->eng.size(); ++i)
-    calls.push_back(derived_at(q0, (size_t)g->first[i], at_most_likely, pct, mean, stddev, values,
-                               n_used, status));
-  return derived_run(g->eng, calls);
+  DerivedCall q;
+  const int rc = q.prepare(exprs, n_expr, names, index, n_names, take, pct_num, pct_den, n_pct,
+                           at_most_likely, pct, mean, stddev, values, n_used, status);
+  return rc != MHX_OK ? rc : run_portions(g, q);
 }
 
 }  // extern "C"

@@ -1,0 +1,160 @@
+// mhx_stage.hpp -- the arithmetic of the batched read-outs' stage buffer as pure functions of
+// plain numbers (no HIP, no engine): how a portion of items is carved into 256-byte aligned
+// pieces, how many items fit the budget, and the order in which portions are worked through.
+// mhx_engine.cpp's portion runner launches what these describe; tests/test_stage_plan.py pins the
+// portion sizes and the carving on the CPU.
+#pragma once
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+
+namespace mhx {
+
+constexpr size_t kStageAlign = 256;
+inline size_t align256(size_t v) { return (v + kStageAlign - 1) & ~(kStageAlign - 1); }
+
+// what a read-out's pieces may take of an engine's stage buffer, whatever the call's size
+constexpr size_t kStageBudget = (size_t)64 << 20;
+// points of x a fit launch works on at a time
+constexpr int64_t kFitChunkPoints = (int64_t)1 << 17;
+
+// hands out consecutive 256-byte aligned offsets
+struct Carver {
+  size_t take(size_t bytes) {
+    const size_t o = end_;
+    end_ += align256(bytes);
+    asked_ += bytes;
+    ++pieces_;
+    return o;
+  }
+  size_t bytes() const { return end_; }    // the buffer the pieces need
+  size_t asked() const { return asked_; }  // ... of which the pieces themselves
+  int pieces() const { return pieces_; }
+
+ private:
+  size_t end_ = 0, asked_ = 0;
+  int pieces_ = 0;
+};
+
+inline int64_t portion_items(size_t budget, size_t fixed_bytes, size_t per_item_bytes) {
+  return std::max<int64_t>(1, (int64_t)((budget - fixed_bytes) / per_item_bytes));
+}
+// The items of one portion, from the piece list that carves it: carve(carver, n) takes the pieces
+// of n items, each of a size linear in n.  What 0 items take is fixed, an item adds the
+// difference, and every piece may lose up to kStageAlign bytes to its alignment.
+template <class Carve>
+int64_t portion_of(Carve&& carve) {
+  Carver none, one;
+  carve(none, 0);
+  carve(one, 1);
+  return portion_items(kStageBudget, none.asked() + (size_t)none.pieces() * kStageAlign, one.asked() - none.asked());
+}
+
+// ---- the pieces of each read-out, in the order they lie in the buffer
+
+// walker-set-get: two double arrays [n][nd], two int arrays [n] (ni of them in use), the index
+// scratch [n][take] of the covariance and factor kernels
+enum { SUM_PERCENTILES = 0, SUM_COVARIANCES = 1, SUM_FACTORS = 2, SUM_BEST = 3 };
+struct SummaryShape {
+  size_t nd[2] = {0, 0};
+  int ni = 0;
+  size_t scratch = 0;  // ints per chain
+};
+inline SummaryShape summary_shape(int kind, int d_, int n_pct, int take) {
+  const size_t d = (size_t)d_, dd = d * d;
+  SummaryShape y;
+  switch (kind) {
+    case SUM_PERCENTILES: y.nd[0] = (size_t)n_pct * d; y.ni = 1; break;
+    case SUM_COVARIANCES: y.nd[0] = dd; y.ni = 2; y.scratch = (size_t)take; break;
+    case SUM_FACTORS: y.nd[0] = y.nd[1] = dd; y.ni = 2; y.scratch = (size_t)take; break;
+    default: y.nd[0] = 1; y.nd[1] = d; break;
+  }
+  return y;
+}
+struct SummaryPieces {
+  size_t dv[2], iv[2], scratch;
+};
+inline SummaryPieces carve_summary(Carver& c, const SummaryShape& y, int64_t n_) {
+  const size_t n = (size_t)n_;
+  SummaryPieces s;
+  for (int k = 0; k < 2; ++k) s.dv[k] = c.take(n * y.nd[k] * sizeof(double));
+  for (int k = 0; k < 2; ++k) s.iv[k] = c.take(k < y.ni ? n * sizeof(int32_t) : 0);
+  s.scratch = c.take(n * y.scratch * sizeof(int32_t));
+  return s;
+}
+
+// fit curves and bands, n items at m points (take 0: parameter vectors [n][d], else the selected
+// steps' slots [n][take] of the chains).  The pieces whose size depends on the items alone come
+// first: they keep their place from one chunk of points to the next.  theta is carved for the
+// bands too, which leave it unused: an item has always been budgeted with it.
+struct FitPieces {
+  size_t sel, n_sel, status, theta, x0, x1, ymax, ymin;
+};
+inline FitPieces carve_fit(Carver& c, int d, int take, int64_t n_, int64_t m_) {
+  const size_t n = (size_t)n_, m = (size_t)m_;
+  FitPieces s;
+  s.sel = c.take(n * (size_t)take * sizeof(int32_t));
+  s.n_sel = c.take(n * sizeof(int32_t));
+  s.status = c.take(n * sizeof(int32_t));
+  s.theta = c.take(n * (size_t)d * sizeof(double));
+  s.x0 = c.take(m * sizeof(double));
+  s.x1 = c.take(m * sizeof(double));
+  s.ymax = c.take(n * m * sizeof(double));
+  s.ymin = c.take(n * m * sizeof(double));
+  return s;
+}
+
+// derived quantities: the values [n][ne][take], the results [n][ne] (percentiles [n][ne][n_pct]),
+// n_used [n], status [n][ne]
+struct DerivedPieces {
+  size_t values, at_best, pct, mean, stddev, n_used, status;
+};
+inline DerivedPieces carve_derived(Carver& c, int ne_, int take, int n_pct, int64_t n_) {
+  const size_t n = (size_t)n_, ne = (size_t)ne_;
+  DerivedPieces s;
+  s.values = c.take(n * ne * (size_t)take * sizeof(double));
+  s.at_best = c.take(n * ne * sizeof(double));
+  s.pct = c.take(n * ne * (size_t)n_pct * sizeof(double));
+  s.mean = c.take(n * ne * sizeof(double));
+  s.stddev = c.take(n * ne * sizeof(double));
+  s.n_used = c.take(n * sizeof(int32_t));
+  s.status = c.take(n * ne * sizeof(int32_t));
+  return s;
+}
+
+// ---- the order of the portions: `items` in portions of at most `per_portion`, each worked
+// through `points` in chunks of at most `chunk` - points first, then items.  The first portion
+// is the largest in both.
+struct Portion {
+  int64_t i0, n, m0, m;
+};
+struct PortionCursor {
+  int64_t items = 0, per_portion = 1, points = 1, chunk = 1;
+  int64_t i0 = 0, m0 = 0;
+  bool done() const { return i0 >= items; }
+  Portion now() const {
+    return {i0, std::min(items - i0, per_portion), m0, std::min(points - m0, chunk)};
+  }
+  void advance() {
+    const Portion p = now();
+    m0 += p.m;
+    if (m0 >= points) {
+      m0 = 0;
+      i0 += p.n;
+    }
+  }
+};
+// The cursor of a call over `items` and `points` (1 unless x goes in chunks): at most
+// kFitChunkPoints points at a time, and the items per portion that carve(carver, n, m) gives at
+// that many points.
+template <class Carve>
+PortionCursor portion_cursor(int64_t items, int64_t points, Carve&& carve) {
+  PortionCursor at;
+  at.items = items;
+  at.points = points;
+  at.chunk = std::min(points, kFitChunkPoints);
+  at.per_portion = portion_of([&](Carver& c, int64_t n) { carve(c, n, at.chunk); });
+  return at;
+}
+
+}  // namespace mhx

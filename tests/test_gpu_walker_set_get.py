@@ -86,7 +86,9 @@ def reduce_best(prob):
     return best
 
 
-def check_crafted(mhx, e, walks, takes):
+def check_crafted(mhx, e, walks, takes, n_checked=None):
+    """every selector of engine e at every take against the mirror and the per-chain route, for
+    the chains whose walks are given: all of them, unless n_checked says how many"""
     from lisp_mcmc_amd import walker as mirror
     capi = mhx.capi
     seen = set()
@@ -113,7 +115,7 @@ def check_crafted(mhx, e, walks, takes):
             seen.add(int(s1))
             b = reduce_best(pr[:t])
             assert bp[c] == pr[b] and np.array_equal(bth[c], th[b]), (take, c)
-        assert len(walks) == n
+        assert len(walks) == (n if n_checked is None else n_checked)
     return seen
 
 
@@ -141,6 +143,45 @@ def test_crafted_histories_every_selector_every_chain_d33(mhx):
     capi = mhx.capi
     assert {capi.L_OK, capi.L_CAUGHT, capi.L_EMPTY} <= seen, seen
     e.close()
+
+
+def test_chains_beyond_one_portion_of_the_stage_buffer(mhx):
+    """d = 33 at take 8: a chain of the factor call takes 2 x 33 x 33 doubles, two ints and 8
+    ints of scratch, 17464 bytes, so 3842 chains fill the 64 MiB of a portion - an engine of 4000
+    chains works through two, and so does either engine of a group of 8000.  (history_capacity 8
+    is asked for; the ring is never shorter than the adaptation windows, 1024 steps.)  Chain c
+    carries walk c % 40; chains 0-39 are checked against the mirror, every other chain must give
+    its walk's results to the bit, and the group what the single engine gives."""
+    rng = np.random.default_rng(4000)
+    d, ring, period, n = 33, 8, 40, 4000
+    per_chain = 2 * d * d * 8 + 2 * 4 + ring * 4
+    assert per_chain == 17464 and ((1 << 26) - 5 * 256) // per_chain == 3842 < n
+    walks = [crafted_walk(rng, 1 + k % ring, d, k % 6) for k in range(period)]
+    assert {len(pr) for pr, _ in walks} == set(range(1, ring + 1))
+    e = line_engine(mhx, n, d=d, used=range(0, 32, 4), history_capacity=ring)
+    g = mhx.Group(2 * n, d, 1, devices=[0, 0], history_capacity=ring)
+    g.set_function(0, mhx.capi.MODEL_POLY, (), list(range(0, 32, 4)))
+    g.set_dataset(0, LF_X, LF_Y, np.full(5, 0.2))
+    assert g.ranges == [(0, n), (n, n)]
+    for obj in (e, g):
+        obj.init_chains(np.linspace(-1.0, 2.0, d))
+    for part, (first, count) in zip([e] + g.engines, [(0, n)] + g.ranges):
+        for c in range(count):
+            part.set_history(c, *walks[(first + c) % period])
+    check_crafted(mhx, e, walks, (ring,), n_checked=period)
+    calls = (lambda o: o.percentiles(ring, PCTS), lambda o: o.covariances(ring),
+             lambda o: o.proposal_factors(ring), lambda o: o.window_best(ring))
+    for which, call in enumerate(calls):
+        single, whole = call(e), call(g)
+        for k in range(len(single)):
+            a, b = np.asarray(single[k]), np.asarray(whole[k])
+            assert a.shape[0] == n and b.shape[0] == 2 * n, (which, k)
+            # every chain is its walk's chain among the first 40 (2n is a multiple of the period)
+            assert a.tobytes() == a[np.arange(n) % period].tobytes(), (which, k)
+            assert b.tobytes() == b[np.arange(2 * n) % period].tobytes(), (which, k)
+            assert b[:n].tobytes() == a.tobytes(), (which, k)
+    e.close()
+    g.close()
 
 
 def outcome(fn):
