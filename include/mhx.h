@@ -26,6 +26,8 @@
  *   nth-percentile             M:1495-1506   -> mhx_percentile_rank (the position rule)
  *   walker-get-data-and-fit    M:1230-1255   -> mhx_eval_function, mhx_get_fit_bands,
  *                                               mhx_band_count, mhx_group_get_fit_bands
+ *   walker-param-histo         M:1361-1369   -> mhx_get_histograms (make-histo M:1541-1564 as
+ *   walker-plot-corner         M:1333-1359   -> mhx_get_pair_grids   counts over given edges)
  *   walker-with-exp            M:1052-1064   -> mhx_get_derived, mhx_group_get_derived (the
  *                                               expression at every step, and its posterior)
  *   walker-modify              M:547-580     -> mhx_walker_modify (+ mhx_set_history)
@@ -71,6 +73,9 @@ extern "C" {
 #define MHX_MAX_BOUNDS 64    /* bounds in one prior-bounds-let block                */
 #define MHX_MAX_PERCENTILES 16 /* percentiles one mhx_get_percentiles call may ask for */
 #define MHX_MAX_DERIVED 16   /* expressions one mhx_get_derived call may evaluate        */
+#define MHX_MAX_HISTO_BINS 1024 /* bins of one column of mhx_get_histograms               */
+#define MHX_MAX_GRID_BINS 64 /* bins a side of one mhx_get_pair_grids grid               */
+#define MHX_MAX_GRID_PAIRS 4096 /* pairs one mhx_get_pair_grids call may count            */
 
 /* ---- status codes ------------------------------------------------------ */
 enum {
@@ -431,7 +436,8 @@ int mhx_get_window_best(mhx_engine* e, int take, double* prob, double* theta);
  * not below mhx_config.history_capacity and the adaptation window). */
 int mhx_get_history_capacity(mhx_engine* e, int32_t* capacity);
 /* HIP-event milliseconds the kernels of the engine's last mhx_get_percentiles / _covariances /
- * _proposal_factors / _window_best / _fit_bands / _derived or mhx_eval_function call ran (all portions; copies excluded). */
+ * _proposal_factors / _window_best / _fit_bands / _derived / _histograms / _pair_grids or
+ * mhx_eval_function call ran (all portions; copies excluded). */
 int mhx_get_summary_timing(mhx_engine* e, double* kernel_ms);
 /* The same for a group, gathered in global chain order like mhx_group_get_state; every
  * device's launch is enqueued before any is waited for. */
@@ -527,6 +533,61 @@ int mhx_group_get_derived(mhx_group* g, const char* const* exprs, int n_expr,
                           const int32_t* pct_num, const int32_t* pct_den, int n_pct,
                           double* at_most_likely, double* pct, double* mean, double* stddev,
                           double* values, int32_t* n_used, int32_t* status);
+
+/* ---- walker-param-histo (M:1361-1369) and walker-plot-corner (M:1333-1359) as counts ---------
+ * The reference bins one parameter of one walk (make-histo M:1541-1557) and scatters every step
+ * of every parameter pair.  Here every chain's window is counted on the device ring over edges
+ * the CALLER supplies, and only integers come back: 20 per parameter instead of the trace, a grid
+ * of pair counts instead of the scatter.  The device forms no edge and adds no floating-point
+ * number, so the counts are exact whatever the order of its threads.
+ * The bin rule, make-histo's: with the edges b_0 <= b_1 <= ... <= b_B of a column, a value v
+ * falls in bin n = the smallest n in 1..B with v <= b_n.  A value equal to b_0 lies in bin 1;
+ * with all edges equal bin 1 holds every value equal to them; v < b_0 counts as `below`, v > b_B
+ * as `above` (make-histo's own edges - (linspace bottom top :len B+1), exact rationals coerced to
+ * double - can leave the greatest value above b_B: the reference drops it, here it is counted);
+ * a NaN is counted nowhere and sets the column's status; +-inf follow the comparisons.
+ * The window is mhx_get_percentiles': the newest min(take, walker-length, steps held) steps,
+ * n_used[n_chains] as there; take in [1, history_capacity]; any output may be NULL; MHX_ESTATE
+ * before mhx_init_chains; a chain in MHX_CHAIN_FP_TRAP is served from the history it has.
+ *   cols[n_cols]   distinct parameter indices in [0, d), 1 <= n_cols <= d, in any order
+ *   edges          [n_cols][n_bins + 1] when edges_per_chain == 0: one set for every chain (the
+ *                  histograms of a walker set are then comparable), or
+ *                  [n_chains][n_cols][n_bins + 1] when edges_per_chain == 1.  Every row free of
+ *                  NaN and non-decreasing, else MHX_EINVAL (mhx_last_error names the chain and
+ *                  the column) and nothing is launched
+ *   n_bins         in [1, MHX_MAX_HISTO_BINS]
+ *   counts[n_chains][n_cols][n_bins]   counts[c][k][n-1] = values of column k in bin n
+ *   outside[n_chains][n_cols][2]       (below, above): the counts and these sum to n_used[c]
+ *                                      unless the column held a NaN
+ *   status[n_chains][n_cols]           1: the column held a NaN, else 0
+ * Worked through in portions whose device scratch stays below 64 MiB whatever the call's size;
+ * mhx_get_summary_timing covers the call. */
+int mhx_get_histograms(mhx_engine* e, int take, const int32_t* cols, int n_cols, int n_bins,
+                       const double* edges, int edges_per_chain, int32_t* counts,
+                       int32_t* outside, int32_t* n_used, int32_t* status);
+/* The joint counts of parameter pairs over the same edges, bin rule and window.  pair_a[q] and
+ * pair_b[q] are two distinct places in cols; any list of 0 <= n_pairs <= MHX_MAX_GRID_PAIRS
+ * pairs; n_bins in [1, MHX_MAX_GRID_BINS].
+ *   counts[n_chains][n_pairs][n_bins][n_bins]  cell [i][j] of pair q: the steps whose
+ *                                      cols[pair_a[q]] value lies in bin i+1 and whose
+ *                                      cols[pair_b[q]] value lies in bin j+1
+ *   n_inside[n_chains][n_pairs]        the steps with both values in a bin (the cells' sum)
+ *   status[n_chains][n_pairs]          1: either column held a NaN, else 0
+ * A call whose pieces for ONE chain (n_pairs n_bins^2 counts and the rest) exceed the 64 MiB of a
+ * portion is refused with MHX_EINVAL; nothing is allocated for it. */
+int mhx_get_pair_grids(mhx_engine* e, int take, const int32_t* cols, int n_cols,
+                       const int32_t* pair_a, const int32_t* pair_b, int n_pairs, int n_bins,
+                       const double* edges, int edges_per_chain, int32_t* counts,
+                       int32_t* n_inside, int32_t* n_used, int32_t* status);
+/* The same for a group, in global chain order (per-chain edges too); every device's work is
+ * enqueued before any is waited for. */
+int mhx_group_get_histograms(mhx_group* g, int take, const int32_t* cols, int n_cols, int n_bins,
+                             const double* edges, int edges_per_chain, int32_t* counts,
+                             int32_t* outside, int32_t* n_used, int32_t* status);
+int mhx_group_get_pair_grids(mhx_group* g, int take, const int32_t* cols, int n_cols,
+                             const int32_t* pair_a, const int32_t* pair_b, int n_pairs, int n_bins,
+                             const double* edges, int edges_per_chain, int32_t* counts,
+                             int32_t* n_inside, int32_t* n_used, int32_t* status);
 
 /* Restore a saved walk (walker-load, sketched in the comments M:987-1001): prob[n], theta[n][d]
  * NEWEST FIRST, as walker-save would have written them.  Sets the ring (newest

@@ -138,6 +138,14 @@ SIGNATURES = {
     "mhx_group_get_derived": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_int,
                                         C.POINTER(C.c_char_p), i32p, C.c_int, C.c_int, i32p, i32p,
                                         C.c_int, f64p, f64p, f64p, f64p, f64p, i32p, i32p]),
+    "mhx_get_histograms": (C.c_int, [C.c_void_p, C.c_int, i32p, C.c_int, C.c_int, f64p, C.c_int,
+                                     i32p, i32p, i32p, i32p]),
+    "mhx_get_pair_grids": (C.c_int, [C.c_void_p, C.c_int, i32p, C.c_int, i32p, i32p, C.c_int, C.c_int,
+                                     f64p, C.c_int, i32p, i32p, i32p, i32p]),
+    "mhx_group_get_histograms": (C.c_int, [C.c_void_p, C.c_int, i32p, C.c_int, C.c_int, f64p, C.c_int,
+                                           i32p, i32p, i32p, i32p]),
+    "mhx_group_get_pair_grids": (C.c_int, [C.c_void_p, C.c_int, i32p, C.c_int, i32p, i32p, C.c_int,
+                                           C.c_int, f64p, C.c_int, i32p, i32p, i32p, i32p]),
 }
 
 _lib = None

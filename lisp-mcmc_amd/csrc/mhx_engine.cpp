@@ -2621,6 +2621,222 @@ int mhx_get_derived(mhx_engine* e, const char* const* exprs, int n_expr, const c
   return rc != MHX_OK ? rc : run_portions(e, q);
 }
 
+// ---- walker-param-histo (M:1361-1369) and walker-plot-corner (M:1333-1359) as integer counts
+// over the caller's edges, for every chain on the device (k_histograms, k_pair_grids).  A
+// portion's pieces: the edges - one set, or the portion's chains' - the counts, what fell outside
+// / inside, n_used, status; the grids' pair list besides.
+extern "C++" {
+// what the two calls share: the window, the columns and the edges
+struct BinSpec {
+  int take = 0, n_cols = 0, n_bins = 0, per_chain = 0;
+  ColList cl{};
+  size_t row() const { return (size_t)n_cols * ((size_t)n_bins + 1); }  // doubles of one set of edge rows
+  // the arguments against every engine of the call; the edges of ALL its chains are read here,
+  // in the caller's (global) chain order, before anything is launched
+  int prepare(const std::vector<mhx_engine*>& engs, int take_, const int32_t* cols, int n_cols_,
+              int n_bins_, int max_bins, const double* edges, int edges_per_chain) {
+    int rc = MHX_OK;
+    int64_t chains = 0;
+    for (const mhx_engine* e : engs) {
+      if ((rc = window_check(e, take_)) != MHX_OK) return rc;
+      chains += e->cfg.n_chains;
+    }
+    const int d = engs[0]->P.d;
+    if (n_bins_ < 1 || n_bins_ > max_bins) return fail(MHX_EINVAL, "n_bins must be in [1,%d]", max_bins);
+    if (n_cols_ < 1 || n_cols_ > d || !cols) return fail(MHX_EINVAL, "n_cols must be in [1, d = %d]", d);
+    if (edges_per_chain != 0 && edges_per_chain != 1) return fail(MHX_EINVAL, "edges_per_chain must be 0 or 1");
+    if (!edges) return fail(MHX_EINVAL, "edges is NULL");
+    take = take_, n_cols = n_cols_, n_bins = n_bins_, per_chain = edges_per_chain;
+    cl.n = n_cols;
+    for (int p = 0; p <= MHX_MAX_PARAMS; ++p) cl.of_param[p] = -1, cl.idx[p] = 0;
+    for (int c = 0; c < n_cols; ++c) {
+      if (cols[c] < 0 || cols[c] >= d) return fail(MHX_EINVAL, "cols[%d] = %d outside [0,%d)", c, cols[c], d);
+      if (cl.of_param[cols[c]] >= 0)
+        return fail(MHX_EINVAL, "cols[%d] = %d is cols[%d] again", c, cols[c], cl.of_param[cols[c]]);
+      cl.of_param[cols[c]] = c;
+      cl.idx[c] = cols[c];
+    }
+    const int64_t sets = per_chain ? chains : 1;
+    for (int64_t s = 0; s < sets; ++s)
+      for (int c = 0; c < n_cols; ++c) {
+        const double* b = edges + (size_t)s * row() + (size_t)c * ((size_t)n_bins + 1);
+        for (int k = 0; k <= n_bins; ++k)
+          if (b[k] != b[k] || (k > 0 && b[k] < b[k - 1]))
+            return fail(MHX_EINVAL, "edges of chain %lld, column %d: edge %d is %s", per_chain ? (long long)s : -1LL,
+                        c, k, b[k] != b[k] ? "a NaN" : "below the edge before it");
+      }
+    return MHX_OK;
+  }
+  int check(const mhx_engine* e) const {
+    const int rc = window_check(e, take);
+    if (rc != MHX_OK) return rc;
+    for (int c = 0; c < n_cols; ++c)
+      if (cl.idx[c] >= e->P.d) return fail(MHX_EINVAL, "cols[%d] = %d outside [0,%d)", c, cl.idx[c], e->P.d);
+    return MHX_OK;
+  }
+  HostDst edges_src(const double* edges) const {
+    return {const_cast<double*>(edges), per_chain ? row() * sizeof(double) : 0};
+  }
+  // the portion's edges into their piece: the shared set, or the rows of the chains from i0 on
+  int upload_edges(mhx_engine* e, const HostDst& src, size_t piece, const Portion& p) const {
+    HIP_TRY(hipMemcpyAsync(e->stage.p + piece, src.at(p.i0), (per_chain ? (size_t)p.n : 1) * row() * sizeof(double),
+                           hipMemcpyHostToDevice, e->stream));
+    return MHX_OK;
+  }
+};
+}  // extern "C++"
+
+struct HistoCall {
+  BinSpec b;
+  // EDGES is a source, not a destination: it stands among dst[] so that a group offsets the
+  // per-chain edges by the engine's first chain as it offsets the results (0 bytes an item: shared)
+  enum { COUNTS, OUTSIDE, N_USED, STATUS, EDGES };
+  HostDst dst[5];
+
+  int prepare(const std::vector<mhx_engine*>& engs, int take, const int32_t* cols, int n_cols, int n_bins,
+              const double* edges, int edges_per_chain, int32_t* counts, int32_t* outside,
+              int32_t* n_used, int32_t* status) {
+    const int rc = b.prepare(engs, take, cols, n_cols, n_bins, MHX_MAX_HISTO_BINS, edges, edges_per_chain);
+    if (rc != MHX_OK) return rc;
+    const size_t nc = (size_t)n_cols * sizeof(int32_t);
+    dst[COUNTS] = {counts, nc * (size_t)n_bins}, dst[OUTSIDE] = {outside, nc * 2};
+    dst[N_USED] = {n_used, sizeof(int32_t)}, dst[STATUS] = {status, nc};
+    dst[EDGES] = b.edges_src(edges);
+    return MHX_OK;
+  }
+  int check(mhx_engine* e) {
+    const int rc = b.check(e);
+    if (rc != MHX_OK) return rc;
+    if (!one_item_fits([&](Carver& c, int64_t n) { carve(e, c, n, 1); }))
+      return fail(MHX_EINVAL, "the pieces of ONE chain exceed the stage budget of %zu bytes", kStageBudget);
+    return MHX_OK;
+  }
+  int64_t items(const mhx_engine* e) const { return e->cfg.n_chains; }
+  int64_t points() const { return 1; }
+  HistoPieces carve(const mhx_engine*, Carver& c, int64_t n, int64_t) const {
+    return carve_histo(c, b.n_cols, b.n_bins, b.per_chain, n);
+  }
+  int upload(mhx_engine* e, const Portion& p) const {
+    Carver c;
+    const HistoPieces s = carve(e, c, p.n, p.m);
+    HIP_TRY(hipMemsetAsync(e->stage.p, 0, c.bytes(), e->stream));
+    return b.upload_edges(e, dst[EDGES], s.edges, p);
+  }
+  int launch(mhx_engine* e, const Portion& p) const {
+    Carver c;
+    const HistoPieces s = carve(e, c, p.n, p.m);
+    const bool lds = !e->knobs.histo_no_lds && histo_lds_bytes(b.n_cols, b.n_bins) <= kPctLdsBudget;
+    HIP_TRY(launch_histograms(e->stream, e->S, p.i0, p.n, b.take, b.cl, b.n_bins, stage_at<double>(e, s.edges),
+                              b.per_chain ? (int64_t)b.row() : 0, lds, stage_at<int32_t>(e, s.counts),
+                              stage_at<int32_t>(e, s.outside), stage_at<int32_t>(e, s.n_used),
+                              stage_at<int32_t>(e, s.status)));
+    return MHX_OK;
+  }
+  int collect(mhx_engine* e, const Portion& p) const {
+    Carver c;
+    const HistoPieces s = carve(e, c, p.n, p.m);
+    const size_t off[4] = {s.counts, s.outside, s.n_used, s.status};
+    for (int k = 0; k < 4; ++k) {
+      const int rc = copy_back(dst[k], p.i0, p.n, e->stage.p + off[k]);
+      if (rc != MHX_OK) return rc;
+    }
+    return MHX_OK;
+  }
+};
+
+struct GridCall {
+  BinSpec b;
+  int n_pairs = 0;
+  std::vector<int32_t> pairs;  // pair_a [n_pairs], then pair_b [n_pairs]
+  enum { COUNTS, N_INSIDE, N_USED, STATUS, EDGES };  // (EDGES: as HistoCall's)
+  HostDst dst[5];
+
+  int prepare(const std::vector<mhx_engine*>& engs, int take, const int32_t* cols, int n_cols,
+              const int32_t* pair_a, const int32_t* pair_b, int n_pairs_, int n_bins, const double* edges,
+              int edges_per_chain, int32_t* counts, int32_t* n_inside, int32_t* n_used, int32_t* status) {
+    const int rc = b.prepare(engs, take, cols, n_cols, n_bins, MHX_MAX_GRID_BINS, edges, edges_per_chain);
+    if (rc != MHX_OK) return rc;
+    if (n_pairs_ < 0 || n_pairs_ > MHX_MAX_GRID_PAIRS || (n_pairs_ > 0 && (!pair_a || !pair_b)))
+      return fail(MHX_EINVAL, "n_pairs must be in [0,%d]", MHX_MAX_GRID_PAIRS);
+    n_pairs = n_pairs_;
+    pairs.assign((size_t)2 * n_pairs, 0);
+    for (int q = 0; q < n_pairs; ++q) {
+      if (pair_a[q] < 0 || pair_a[q] >= n_cols || pair_b[q] < 0 || pair_b[q] >= n_cols || pair_a[q] == pair_b[q])
+        return fail(MHX_EINVAL, "pair %d: (%d, %d) are not two distinct places in cols[%d]", q, pair_a[q],
+                    pair_b[q], n_cols);
+      pairs[(size_t)q] = pair_a[q];
+      pairs[(size_t)n_pairs + q] = pair_b[q];
+    }
+    const size_t np = (size_t)n_pairs * sizeof(int32_t);
+    dst[COUNTS] = {counts, np * (size_t)n_bins * (size_t)n_bins}, dst[N_INSIDE] = {n_inside, np};
+    dst[N_USED] = {n_used, sizeof(int32_t)}, dst[STATUS] = {status, np};
+    dst[EDGES] = b.edges_src(edges);
+    return MHX_OK;
+  }
+  int check(mhx_engine* e) {
+    const int rc = b.check(e);
+    if (rc != MHX_OK) return rc;
+    if (!one_item_fits([&](Carver& c, int64_t n) { carve(e, c, n, 1); }))
+      return fail(MHX_EINVAL, "the pieces of ONE chain (%d pairs of %d x %d cells) exceed the stage budget of %zu bytes",
+                  n_pairs, b.n_bins, b.n_bins, kStageBudget);
+    return MHX_OK;
+  }
+  int64_t items(const mhx_engine* e) const { return e->cfg.n_chains; }
+  int64_t points() const { return 1; }
+  GridPieces carve(const mhx_engine*, Carver& c, int64_t n, int64_t) const {
+    return carve_grid(c, b.n_cols, b.n_bins, n_pairs, b.per_chain, n);
+  }
+  int upload(mhx_engine* e, const Portion& p) const {
+    Carver c;
+    const GridPieces s = carve(e, c, p.n, p.m);
+    HIP_TRY(hipMemsetAsync(e->stage.p, 0, c.bytes(), e->stream));
+    if (n_pairs > 0)
+      HIP_TRY(hipMemcpyAsync(e->stage.p + s.pairs, pairs.data(), pairs.size() * sizeof(int32_t),
+                             hipMemcpyHostToDevice, e->stream));
+    return b.upload_edges(e, dst[EDGES], s.edges, p);
+  }
+  int launch(mhx_engine* e, const Portion& p) const {
+    Carver c;
+    const GridPieces s = carve(e, c, p.n, p.m);
+    const bool lds = !e->knobs.histo_no_lds && grid_lds_bytes(b.take, b.n_cols, b.n_bins, n_pairs) <= kPctLdsBudget;
+    HIP_TRY(launch_pair_grids(e->stream, e->S, p.i0, p.n, b.take, b.cl, b.n_bins, n_pairs,
+                              stage_at<double>(e, s.edges), b.per_chain ? (int64_t)b.row() : 0,
+                              stage_at<int32_t>(e, s.pairs), lds, stage_at<int32_t>(e, s.counts),
+                              stage_at<int32_t>(e, s.n_inside), stage_at<int32_t>(e, s.n_used),
+                              stage_at<int32_t>(e, s.status)));
+    return MHX_OK;
+  }
+  int collect(mhx_engine* e, const Portion& p) const {
+    Carver c;
+    const GridPieces s = carve(e, c, p.n, p.m);
+    const size_t off[4] = {s.counts, s.n_inside, s.n_used, s.status};
+    for (int k = 0; k < 4; ++k) {
+      const int rc = copy_back(dst[k], p.i0, p.n, e->stage.p + off[k]);
+      if (rc != MHX_OK) return rc;
+    }
+    return MHX_OK;
+  }
+};
+
+int mhx_get_histograms(mhx_engine* e, int take, const int32_t* cols, int n_cols, int n_bins,
+                       const double* edges, int edges_per_chain, int32_t* counts, int32_t* outside,
+                       int32_t* n_used, int32_t* status) {
+  if (!e) return fail(MHX_EINVAL, "engine is NULL");
+  HistoCall q;
+  const int rc = q.prepare({e}, take, cols, n_cols, n_bins, edges, edges_per_chain, counts, outside, n_used, status);
+  return rc != MHX_OK ? rc : run_portions(e, q);
+}
+int mhx_get_pair_grids(mhx_engine* e, int take, const int32_t* cols, int n_cols, const int32_t* pair_a,
+                       const int32_t* pair_b, int n_pairs, int n_bins, const double* edges,
+                       int edges_per_chain, int32_t* counts, int32_t* n_inside, int32_t* n_used,
+                       int32_t* status) {
+  if (!e) return fail(MHX_EINVAL, "engine is NULL");
+  GridCall q;
+  const int rc = q.prepare({e}, take, cols, n_cols, pair_a, pair_b, n_pairs, n_bins, edges, edges_per_chain,
+                           counts, n_inside, n_used, status);
+  return rc != MHX_OK ? rc : run_portions(e, q);
+}
+
 int mhx_set_history(mhx_engine* e, int64_t chain, const double* prob, const double* theta, int n) {
   if (!e || !prob || !theta) return fail(MHX_EINVAL, "NULL argument");
   if (!e->chains_ready) return fail(MHX_ESTATE, "mhx_init_chains has not been called");
@@ -3159,6 +3375,25 @@ int mhx_group_get_derived(mhx_group* g, const char* const* exprs, int n_expr,
   DerivedCall q;
   const int rc = q.prepare(exprs, n_expr, names, index, n_names, take, pct_num, pct_den, n_pct,
                            at_most_likely, pct, mean, stddev, values, n_used, status);
+  return rc != MHX_OK ? rc : run_portions(g, q);
+}
+
+int mhx_group_get_histograms(mhx_group* g, int take, const int32_t* cols, int n_cols, int n_bins,
+                             const double* edges, int edges_per_chain, int32_t* counts,
+                             int32_t* outside, int32_t* n_used, int32_t* status) {
+  if (!g) return fail(MHX_EINVAL, "group is NULL");
+  HistoCall q;
+  const int rc = q.prepare(g->eng, take, cols, n_cols, n_bins, edges, edges_per_chain, counts, outside, n_used, status);
+  return rc != MHX_OK ? rc : run_portions(g, q);
+}
+int mhx_group_get_pair_grids(mhx_group* g, int take, const int32_t* cols, int n_cols,
+                             const int32_t* pair_a, const int32_t* pair_b, int n_pairs, int n_bins,
+                             const double* edges, int edges_per_chain, int32_t* counts,
+                             int32_t* n_inside, int32_t* n_used, int32_t* status) {
+  if (!g) return fail(MHX_EINVAL, "group is NULL");
+  GridCall q;
+  const int rc = q.prepare(g->eng, take, cols, n_cols, pair_a, pair_b, n_pairs, n_bins, edges, edges_per_chain,
+                           counts, n_inside, n_used, status);
   return rc != MHX_OK ? rc : run_portions(g, q);
 }
 

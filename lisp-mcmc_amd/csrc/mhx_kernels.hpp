@@ -3013,6 +3013,193 @@ __global__ __launch_bounds__(kPctThreads) void k_percentiles(ChainState S, int64
     }
 }
 
+// The place of v among the ascending edges b[0 .. nb] (make-histo M:1548-1557 as a bin rule: v
+// falls in bin n = the smallest n in 1..nb with v <= b[n]): 0 below b[0], n, nb + 1 above b[nb],
+// -1 a NaN.  A lower-bound search over b[1 .. nb]: at most 11 probes at nb = 1024.
+__device__ __forceinline__ int histo_slot(const double* b, int nb, double v) {
+  if (v != v) return -1;
+  if (v < b[0]) return 0;
+  int lo = 1, n = nb;
+  while (n > 0) {
+    const int half = n >> 1;
+    if (b[lo + half] < v) {
+      lo += half + 1;
+      n -= half + 1;
+    } else {
+      n = half;
+    }
+  }
+  return lo;
+}
+
+// mhx_get_histograms.  One workgroup of kPctThreads per chain.  The window's rows - t x d
+// contiguous doubles, two runs when the ring has wrapped - are read ONCE, coalesced, as
+// k_percentiles reads them; an element of a column that is asked for finds its place among that
+// column's edges and adds 1 to an int32 count.  Integer additions only: any order of the threads
+// gives the same counts.
+//   use_lds = 1: the chain's edge rows [nc][nb + 1] are copied to LDS, the counts live there
+//     ([nc][cpitch]: below, the nb bins, above; cpitch is odd, which spreads equal bins of
+//     neighbouring columns over the banks) and are written out once at the end
+//   use_lds = 0: edges and counts do not fit: the edges are read from the stage buffer and the
+//     counts go straight into the portion's pieces (zeroed by the host) with global atomics
+// edges + i * edge_stride: chain i's rows (edge_stride 0: one set for all).  counts [n][nc][nb],
+// outside [n][nc][2] = (below, above), n_used [n], status [n][nc] (1: the column held a NaN).
+__global__ __launch_bounds__(kPctThreads) void k_histograms(
+    ChainState S, int64_t c0, int take, ColList cl, int nb, const double* __restrict__ edges,
+    int64_t edge_stride, int use_lds, int cpitch, int32_t* __restrict__ counts,
+    int32_t* __restrict__ outside, int32_t* __restrict__ n_used, int32_t* __restrict__ status) {
+  const int d = S.d, nc = cl.n, ne = nb + 1, tid = threadIdx.x;
+  const int64_t i = blockIdx.x;
+  const Ring ring = ring_of(S, c0 + i);
+  const int t = ring_held(ring, take);
+  if (tid == 0) n_used[i] = t;
+  const double* ge = edges + i * edge_stride;
+  double* le = reinterpret_cast<double*>(mhx_lds_raw);
+  int32_t* cnt = reinterpret_cast<int32_t*>(le + nc * ne);
+  int32_t* nan = cnt + nc * cpitch;
+  if (use_lds) {
+    for (int f = tid; f < nc * ne; f += kPctThreads) le[f] = ge[f];
+    for (int f = tid; f < nc * cpitch + nc; f += kPctThreads) cnt[f] = 0;
+    __syncthreads();
+  }
+  // element f = s d + p of the window, oldest row first; (s, p) follow f without a division
+  const int64_t oldest = ring.nh - t;
+  const int ds = kPctThreads / d, dp = kPctThreads - ds * d;
+  int s = tid / d, p = tid - s * d;
+  for (int f = tid; f < t * d; f += kPctThreads) {
+    const int c = cl.of_param[p];
+    if (c >= 0) {
+      const int64_t slot = (oldest + s) & (int64_t)ring.mask;
+      const double v = ring.theta[slot * d + p];
+      if (use_lds) {
+        const int k = histo_slot(le + c * ne, nb, v);
+        if (k < 0)
+          nan[c] = 1;
+        else
+          atomicAdd(&cnt[c * cpitch + k], 1);
+      } else {
+        const int k = histo_slot(ge + c * ne, nb, v);
+        const int64_t col = i * nc + c;
+        if (k < 0)
+          status[col] = 1;
+        else if (k == 0 || k > nb)
+          atomicAdd(&outside[col * 2 + (k > nb ? 1 : 0)], 1);
+        else
+          atomicAdd(&counts[col * nb + (k - 1)], 1);
+      }
+    }
+    s += ds;
+    p += dp;
+    if (p >= d) {
+      p -= d;
+      ++s;
+    }
+  }
+  if (!use_lds) return;
+  __syncthreads();
+  for (int f = tid; f < nc * nb; f += kPctThreads) {
+    const int c = f / nb, k = f - c * nb;
+    counts[i * nc * nb + f] = cnt[c * cpitch + 1 + k];
+  }
+  for (int c = tid; c < nc; c += kPctThreads) {
+    outside[(i * nc + c) * 2] = cnt[c * cpitch];
+    outside[(i * nc + c) * 2 + 1] = cnt[c * cpitch + nb + 1];
+    status[i * nc + c] = nan[c];
+  }
+}
+
+// mhx_get_pair_grids.  One workgroup of kPctThreads per chain; pairs [2][np]: pair q counts the
+// steps by (bin of column pair_a[q], bin of column pair_b[q]) in counts [n][np][nb][nb];
+// n_inside [n][np] the steps with both values in a bin, status [n][np] (1: either column held a
+// NaN), n_used [n].  Integer additions only, as k_histograms.
+//   use_lds = 1: the window is read ONCE, coalesced, and the place of every (column, step) laid
+//     down in LDS as a 16-bit value (0xffff a NaN), one row of `ipitch` values per column - an
+//     odd count of 32-bit words, so that the columns of one step fall on different banks for the
+//     transposing store.  Every pair is then counted from two unit-stride rows into its cells
+//     in LDS; cells, n_inside and status are written out once at the end
+//   use_lds = 0: edges + cells + places do not fit: a step's two values are read and placed per
+//     pair, and the counts go straight into the portion's pieces (zeroed by the host)
+__global__ __launch_bounds__(kPctThreads) void k_pair_grids(
+    ChainState S, int64_t c0, int take, ColList cl, int nb, int np,
+    const double* __restrict__ edges, int64_t edge_stride, const int32_t* __restrict__ pairs,
+    int use_lds, int ipitch, int32_t* __restrict__ counts, int32_t* __restrict__ n_inside,
+    int32_t* __restrict__ n_used, int32_t* __restrict__ status) {
+  const int d = S.d, nc = cl.n, ne = nb + 1, cells = nb * nb, tid = threadIdx.x;
+  const int64_t i = blockIdx.x;
+  const Ring ring = ring_of(S, c0 + i);
+  const int t = ring_held(ring, take);
+  if (tid == 0) n_used[i] = t;
+  const double* ge = edges + i * edge_stride;
+  const int64_t oldest = ring.nh - t;
+  double* le = reinterpret_cast<double*>(mhx_lds_raw);
+  int32_t* cnt = reinterpret_cast<int32_t*>(le + nc * ne);
+  int32_t* inside = cnt + np * cells;
+  int32_t* nan = inside + np;
+  unsigned short* place = reinterpret_cast<unsigned short*>(nan + nc);
+  if (use_lds) {
+    for (int f = tid; f < nc * ne; f += kPctThreads) le[f] = ge[f];
+    for (int f = tid; f < np * cells + np + nc; f += kPctThreads) cnt[f] = 0;
+    __syncthreads();
+    const int ds = kPctThreads / d, dp = kPctThreads - ds * d;
+    int s = tid / d, p = tid - s * d;
+    for (int f = tid; f < t * d; f += kPctThreads) {
+      const int c = cl.of_param[p];
+      if (c >= 0) {
+        const int64_t slot = (oldest + s) & (int64_t)ring.mask;
+        const int k = histo_slot(le + c * ne, nb, ring.theta[slot * d + p]);
+        if (k < 0) nan[c] = 1;
+        place[c * ipitch + s] = (unsigned short)k;
+      }
+      s += ds;
+      p += dp;
+      if (p >= d) {
+        p -= d;
+        ++s;
+      }
+    }
+    __syncthreads();
+  }
+  for (int q = 0; q < np; ++q) {
+    const int a = pairs[q], b = pairs[np + q];
+    int local = 0, bad = 0;
+    for (int s = tid; s < t; s += kPctThreads) {
+      int ka, kb;
+      if (use_lds) {
+        ka = place[a * ipitch + s];
+        kb = place[b * ipitch + s];
+      } else {
+        const double* row = ring.theta + ((oldest + s) & (int64_t)ring.mask) * d;
+        ka = histo_slot(ge + a * ne, nb, row[cl.idx[a]]);
+        kb = histo_slot(ge + b * ne, nb, row[cl.idx[b]]);
+        bad |= (ka < 0 || kb < 0) ? 1 : 0;
+      }
+      if (ka >= 1 && ka <= nb && kb >= 1 && kb <= nb) {
+        const int cell = (ka - 1) * nb + (kb - 1);
+        if (use_lds)
+          atomicAdd(&cnt[q * cells + cell], 1);
+        else
+          atomicAdd(&counts[(i * np + q) * cells + cell], 1);
+        ++local;
+      }
+    }
+    const int total = wave_sum_i(local);
+    if (lane_id() == 0 && total > 0) {
+      if (use_lds)
+        atomicAdd(&inside[q], total);
+      else
+        atomicAdd(&n_inside[i * np + q], total);
+    }
+    if (bad) status[i * np + q] = 1;
+  }
+  if (!use_lds) return;
+  __syncthreads();
+  for (int f = tid; f < np * cells; f += kPctThreads) counts[i * np * cells + f] = cnt[f];
+  for (int q = tid; q < np; q += kPctThreads) {
+    n_inside[i * np + q] = inside[q];
+    status[i * np + q] = (nan[pairs[q]] | nan[pairs[np + q]]) != 0 ? 1 : 0;
+  }
+}
+
 // mhx_get_derived, second half: the posterior summaries of the values mhx_user_derived left in
 // the portion's staging buffer, vals [n][ne][pitch] newest first.  One workgroup of kPctWaves
 // wavefronts per chain, as k_percentiles, the expressions in the parameters' place.

@@ -101,6 +101,28 @@ hipError_t launch_derived_summary(hipStream_t st, const ChainState& S, int64_t c
                                   int take, int ne, const PctList& pc, bool use_lds,
                                   const double* vals, double* pct, double* mean, double* stddev,
                                   int32_t* n_used, int32_t* status);
+// mhx_get_histograms / mhx_get_pair_grids (k_histograms, k_pair_grids): the pitch of a column's
+// counts (below, the bins, above; odd) and of a column's 16-bit places (an odd count of 32-bit
+// words), and the LDS a workgroup needs for edges + counts (+ places).  Where that exceeds
+// kPctLdsBudget the caller passes use_lds = false and zeroed outputs: the counts then go straight
+// to memory.  edges: one set [nc][nb + 1] (edge_stride 0) or one per chain of the launch.
+inline int histo_count_pitch(int nb) { return (nb + 2) | 1; }
+inline int grid_place_pitch(int take) { return 2 * (((take + 1) / 2) | 1); }
+inline size_t histo_lds_bytes(int nc, int nb) {
+  return (size_t)nc * (nb + 1) * sizeof(double) + ((size_t)nc * histo_count_pitch(nb) + nc) * sizeof(int32_t);
+}
+inline size_t grid_lds_bytes(int take, int nc, int nb, int np) {
+  return (size_t)nc * (nb + 1) * sizeof(double) + ((size_t)np * nb * nb + np + nc) * sizeof(int32_t) +
+         (size_t)nc * grid_place_pitch(take) * sizeof(uint16_t);
+}
+hipError_t launch_histograms(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
+                             const ColList& cl, int nb, const double* edges, int64_t edge_stride,
+                             bool use_lds, int32_t* counts, int32_t* outside, int32_t* n_used,
+                             int32_t* status);
+hipError_t launch_pair_grids(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
+                             const ColList& cl, int nb, int np, const double* edges,
+                             int64_t edge_stride, const int32_t* pairs, bool use_lds,
+                             int32_t* counts, int32_t* n_inside, int32_t* n_used, int32_t* status);
 hipError_t launch_covariances(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
                               int* uniq, double* cov, int32_t* n_unique, int32_t* status);
 hipError_t launch_l_matrices(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,

@@ -264,6 +264,12 @@ hipError_t summary_configure() {
   if (e == hipSuccess)
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_derived_summary),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPctLdsBudget);
+  if (e == hipSuccess)
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_histograms),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPctLdsBudget);
+  if (e == hipSuccess)
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pair_grids),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPctLdsBudget);
   return e;
 }
 hipError_t launch_percentiles(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
@@ -285,6 +291,30 @@ hipError_t launch_derived_summary(hipStream_t st, const ChainState& S, int64_t c
   k_derived_summary<<<dim3((unsigned)n), dim3(kPctThreads), lds, st>>>(
       S, c0, take, ne, take, pc, use_lds ? 1 : 0, pct_column_pitch(take, ne), vals, pct, mean,
       stddev, n_used, status);
+  return hipGetLastError();
+}
+hipError_t launch_histograms(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
+                             const ColList& cl, int nb, const double* edges, int64_t edge_stride,
+                             bool use_lds, int32_t* counts, int32_t* outside, int32_t* n_used,
+                             int32_t* status) {
+  if (n <= 0) return hipSuccess;
+  const size_t lds = use_lds ? histo_lds_bytes(cl.n, nb) : 0;
+  if (lds > kPctLdsBudget) return hipErrorInvalidValue;
+  k_histograms<<<dim3((unsigned)n), dim3(kPctThreads), lds, st>>>(
+      S, c0, take, cl, nb, edges, edge_stride, use_lds ? 1 : 0, histo_count_pitch(nb), counts,
+      outside, n_used, status);
+  return hipGetLastError();
+}
+hipError_t launch_pair_grids(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
+                             const ColList& cl, int nb, int np, const double* edges,
+                             int64_t edge_stride, const int32_t* pairs, bool use_lds,
+                             int32_t* counts, int32_t* n_inside, int32_t* n_used, int32_t* status) {
+  if (n <= 0) return hipSuccess;
+  const size_t lds = use_lds ? grid_lds_bytes(take, cl.n, nb, np) : 0;
+  if (lds > kPctLdsBudget) return hipErrorInvalidValue;
+  k_pair_grids<<<dim3((unsigned)n), dim3(kPctThreads), lds, st>>>(
+      S, c0, take, cl, nb, np, edges, edge_stride, pairs, use_lds ? 1 : 0, grid_place_pitch(take),
+      counts, n_inside, n_used, status);
   return hipGetLastError();
 }
 hipError_t launch_covariances(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,

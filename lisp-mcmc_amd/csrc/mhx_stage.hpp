@@ -122,6 +122,49 @@ inline DerivedPieces carve_derived(Carver& c, int ne_, int take, int n_pct, int6
   return s;
 }
 
+// posterior histograms: the caller's edges [nc][nb + 1] - one set for every chain (per_chain 0:
+// the piece does not grow with n and comes first either way) or [n][nc][nb + 1] - the counts
+// [n][nc][nb], (below, above) [n][nc][2], n_used [n], status [n][nc]
+struct HistoPieces {
+  size_t edges, counts, outside, n_used, status;
+};
+inline HistoPieces carve_histo(Carver& c, int nc_, int nb_, int per_chain, int64_t n_) {
+  const size_t n = (size_t)n_, nc = (size_t)nc_, nb = (size_t)nb_;
+  HistoPieces s;
+  s.edges = c.take((per_chain ? n : 1) * nc * (nb + 1) * sizeof(double));
+  s.counts = c.take(n * nc * nb * sizeof(int32_t));
+  s.outside = c.take(n * nc * 2 * sizeof(int32_t));
+  s.n_used = c.take(n * sizeof(int32_t));
+  s.status = c.take(n * nc * sizeof(int32_t));
+  return s;
+}
+// pair-count grids: the edges as above and the pair list (pair_a [np], pair_b [np]), neither
+// growing with n unless the edges are per chain; the cells [n][np][nb][nb], n_inside [n][np],
+// n_used [n], status [n][np]
+struct GridPieces {
+  size_t edges, pairs, counts, n_inside, n_used, status;
+};
+inline GridPieces carve_grid(Carver& c, int nc_, int nb_, int np_, int per_chain, int64_t n_) {
+  const size_t n = (size_t)n_, nc = (size_t)nc_, nb = (size_t)nb_, np = (size_t)np_;
+  GridPieces s;
+  s.edges = c.take((per_chain ? n : 1) * nc * (nb + 1) * sizeof(double));
+  s.pairs = c.take(2 * np * sizeof(int32_t));
+  s.counts = c.take(n * np * nb * nb * sizeof(int32_t));
+  s.n_inside = c.take(n * np * sizeof(int32_t));
+  s.n_used = c.take(n * sizeof(int32_t));
+  s.status = c.take(n * np * sizeof(int32_t));
+  return s;
+}
+// Whether ONE item of a piece list fits the budget at all, by portion_of's own accounting
+// (portion_of answers 1 either way: a read-out that must not outgrow the budget asks first).
+template <class Carve>
+bool one_item_fits(Carve&& carve) {
+  Carver none, one;
+  carve(none, 0);
+  carve(one, 1);
+  return one.asked() + (size_t)none.pieces() * kStageAlign <= kStageBudget;
+}
+
 // ---- the order of the portions: `items` in portions of at most `per_portion`, each worked
 // through `points` in chunks of at most `chunk` - points first, then items.  The first portion
 // is the largest in both.

@@ -155,6 +155,13 @@ struct PctList {
   int32_t num[MHX_MAX_PERCENTILES], den[MHX_MAX_PERCENTILES];
 };
 
+// the parameters one mhx_get_histograms / mhx_get_pair_grids call bins (a kernel argument):
+// idx[c] = the parameter of column c, of_param[p] = the column of parameter p or -1
+struct ColList {
+  int32_t n;
+  int32_t idx[MHX_MAX_PARAMS + 1], of_param[MHX_MAX_PARAMS + 1];
+};
+
 // walker-get-data-and-fit's count of enveloped steps, (ceiling (* 0.66 take)) M:1250
 // (include/mhx.h: mhx_band_count): 0.66 is a single float and so is the product.
 #ifndef __HIPCC_RTC__

@@ -113,6 +113,52 @@ class _Summaries:
             out["n_used"].ctypes.data_as(capi.i32p), out["status"].ctypes.data_as(capi.i32p)))
         return out
 
+    def _bin_args(self, cols, edges):
+        cols = [int(c) for c in cols]
+        ea = np.ascontiguousarray(edges, dtype=np.float64)
+        if ea.ndim not in (2, 3) or ea.shape[-2] != len(cols) or \
+                (ea.ndim == 3 and ea.shape[0] != self.n_chains):
+            raise ValueError("edges must be [n_cols, n_bins + 1] or [n_chains, n_cols, n_bins + 1], "
+                             "not %r for %d columns" % (ea.shape, len(cols)))
+        return cols, ea, int(ea.shape[-1]) - 1, int(ea.ndim == 3)
+
+    def histograms(self, take, cols, edges):
+        """make-histo's counts (M:1541-1557) of the parameters `cols` over every chain's newest
+        `take` steps (mhx_get_histograms).  edges: [n_cols, n_bins + 1], one set for every chain,
+        or [n_chains, n_cols, n_bins + 1]; a value v falls in bin n = the smallest n in 1..n_bins
+        with v <= edges[n].  A dict of counts [n_chains, n_cols, n_bins], outside [n_chains,
+        n_cols, 2] (below edges[0], above edges[-1]), n_used [n_chains] and status [n_chains,
+        n_cols] (1: the column held a NaN, which is counted nowhere)."""
+        cols, ea, nb, per_chain = self._bin_args(cols, edges)
+        ca, colp = capi.as_i32(cols or [0])
+        n, nc = self.n_chains, len(cols)
+        out = {"counts": np.zeros((n, nc, nb), dtype=np.int32), "outside": np.zeros((n, nc, 2), dtype=np.int32),
+               "n_used": np.zeros(n, dtype=np.int32), "status": np.zeros((n, nc), dtype=np.int32)}
+        capi.check(self._summary("histograms")(
+            self._h, int(take), colp, nc, nb, ea.ctypes.data_as(capi.f64p), per_chain,
+            *(out[k].ctypes.data_as(capi.i32p) for k in ("counts", "outside", "n_used", "status"))))
+        return out
+
+    def pair_grids(self, take, cols, pairs, edges):
+        """the joint counts of parameter pairs over every chain's newest `take` steps
+        (mhx_get_pair_grids): the corner plot as grids.  pairs: (a, b) places in `cols`; edges
+        and the bin rule as for histograms().  A dict of counts [n_chains, n_pairs, n_bins,
+        n_bins] (cell [i, j]: cols[a] in bin i+1 and cols[b] in bin j+1), n_inside [n_chains,
+        n_pairs], n_used [n_chains] and status [n_chains, n_pairs] (1: either column held a NaN)."""
+        cols, ea, nb, per_chain = self._bin_args(cols, edges)
+        pairs = [(int(a), int(b)) for a, b in pairs]
+        ca, colp = capi.as_i32(cols or [0])
+        pa, pap = capi.as_i32([a for a, _ in pairs] or [0])
+        pb, pbp = capi.as_i32([b for _, b in pairs] or [0])
+        n, nc, npairs = self.n_chains, len(cols), len(pairs)
+        out = {"counts": np.zeros((n, npairs, nb, nb), dtype=np.int32),
+               "n_inside": np.zeros((n, npairs), dtype=np.int32),
+               "n_used": np.zeros(n, dtype=np.int32), "status": np.zeros((n, npairs), dtype=np.int32)}
+        capi.check(self._summary("pair_grids")(
+            self._h, int(take), colp, nc, pap, pbp, npairs, nb, ea.ctypes.data_as(capi.f64p), per_chain,
+            *(out[k].ctypes.data_as(capi.i32p) for k in ("counts", "n_inside", "n_used", "status"))))
+        return out
+
 
 def band_count(take):
     """(ceiling (* 0.66 take)) M:1250 in the reference's single-float arithmetic (mhx_band_count)"""

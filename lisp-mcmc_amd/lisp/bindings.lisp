@@ -211,6 +211,21 @@ library, or without a gfx950 device, walker-create signals MHX-ERROR."
   (take :int) (pct-num :pointer) (pct-den :pointer) (n-pct :int) (at-most-likely :pointer)
   (pct :pointer) (mean :pointer) (stddev :pointer) (values :pointer) (n-used :pointer)
   (status :pointer))
+;; walker-param-histo / walker-plot-corner as counts over the caller's edges
+(cffi:defcfun ("mhx_get_histograms" %mhx-get-histograms) :int
+  (e :pointer) (take :int) (cols :pointer) (n-cols :int) (n-bins :int) (edges :pointer)
+  (edges-per-chain :int) (counts :pointer) (outside :pointer) (n-used :pointer) (status :pointer))
+(cffi:defcfun ("mhx_get_pair_grids" %mhx-get-pair-grids) :int
+  (e :pointer) (take :int) (cols :pointer) (n-cols :int) (pair-a :pointer) (pair-b :pointer)
+  (n-pairs :int) (n-bins :int) (edges :pointer) (edges-per-chain :int) (counts :pointer)
+  (n-inside :pointer) (n-used :pointer) (status :pointer))
+(cffi:defcfun ("mhx_group_get_histograms" %mhx-group-get-histograms) :int
+  (g :pointer) (take :int) (cols :pointer) (n-cols :int) (n-bins :int) (edges :pointer)
+  (edges-per-chain :int) (counts :pointer) (outside :pointer) (n-used :pointer) (status :pointer))
+(cffi:defcfun ("mhx_group_get_pair_grids" %mhx-group-get-pair-grids) :int
+  (g :pointer) (take :int) (cols :pointer) (n-cols :int) (pair-a :pointer) (pair-b :pointer)
+  (n-pairs :int) (n-bins :int) (edges :pointer) (edges-per-chain :int) (counts :pointer)
+  (n-inside :pointer) (n-used :pointer) (status :pointer))
 
 (defmacro with-c-call (&body body)
   "HIP/RCCL runtime code may raise inexact/invalid flags that SBCL turns into conditions;

@@ -19,6 +19,8 @@
    #:walker-destroy
    #:walker-get-data-and-fit #:walker-get-data-and-fit-no-stddev #:walker-get-residuals
    #:walker-with-exp #:walker-exp-get #:walker-set-exp-get
+   #:make-histo #:make-histo-x #:walker-param-histo #:walker-set-param-histo
+   #:walker-set-corner-grid
    #:walker-save #:walker-load #:diagonal-covariance
    #:mfit-walker-estop #:request-stop
    ;; likelihood / prior designators

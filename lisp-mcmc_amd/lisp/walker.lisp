@@ -685,6 +685,148 @@ condition is signalled for the first chain walker-get would signal it for, as ma
                                              append (list k (aref l i i))))))))))
         (t (per-chain))))))
 
+;;; ------------------------------------------------------------------ histograms M:1361-1369, M:1541-1564
+;;; walker-param-histo without the plot, and for a whole walker set the same counts - and the
+;;; corner plot as grids of pair counts - from the device (mhx_get_histograms, mhx_get_pair_grids):
+;;; the boundaries are make-histo's own, formed here with rationals; no history crosses to the host.
+(defun %histo-x (bottom top num-bins)
+  "make-histo-x's list M:1563-1564 from the extremes (one bin: the reference divides by zero in a
+linspace of one element; the bin's centre is returned)"
+  (let ((start (+ bottom (/ (/ (- top bottom) num-bins) 2))))
+    (if (= num-bins 1)
+        (list (coerce start 'double-float))
+        (%even-grid start top num-bins))))
+
+(defun make-histo (sequence num-bins)
+  "(make-histo sequence num-bins) M:1542-1557 on an ascending SEQUENCE: count n is the number of
+elements not yet counted that are <= boundary n of (linspace bottom top :len (1+ num-bins)).
+NUM-BINS is required: the reference's automatic count is not mirrored."
+  (let* ((bottom (reduce #'min sequence))
+         (top (reduce #'max sequence))
+         (boundaries (%even-grid bottom top (1+ num-bins)))
+         (left (coerce sequence 'list)))
+    (loop for boundary in (cdr boundaries)
+          collect (let ((pos (or (position-if (lambda (v) (> v boundary)) left)
+                                 (length left))))
+                    (setf left (nthcdr pos left))
+                    pos))))
+
+(defun make-histo-x (sequence num-bins)
+  "(make-histo-x sequence num-bins) M:1559-1564"
+  (%histo-x (reduce #'min sequence) (reduce #'max sequence) num-bins))
+
+(defun walker-param-histo (walker key &key (take 10000) (bins 20) (chain 0))
+  "(walker-param-histo walker key &key take bins) M:1361-1369 without the plot: the list
+(histo-x histo) the reference hands to gnuplot"
+  (let ((ascending (sort (copy-seq (walker-get walker :get :param :param key :take take :chain chain))
+                         #'<)))
+    (list (make-histo-x ascending bins) (make-histo ascending bins))))
+
+(defun %bin-window (walker take who)
+  "the window the device serves for :take TAKE (nil: every walk whole), warning when a walk's
+window reaches past the ring"
+  (let* ((longest (reduce #'max (%set-lengths walker)))
+         (wanted (max 1 (if take (min take longest) longest)))
+         (ring (cffi:with-foreign-object (cap :int32)
+                 (with-c-call
+                   (check (%mhx-get-history-capacity (first (all-engines walker)) cap)))
+                 (cffi:mem-ref cap :int32))))
+    (when (> wanted ring)
+      (warn "~a :take ~d: the device history ring holds the newest ~d steps of a walk; create the walker with :history-capacity >= the walks' length to keep them all"
+            who wanted ring))
+    (min wanted ring)))
+
+(defun %key-columns (walker keys)
+  "the places of KEYS (nil: all) among the walker's parameter keys"
+  (let ((all (walker-param-keys walker)))
+    (loop for k in (or keys all)
+          collect (or (position k all)
+                      (error "~s is no parameter key of the walker" k)))))
+
+(defun %fill-reference-edges (walker window cols bins edges)
+  "make-histo's boundaries of every chain and column into EDGES [n][nc][bins + 1], from the 0 and
+100 per cent points of the window (mhx_get_percentiles); returns the extremes ((lo hi) ...) per
+chain and column"
+  (let ((n (walker-n-chains walker))
+        (d (walker-n-params walker))
+        (nc (length cols))
+        (none (cffi:null-pointer)))
+    (cffi:with-foreign-objects ((num :int32 2) (den :int32 2) (out :double (* n 2 d)))
+      (fill-int32s num '(0 100))
+      (fill-int32s den '(1 1))
+      (%set-call walker #'%mhx-get-percentiles #'%mhx-group-get-percentiles window num den 2 out none)
+      (loop for c below n
+            collect (loop for p in cols
+                          for j from 0
+                          collect (let ((lo (cffi:mem-aref out :double (+ (* c 2 d) p)))
+                                        (hi (cffi:mem-aref out :double (+ (* c 2 d) d p))))
+                                    (fill-doubles (cffi:inc-pointer edges (* 8 (1+ bins) (+ (* c nc) j)))
+                                                  (%even-grid lo hi (1+ bins)))
+                                    (list lo hi)))))))
+
+(defun walker-set-param-histo (walker &key keys (take 10000) (bins 20))
+  "walker-param-histo for every chain of the set and every key of KEYS (nil: all) from three
+device calls: a list with, chain by chain, the plist (key (histo-x histo) ...)"
+  (let* ((n (walker-n-chains walker))
+         (cols (%key-columns walker keys))
+         (names (or keys (walker-param-keys walker)))
+         (nc (length cols))
+         (window (%bin-window walker take "walker-set-param-histo"))
+         (none (cffi:null-pointer)))
+    (cffi:with-foreign-objects ((edges :double (* n nc (1+ bins))) (colp :int32 nc)
+                                (counts :int32 (* n nc bins)))
+      (fill-int32s colp cols)
+      (let ((extremes (%fill-reference-edges walker window cols bins edges)))
+        (%set-call walker #'%mhx-get-histograms #'%mhx-group-get-histograms
+                   window colp nc bins edges 1 counts none none none)
+        (loop for c below n
+              for chain-extremes in extremes
+              collect (loop for k in names
+                            for j from 0
+                            for (lo hi) in chain-extremes
+                            append (list k (list (%histo-x lo hi bins)
+                                                 (loop for b below bins
+                                                       collect (cffi:mem-aref counts :int32
+                                                                              (+ (* bins (+ (* c nc) j)) b)))))))))))
+
+(defun %permute-params (params)
+  "walker-plot-corner's pair list M:1334-1340"
+  (loop for (head . others) on params
+        append (loop for other in others collect (list head other))))
+
+(defun walker-set-corner-grid (walker &key take (bins 20) keys)
+  "walker-plot-corner M:1333-1359 as counts: for every chain of the set a list of ((key1 key2) grid)
+in the reference's pair order, GRID a BINS x BINS array whose cell (i j) counts the steps with key1
+in bin i+1 and key2 in bin j+1 of make-histo's boundaries for that chain and key.  TAKE nil: the
+whole walk."
+  (let* ((n (walker-n-chains walker))
+         (cols (%key-columns walker keys))
+         (names (or keys (walker-param-keys walker)))
+         (nc (length cols))
+         (places (%permute-params (loop for j below nc collect j)))
+         (np (length places))
+         (window (%bin-window walker take "walker-set-corner-grid"))
+         (none (cffi:null-pointer)))
+    (cffi:with-foreign-objects ((edges :double (* n nc (1+ bins))) (colp :int32 nc)
+                                (pa :int32 (max 1 np)) (pb :int32 (max 1 np))
+                                (counts :int32 (max 1 (* n np bins bins))))
+      (fill-int32s colp cols)
+      (fill-int32s pa (mapcar #'first places))
+      (fill-int32s pb (mapcar #'second places))
+      (%fill-reference-edges walker window cols bins edges)
+      (%set-call walker #'%mhx-get-pair-grids #'%mhx-group-get-pair-grids
+                 window colp nc pa pb np bins edges 1 counts none none none)
+      (loop for c below n
+            collect (loop for (a b) in places
+                          for q from 0
+                          collect (let ((grid (make-array (list bins bins) :element-type 'fixnum)))
+                                    (dotimes (i bins)
+                                      (dotimes (j bins)
+                                        (setf (aref grid i j)
+                                              (cffi:mem-aref counts :int32
+                                                             (+ (* bins bins (+ (* c np) q)) (* i bins) j)))))
+                                    (list (list (elt names a) (elt names b)) grid)))))))
+
 ;;; ------------------------------------------------------------------ data and fit M:1208-1283
 ;;; The numbers behind the reference's plots.  The :function lives on the device, so the fit
 ;;; curve is mhx_eval_function and the envelope of the model over the most probable two thirds of

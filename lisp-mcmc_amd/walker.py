@@ -16,6 +16,10 @@ walker-adaptive-steps path (M: = mcmc-fitting.lisp):
                                                walker_set_get_data_and_fit)
     walker-with-exp              M:1052-1064   walker_with_exp, walker_set_with_exp; its posterior
                                                walker_exp_get, walker_set_exp_get
+    walker-param-histo           M:1361-1369   walker_param_histo (the two lists, no plot;
+                                               make_histo / make_histo_x M:1541-1564),
+                                               walker_set_param_histo
+    walker-plot-corner           M:1333-1359   walker_set_corner_grid (pair counts on a grid)
     walker-modify                M:547-580     walker_modify
     prior-bounds-let             M:346-369     prior_bounds
     mfit-walker-estop            M:860-861     request_stop
@@ -776,6 +780,121 @@ def walker_with_exp(walker, exp, take=1000, chain=0):
     reference, where :most-likely-params ignores it too (M:511-515).  KeyError for a keyword
     that is no parameter key, SexprError for an operator the device grammar lacks."""
     return walker_set_with_exp(walker, exp, take)[chain]
+
+
+def _exact_linspace(start, end, n):
+    """(linspace start end :len n) M:235-248 for doubles: (rational start) + i (rational (end -
+    start)) / (n - 1) exactly - integers over one common denominator - each coerced to double by
+    one correctly rounded division"""
+    start, end = float(start), float(end)
+    ps, qs = start.as_integer_ratio()
+    pd, qd = (end - start).as_integer_ratio()
+    den = qs * qd * (n - 1)
+    first, step = ps * qd * (n - 1), pd * qs
+    return [(first + i * step) / den for i in range(n)]
+
+
+def histo_edges(bottom, top, num_bins):
+    """make-histo's boundaries M:1547: (linspace bottom top :len num-bins + 1).  The last can
+    round below `top`: make-histo then leaves the greatest values out of every bin."""
+    return _exact_linspace(bottom, top, int(num_bins) + 1)
+
+
+def _histo_x(bottom, top, num_bins):
+    """make-histo-x's list M:1563-1564 from the extremes.  One bin: the reference divides by
+    zero (a linspace of one element); the bin's centre is returned here."""
+    bottom, top = float(bottom), float(top)
+    start = bottom + (top - bottom) / num_bins / 2
+    return [start] if num_bins == 1 else _exact_linspace(start, top, num_bins)
+
+
+def make_histo(sequence, num_bins):
+    """(make-histo sequence num-bins) M:1542-1557 on an ASCENDING sequence, as walker-param-histo
+    hands it over: count n = the values not yet counted that are <= boundary n, i.e. a value falls
+    in the first bin whose upper boundary is not below it.  num_bins is required (the reference's
+    automatic count is not mirrored)."""
+    v = np.asarray(sequence, dtype=np.float64)
+    upto = np.searchsorted(v, histo_edges(v.min(), v.max(), num_bins)[1:], side="right")
+    return [int(c) for c in np.diff(upto, prepend=0)]
+
+
+def make_histo_x(sequence, num_bins):
+    """(make-histo-x sequence num-bins) M:1559-1564: the abscissae the reference plots the counts
+    at - from half a bin above the least value to the greatest, in num_bins exact steps"""
+    v = np.asarray(sequence, dtype=np.float64)
+    return _histo_x(v.min(), v.max(), int(num_bins))
+
+
+def walker_param_histo(walker, key, take=10000, bins=20, chain=0):
+    """(walker-param-histo walker key &key take bins) M:1361-1369 without the plot: (histo_x,
+    histo), the two lists the reference hands to gnuplot, of one chain's trace."""
+    values = sorted(walker_get(walker, ":param", take=take, param=key, chain=chain))
+    return make_histo_x(values, bins), make_histo(values, bins)
+
+
+def _bin_window(walker, take, who):
+    """the window the device serves for :take `take` (None: every walk whole),
+    with walker_set_get's warning when a walk's window reaches past the ring"""
+    e = walker.engine
+    cap = e.state()["length"].astype(np.int64)
+    t = cap if take is None else np.minimum(int(take), cap)
+    ring = e.history_capacity()
+    widest = max(int(t.max()), 1)
+    if int((t > ring).sum()):
+        warnings.warn(HistoryTruncated(
+            "%s :take %s: the device history ring holds the newest %d steps of a walk and %d of the "
+            "set's %d windows reach past it (the widest asks for %d); create the walker with "
+            "history_capacity >= the walks' length to keep them all"
+            % (who, take, ring, int((t > ring).sum()), e.n_chains, widest)), stacklevel=3)
+    return min(widest, ring)
+
+
+def _reference_edges(walker, window, cols, bins):
+    """make-histo's own boundaries for every chain and column, [n_chains, n_cols, bins + 1], and
+    the extremes they come from: the 0 and 100 per cent points of the window, from the device"""
+    pct, _ = walker.engine.percentiles(window, [(0, 1), (100, 1)])
+    lo, hi = pct[:, 0, cols], pct[:, 1, cols]
+    edges = np.array([[histo_edges(lo[c, j], hi[c, j], bins) for j in range(len(cols))]
+                      for c in range(lo.shape[0])])
+    return edges, lo, hi
+
+
+def _key_columns(walker, keys):
+    names = list(walker.param_keys) if keys is None else [_key(k) for k in keys]
+    return names, [list(walker.param_keys).index(k) for k in names]
+
+
+def walker_set_param_histo(walker, keys=None, take=10000, bins=20):
+    """walker_param_histo for every chain of the set and every key (None: all) from three device
+    calls and no history moved: the extremes (mhx_get_percentiles), the reference's exact
+    boundaries formed on the host, the counts (mhx_get_histograms).  A list with, chain by chain,
+    {key: (histo_x, histo)} - what walker_param_histo(walker, key, take, bins, chain=c) returns."""
+    names, cols = _key_columns(walker, keys)
+    window = _bin_window(walker, take, "walker-set-param-histo")
+    edges, lo, hi = _reference_edges(walker, window, cols, int(bins))
+    counts = walker.engine.histograms(window, cols, edges)["counts"]
+    return [{k: (_histo_x(lo[c, j], hi[c, j], int(bins)), counts[c, j].tolist())
+             for j, k in enumerate(names)} for c in range(counts.shape[0])]
+
+
+def permute_params(params):
+    """walker-plot-corner's pair list M:1334-1340: (p_i, p_j) for i < j, i outermost"""
+    return [(params[i], params[j]) for i in range(len(params) - 1) for j in range(i + 1, len(params))]
+
+
+def walker_set_corner_grid(walker, take=None, bins=20, keys=None):
+    """walker-plot-corner M:1333-1359 as counts: for every chain of the set, the reference's list
+    of key pairs and, for each, the bins x bins grid of step counts - cell [i, j]: the first key
+    in bin i+1 and the second in bin j+1 of make-histo's boundaries for that chain and key - in
+    place of the scatter of every step (mhx_get_pair_grids; no history moved).  A list with, chain
+    by chain, [((key1, key2), grid), ...] in the reference's pair order; take None: the whole walk."""
+    names, cols = _key_columns(walker, keys)
+    window = _bin_window(walker, take, "walker-set-corner-grid")
+    edges, _, _ = _reference_edges(walker, window, cols, int(bins))
+    places = permute_params(list(range(len(cols))))
+    counts = walker.engine.pair_grids(window, cols, places, edges)["counts"]
+    return [[((names[a], names[b]), counts[c, q].copy()) for q, (a, b) in enumerate(places)]
+            for c in range(counts.shape[0])]
 
 
 def walker_modify(walker, modify=None, **kw):
