@@ -28,6 +28,8 @@
  *                                               mhx_band_count, mhx_group_get_fit_bands
  *   walker-param-histo         M:1361-1369   -> mhx_get_histograms (make-histo M:1541-1564 as
  *   walker-plot-corner         M:1333-1359   -> mhx_get_pair_grids   counts over given edges)
+ *   (no counterpart: the reference judges convergence by eye, walker-catepillar-plots
+ *    M:1294-1310)                           -> mhx_get_autocorr, mhx_split_rhat
  *   walker-with-exp            M:1052-1064   -> mhx_get_derived, mhx_group_get_derived (the
  *                                               expression at every step, and its posterior)
  *   walker-modify              M:547-580     -> mhx_walker_modify (+ mhx_set_history)
@@ -76,6 +78,7 @@ extern "C" {
 #define MHX_MAX_HISTO_BINS 1024 /* bins of one column of mhx_get_histograms               */
 #define MHX_MAX_GRID_BINS 64 /* bins a side of one mhx_get_pair_grids grid               */
 #define MHX_MAX_GRID_PAIRS 4096 /* pairs one mhx_get_pair_grids call may count            */
+#define MHX_MAX_AUTOCORR_LAG 1023 /* greatest lag of one mhx_get_autocorr call              */
 
 /* ---- status codes ------------------------------------------------------ */
 enum {
@@ -588,6 +591,74 @@ int mhx_group_get_pair_grids(mhx_group* g, int take, const int32_t* cols, int n_
                              const int32_t* pair_a, const int32_t* pair_b, int n_pairs, int n_bins,
                              const double* edges, int edges_per_chain, int32_t* counts,
                              int32_t* n_inside, int32_t* n_used, int32_t* status);
+
+/* ---- how much the windows are worth: autocorrelation time, effective sample size and the half
+ * moments of split R-hat, of every chain and every requested parameter in ONE device launch.  The
+ * reference has no such function (its convergence checks are plots): the definitions are this
+ * library's own and fix the results to the last bit - plain IEEE binary64 operations in the order
+ * stated, no fused multiply-add, nothing clamped.
+ * The window is mhx_get_percentiles': the newest t = min(take, walker-length, steps held) steps
+ * x_0 (newest) ... x_{t-1} of column p, n_used[c] = t.
+ *   m      = (x_0 + x_1 + ... + x_{t-1}) / t       the serial sum newest first, one division
+ *   dev_s  = x_s - m
+ *   L      = min(max_lag, t - 1)                   n_lags[c]
+ *   c_k    = (sum_{s = 0}^{t-1-k} dev_s dev_{s+k}) / t   for k = 0 .. L: every product rounded,
+ *            added serially in ascending s to a sum that starts at 0.0, one division
+ *   rho_k  = c_k / c_0                             acf[c][k][0 .. L]
+ *   P_j    = rho_{2j} + rho_{2j+1}                 for every j with 2j + 1 <= L
+ *   S      = P_0 + P_1 + ...  serially from 0.0, ending before the first P_j for which P_j > 0 is
+ *            false (a NaN ends it too): Geyer's initial positive sequence
+ *   tau    = 2 S - 1,  ess = t / tau               (a two-step window: tau = 0, ess = +inf)
+ * status[c][k], a sum of
+ *   MHX_AUTOCORR_NONFINITE  a value of the column's window is not finite: the column's numbers
+ *                           and its other bits are unspecified (other columns and chains are not
+ *                           touched by it)
+ *   MHX_AUTOCORR_CONSTANT   c_0 == 0 - one step, or a chain that never moved in the window: the
+ *                           rho are the IEEE 0/0, and tau is rho_0 (that NaN) in place of 2 S - 1,
+ *                           so that tau and ess are NaN
+ *   MHX_AUTOCORR_OPEN       the lags ran out before any P_j ended the sum: max_lag was too small
+ *                           for this chain and tau is a lower bound.  (A one-step window has no
+ *                           P_j at all: CONSTANT and OPEN.)
+ * The halves of split R-hat: h = floor(t / 2); half 0 holds x_0 .. x_{h-1} (the newer steps),
+ * half 1 x_{t-h} .. x_{t-1} (the older; for odd t the middle step belongs to neither).
+ *   half_mean[c][k][2]  the serial sum newest first / h
+ *   half_var[c][k][2]   the serial sum newest first of (x - half_mean) (x - half_mean), / (h - 1)
+ *                       (h = 1: the IEEE 0/0, as mhx_get_derived's standard deviation of one
+ *                       step); with h = 0 neither is written
+ * Arguments: cols[n_cols] distinct parameter indices in [0, d), 1 <= n_cols <= d, in any order;
+ * max_lag in [1, MHX_MAX_AUTOCORR_LAG]; take in [1, history_capacity].  tau, ess, status
+ * [n_chains][n_cols]; acf [n_chains][n_cols][max_lag + 1], entries beyond n_lags[c] are not
+ * written; n_lags, n_used [n_chains].  Any output may be NULL.  MHX_ESTATE before
+ * mhx_init_chains; a chain in MHX_CHAIN_FP_TRAP is served from the history it has.  Worked
+ * through in portions whose device scratch stays below 64 MiB; mhx_get_summary_timing covers the
+ * call. */
+enum {
+  MHX_AUTOCORR_NONFINITE = 1,
+  MHX_AUTOCORR_CONSTANT = 2,
+  MHX_AUTOCORR_OPEN = 4
+};
+int mhx_get_autocorr(mhx_engine* e, int take, const int32_t* cols, int n_cols, int max_lag,
+                     double* tau, double* ess, double* acf, double* half_mean,
+                     double* half_var, int32_t* n_lags, int32_t* n_used, int32_t* status);
+/* The same for a group, in global chain order; every device's work is enqueued before any is
+ * waited for. */
+int mhx_group_get_autocorr(mhx_group* g, int take, const int32_t* cols, int n_cols, int max_lag,
+                           double* tau, double* ess, double* acf, double* half_mean,
+                           double* half_var, int32_t* n_lags, int32_t* n_used, int32_t* status);
+/* Split R-hat of every column from the half moments exactly as mhx_get_autocorr fills them.  Host
+ * only: needs no engine and no device.  For one column, over the M = 2 n_chains sequences in the
+ * order chain 0 half 0, chain 0 half 1, chain 1 half 0, ...:
+ *   W        = (the serial sum of the variances) / M
+ *   mu       = (the serial sum of the means) / M
+ *   B_over_h = (the serial sum of (mu_i - mu) (mu_i - mu)) / (M - 1)
+ *   var_plus = ((h - 1) / h) W + B_over_h           (h - 1) / h one double division
+ *   rhat[k]  = sqrt(var_plus / W)                   (W = 0 follows IEEE)
+ * every sum from its first term.  MHX_EINVAL - mhx_last_error names the first offending chain -
+ * unless n_chains >= 1, every chain has the same h = floor(n_used / 2), and h >= 2: chains of
+ * unequal windows are not comparable by this statistic (pick a take no longer than the shortest
+ * walk).  rhat [n_cols] may be NULL. */
+int mhx_split_rhat(const double* half_mean, const double* half_var, const int32_t* n_used,
+                   int64_t n_chains, int n_cols, double* rhat);
 
 /* Restore a saved walk (walker-load, sketched in the comments M:987-1001): prob[n], theta[n][d]
  * NEWEST FIRST, as walker-save would have written them.  Sets the ring (newest

@@ -24,6 +24,7 @@ LIK_NORMAL, LIK_NORMAL_CUTOFF, LIK_POISSON, LIK_EXPR = 0, 1, 2, 3
 ADAPT_FAITHFUL, ADAPT_POOLED = 0, 1
 CHAIN_RUNNING, CHAIN_DONE, CHAIN_FP_TRAP, CHAIN_STOPPED = 0, 1, 2, 3
 L_OK, L_CAUGHT, L_INVALID, L_EMPTY = 0, 1, 2, 3
+AUTOCORR_NONFINITE, AUTOCORR_CONSTANT, AUTOCORR_OPEN, MAX_AUTOCORR_LAG = 1, 2, 4, 1023
 
 
 class Config(C.Structure):
@@ -146,6 +147,11 @@ SIGNATURES = {
                                            i32p, i32p, i32p, i32p]),
     "mhx_group_get_pair_grids": (C.c_int, [C.c_void_p, C.c_int, i32p, C.c_int, i32p, i32p, C.c_int,
                                            C.c_int, f64p, C.c_int, i32p, i32p, i32p, i32p]),
+    "mhx_get_autocorr": (C.c_int, [C.c_void_p, C.c_int, i32p, C.c_int, C.c_int, f64p, f64p, f64p, f64p,
+                                   f64p, i32p, i32p, i32p]),
+    "mhx_group_get_autocorr": (C.c_int, [C.c_void_p, C.c_int, i32p, C.c_int, C.c_int, f64p, f64p, f64p,
+                                         f64p, f64p, i32p, i32p, i32p]),
+    "mhx_split_rhat": (C.c_int, [f64p, f64p, i32p, C.c_int64, C.c_int, f64p]),
 }
 
 _lib = None

@@ -2626,6 +2626,19 @@ int mhx_get_derived(mhx_engine* e, const char* const* exprs, int n_expr, const c
 // portion's pieces: the edges - one set, or the portion's chains' - the counts, what fell outside
 // / inside, n_used, status; the grids' pair list besides.
 extern "C++" {
+// the distinct parameters cols[0 .. n_cols) of a vector of d, 1 <= n_cols <= d, as a kernel's ColList
+static int fill_cols(ColList* cl, const int32_t* cols, int n_cols, int d) {
+  cl->n = n_cols;
+  for (int p = 0; p <= MHX_MAX_PARAMS; ++p) cl->of_param[p] = -1, cl->idx[p] = 0;
+  for (int c = 0; c < n_cols; ++c) {
+    if (cols[c] < 0 || cols[c] >= d) return fail(MHX_EINVAL, "cols[%d] = %d outside [0,%d)", c, cols[c], d);
+    if (cl->of_param[cols[c]] >= 0)
+      return fail(MHX_EINVAL, "cols[%d] = %d is cols[%d] again", c, cols[c], cl->of_param[cols[c]]);
+    cl->of_param[cols[c]] = c;
+    cl->idx[c] = cols[c];
+  }
+  return MHX_OK;
+}
 // what the two calls share: the window, the columns and the edges
 struct BinSpec {
   int take = 0, n_cols = 0, n_bins = 0, per_chain = 0;
@@ -2647,15 +2660,7 @@ struct BinSpec {
     if (edges_per_chain != 0 && edges_per_chain != 1) return fail(MHX_EINVAL, "edges_per_chain must be 0 or 1");
     if (!edges) return fail(MHX_EINVAL, "edges is NULL");
     take = take_, n_cols = n_cols_, n_bins = n_bins_, per_chain = edges_per_chain;
-    cl.n = n_cols;
-    for (int p = 0; p <= MHX_MAX_PARAMS; ++p) cl.of_param[p] = -1, cl.idx[p] = 0;
-    for (int c = 0; c < n_cols; ++c) {
-      if (cols[c] < 0 || cols[c] >= d) return fail(MHX_EINVAL, "cols[%d] = %d outside [0,%d)", c, cols[c], d);
-      if (cl.of_param[cols[c]] >= 0)
-        return fail(MHX_EINVAL, "cols[%d] = %d is cols[%d] again", c, cols[c], cl.of_param[cols[c]]);
-      cl.of_param[cols[c]] = c;
-      cl.idx[c] = cols[c];
-    }
+    if ((rc = fill_cols(&cl, cols, n_cols, d)) != MHX_OK) return rc;
     const int64_t sets = per_chain ? chains : 1;
     for (int64_t s = 0; s < sets; ++s)
       for (int c = 0; c < n_cols; ++c) {
@@ -2835,6 +2840,170 @@ int mhx_get_pair_grids(mhx_engine* e, int take, const int32_t* cols, int n_cols,
   const int rc = q.prepare({e}, take, cols, n_cols, pair_a, pair_b, n_pairs, n_bins, edges, edges_per_chain,
                            counts, n_inside, n_used, status);
   return rc != MHX_OK ? rc : run_portions(e, q);
+}
+
+// ---- autocorrelation time, effective sample size and the half moments of split R-hat of every
+// chain on the device (k_autocorr; include/mhx.h has the definitions).  A portion's pieces: rho -
+// which the kernel reads back, so it is carved whether or not the caller wants it - tau, ess, the
+// half means and variances, n_lags, n_used, status.
+extern "C++" {
+struct AutocorrCall {
+  int take = 0, max_lag = 0;
+  ColList cl{};
+  enum { ACF, TAU, ESS, HALF_MEAN, HALF_VAR, N_LAGS, N_USED, STATUS };
+  HostDst dst[8];
+
+  int prepare(const std::vector<mhx_engine*>& engs, int take_, const int32_t* cols, int n_cols, int max_lag_,
+              double* tau, double* ess, double* acf, double* half_mean, double* half_var, int32_t* n_lags,
+              int32_t* n_used, int32_t* status) {
+    for (const mhx_engine* e : engs) {
+      const int rc = window_check(e, take_);
+      if (rc != MHX_OK) return rc;
+    }
+    const int d = engs[0]->P.d;
+    if (max_lag_ < 1 || max_lag_ > MHX_MAX_AUTOCORR_LAG)
+      return fail(MHX_EINVAL, "max_lag must be in [1,%d]", MHX_MAX_AUTOCORR_LAG);
+    if (n_cols < 1 || n_cols > d || !cols) return fail(MHX_EINVAL, "n_cols must be in [1, d = %d]", d);
+    take = take_, max_lag = max_lag_;
+    const int rc = fill_cols(&cl, cols, n_cols, d);
+    if (rc != MHX_OK) return rc;
+    const size_t nc = (size_t)n_cols * sizeof(double);
+    dst[ACF] = {acf, nc * ((size_t)max_lag + 1)};
+    dst[TAU] = {tau, nc}, dst[ESS] = {ess, nc};
+    dst[HALF_MEAN] = {half_mean, nc * 2}, dst[HALF_VAR] = {half_var, nc * 2};
+    dst[N_LAGS] = {n_lags, sizeof(int32_t)}, dst[N_USED] = {n_used, sizeof(int32_t)};
+    dst[STATUS] = {status, (size_t)n_cols * sizeof(int32_t)};
+    return MHX_OK;
+  }
+  int check(mhx_engine* e) {
+    const int rc = window_check(e, take);
+    if (rc != MHX_OK) return rc;
+    for (int c = 0; c < cl.n; ++c)
+      if (cl.idx[c] >= e->P.d) return fail(MHX_EINVAL, "cols[%d] = %d outside [0,%d)", c, cl.idx[c], e->P.d);
+    return MHX_OK;
+  }
+  int64_t items(const mhx_engine* e) const { return e->cfg.n_chains; }
+  int64_t points() const { return 1; }
+  AutocorrPieces carve(const mhx_engine*, Carver& c, int64_t n, int64_t) const {
+    return carve_autocorr(c, cl.n, max_lag, n);
+  }
+  // (the kernel writes every entry that collect() copies: nothing to clear)
+  int upload(mhx_engine*, const Portion&) const { return MHX_OK; }
+  int launch(mhx_engine* e, const Portion& p) const {
+    Carver c;
+    const AutocorrPieces s = carve(e, c, p.n, p.m);
+    const bool lds = !e->knobs.autocorr_no_lds && autocorr_lds_bytes(take, cl.n, true) <= kPctLdsBudget;
+    HIP_TRY(launch_autocorr(e->stream, e->S, p.i0, p.n, take, cl, max_lag, lds, stage_at<double>(e, s.acf),
+                            stage_at<double>(e, s.tau), stage_at<double>(e, s.ess),
+                            stage_at<double>(e, s.half_mean), stage_at<double>(e, s.half_var),
+                            stage_at<int32_t>(e, s.n_lags), stage_at<int32_t>(e, s.n_used),
+                            stage_at<int32_t>(e, s.status)));
+    return MHX_OK;
+  }
+  // the items of [0, n) for which whole(item) holds, in runs of one copy each
+  template <class Whole>
+  static int copy_runs(const HostDst& h, int64_t i0, int64_t n, const unsigned char* dev, Whole whole) {
+    for (int64_t a = 0; a < n;) {
+      if (!whole(a)) {
+        ++a;
+        continue;
+      }
+      int64_t b = a;
+      while (b < n && whole(b)) ++b;
+      HIP_TRY(hipMemcpy(h.at(i0 + a), dev + (size_t)a * h.item_bytes, (size_t)(b - a) * h.item_bytes,
+                        hipMemcpyDeviceToHost));
+      a = b;
+    }
+    return MHX_OK;
+  }
+  int collect(mhx_engine* e, const Portion& p) const {
+    Carver c;
+    const AutocorrPieces s = carve(e, c, p.n, p.m);
+    const int which[5] = {TAU, ESS, N_LAGS, N_USED, STATUS};
+    const size_t off[5] = {s.tau, s.ess, s.n_lags, s.n_used, s.status};
+    int rc = MHX_OK;
+    for (int k = 0; k < 5; ++k)
+      if ((rc = copy_back(dst[which[k]], p.i0, p.n, e->stage.p + off[k])) != MHX_OK) return rc;
+    if (!dst[ACF].p && !dst[HALF_MEAN].p && !dst[HALF_VAR].p) return MHX_OK;
+    // what the kernel did not write is not the caller's to lose: the half moments of a window of
+    // fewer than two steps, rho beyond n_lags
+    const size_t n = (size_t)p.n;
+    std::vector<int32_t> used(n), lags(n);
+    HIP_TRY(hipMemcpy(used.data(), stage_at<int32_t>(e, s.n_used), n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(lags.data(), stage_at<int32_t>(e, s.n_lags), n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    const auto halves = [&](int64_t a) { return used[(size_t)a] >= 2; };
+    if (dst[HALF_MEAN].p && (rc = copy_runs(dst[HALF_MEAN], p.i0, p.n, e->stage.p + s.half_mean, halves)) != MHX_OK)
+      return rc;
+    if (dst[HALF_VAR].p && (rc = copy_runs(dst[HALF_VAR], p.i0, p.n, e->stage.p + s.half_var, halves)) != MHX_OK)
+      return rc;
+    if (dst[ACF].p) {
+      // whole runs of chains with every lag in one copy; neighbours that share a smaller n_lags in
+      // one 2-D copy (the rows of a run lie at one pitch: its height is the run's columns)
+      if ((rc = copy_runs(dst[ACF], p.i0, p.n, e->stage.p + s.acf,
+                          [&](int64_t a) { return lags[(size_t)a] == max_lag; })) != MHX_OK)
+        return rc;
+      const size_t row = ((size_t)max_lag + 1) * sizeof(double);
+      for (int64_t a = 0; a < p.n;) {
+        const int32_t la = lags[(size_t)a];
+        int64_t b = a + 1;
+        while (b < p.n && lags[(size_t)b] == la) ++b;
+        if (la >= 0 && la < max_lag)
+          HIP_TRY(hipMemcpy2D(dst[ACF].at(p.i0 + a), row, e->stage.p + s.acf + (size_t)a * dst[ACF].item_bytes, row,
+                              ((size_t)la + 1) * sizeof(double), (size_t)(b - a) * (size_t)cl.n,
+                              hipMemcpyDeviceToHost));
+        a = b;
+      }
+    }
+    return MHX_OK;
+  }
+};
+}  // extern "C++"
+
+int mhx_get_autocorr(mhx_engine* e, int take, const int32_t* cols, int n_cols, int max_lag, double* tau,
+                     double* ess, double* acf, double* half_mean, double* half_var, int32_t* n_lags,
+                     int32_t* n_used, int32_t* status) {
+  if (!e) return fail(MHX_EINVAL, "engine is NULL");
+  AutocorrCall q;
+  const int rc = q.prepare({e}, take, cols, n_cols, max_lag, tau, ess, acf, half_mean, half_var, n_lags, n_used, status);
+  return rc != MHX_OK ? rc : run_portions(e, q);
+}
+
+// Split R-hat from the half moments of mhx_get_autocorr: host arithmetic only, every sum serial
+// from its first term (include/mhx.h).
+int mhx_split_rhat(const double* half_mean, const double* half_var, const int32_t* n_used, int64_t n_chains,
+                   int n_cols, double* rhat) {
+  if (!half_mean || !half_var || !n_used) return fail(MHX_EINVAL, "NULL argument");
+  if (n_chains < 1) return fail(MHX_EINVAL, "n_chains must be >= 1");
+  if (n_cols < 1) return fail(MHX_EINVAL, "n_cols must be >= 1");
+  const int32_t h = n_used[0] / 2;
+  if (n_used[0] < 0 || h < 2)
+    return fail(MHX_EINVAL, "chain 0: a window of %d steps has halves of %d, fewer than 2", n_used[0], h);
+  for (int64_t c = 1; c < n_chains; ++c)
+    if (n_used[c] < 0 || n_used[c] / 2 != h)
+      return fail(MHX_EINVAL, "chain %lld: a window of %d steps, halves of %d where chain 0 has %d",
+                  (long long)c, n_used[c], n_used[c] / 2, h);
+  if (!rhat) return MHX_OK;
+  const int64_t M = 2 * n_chains;
+  const size_t pitch = (size_t)n_cols * 2;
+  const double shrink = (double)(h - 1) / (double)h;
+  for (int k = 0; k < n_cols; ++k) {
+    const double *mu = half_mean + (size_t)k * 2, *var = half_var + (size_t)k * 2;
+    double sv = var[0], sm = mu[0];
+    for (int64_t q = 1; q < M; ++q) {
+      sv = sv + var[(size_t)(q / 2) * pitch + (size_t)(q % 2)];
+      sm = sm + mu[(size_t)(q / 2) * pitch + (size_t)(q % 2)];
+    }
+    const double W = sv / (double)M, mean = sm / (double)M;
+    double sb = (mu[0] - mean) * (mu[0] - mean);
+    for (int64_t q = 1; q < M; ++q) {
+      const double u = mu[(size_t)(q / 2) * pitch + (size_t)(q % 2)] - mean;
+      sb = sb + u * u;
+    }
+    const double b_over_h = sb / (double)(M - 1);
+    const double var_plus = shrink * W + b_over_h;
+    rhat[k] = __builtin_sqrt(var_plus / W);
+  }
+  return MHX_OK;
 }
 
 int mhx_set_history(mhx_engine* e, int64_t chain, const double* prob, const double* theta, int n) {
@@ -3394,6 +3563,15 @@ int mhx_group_get_pair_grids(mhx_group* g, int take, const int32_t* cols, int n_
   GridCall q;
   const int rc = q.prepare(g->eng, take, cols, n_cols, pair_a, pair_b, n_pairs, n_bins, edges, edges_per_chain,
                            counts, n_inside, n_used, status);
+  return rc != MHX_OK ? rc : run_portions(g, q);
+}
+
+int mhx_group_get_autocorr(mhx_group* g, int take, const int32_t* cols, int n_cols, int max_lag, double* tau,
+                           double* ess, double* acf, double* half_mean, double* half_var, int32_t* n_lags,
+                           int32_t* n_used, int32_t* status) {
+  if (!g) return fail(MHX_EINVAL, "group is NULL");
+  AutocorrCall q;
+  const int rc = q.prepare(g->eng, take, cols, n_cols, max_lag, tau, ess, acf, half_mean, half_var, n_lags, n_used, status);
   return rc != MHX_OK ? rc : run_portions(g, q);
 }
 

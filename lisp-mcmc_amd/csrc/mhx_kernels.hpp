@@ -3200,6 +3200,200 @@ __global__ __launch_bounds__(kPctThreads) void k_pair_grids(
   }
 }
 
+// mhx_get_autocorr (include/mhx.h has the definitions; they fix every bit).  One workgroup of
+// kPctThreads per chain; x_0 is the NEWEST step of the window.
+//   1 the window's rows - t x d contiguous doubles, two runs when the ring has wrapped - are read
+//     ONCE, coalesced, as k_percentiles reads them; the requested columns are laid down in LDS
+//     newest first, one column of `tpad` doubles each; a value that is not finite marks its column
+//   2 the serial sums ahead of the lags: column c belongs to wave c % kPctWaves, and three lanes
+//     of that wave walk it at once - the mean, the newer half's mean and then variance, the older
+//     half's - in one loop of uniform length, so a wave keeps 3 x (its columns) chains in flight;
+//     the column is then rewritten in place as dev_s = x_s - m
+//   3 a task is (column, 256 lags), dealt over the waves: lane l runs the serial sums of the lags
+//     256 g + 64 j + l, j = 0..3 - four independent chains of adds - over s.  dev_s is one address
+//     for the whole wave (a broadcast), dev_{s + k} consecutive addresses across the lanes (free
+//     of bank conflicts): the defined order is the fast one, and no sum crosses lanes.  The loop
+//     runs unpredicated while every lane's s + k stays below t, the rest under a select (what a
+//     lane reads past its column - at most 255 doubles, kAcTail - is never added)
+//   4 c_k goes to the portion's acf piece, c_0 to LDS besides; the thread that wrote c_k then
+//     replaces it by rho_k = c_k / c_0
+//   5 one thread per column forms Geyer's sum from the written rho, tau, ess and the status
+// use_lds = 0 (the columns do not fit, or MHX_AUTOCORR_NO_LDS): the same arithmetic, every x read
+// from ring.theta and dev formed as it is used - x_s - m rounds the same wherever it is done.
+constexpr int kAcLagsPerTask = 4 * kWave;
+constexpr int kAcTail = kAcLagsPerTask;  // doubles after the last column that a lane may read
+template <bool kLds>
+__device__ __forceinline__ void autocorr_body(const Ring& ring, const ColList& cl, int t, int L,
+                                              int nl, int tpad, int64_t i, double* acf, double* tau,
+                                              double* ess, double* half_mean, double* half_var,
+                                              int32_t* status) {
+  const int d = ring.d, nc = cl.n, tid = threadIdx.x, w = wave_in_group(), l = lane_id();
+  double* col = reinterpret_cast<double*>(mhx_lds_raw);
+  double* mean_of = col + (kLds ? (size_t)nc * tpad + kAcTail : 0);
+  double* c0_of = mean_of + nc;
+  int32_t* bad_of = reinterpret_cast<int32_t*>(c0_of + nc);
+  for (int c = tid; c < nc; c += kPctThreads) mean_of[c] = 0.0, c0_of[c] = 0.0, bad_of[c] = 0;
+  __syncthreads();
+  {  // 1: element f = s d + p of the window, oldest row first
+    const int64_t oldest = ring.nh - t;
+    const int ds = kPctThreads / d, dp = kPctThreads - ds * d;
+    int s = tid / d, p = tid - s * d;
+    for (int f = tid; f < t * d; f += kPctThreads) {
+      const int c = cl.of_param[p];
+      if (c >= 0) {
+        const int64_t slot = (oldest + s) & (int64_t)ring.mask;
+        const double v = ring.theta[slot * d + p];
+        if (!finite_f64(v)) bad_of[c] = 1;
+        if (kLds) col[(size_t)c * tpad + (t - 1 - s)] = v;
+      }
+      s += ds;
+      p += dp;
+      if (p >= d) {
+        p -= d;
+        ++s;
+      }
+    }
+  }
+  __syncthreads();
+  auto x_at = [&](int c, int s) -> double {
+    return kLds ? col[(size_t)c * tpad + s] : ring.theta[(int64_t)ring.slot(s) * d + cl.idx[c]];
+  };
+  const int h = t / 2;
+  {  // 2: lane 3 q + j of wave w, column w + kPctWaves q: j = 0 the window, 1 and 2 its halves
+    const int q = l / 3, j = l - 3 * q, c = w + kPctWaves * q;
+    const bool mine = l < 48 && c < nc;
+    const int cc = mine ? c : 0, start = j == 2 ? t - h : 0, len = mine ? (j == 0 ? t : h) : 0;
+    const int last = t > 0 ? t - 1 : 0;
+    double sum = x_at(cc, start < last ? start : last);
+#pragma unroll 8
+    for (int s = 1; s < t; ++s) {
+      const int u = start + s;
+      const double x = x_at(cc, u < last ? u : last);
+      sum = s < len ? sum + x : sum;
+    }
+    const double m = sum / (double)len;
+    if (mine && j == 0 && t > 0) mean_of[c] = m;
+    if (mine && j > 0 && h > 0) {
+      const double u0 = x_at(cc, start) - m;
+      double sq = u0 * u0;
+#pragma unroll 8
+      for (int s = 1; s < h; ++s) {
+        const double u = x_at(cc, start + s) - m;
+        sq = sq + u * u;
+      }
+      half_mean[(i * nc + c) * 2 + (j - 1)] = m;
+      half_var[(i * nc + c) * 2 + (j - 1)] = sq / (double)(h - 1);
+    }
+  }
+  __syncthreads();
+  if (kLds) {
+    for (int f = tid; f < nc * t; f += kPctThreads) {
+      const int c = f / t, s = f - c * t;
+      col[(size_t)c * tpad + s] = col[(size_t)c * tpad + s] - mean_of[c];
+    }
+    __syncthreads();
+  }
+  // 3, 4: the lags
+  const int ngrp = (L + kAcLagsPerTask) / kAcLagsPerTask;  // L = -1 (no step): none
+  for (int T = w; T < nc * ngrp; T += kPctWaves) {
+    const int c = T / ngrp, g = T - c * ngrp, k0 = kAcLagsPerTask * g + l;
+    const double m = mean_of[c];
+    auto dev = [&](int s) -> double { return kLds ? col[(size_t)c * tpad + s] : x_at(c, s) - m; };
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    // s + k < t for every lag of the task while s < t - 256 g - 255
+    const int s_all = t - kAcLagsPerTask * g - (kAcLagsPerTask - 1), s_end = t - kAcLagsPerTask * g;
+    int s = 0;
+#pragma unroll 4
+    for (; s < s_all; ++s) {
+      const double a = dev(s);
+      const int u = s + k0;
+      a0 = a0 + a * dev(u);
+      a1 = a1 + a * dev(u + kWave);
+      a2 = a2 + a * dev(u + 2 * kWave);
+      a3 = a3 + a * dev(u + 3 * kWave);
+    }
+    for (; s < s_end; ++s) {
+      const double a = dev(s);
+      const int u = s + k0;
+      if (kLds) {
+        const double b0 = dev(u), b1 = dev(u + kWave), b2 = dev(u + 2 * kWave), b3 = dev(u + 3 * kWave);
+        a0 = u < t ? a0 + a * b0 : a0;
+        a1 = u + kWave < t ? a1 + a * b1 : a1;
+        a2 = u + 2 * kWave < t ? a2 + a * b2 : a2;
+        a3 = u + 3 * kWave < t ? a3 + a * b3 : a3;
+      } else {
+        if (u < t) a0 = a0 + a * dev(u);
+        if (u + kWave < t) a1 = a1 + a * dev(u + kWave);
+        if (u + 2 * kWave < t) a2 = a2 + a * dev(u + 2 * kWave);
+        if (u + 3 * kWave < t) a3 = a3 + a * dev(u + 3 * kWave);
+      }
+    }
+    double* out = acf + (i * nc + c) * nl;
+    const double av[4] = {a0, a1, a2, a3};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int k = k0 + j * kWave;
+      if (k <= L) {
+        const double ck = av[j] / (double)t;
+        out[k] = ck;
+        if (k == 0) c0_of[c] = ck;
+      }
+    }
+  }
+  __syncthreads();
+  for (int T = w; T < nc * ngrp; T += kPctWaves) {
+    const int c = T / ngrp, g = T - c * ngrp, k0 = kAcLagsPerTask * g + l;
+    double* out = acf + (i * nc + c) * nl;
+    const double c0v = c0_of[c];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int k = k0 + j * kWave;
+      if (k <= L) out[k] = out[k] / c0v;
+    }
+  }
+  __threadfence_block();
+  __syncthreads();
+  // 5: column 4 l + w, so that the columns spread over the waves
+  const int c = kPctWaves * l + w;
+  if (c < nc) {
+    const double* rho = acf + (i * nc + c) * nl;
+    double sum = 0.0;
+    bool open = true;
+    for (int j = 0; 2 * j + 1 <= L; ++j) {
+      const double pj = rho[2 * j] + rho[2 * j + 1];
+      if (!(pj > 0.0)) {
+        open = false;
+        break;
+      }
+      sum = sum + pj;
+    }
+    const double c0v = c0_of[c];
+    const bool constant = c0v == 0.0;
+    const double tv = constant ? c0v / c0v : 2.0 * sum - 1.0;
+    tau[i * nc + c] = tv;
+    ess[i * nc + c] = (double)t / tv;
+    status[i * nc + c] = (bad_of[c] ? MHX_AUTOCORR_NONFINITE : 0) | (constant ? MHX_AUTOCORR_CONSTANT : 0) |
+                         (open ? MHX_AUTOCORR_OPEN : 0);
+  }
+}
+// acf [n][nc][max_lag + 1], tau / ess / status [n][nc], half_mean / half_var [n][nc][2], n_lags /
+// n_used [n]
+__global__ __launch_bounds__(kPctThreads) void k_autocorr(
+    ChainState S, int64_t c0, int take, ColList cl, int max_lag, int use_lds, int tpad, double* acf,
+    double* __restrict__ tau, double* __restrict__ ess, double* __restrict__ half_mean,
+    double* __restrict__ half_var, int32_t* __restrict__ n_lags, int32_t* __restrict__ n_used,
+    int32_t* __restrict__ status) {
+  const int64_t i = blockIdx.x;
+  const Ring ring = ring_of(S, c0 + i);
+  const int t = ring_held(ring, take);
+  const int L = max_lag < t - 1 ? max_lag : t - 1;
+  if (threadIdx.x == 0) n_used[i] = t, n_lags[i] = L;
+  if (use_lds)
+    autocorr_body<true>(ring, cl, t, L, max_lag + 1, tpad, i, acf, tau, ess, half_mean, half_var, status);
+  else
+    autocorr_body<false>(ring, cl, t, L, max_lag + 1, tpad, i, acf, tau, ess, half_mean, half_var, status);
+}
+
 // mhx_get_derived, second half: the posterior summaries of the values mhx_user_derived left in
 // the portion's staging buffer, vals [n][ne][pitch] newest first.  One workgroup of kPctWaves
 // wavefronts per chain, as k_percentiles, the expressions in the parameters' place.

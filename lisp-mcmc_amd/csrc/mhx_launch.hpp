@@ -123,6 +123,18 @@ hipError_t launch_pair_grids(hipStream_t st, const ChainState& S, int64_t c0, in
                              const ColList& cl, int nb, int np, const double* edges,
                              int64_t edge_stride, const int32_t* pairs, bool use_lds,
                              int32_t* counts, int32_t* n_inside, int32_t* n_used, int32_t* status);
+// mhx_get_autocorr (k_autocorr): the LDS a workgroup needs for nc columns of a window of `take`
+// steps - the pitch of k_percentiles, 256 doubles a lane may read past the last column, and a
+// mean, a c_0 and a flag per column.  Above kPctLdsBudget, or with use_lds = false, the columns
+// stay in memory.  acf [n][nc][max_lag + 1] is written AND read back by the kernel.
+inline size_t autocorr_lds_bytes(int take, int nc, bool use_lds) {
+  return (use_lds ? ((size_t)nc * pct_column_pitch(take, nc) + 256) * sizeof(double) : 0) +
+         (size_t)nc * (2 * sizeof(double) + sizeof(int32_t));
+}
+hipError_t launch_autocorr(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
+                           const ColList& cl, int max_lag, bool use_lds, double* acf, double* tau,
+                           double* ess, double* half_mean, double* half_var, int32_t* n_lags,
+                           int32_t* n_used, int32_t* status);
 hipError_t launch_covariances(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
                               int* uniq, double* cov, int32_t* n_unique, int32_t* status);
 hipError_t launch_l_matrices(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,

@@ -270,6 +270,9 @@ hipError_t summary_configure() {
   if (e == hipSuccess)
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pair_grids),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPctLdsBudget);
+  if (e == hipSuccess)
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_autocorr),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPctLdsBudget);
   return e;
 }
 hipError_t launch_percentiles(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
@@ -315,6 +318,19 @@ hipError_t launch_pair_grids(hipStream_t st, const ChainState& S, int64_t c0, in
   k_pair_grids<<<dim3((unsigned)n), dim3(kPctThreads), lds, st>>>(
       S, c0, take, cl, nb, np, edges, edge_stride, pairs, use_lds ? 1 : 0, grid_place_pitch(take),
       counts, n_inside, n_used, status);
+  return hipGetLastError();
+}
+hipError_t launch_autocorr(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
+                           const ColList& cl, int max_lag, bool use_lds, double* acf, double* tau,
+                           double* ess, double* half_mean, double* half_var, int32_t* n_lags,
+                           int32_t* n_used, int32_t* status) {
+  static_assert(kAcTail == 256, "autocorr_lds_bytes leaves 256 doubles after the last column");
+  if (n <= 0) return hipSuccess;
+  const size_t lds = autocorr_lds_bytes(take, cl.n, use_lds);
+  if (lds > kPctLdsBudget) return hipErrorInvalidValue;
+  k_autocorr<<<dim3((unsigned)n), dim3(kPctThreads), lds, st>>>(
+      S, c0, take, cl, max_lag, use_lds ? 1 : 0, pct_column_pitch(take, cl.n), acf, tau, ess,
+      half_mean, half_var, n_lags, n_used, status);
   return hipGetLastError();
 }
 hipError_t launch_covariances(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,

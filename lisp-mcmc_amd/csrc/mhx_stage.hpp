@@ -155,6 +155,26 @@ inline GridPieces carve_grid(Carver& c, int nc_, int nb_, int np_, int per_chain
   s.status = c.take(n * np * sizeof(int32_t));
   return s;
 }
+// autocorrelation read-out: rho [n][nc][max_lag + 1] - always carved: the kernel writes it and reads
+// it back for Geyer's sum, whether the caller asks for it or not - tau, ess [n][nc], half_mean,
+// half_var [n][nc][2], n_lags, n_used [n], status [n][nc].  One chain's pieces are about 0.5 MB at
+// most (nc = 63, max_lag = 1023): they always fit the budget.
+struct AutocorrPieces {
+  size_t acf, tau, ess, half_mean, half_var, n_lags, n_used, status;
+};
+inline AutocorrPieces carve_autocorr(Carver& c, int nc_, int max_lag, int64_t n_) {
+  const size_t n = (size_t)n_, nc = (size_t)nc_, nl = (size_t)max_lag + 1;
+  AutocorrPieces s;
+  s.acf = c.take(n * nc * nl * sizeof(double));
+  s.tau = c.take(n * nc * sizeof(double));
+  s.ess = c.take(n * nc * sizeof(double));
+  s.half_mean = c.take(n * nc * 2 * sizeof(double));
+  s.half_var = c.take(n * nc * 2 * sizeof(double));
+  s.n_lags = c.take(n * sizeof(int32_t));
+  s.n_used = c.take(n * sizeof(int32_t));
+  s.status = c.take(n * nc * sizeof(int32_t));
+  return s;
+}
 // Whether ONE item of a piece list fits the budget at all, by portion_of's own accounting
 // (portion_of answers 1 either way: a read-out that must not outgrow the budget asks first).
 template <class Carve>

@@ -159,6 +159,52 @@ class _Summaries:
             *(out[k].ctypes.data_as(capi.i32p) for k in ("counts", "n_inside", "n_used", "status"))))
         return out
 
+    def autocorr(self, take, cols, max_lag, acf=False):
+        """how much every chain's newest `take` steps of the parameters `cols` are worth
+        (mhx_get_autocorr, which has the definitions): a dict of tau and ess [n_chains, n_cols] -
+        the integrated autocorrelation time by Geyer's initial positive sequence over lags up to
+        max_lag, and n_used / tau - status [n_chains, n_cols] (AUTOCORR_NONFINITE 1, _CONSTANT 2,
+        _OPEN 4: max_lag was too small, tau is a lower bound), n_lags and n_used [n_chains], and
+        the moments of the window's two halves, half_mean and half_var [n_chains, n_cols, 2], for
+        split_rhat() - NaN where a window has fewer than two steps.  acf=True adds acf [n_chains,
+        n_cols, max_lag + 1], NaN beyond n_lags."""
+        cols = [int(c) for c in cols]
+        ca, colp = capi.as_i32(cols or [0])
+        n, nc = self.n_chains, len(cols)
+        out = {"tau": np.zeros((n, nc)), "ess": np.zeros((n, nc)),
+               "n_lags": np.zeros(n, dtype=np.int32),
+               "half_mean": np.full((n, nc, 2), np.nan), "half_var": np.full((n, nc, 2), np.nan),
+               "n_used": np.zeros(n, dtype=np.int32), "status": np.zeros((n, nc), dtype=np.int32)}
+        if acf:
+            out["acf"] = np.full((n, nc, int(max_lag) + 1), np.nan)
+        capi.check(self._summary("autocorr")(
+            self._h, int(take), colp, nc, int(max_lag),
+            *(out[k].ctypes.data_as(capi.f64p) if k in out else None
+              for k in ("tau", "ess", "acf", "half_mean", "half_var")),
+            *(out[k].ctypes.data_as(capi.i32p) for k in ("n_lags", "n_used", "status"))))
+        return out
+
+
+def split_rhat(half_mean, half_var, n_used):
+    """split R-hat of every column (mhx_split_rhat: host arithmetic, no device) from the half
+    moments [n_chains, n_cols, 2] and n_used [n_chains] as Engine.autocorr returns them.
+    ValueError, with the library's message, unless every chain's window has the same half length
+    and that is at least 2."""
+    hm = np.ascontiguousarray(half_mean, dtype=np.float64)
+    hv = np.ascontiguousarray(half_var, dtype=np.float64)
+    nu = np.ascontiguousarray(n_used, dtype=np.int32)
+    if hm.ndim != 3 or hm.shape[2] != 2 or hv.shape != hm.shape or nu.shape != (hm.shape[0],):
+        raise ValueError("half_mean and half_var must be [n_chains, n_cols, 2] and n_used [n_chains], "
+                         "not %r, %r, %r" % (hm.shape, hv.shape, nu.shape))
+    rhat = np.zeros(hm.shape[1])
+    rc = capi.lib().mhx_split_rhat(hm.ctypes.data_as(capi.f64p), hv.ctypes.data_as(capi.f64p),
+                                   nu.ctypes.data_as(capi.i32p), hm.shape[0], hm.shape[1],
+                                   rhat.ctypes.data_as(capi.f64p))
+    if rc == capi.EINVAL:
+        raise ValueError(capi.lib().mhx_last_error().decode())
+    capi.check(rc)
+    return rhat
+
 
 def band_count(take):
     """(ceiling (* 0.66 take)) M:1250 in the reference's single-float arithmetic (mhx_band_count)"""

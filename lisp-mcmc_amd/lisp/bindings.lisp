@@ -226,6 +226,18 @@ library, or without a gfx950 device, walker-create signals MHX-ERROR."
   (g :pointer) (take :int) (cols :pointer) (n-cols :int) (pair-a :pointer) (pair-b :pointer)
   (n-pairs :int) (n-bins :int) (edges :pointer) (edges-per-chain :int) (counts :pointer)
   (n-inside :pointer) (n-used :pointer) (status :pointer))
+;; autocorrelation time, effective sample size, the half moments of split R-hat; split R-hat
+(cffi:defcfun ("mhx_get_autocorr" %mhx-get-autocorr) :int
+  (e :pointer) (take :int) (cols :pointer) (n-cols :int) (max-lag :int) (tau :pointer)
+  (ess :pointer) (acf :pointer) (half-mean :pointer) (half-var :pointer) (n-lags :pointer)
+  (n-used :pointer) (status :pointer))
+(cffi:defcfun ("mhx_group_get_autocorr" %mhx-group-get-autocorr) :int
+  (g :pointer) (take :int) (cols :pointer) (n-cols :int) (max-lag :int) (tau :pointer)
+  (ess :pointer) (acf :pointer) (half-mean :pointer) (half-var :pointer) (n-lags :pointer)
+  (n-used :pointer) (status :pointer))
+(cffi:defcfun ("mhx_split_rhat" %mhx-split-rhat) :int
+  (half-mean :pointer) (half-var :pointer) (n-used :pointer) (n-chains :int64) (n-cols :int)
+  (rhat :pointer))
 
 (defmacro with-c-call (&body body)
   "HIP/RCCL runtime code may raise inexact/invalid flags that SBCL turns into conditions;

@@ -827,6 +827,54 @@ whole walk."
                                                              (+ (* bins bins (+ (* c np) q)) (* i bins) j)))))
                                     (list (list (elt names a) (elt names b)) grid)))))))
 
+;;; ------------------------------------------------------------------ what a window is worth
+;;; The reference judges convergence by eye (walker-catepillar-plots M:1294-1310); these are the
+;;; numbers one asks of a walker set first, every chain from one device call (mhx_get_autocorr,
+;;; whose comment in include/mhx.h has the definitions).
+(defun walker-set-autocorr (walker &key keys (take 1000) (max-lag 255))
+  "For every chain of the set the plist (key (:tau tau :ess ess :status status) ...) over KEYS
+(nil: all): the integrated autocorrelation time of the newest TAKE steps by Geyer's initial
+positive sequence over lags up to MAX-LAG, steps / tau, and 0 or a sum of 1 (a value that is not
+finite), 2 (the chain did not move: tau is a NaN) and 4 (MAX-LAG too small: tau is a lower bound)."
+  (let* ((n (walker-n-chains walker))
+         (cols (%key-columns walker keys))
+         (names (or keys (walker-param-keys walker)))
+         (nc (length cols))
+         (window (%bin-window walker take "walker-set-autocorr"))
+         (none (cffi:null-pointer)))
+    (cffi:with-foreign-objects ((colp :int32 nc) (tau :double (* n nc)) (ess :double (* n nc))
+                                (status :int32 (* n nc)))
+      (fill-int32s colp cols)
+      (%set-call walker #'%mhx-get-autocorr #'%mhx-group-get-autocorr
+                 window colp nc max-lag tau ess none none none none none status)
+      (loop for c below n
+            collect (loop for k in names
+                          for j from 0
+                          append (list k (list :tau (cffi:mem-aref tau :double (+ (* c nc) j))
+                                               :ess (cffi:mem-aref ess :double (+ (* c nc) j))
+                                               :status (cffi:mem-aref status :int32 (+ (* c nc) j)))))))))
+
+(defun walker-set-rhat (walker &key keys (take 1000))
+  "Split R-hat over the set's chains, the plist (key rhat ...) over KEYS (nil: all): each chain's
+newest TAKE steps cut in two halves (mhx_get_autocorr's half moments, mhx_split_rhat).  MHX-ERROR
+when the chains' windows differ in length or hold fewer than four steps."
+  (let* ((n (walker-n-chains walker))
+         (cols (%key-columns walker keys))
+         (names (or keys (walker-param-keys walker)))
+         (nc (length cols))
+         (window (%bin-window walker take "walker-set-rhat"))
+         (none (cffi:null-pointer)))
+    (cffi:with-foreign-objects ((colp :int32 nc) (hm :double (* n nc 2)) (hv :double (* n nc 2))
+                                (used :int32 n) (rhat :double nc))
+      (fill-int32s colp cols)
+      (%set-call walker #'%mhx-get-autocorr #'%mhx-group-get-autocorr
+                 window colp nc 1 none none none hm hv none used none)
+      (with-c-call
+        (check (%mhx-split-rhat hm hv used n nc rhat)))
+      (loop for k in names
+            for j from 0
+            append (list k (cffi:mem-aref rhat :double j))))))
+
 ;;; ------------------------------------------------------------------ data and fit M:1208-1283
 ;;; The numbers behind the reference's plots.  The :function lives on the device, so the fit
 ;;; curve is mhx_eval_function and the envelope of the model over the most probable two thirds of

@@ -39,7 +39,7 @@ import warnings
 import numpy as np
 
 from . import _capi as capi
-from .engine import Engine
+from .engine import Engine, split_rhat
 from .models import Model
 
 _LIKS = {
@@ -895,6 +895,85 @@ def walker_set_corner_grid(walker, take=None, bins=20, keys=None):
     counts = walker.engine.pair_grids(window, cols, places, edges)["counts"]
     return [[((names[a], names[b]), counts[c, q].copy()) for q, (a, b) in enumerate(places)]
             for c in range(counts.shape[0])]
+
+
+def _serial_sum(v, start=None):
+    """v[0] + v[1] + ... in that order (np.cumsum is a serial sum), from `start` if given"""
+    v = np.asarray(v, dtype=np.float64)
+    if start is not None:
+        v = np.concatenate(([start], v))
+    return np.cumsum(v)[-1]
+
+
+def autocorr(sequence, max_lag):
+    """The definitions of mhx_get_autocorr (include/mhx.h) on the host, for one NEWEST-FIRST
+    sequence: (acf, tau, ess, status) - rho_0 .. rho_L with L = min(max_lag, len - 1), Geyer's
+    initial-positive-sequence autocorrelation time, len / tau, and the status bits
+    (capi.AUTOCORR_NONFINITE / _CONSTANT / _OPEN).  Every sum in the device's serial order, so the
+    numbers are the device's to the last bit; also the per-chain host route (one trace, this)."""
+    x = np.asarray(sequence, dtype=np.float64)
+    t, max_lag = len(x), int(max_lag)
+    if t < 1 or x.ndim != 1:
+        raise ValueError("autocorr needs a sequence of at least one step")
+    if not 1 <= max_lag <= capi.MAX_AUTOCORR_LAG:
+        raise ValueError("max_lag must be in [1,%d]" % capi.MAX_AUTOCORR_LAG)
+    with np.errstate(all="ignore"):
+        dev = x - _serial_sum(x) / t
+        lags = min(max_lag, t - 1)
+        c = np.array([_serial_sum(dev[:t - k] * dev[k:], 0.0) / t for k in range(lags + 1)])
+        rho = c / c[0]
+        total, is_open = 0.0, True
+        for j in range((lags + 1) // 2):
+            p = rho[2 * j] + rho[2 * j + 1]
+            if not p > 0:
+                is_open = False
+                break
+            total = total + p
+        constant = bool(c[0] == 0)
+        tau = float(rho[0]) if constant else float(2.0 * total - 1.0)
+        ess = float(np.float64(t) / np.float64(tau))
+    status = (0 if np.isfinite(x).all() else capi.AUTOCORR_NONFINITE) | \
+        (capi.AUTOCORR_CONSTANT if constant else 0) | (capi.AUTOCORR_OPEN if is_open else 0)
+    return rho, tau, ess, status
+
+
+def walker_set_autocorr(walker, keys=None, take=1000, max_lag=255, acf=False):
+    """For every chain of the set and every key (None: all), what its newest `take` steps are
+    worth - one device call (mhx_get_autocorr), no history moved.  A list with, chain by chain,
+    {key: {"tau": the integrated autocorrelation time (Geyer's initial positive sequence over
+    lags up to max_lag), "ess": steps / tau, "status": 0, or a sum of 1 (a value that is not
+    finite), 2 (the chain did not move: tau is NaN) and 4 (max_lag too small: tau is a lower
+    bound)}}; acf=True adds "acf", the autocorrelations of lags 0 to min(max_lag, steps - 1).
+    The reference has no counterpart: it judges a walk by its caterpillar plots."""
+    names, cols = _key_columns(walker, keys)
+    window = _bin_window(walker, take, "walker-set-autocorr")
+    r = walker.engine.autocorr(window, cols, int(max_lag), acf=acf)
+    out = []
+    for c in range(r["tau"].shape[0]):
+        entry = {}
+        for j, k in enumerate(names):
+            entry[k] = {"tau": float(r["tau"][c, j]), "ess": float(r["ess"][c, j]),
+                        "status": int(r["status"][c, j])}
+            if acf:
+                entry[k]["acf"] = r["acf"][c, j, :r["n_lags"][c] + 1].copy()
+        out.append(entry)
+    return out
+
+
+def walker_autocorr(walker, key, take=1000, max_lag=255, chain=0):
+    """one chain's entry of walker_set_autocorr for one key: {"tau", "ess", "status"}"""
+    return walker_set_autocorr(walker, [key], take, max_lag)[chain][_key(key)]
+
+
+def walker_set_rhat(walker, keys=None, take=1000):
+    """split R-hat of every key (None: all) over the set's chains: {key: rhat}, each chain's
+    newest `take` steps cut in two halves (mhx_get_autocorr's half moments, mhx_split_rhat).
+    ValueError when the chains' windows differ in length or hold fewer than four steps: pick a
+    take no longer than the shortest walk."""
+    names, cols = _key_columns(walker, keys)
+    window = _bin_window(walker, take, "walker-set-rhat")
+    r = walker.engine.autocorr(window, cols, 1)
+    return dict(zip(names, (float(v) for v in split_rhat(r["half_mean"], r["half_var"], r["n_used"]))))
 
 
 def walker_modify(walker, modify=None, **kw):
