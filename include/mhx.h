@@ -216,6 +216,43 @@ int mhx_set_dataset(mhx_engine* e, int k, const double* x, const double* y,
  * MHX_LIK_NORMAL_CUTOFF (MHX_EUNSUPPORTED). */
 int mhx_set_dataset_cols(mhx_engine* e, int k, const double* const* xcols, int n_cols,
                          const double* y, const double* sigma, size_t n, int likelihood);
+/* A DATASET PER WALKER (nv-specific.lisp:5-10, 50-66: one walker per column of a file, all on the
+ * same frequency sweep): walker c of the engine fits (x, y[c], sigma of c) with function k.
+ * y is [n_chains][n] row-major; sigma_kind says what `sigma` holds (below).  The engine copies and
+ * prepares each walker's values exactly as mhx_set_dataset prepares a shared dataset: y/sigma and
+ * 1/sigma by the same host divisions, the constant sum_i(-1/2 log 2pi - log sigma_i) in the same
+ * order - one constant per walker.
+ *   THE SUM, stated once for every kernel, family, slot and form:  the walker's arrays are padded
+ *   to a multiple of 128 points with (x_last, 0, 0).  Lane l of the walker's wave takes points
+ *   l, l + 64, l + 128, ... in that order; the even blocks of 64 go into one accumulator, the odd
+ *   ones into a second, each point as  r = fma(-f(x), 1/sigma, y/sigma), acc = fma(r, r, acc)
+ *   (the (y/sigma - f(x)/sigma)^2 of mhx_set_dataset), f by the model's guarded direct form - what
+ *   mhx_eval_function evaluates: no fast path, no uniform-grid recurrence, no peak skipping; the
+ *   two accumulators are added, the 64 lanes by the engine's butterfly, and the result is
+ *   fma(-1/2, sum, the walker's constant).  A walker's bits depend on its own data, parameters and
+ *   draws only - not on the other walkers of the launch, nor on whether the planes sit in LDS
+ *   (where a workgroup's share fits the tile buffers: csrc/mhx_plan.hpp, planes_resident) or are
+ *   streamed from memory (MHX_PLANES_NO_LDS=1: always).
+ * Randomness, controller and history are those of a shared dataset: walker c does what the
+ * reference would do with walker c's data alone.
+ * MHX_LIK_NORMAL and one column of x only: the other likelihoods are refused here, a problem that
+ * also uses two columns of x (mhx_set_dataset_cols) and MHX_ADAPT_POOLED (one pooled covariance
+ * assumes one posterior) here or when the problem is finalised, all with MHX_EUNSUPPORTED.  n == 0,
+ * a NULL x or y, or an unknown sigma_kind: MHX_EINVAL.  Functions set this way and with
+ * mhx_set_dataset may be mixed in one global fit; a later mhx_set_dataset* call for the same k
+ * replaces this one.  Such a problem always runs in kernels compiled at run time (hiprtc; without
+ * it: MHX_EUNSUPPORTED with hiprtc's message) and in the batch form.
+ * mhx_logpost on such an engine: row i of theta is evaluated on the data of walker
+ * i mod n_chains.  mhx_eval_function, mhx_get_fit_bands and the read-outs of the history are
+ * unchanged: they read the model, the shared x and the ring only. */
+enum {
+  MHX_SIGMA_NONE = 0,      /* sigma == NULL: 1.0 everywhere (M:1144)                  */
+  MHX_SIGMA_SHARED = 1,    /* sigma[n]: one per point, the same for every walker       */
+  MHX_SIGMA_PER_CHAIN = 2, /* sigma[n_chains]: one scalar per walker (nv-data-std-dev) */
+  MHX_SIGMA_PER_POINT = 3  /* sigma[n_chains][n]                                       */
+};
+int mhx_set_dataset_planes(mhx_engine* e, int k, const double* x, const double* y,
+                           const double* sigma, int sigma_kind, size_t n, int likelihood);
 /* prior-bounds-let block of function k (M:346-369): idx[i] < 0 means "key absent from
  * the plist" (getf default 0d0, M:353).  n == 0 -> log-prior-flat (M:340-343). */
 int mhx_set_bounds(mhx_engine* e, int k, const int32_t* idx, const double* lo,
@@ -345,6 +382,10 @@ int mhx_group_set_function(mhx_group* g, int k, int model_id, const int32_t* sha
                            const int32_t* param_index, int n_index);
 int mhx_group_set_dataset(mhx_group* g, int k, const double* x, const double* y,
                           const double* sigma, size_t n, int likelihood);
+/* (y and a per-walker sigma cover ALL chains of the group: every member engine gets the rows of
+ * its chain range, mhx_group_chain_range) */
+int mhx_group_set_dataset_planes(mhx_group* g, int k, const double* x, const double* y,
+                                 const double* sigma, int sigma_kind, size_t n, int likelihood);
 int mhx_group_set_dataset_cols(mhx_group* g, int k, const double* const* xcols, int n_cols,
                                const double* y, const double* sigma, size_t n, int likelihood);
 int mhx_group_set_bounds(mhx_group* g, int k, const int32_t* idx, const double* lo,

@@ -19,7 +19,7 @@ from . import ingest  # noqa: F401
 from .ingest import read_file_to_data, create_walker_data  # noqa: F401
 from .saveload import walker_save, walker_load  # noqa: F401
 from .walker import (  # noqa: F401
-    Walker, WalkerStep, walker_create, mcmc_fit, walker_adaptive_steps,
+    Walker, WalkerStep, walker_create, walker_set_create, data_separated, planes_layout, mcmc_fit, walker_adaptive_steps,
     walker_adaptive_steps_full, walker_many_steps, walker_take_step, walker_get, walker_set_get,
     walker_modify, prior_bounds, log_prior_flat, request_stop, create_log_liklihood_function,
     walker_get_data_and_fit, walker_get_data_and_fit_no_stddev, walker_get_residuals,
@@ -31,6 +31,7 @@ from .walker import (  # noqa: F401
 )
 
 __all__ = ["capi", "MhxError", "Engine", "Group", "comm_unique_id", "partition", "models", "Walker", "WalkerStep", "walker_create",
+           "walker_set_create", "data_separated", "planes_layout",
            "mcmc_fit", "walker_adaptive_steps", "walker_adaptive_steps_full",
            "walker_many_steps", "walker_take_step", "walker_get", "walker_set_get", "walker_modify",
            "prior_bounds", "log_prior_flat", "request_stop", "create_log_liklihood_function",

@@ -22,6 +22,7 @@ MODEL_POLY, MODEL_GAUSS_PEAKS, MODEL_LORENTZ_PEAKS, MODEL_LORDER_MIXED = 0, 1, 2
 MODEL_EXP_DECAY, MODEL_SINUSOID, MODEL_PVOIGT2, MODEL_EXPR = 4, 5, 6, 7
 LIK_NORMAL, LIK_NORMAL_CUTOFF, LIK_POISSON, LIK_EXPR = 0, 1, 2, 3
 ADAPT_FAITHFUL, ADAPT_POOLED = 0, 1
+SIGMA_NONE, SIGMA_SHARED, SIGMA_PER_CHAIN, SIGMA_PER_POINT = 0, 1, 2, 3
 CHAIN_RUNNING, CHAIN_DONE, CHAIN_FP_TRAP, CHAIN_STOPPED = 0, 1, 2, 3
 L_OK, L_CAUGHT, L_INVALID, L_EMPTY = 0, 1, 2, 3
 AUTOCORR_NONFINITE, AUTOCORR_CONSTANT, AUTOCORR_OPEN, MAX_AUTOCORR_LAG = 1, 2, 4, 1023
@@ -54,6 +55,8 @@ SIGNATURES = {
     "mhx_set_dataset": (C.c_int, [C.c_void_p, C.c_int, f64p, f64p, f64p, C.c_size_t, C.c_int]),
     "mhx_set_dataset_cols": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(f64p), C.c_int, f64p, f64p,
                                        C.c_size_t, C.c_int]),
+    "mhx_set_dataset_planes": (C.c_int, [C.c_void_p, C.c_int, f64p, f64p, f64p, C.c_int, C.c_size_t,
+                                         C.c_int]),
     "mhx_set_bounds": (C.c_int, [C.c_void_p, C.c_int, i32p, f64p, f64p, C.c_int]),
     "mhx_set_function_expr": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.POINTER(C.c_char_p),
                                         i32p, C.c_int]),
@@ -101,6 +104,8 @@ SIGNATURES = {
     "mhx_group_set_dataset": (C.c_int, [C.c_void_p, C.c_int, f64p, f64p, f64p, C.c_size_t, C.c_int]),
     "mhx_group_set_dataset_cols": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(f64p), C.c_int, f64p, f64p,
                                              C.c_size_t, C.c_int]),
+    "mhx_group_set_dataset_planes": (C.c_int, [C.c_void_p, C.c_int, f64p, f64p, f64p, C.c_int,
+                                               C.c_size_t, C.c_int]),
     "mhx_group_set_bounds": (C.c_int, [C.c_void_p, C.c_int, i32p, f64p, f64p, C.c_int]),
     "mhx_group_set_function_expr": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p,
                                               C.POINTER(C.c_char_p), i32p, C.c_int]),

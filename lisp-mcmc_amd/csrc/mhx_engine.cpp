@@ -79,6 +79,13 @@ struct Dataset {
   size_t n = 0;            // data points (hx holds the pads too)
   bool no_rec = false;     // MHX_NO_RECURRENCE=1 when the dataset was set
   bool set = false;
+  // a dataset per walker (mhx_set_dataset_planes): x (and a shared 1/sigma) above, the walkers'
+  // own arrays here; pdesc = the device copy of pd, which finalize_problem completes
+  bool planes = false;
+  int sigma_kind = MHX_SIGMA_NONE;
+  DevBuf<double> py, pw, pconst;
+  PlaneDesc pd{};
+  DevBuf<PlaneDesc> pdesc;
 };
 
 int64_t steps_to_settle_of(int d) { return 10 * (int64_t)std::max(50, d); }  // M:873
@@ -410,6 +417,19 @@ int finalize_problem(mhx_engine* e) {
   sh.pooled = e->cfg.adapt_mode == MHX_ADAPT_POOLED;
   sh.persist_off = e->persist_off;
   sh.cus = e->cus;
+  // a dataset per walker: what it cannot be combined with, by name
+  int n_planes = 0;
+  for (int k = 0; k < e->P.K; ++k) n_planes += e->data[k].planes ? 1 : 0;
+  sh.planes = n_planes > 0;
+  if (sh.planes) {
+    if (sh.pooled)
+      return fail(MHX_EUNSUPPORTED, "a dataset per walker (mhx_set_dataset_planes) with "
+                                    "MHX_ADAPT_POOLED: one pooled covariance assumes one posterior");
+    for (int k = 0; k < e->P.K; ++k)
+      if (e->P.fn[k].n_xcols > 1)
+        return fail(MHX_EUNSUPPORTED, "a dataset per walker (mhx_set_dataset_planes) in a problem "
+                                      "whose dataset %d has two columns of x (mhx_set_dataset_cols)", k);
+  }
   e->fam = choose_family(sh, kn) == 16 ? &family_w16() : &family_w8();
   sh.waves_per_group = e->fam->waves_per_group;
   sh.tile_points = e->fam->tile_points;
@@ -481,6 +501,43 @@ int finalize_problem(mhx_engine* e) {
     // with one chain, -5 % with 512 and -15 % with 2048 chains: only the single-walker case, the
     // reference's own way of working, gets it
     f.solo = (e->P.K == 1 && nt == 1 && e->cfg.n_chains <= e->fam->waves_per_group) ? 1 : 0;
+    if (D.planes) {  // (no per-window grids, no resident tile: a sweep of its own, planes_loglik)
+      f.tgh = nullptr;
+      f.solo = 2;
+    }
+  }
+  // ... resident in the tile buffers or streamed (mhx_plan.hpp: planes_resident), one decision for
+  // the problem; the layout of GroupLds::tiles follows the functions' order
+  bool planes_res = false;
+  if (sh.planes) {
+    int64_t pn[MHX_MAX_FUNCTIONS];
+    int pk[MHX_MAX_FUNCTIONS];
+    int np_ = 0;
+    for (int k = 0; k < e->P.K; ++k)
+      if (e->data[k].planes) {
+        pn[np_] = e->P.fn[k].n;
+        pk[np_++] = e->data[k].sigma_kind;
+      }
+    planes_res = planes_resident(pn, pk, np_, e->P.K, e->fam->waves_per_group, kn);
+    int64_t off = 0;
+    for (int k = 0; k < e->P.K; ++k) {
+      Dataset& D = e->data[k];
+      if (!D.planes) continue;
+      PlaneDesc& pd = D.pd;
+      pd.resident = planes_res ? 1 : 0;
+      pd.bit = 1 << k;
+      pd.off_x = pd.off_w = pd.off_rows = pd.row_stride = 0;
+      if (planes_res) {
+        pd.off_x = (int32_t)off;
+        pd.off_w = (int32_t)(off + pd.pitch);
+        off += planes_shared_doubles(e->P.fn[k].n, D.sigma_kind);
+        pd.off_rows = (int32_t)off;
+        pd.row_stride = (int32_t)planes_wave_doubles(e->P.fn[k].n, D.sigma_kind);
+        off += (int64_t)e->fam->waves_per_group * pd.row_stride;
+      }
+      HIP_TRY(hipMemcpy(D.pdesc.p, &pd, sizeof(PlaneDesc), hipMemcpyHostToDevice));
+      e->P.fn[k].c = reinterpret_cast<const double*>(D.pdesc.p);
+    }
   }
   // MHX_NO_TILE_SKIP=1: evaluate every Gaussian peak at every point (the skipping is exact, so
   // this only exists to show that the results do not change)
@@ -550,7 +607,7 @@ int finalize_problem(mhx_engine* e) {
   bool any_wgrid = false;
   for (int k = 0; k < e->P.K; ++k) {
     FnDesc& f = e->P.fn[k];
-    const bool can = specialise && f.tgh != nullptr && f.model == MHX_MODEL_GAUSS_PEAKS &&
+    const bool can = specialise && !e->data[k].planes && f.tgh != nullptr && f.model == MHX_MODEL_GAUSS_PEAKS &&
                      f.shape[0] >= 1 && f.shape[0] <= 2 && f.shape[1] >= 1 && f.shape[1] <= 6 &&
                      f.lik != MHX_LIK_EXPR;
     if (!can) f.tgh = nullptr;  // (nobody would read it: the direct form everywhere, as before)
@@ -566,11 +623,13 @@ int finalize_problem(mhx_engine* e) {
                       (f0.model == MHX_MODEL_GAUSS_PEAKS || f0.model == MHX_MODEL_LORENTZ_PEAKS ||
                        f0.model == MHX_MODEL_POLY) &&
                       e->prior_expr[0].expr.empty() && !builtin_model_type(f0).empty() &&
-                      e->cfg.adapt_mode != MHX_ADAPT_POOLED;
-  const int aot = (any_expr || any_wgrid || any_er) ? SPEC_GENERIC : select_spec(e->P);
+                      e->cfg.adapt_mode != MHX_ADAPT_POOLED && !sh.planes;
+  // a dataset per walker has its sweep in programs compiled at run time only (MHX_PLANES)
+  const bool any_planes = sh.planes;
+  const int aot = (any_expr || any_wgrid || any_er || any_planes) ? SPEC_GENERIC : select_spec(e->P);
   e->rtc_note.clear();
   HIP_TRY(hipMemcpy(e->dP.p, &e->P, sizeof(ProblemDesc), hipMemcpyHostToDevice));
-  if (!any_expr && !any_wgrid && !any_er && (aot != SPEC_GENERIC || !specialise)) {
+  if (!any_expr && !any_wgrid && !any_er && !any_planes && (aot != SPEC_GENERIC || !specialise)) {
     e->spec = force_generic ? SPEC_GENERIC : aot;
     e->user_prog.reset();
   } else {
@@ -582,15 +641,23 @@ int finalize_problem(mhx_engine* e) {
         f.user_slot = (int)models.size();
         models.push_back(e->fn_expr[k]);
         models.back().lik = f.lik;
+        models.back().planes = e->data[k].planes;
         if (f.lik == MHX_LIK_EXPR) models.back().lik_expr = e->lik_expr[k];
       } else {
         const std::string type = specialise ? builtin_model_type(f) : std::string();
-        if (!type.empty()) {
+        if (type.empty() && e->data[k].planes) {  // (the run-time dispatch, on planes)
+          f.user_slot = (int)models.size();
+          UserExpr u;
+          u.lik = f.lik;
+          u.planes = u.dispatch = true;
+          models.push_back(u);
+        } else if (!type.empty()) {
           f.user_slot = (int)models.size();
           UserExpr u;
           u.builtin = type;
           u.lik = f.lik;
           u.wgrid = f.tgh != nullptr;
+          u.planes = e->data[k].planes;
           u.early_reject = any_er;
           models.push_back(u);
         } else {
@@ -609,8 +676,9 @@ int finalize_problem(mhx_engine* e) {
     if (prog) {
       e->user_prog = prog;
       e->spec = SPEC_USER;
-    } else if (any_expr) {
-      return fail(MHX_EUNSUPPORTED, "%s", err.c_str());
+    } else if (any_expr || any_planes) {
+      return fail(MHX_EUNSUPPORTED, "%s%s", any_planes ? "a dataset per walker needs kernels compiled at run time: " : "",
+                  err.c_str());
     } else {  // enumerated models only: the generic kernels serve (no hiprtc on this machine?)
       e->rtc_note = err.substr(0, err.find('\n'));
       for (int k = 0; k < e->P.K; ++k) e->P.fn[k].user_slot = -1;
@@ -667,10 +735,11 @@ int finalize_problem(mhx_engine* e) {
     for (int k = 0; k < e->P.K; ++k) {
       const FnDesc& f = e->P.fn[k];
       const std::string t = f.model == MHX_MODEL_EXPR ? std::string("expr")
-                            : (f.user_slot >= 0 ? builtin_model_type(f) + (f.tgh ? "+wgrid" : "") +
-                                                      (any_er ? "+early-reject" : "")
-                                                : std::string("generic"));
-      e->kernel_name += (k ? ", " : "") + t + ":" + kLik[f.lik & 3];
+                            : (f.user_slot >= 0 && !builtin_model_type(f).empty() && !(e->data[k].planes && !specialise)
+                                   ? builtin_model_type(f) + (f.tgh ? "+wgrid" : "") + (any_er ? "+early-reject" : "")
+                                   : std::string("generic"));
+      e->kernel_name += (k ? ", " : "") + t + ":" + kLik[f.lik & 3] +
+                        (e->data[k].planes ? (planes_res ? "+planes(resident)" : "+planes(streamed)") : "");
     }
     e->kernel_name += "]";
   } else {
@@ -1497,6 +1566,87 @@ static int set_dataset_impl(mhx_engine* e, int k, const double* x, const double*
     }
   }
   D.set = true;
+  if (D.planes) {  // (a shared dataset replaces a dataset per walker)
+    D.planes = false;
+    D.py.release();
+    D.pw.release();
+    D.pconst.release();
+  }
+  e->problem_dirty = true;
+  return MHX_OK;
+}
+
+static int planes_refuse_lik(int likelihood) {
+  static const char* kName[] = {"MHX_LIK_NORMAL", "MHX_LIK_NORMAL_CUTOFF", "MHX_LIK_POISSON", "MHX_LIK_EXPR"};
+  if (likelihood < MHX_LIK_NORMAL || likelihood > MHX_LIK_EXPR)
+    return fail(MHX_EINVAL, "unknown likelihood %d", likelihood);
+  if (likelihood != MHX_LIK_NORMAL)
+    return fail(MHX_EUNSUPPORTED, "a dataset per walker (mhx_set_dataset_planes) with %s: only "
+                                  "MHX_LIK_NORMAL has a per-walker sweep", kName[likelihood]);
+  return MHX_OK;
+}
+
+int mhx_set_dataset_planes(mhx_engine* e, int k, const double* x, const double* y,
+                           const double* sigma, int sigma_kind, size_t n, int likelihood) {
+  if (!e) return fail(MHX_EINVAL, "engine is NULL");
+  if (k < 0 || k >= e->P.K) return fail(MHX_EINVAL, "dataset index %d out of range", k);
+  if (n == 0 || !x || !y) return fail(MHX_EINVAL, "mhx_set_dataset_planes: n == 0 or x / y is NULL");
+  if (sigma_kind < MHX_SIGMA_NONE || sigma_kind > MHX_SIGMA_PER_POINT ||
+      (sigma_kind != MHX_SIGMA_NONE) != (sigma != nullptr))
+    return fail(MHX_EINVAL, "mhx_set_dataset_planes: sigma_kind %d does not go with a%s sigma",
+                sigma_kind, sigma ? "" : " NULL");
+  int rc = planes_refuse_lik(likelihood);
+  if (rc != MHX_OK) return rc;
+  if (e->cfg.adapt_mode == MHX_ADAPT_POOLED)
+    return fail(MHX_EUNSUPPORTED, "a dataset per walker (mhx_set_dataset_planes) with "
+                                  "MHX_ADAPT_POOLED: one pooled covariance assumes one posterior");
+  const size_t C = (size_t)e->cfg.n_chains;
+  const size_t ns = sigma_kind == MHX_SIGMA_SHARED ? n : sigma_kind == MHX_SIGMA_PER_CHAIN ? C
+                    : sigma_kind == MHX_SIGMA_PER_POINT ? C * n : 0;
+  for (size_t i = 0; i < ns; ++i)
+    if (!(sigma[i] > 0.0) || !std::isfinite(sigma[i]))
+      return fail(MHX_EINVAL, "sigma[%zu] = %g must be finite and > 0 (M:376)", i, sigma[i]);
+  // x, its ranges and grid, and the shared 1/sigma: as a shared dataset (row 0 stands in for y)
+  rc = set_dataset_impl(e, k, x, nullptr, y, sigma_kind == MHX_SIGMA_SHARED ? sigma : nullptr, n,
+                        MHX_LIK_NORMAL);
+  if (rc != MHX_OK) return rc;
+  Dataset& D = e->data[k];
+  D.set = false;  // (until the planes are in place)
+  const size_t pitch = ((n + kPlanePad - 1) / kPlanePad) * kPlanePad;
+  const bool wplane = sigma_kind == MHX_SIGMA_PER_POINT;
+  const bool wscalar = sigma_kind == MHX_SIGMA_PER_CHAIN || sigma_kind == MHX_SIGMA_NONE;
+  std::vector<double> hy(C * pitch, 0.0), hw(wplane ? C * pitch : (wscalar ? C : 1), 0.0), hc(C);
+  const double half_log_2pi = -0.5 * std::log(2.0 * M_PI);
+  for (size_t c = 0; c < C; ++c) {
+    long double csum = 0.0L;
+    for (size_t i = 0; i < n; ++i) {  // (the arithmetic of set_dataset_impl, point by point)
+      const double sg = sigma_kind == MHX_SIGMA_NONE ? 1.0
+                        : sigma_kind == MHX_SIGMA_SHARED ? sigma[i]
+                        : sigma_kind == MHX_SIGMA_PER_CHAIN ? sigma[c] : sigma[c * n + i];
+      const double w = 1.0 / sg;
+      hy[c * pitch + i] = y[c * n + i] * w;
+      if (wplane) hw[c * pitch + i] = w;
+      else if (wscalar) hw[c] = w;
+      csum += (long double)(half_log_2pi + (-1.0 * std::log(sg)));
+    }
+    hc[c] = (double)csum;
+  }
+  if (D.py.alloc(hy.size(), false) != hipSuccess || D.pw.alloc(hw.size(), false) != hipSuccess ||
+      D.pconst.alloc(C, false) != hipSuccess || (!D.pdesc.p && D.pdesc.alloc(1) != hipSuccess))
+    return fail(MHX_ENOMEM, "hipMalloc of dataset %d (%zu walkers x %zu points) failed", k, C, pitch);
+  HIP_TRY(hipMemcpy(D.py.p, hy.data(), hy.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(D.pw.p, hw.data(), hw.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(D.pconst.p, hc.data(), C * sizeof(double), hipMemcpyHostToDevice));
+  D.pd = PlaneDesc{};
+  D.pd.y = D.py.p;
+  D.pd.w = D.pw.p;
+  D.pd.lik_const = D.pconst.p;
+  D.pd.n_rows = (int64_t)C;
+  D.pd.pitch = (int64_t)pitch;
+  D.pd.w_kind = wplane ? kPlaneWPlane : (wscalar ? kPlaneWScalar : kPlaneWShared);
+  D.sigma_kind = sigma_kind;
+  D.planes = true;
+  D.set = true;
   e->problem_dirty = true;
   return MHX_OK;
 }
@@ -1697,6 +1847,8 @@ int mhx_logpost(mhx_engine* e, const double* theta, size_t n, double* out, doubl
   if (rc != MHX_OK) return rc;
   if ((rc = finalize_problem(e)) != MHX_OK) return rc;
   if (n == 0) return MHX_OK;
+  if (e->shape.planes && n > (size_t)INT32_MAX)  // (a wave keeps its row in 32 bits: plane_walker_set)
+    return fail(MHX_EINVAL, "mhx_logpost on a dataset per walker takes at most 2^31 - 1 rows");
   const int d = e->P.d;
   const size_t o_th = 0, o_out = align256(n * d * sizeof(double)),
                o_parts = o_out + align256(n * sizeof(double));
@@ -3342,6 +3494,20 @@ int mhx_group_set_function(mhx_group* g, int k, int model_id, const int32_t* sha
 int mhx_group_set_dataset(mhx_group* g, int k, const double* x, const double* y,
                           const double* sigma, size_t n, int likelihood) {
   MHX_GROUP_EACH(mhx_set_dataset(e, k, x, y, sigma, n, likelihood));  // replicated on every GPU
+}
+int mhx_group_set_dataset_planes(mhx_group* g, int k, const double* x, const double* y,
+                                 const double* sigma, int sigma_kind, size_t n, int likelihood) {
+  if (!g) return fail(MHX_EINVAL, "group is NULL");
+  if (n == 0 || !x || !y) return fail(MHX_EINVAL, "mhx_group_set_dataset_planes: n == 0 or x / y is NULL");
+  for (size_t i = 0; i < g->eng.size(); ++i) {  // every member: the rows of its chain range
+    const size_t first = (size_t)g->first[i];
+    const double* sg = !sigma ? nullptr
+                       : sigma_kind == MHX_SIGMA_PER_CHAIN ? sigma + first
+                       : sigma_kind == MHX_SIGMA_PER_POINT ? sigma + first * n : sigma;
+    const int rc = mhx_set_dataset_planes(g->eng[i], k, x, y + first * n, sg, sigma_kind, n, likelihood);
+    if (rc != MHX_OK) return rc;
+  }
+  return MHX_OK;
 }
 int mhx_group_set_dataset_cols(mhx_group* g, int k, const double* const* xcols, int n_cols,
                                const double* y, const double* sigma, size_t n, int likelihood) {

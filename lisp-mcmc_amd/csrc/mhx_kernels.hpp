@@ -1142,6 +1142,139 @@ struct GenericSpec {
   }
 };
 
+#ifdef MHX_PLANES
+// ------------------------------------------------------------------------------------------
+// A dataset per walker (mhx_set_dataset_planes; PlaneDesc, mhx_types.hpp).  Only in programs
+// compiled at run time with MHX_PLANES: the ahead-of-time kernels know nothing of it.
+// ------------------------------------------------------------------------------------------
+#ifdef MHX_EARLY_REJECT
+#error "early rejection keeps its thresholds where the planes keep the walker of a wave"
+#endif
+// Which walker wave w serves in this launch: its chain in the stepping kernels (through
+// ChainState::slot_chain when the slots are packed), its row of theta in k_logpost; -1: none.
+// Kept in GroupLds::deal_cost, which only dealing (not compiled) and early rejection write.
+__device__ __forceinline__ void plane_walker_set(GroupLds& lds, int w, int64_t c) {
+  if (lane_id() == 0) lds.deal_cost[w] = (int)c;
+}
+
+// THE SUM (include/mhx.h, mhx_set_dataset_planes).  Lane l takes points l, l + 64, l + 128, ... of
+// the padded plane in that order, the even blocks of 64 into acc0 and the odd ones into acc1, each
+// as r = fma(-f(x), 1/sigma, y/sigma), acc = fma(r, r, acc); then wave_sum(acc0 + acc1).  fx, fy,
+// fw fetch element i of x, y/sigma, 1/sigma - from LDS or from memory: the arithmetic does not
+// know which.  The loads of a pair of blocks are issued an iteration ahead of their use (the last
+// pair is fetched twice instead of branching).  KIND == kPlaneWScalar: one 1/sigma for the
+// walker's n points and 0 on the pads.
+template <class Model, int KIND, class FX, class FY, class FW>
+__device__ __forceinline__ double planes_sum(const typename Model::Prep& prep, int64_t n,
+                                             int64_t n_pad, double wc, FX fx, FY fy, FW fw) {
+  const int l = lane_id();
+  double acc0 = 0.0, acc1 = 0.0;
+  int64_t i = l;
+  double x0 = fx(i), x1 = fx(i + kWave), y0 = fy(i), y1 = fy(i + kWave);
+  double w0 = 0.0, w1 = 0.0;
+  if constexpr (KIND != kPlaneWScalar) { w0 = fw(i); w1 = fw(i + kWave); }
+  for (; i < n_pad; i += 2 * kWave) {
+    const int64_t j = i + 2 * kWave < n_pad ? i + 2 * kWave : i;
+    const double xn0 = fx(j), xn1 = fx(j + kWave), yn0 = fy(j), yn1 = fy(j + kWave);
+    double wn0 = 0.0, wn1 = 0.0;
+    if constexpr (KIND != kPlaneWScalar) { wn0 = fw(j); wn1 = fw(j + kWave); }
+    if constexpr (KIND == kPlaneWScalar) {
+      w0 = i < n ? wc : 0.0;
+      w1 = i + kWave < n ? wc : 0.0;
+    }
+    const double m0 = model_eval<Model, false>(prep, x0), m1 = model_eval<Model, false>(prep, x1);
+    const double r0 = __builtin_fma(-m0, w0, y0), r1 = __builtin_fma(-m1, w1, y1);
+    acc0 = __builtin_fma(r0, r0, acc0);
+    acc1 = __builtin_fma(r1, r1, acc1);
+    x0 = xn0; x1 = xn1; y0 = yn0; y1 = yn1; w0 = wn0; w1 = wn1;
+  }
+  return wave_sum(acc0 + acc1);
+}
+
+// The likelihood of function f for the walker of this wave.  Collective over the workgroup in
+// the resident form's FIRST call of a launch only (two barriers around the fill); afterwards, and
+// in the streamed form, a wave is on its own.  The model goes by prepare and the guarded direct
+// eval, as model_values: no fast path, no recurrence, no tile skipping - a walker's bits depend on
+// its own data, parameters and draws alone, whatever the form, the family and the company.
+template <class Model, bool DYN, int KIND, class PF>
+__device__ __forceinline__ double planes_loglik_kind(const FnDesc& f, const PlaneDesc& pd, PF pf,
+                                                     bool active, GroupLds& lds, double* scratch) {
+  const int w = wave_in_group(), l = lane_id();
+  const int cw = __builtin_amdgcn_readfirstlane(*(volatile int*)&lds.deal_cost[w]);
+  const bool mine = cw >= 0;
+  const int64_t n_rows = pd.n_rows;
+  // (mhx_logpost: row i of theta is judged on the data of walker i mod n_chains)
+  const int64_t row = !mine ? 0 : (cw < n_rows ? (int64_t)cw : (int64_t)((unsigned)cw % (unsigned)n_rows));
+  const int64_t n = f.n, np = pd.pitch;
+  const double* __restrict__ yg = pd.y + row * np;
+  const double* __restrict__ wg = KIND == kPlaneWPlane ? pd.w + row * np : f.w;
+  const double* __restrict__ xg = f.x;
+  const double wc = KIND == kPlaneWScalar ? uniform_f64(pd.w[row]) : 0.0;
+  double* T = &lds.tiles[0][0][0];
+  const bool res = __builtin_amdgcn_readfirstlane(pd.resident) != 0;
+  const int bit = __builtin_amdgcn_readfirstlane(pd.bit);
+  double* Tx = T + pd.off_x;
+  double* Tw = KIND == kPlaneWPlane ? T + pd.off_rows + w * pd.row_stride + np : T + pd.off_w;
+  double* Ty = T + pd.off_rows + w * pd.row_stride;
+  if (res && (__builtin_amdgcn_readfirstlane(*(volatile int*)&lds.resident) & bit) == 0) {
+    __syncthreads();  // (everybody has looked at the flag; the tiles' last readers are through)
+    for (int64_t i = threadIdx.x; i < np; i += kThreads) {
+      Tx[i] = xg[i];
+      if constexpr (KIND == kPlaneWShared) Tw[i] = wg[i];
+    }
+    if (mine)
+      for (int64_t i = l; i < np; i += kWave) {
+        Ty[i] = yg[i];
+        if constexpr (KIND == kPlaneWPlane) Tw[i] = wg[i];
+      }
+    if (threadIdx.x == 0) lds.resident = lds.resident | bit;
+    __syncthreads();
+  }
+  const typename Model::Prep prep = [&] {
+    if constexpr (DYN) return Model::prepare(pf, f, scratch);
+    else return model_prepare<Model>(pf, f, scratch);
+  }();
+  __builtin_amdgcn_wave_barrier();  // (the wave's own writes to its scratch in prepare)
+  double s = 0.0;
+  if (active && mine) {
+    if (res)
+      s = planes_sum<Model, KIND>(prep, n, np, wc, [&](int64_t i) { return Tx[i]; },
+                                  [&](int64_t i) { return Ty[i]; }, [&](int64_t i) { return Tw[i]; });
+    else
+      s = planes_sum<Model, KIND>(prep, n, np, wc, [&](int64_t i) { return xg[i]; },
+                                  [&](int64_t i) { return yg[i]; }, [&](int64_t i) { return wg[i]; });
+  }
+  __builtin_amdgcn_wave_barrier();  // (... which the next function's prepare overwrites)
+  // finish_lik<MHX_LIK_NORMAL> with the walker's own constant
+  return __builtin_fma(-0.5, s, uniform_f64(pd.lik_const[row]));
+}
+template <class Model, bool DYN = false, class PF>
+__device__ __forceinline__ double planes_loglik(const FnDesc& f, PF pf, bool active, GroupLds& lds,
+                                                double* scratch) {
+  static_assert(model_xcols<Model>::value == 1, "one column of x");
+  const PlaneDesc& pd = *reinterpret_cast<const PlaneDesc*>(f.c);
+  switch (__builtin_amdgcn_readfirstlane(pd.w_kind)) {
+    case kPlaneWShared: return planes_loglik_kind<Model, DYN, kPlaneWShared>(f, pd, pf, active, lds, scratch);
+    case kPlaneWScalar: return planes_loglik_kind<Model, DYN, kPlaneWScalar>(f, pd, pf, active, lds, scratch);
+    default: return planes_loglik_kind<Model, DYN, kPlaneWPlane>(f, pd, pf, active, lds, scratch);
+  }
+}
+// ... of an enumerated model without a compile-time type: GenericSpec's dispatch
+template <class PF>
+__device__ __forceinline__ double planes_loglik_dispatch(const FnDesc& f, PF pf, bool active,
+                                                         GroupLds& lds, double* scratch) {
+  switch (f.model) {
+    case MHX_MODEL_POLY: return planes_loglik<PolyModelDyn, true>(f, pf, active, lds, scratch);
+    case MHX_MODEL_GAUSS_PEAKS: return planes_loglik<PeaksModelDyn<false>, true>(f, pf, active, lds, scratch);
+    case MHX_MODEL_LORENTZ_PEAKS: return planes_loglik<PeaksModelDyn<true>, true>(f, pf, active, lds, scratch);
+    case MHX_MODEL_LORDER_MIXED: return planes_loglik<LorderModel>(f, pf, active, lds, scratch);
+    case MHX_MODEL_EXP_DECAY: return planes_loglik<ExpDecayModel>(f, pf, active, lds, scratch);
+    case MHX_MODEL_SINUSOID: return planes_loglik<SinusoidModel>(f, pf, active, lds, scratch);
+    default: return planes_loglik<PVoigt2Model>(f, pf, active, lds, scratch);
+  }
+}
+#endif  // MHX_PLANES
+
 // ------------------------------------------------------------------------------------------
 // prior-bounds-let (M:346-369) and the posterior sum of walker-make-step (M:1067-1070)
 // ------------------------------------------------------------------------------------------
@@ -1676,6 +1809,9 @@ __device__ __forceinline__ void k_logpost_body(const ProblemDesc* __restrict__ P
   const int w = wave_in_group(), l = lane_id(), d = P.d;
   const int64_t c = (int64_t)blockIdx.x * kWavesPerGroup + w;
   const bool valid = c < n;
+#ifdef MHX_PLANES
+  plane_walker_set(lds, w, valid ? c : -1);
+#endif
   if (l < d) lds.prop[w][l] = valid ? theta[c * d + l] : 0.0;
   double ll, lp;
   const double v = group_logpost<Spec>(P, valid, lds, w, &ll, &lp);
@@ -1709,6 +1845,9 @@ __device__ __forceinline__ void k_init_body(const ProblemDesc* __restrict__ Pp, 
   const int w = wave_in_group(), l = lane_id(), d = P.d;
   const int64_t c = (int64_t)blockIdx.x * kWavesPerGroup + w;
   const bool valid = c < S.n_chains;
+#ifdef MHX_PLANES
+  plane_walker_set(lds, w, valid ? c : -1);
+#endif
   const double th = (valid && l < d) ? S.theta[c * d + l] : 0.0;
   if (l < d) lds.prop[w][l] = th;
   double ll, lp;
@@ -1906,6 +2045,9 @@ __device__ __forceinline__ void k_step_injected_body(
   const int w = wave_in_group(), l = lane_id(), d = P.d;
   const int64_t c = (int64_t)blockIdx.x * kWavesPerGroup + w;
   const bool valid = c < S.n_chains;
+#ifdef MHX_PLANES
+  plane_walker_set(lds, w, valid ? c : -1);
+#endif
   ChainRegs r;
   double thp = 0.0;
   bool run = false;
@@ -1992,6 +2134,9 @@ __device__ __forceinline__ void k_adaptive_body(const ProblemDesc* __restrict__ 
       in_range && S.slot_chain ? (int64_t)__builtin_amdgcn_readfirstlane(S.slot_chain[slot]) : slot;
   const bool valid = in_range && mapped >= 0;  // (-1: an empty slot of the map)
   const int64_t c = valid ? mapped : 0;
+#ifdef MHX_PLANES
+  plane_walker_set(lds, w, valid ? c : -1);
+#endif
   ChainRegs r;
   r.status = MHX_CHAIN_DONE;
   if (valid) chain_load(S, c, d, r);

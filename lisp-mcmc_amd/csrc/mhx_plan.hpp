@@ -37,6 +37,7 @@ struct EngineKnobs {
   bool summary_no_lds = false;      // MHX_SUMMARY_NO_LDS: k_percentiles reads its columns from memory even where they fit LDS
   bool histo_no_lds = false;        // MHX_HISTO_NO_LDS: k_histograms / k_pair_grids count straight into memory even where LDS would hold them
   bool autocorr_no_lds = false;     // MHX_AUTOCORR_NO_LDS: k_autocorr reads the window from memory even where its columns fit LDS
+  bool planes_no_lds = false;       // MHX_PLANES_NO_LDS: a dataset per walker is streamed from memory even where it fits LDS
 #ifdef MHX_DEBUG_HOOKS
   bool test_lose_sweepers = false;  // MHX_TEST_LOSE_SWEEPERS: k_persist's sweep workgroups never come (test library)
 #endif
@@ -53,6 +54,7 @@ inline EngineKnobs read_knobs() {
       {"MHX_NO_COMPACT", &EngineKnobs::no_compact}, {"MHX_COMPACT_ALWAYS", &EngineKnobs::compact_always},
       {"MHX_NO_GRAPH", &EngineKnobs::no_graph}, {"MHX_SUMMARY_NO_LDS", &EngineKnobs::summary_no_lds},
       {"MHX_HISTO_NO_LDS", &EngineKnobs::histo_no_lds}, {"MHX_AUTOCORR_NO_LDS", &EngineKnobs::autocorr_no_lds},
+      {"MHX_PLANES_NO_LDS", &EngineKnobs::planes_no_lds},
 #ifdef MHX_DEBUG_HOOKS
       {"MHX_TEST_LOSE_SWEEPERS", &EngineKnobs::test_lose_sweepers},
 #endif
@@ -84,6 +86,7 @@ struct ProblemShape {
   int cus = 256;            // compute units of the device
   int per_cu = 0;           // k_persist workgroups a CU holds at once
   int per_cu_ts = 0;        // k_persist_ts workgroups a CU holds at once
+  bool planes = false;      // a function has a dataset per walker (mhx_set_dataset_planes): the batch kernels only
 };
 
 // the launch form: the batch kernels (split_slices == 0), the per-chain split mode (split_slices
@@ -143,7 +146,7 @@ inline int64_t trim_slices(int64_t nwin, int64_t ts) {
 // fit, split mode costs 7.6 us per iteration instead of the two launches' 14 and pays off on
 // shorter datasets (4096 points: 13.4 us in the batch kernel).
 inline int choose_split(const ProblemShape& s, const EngineKnobs& k, int64_t cap_pc) {
-  if (!s.capable || s.pooled) return 0;
+  if (!s.capable || s.pooled || s.planes) return 0;
   const int64_t C = s.chains;
   const int W = s.waves_per_group;
   const int64_t by_data = s.longest / (512 * (int64_t)W);
@@ -191,7 +194,7 @@ inline int choose_split(const ProblemShape& s, const EngineKnobs& k, int64_t cap
 // so it serves from 4 windows on - unless the per-chain persistent form fits, which is quicker
 // still on short datasets (20000 points, 8 ... 64 chains: 7.7 ... 8.7 us).
 inline int choose_tsplit(const ProblemShape& s, const EngineKnobs& k, int64_t cap_pc, int64_t cap_ts) {
-  if (!s.capable || s.pooled) return 0;
+  if (!s.capable || s.pooled || s.planes) return 0;
   const int64_t nwin = s.nwin;
   const int64_t C = s.chains;
   const int W = s.waves_per_group;
@@ -297,6 +300,35 @@ inline LaunchPlan plan_modes(const ProblemShape& s, const EngineKnobs& k) {
   p.persist = want && persist_allowed(s, k) && slices >= (p.tsplit ? 2 : 1) && units * (1 + slices) <= cap;
   if (p.persist && p.tsplit) p.split_slices = p.ts_initial = (int)slices;
   return p;
+}
+
+// A dataset per walker (mhx_set_dataset_planes): resident in LDS or streamed from memory.
+// The resident form keeps, in the space the tile buffers occupy (GroupLds::tiles: 2 * kMaxArrays
+// tiles - 8192 doubles in the 8-wave family, 16384 in the 16-wave family), of every function its
+// shared x, its shared 1/sigma where there is one (MHX_SIGMA_SHARED), and for each wave of the
+// workgroup the walker's y/sigma and - MHX_SIGMA_PER_POINT only - its 1/sigma, each padded to
+// kPlanePad points.  It needs the tile buffers for itself: a problem that also has a function on
+// a shared dataset (whose sweep stages tiles there) is streamed.  MHX_PLANES_NO_LDS=1: streamed.
+inline int64_t planes_pad(int64_t n) { return std::max<int64_t>(ceil_div(n, kPlanePad), 1) * kPlanePad; }
+inline int64_t planes_lds_capacity(int waves_per_group) {
+  return 2 * (int64_t)kMaxArrays * tile_points_of(waves_per_group);
+}
+// doubles of function k: shared ones and those of each wave
+inline int64_t planes_shared_doubles(int64_t n, int sigma_kind) {
+  return planes_pad(n) * (sigma_kind == MHX_SIGMA_SHARED ? 2 : 1);
+}
+inline int64_t planes_wave_doubles(int64_t n, int sigma_kind) {
+  return planes_pad(n) * (sigma_kind == MHX_SIGMA_PER_POINT ? 2 : 1);
+}
+// n[k], sigma_kind[k]: the K_planes functions with a dataset per walker; K: all functions
+inline bool planes_resident(const int64_t* n, const int* sigma_kind, int K_planes, int K,
+                            int waves_per_group, const EngineKnobs& k) {
+  if (k.planes_no_lds || K_planes < 1 || K_planes != K) return false;
+  int64_t need = 0;
+  for (int i = 0; i < K_planes; ++i)
+    need += planes_shared_doubles(n[i], sigma_kind[i]) +
+            (int64_t)waves_per_group * planes_wave_doubles(n[i], sigma_kind[i]);
+  return need <= planes_lds_capacity(waves_per_group);
 }
 
 // A repack of the chains still walking is due when a quarter of those dealt at the last deal

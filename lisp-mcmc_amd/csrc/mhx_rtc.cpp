@@ -169,6 +169,9 @@ static std::string generate(const std::vector<UserExpr>& models,
   bool early_reject = false;
   for (const UserExpr& m : models) early_reject = early_reject || m.early_reject;
   if (early_reject) s << "#define MHX_EARLY_REJECT 1\n";
+  bool planes = false;
+  for (const UserExpr& m : models) planes = planes || m.planes;
+  if (planes) s << "#define MHX_PLANES 1\n";
   s << "#define MHX_USER_THREADS " << threads << "\n"
     << "#include \"mhx_kernels.hpp\"\n"
        "namespace mhx {\n"
@@ -204,6 +207,7 @@ static std::string generate(const std::vector<UserExpr>& models,
       s << "using UserModel" << m << " = " << u.builtin << ";\n";
       continue;
     }
+    if (u.dispatch) continue;  // (no type: planes_loglik_dispatch / GenericSpec::values)
     s << "struct UserModel" << m << " {\n"
       << "  struct Prep { double p[" << (np > 0 ? np : 1) << "]; };\n"
       << "  template <class PF>\n"
@@ -237,7 +241,7 @@ static std::string generate(const std::vector<UserExpr>& models,
   deal_any << "false";
   for (size_t m = 0; m < models.size(); ++m) {
     const int lik = models[m].lik;
-    if (!models[m].builtin.empty() && lik >= 0 && lik <= 2) {
+    if (!models[m].builtin.empty() && lik >= 0 && lik <= 2 && !models[m].planes) {
       const char* wg = models[m].wgrid ? ", true" : "";
       deal_any << " || FixedSpec<UserModel" << m << ", " << kLikName[lik] << wg << ">::kDeal";
       deal_cases << "      case " << m << ": return FixedSpec<UserModel" << m << ", " << kLikName[lik]
@@ -257,7 +261,12 @@ static std::string generate(const std::vector<UserExpr>& models,
   // a slot belongs to one function, whose likelihood is known now: only that sweep is compiled
   for (size_t m = 0; m < models.size(); ++m) {
     const int lik = models[m].lik;
-    if (!models[m].builtin.empty() && lik >= 0 && lik <= 2)
+    if (models[m].planes)  // a dataset per walker: a sweep of its own (MHX_LIK_NORMAL only)
+      s << "      case " << m << ": return "
+        << (models[m].dispatch ? std::string("planes_loglik_dispatch")
+                               : "planes_loglik<UserModel" + std::to_string(m) + ">")
+        << "(f, pf, active, lds, scratch);\n";
+    else if (!models[m].builtin.empty() && lik >= 0 && lik <= 2)
       // the whole FixedSpec: fast-path vote, tile-level peak skipping, parameters in SGPRs
       s << "      case " << m << ": return FixedSpec<UserModel" << m << ", " << kLikName[lik]
         << (models[m].wgrid ? ", true" : "") << ">::loglik(f, pf, active, lds, scratch);\n";
@@ -289,8 +298,11 @@ static std::string generate(const std::vector<UserExpr>& models,
        "      const double (&x0)[PTS], const double (&x1)[PTS], double (&v)[PTS]) {\n"
        "    switch (f.user_slot) {\n";
   for (size_t m = 0; m < models.size(); ++m)
-    s << "      case " << m << ": return model_values<UserModel" << m
-      << ", PTS>(f, pf, scratch, x0, x1, v);\n";
+    if (models[m].dispatch)
+      s << "      case " << m << ": return GenericSpec::values<PTS>(f, pf, scratch, x0, x1, v);\n";
+    else
+      s << "      case " << m << ": return model_values<UserModel" << m
+        << ", PTS>(f, pf, scratch, x0, x1, v);\n";
   s << (builtin_fallback
             ? "      default: return GenericSpec::values<PTS>(f, pf, scratch, x0, x1, v);\n"
             : "      default: (void)scratch; return;  // every function has a slot\n")

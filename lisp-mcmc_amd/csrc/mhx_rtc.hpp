@@ -29,6 +29,11 @@ struct UserExpr {
                          // (FnDesc::tgh) - its kernel is FixedSpec<Model, LIK, true>
   bool early_reject = false;  // builtin models: compile the program with sweep()'s exact early
                               // rejection (-DMHX_EARLY_REJECT; mhx_kernels.hpp)
+  bool planes = false;   // models: the function has a dataset per walker (mhx_set_dataset_planes):
+                         // its likelihood is planes_loglik, and the program is compiled with
+                         // MHX_PLANES (mhx_kernels.hpp)
+  bool dispatch = false; // planes models: an enumerated model without a compile-time type - the
+                         // slot goes through the run-time dispatch on FnDesc::model
   int lik = -1;          // models: the function's likelihood kind (-1: dispatch at run time)
   std::string lik_expr;  // models with MHX_LIK_EXPR: the per-point term over y, model, error
 };

@@ -52,6 +52,7 @@ struct FnDesc {
   const double* txhi;  // +inf when it holds a non-finite x): what tile-level peak skipping tests against
   int32_t tile_skip;   // 0: evaluate every peak for every point (MHX_NO_TILE_SKIP=1)
   int32_t solo;        // 1: the problem's only function and a single tile - it stays in LDS
+                       // 2: a dataset per walker (mhx_set_dataset_planes): c points to a PlaneDesc
   int32_t user_slot;  // >= 0: index of the run-time compiled expression model (MHX_MODEL_EXPR)
   int32_t prior_slot; // >= 0: index of the run-time compiled prior body, else -1
   int32_t no_yw;      // 1: never take the two-array "yw" tiles of the all-recurrence steps (MHX_NO_YW=1)
@@ -60,6 +61,29 @@ struct FnDesc {
   // x_w + i h (to 8 ulp of its max |x|), 0 where they are not; nullptr when the WHOLE dataset is
   // one grid (grid_H != 0) or no window is.  Runs of windows on one grid carry the same bits.
   const double* tgh;
+};
+
+// A dataset per walker (mhx_set_dataset_planes; include/mhx.h states the sum).  x is the
+// function's own, shared array (FnDesc::x, padded as ever); every walker brings
+//   y          [n_rows][pitch]  y/sigma of walker r in row r, pads 0; pitch = n padded to 128
+//   w          kPlaneWPlane: [n_rows][pitch] 1/sigma, pads 0;  kPlaneWScalar: [n_rows], one
+//              1/sigma per walker (MHX_SIGMA_PER_CHAIN; MHX_SIGMA_NONE: 1.0);  kPlaneWShared:
+//              unused - the function's shared FnDesc::w serves every walker
+//   lik_const  [n_rows]  sum_i(-1/2 log 2pi - log sigma_i) of walker r
+// FnDesc::c of such a function (FnDesc::solo == 2) points to this, in device memory.  Only
+// programs compiled at run time with MHX_PLANES read it (mhx_kernels.hpp: planes_loglik).
+// resident != 0: the arrays fit GroupLds::tiles (mhx_plan.hpp: planes_resident) - the shared ones
+// at off_x / off_w, wave s of the workgroup's own at off_rows + s * row_stride (y, then w when it
+// is a plane), all counted in doubles.  bit: the function's flag in GroupLds::resident.
+enum { kPlaneWShared = 0, kPlaneWScalar = 1, kPlaneWPlane = 2 };
+constexpr int kPlanePad = 2 * kWave;  // a lane takes two points per iteration of the sum
+struct PlaneDesc {
+  const double* y;
+  const double* w;
+  const double* lik_const;
+  int64_t n_rows, pitch;
+  int32_t w_kind, resident, bit;
+  int32_t off_x, off_w, off_rows, row_stride;
 };
 
 struct ProblemDesc {

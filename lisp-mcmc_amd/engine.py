@@ -225,6 +225,26 @@ def _x_columns(owner, fn, x, m):
     return xa, xa.ctypes.data_as(capi.f64p), int(xa.shape[0]), int(xa.shape[1])
 
 
+def _planes_args(n_chains, x, y, sigma, sigma_kind):
+    """the arrays of mhx_set_dataset_planes, checked: x [n], y [n_chains][n], sigma by its kind"""
+    xa, xp = capi.as_f64(x)
+    ya, yp = capi.as_f64(y)
+    if xa.ndim != 1 or ya.shape != (n_chains, xa.size):
+        raise ValueError("x must be [n] and y [n_chains][n]")
+    want = {capi.SIGMA_NONE: None, capi.SIGMA_SHARED: (xa.size,), capi.SIGMA_PER_CHAIN: (n_chains,),
+            capi.SIGMA_PER_POINT: (n_chains, xa.size)}
+    if sigma_kind not in want:
+        raise ValueError("sigma_kind must be one of SIGMA_NONE, _SHARED, _PER_CHAIN, _PER_POINT")
+    sa, sp = None, None
+    if (sigma is None) != (want[sigma_kind] is None):
+        raise ValueError("sigma is None exactly with SIGMA_NONE")
+    if sigma is not None:
+        sa, sp = capi.as_f64(sigma)
+        if sa.shape != want[sigma_kind]:
+            raise ValueError("sigma must be %r for this sigma_kind" % (want[sigma_kind],))
+    return (xa, ya, sa), (xp, yp, sp)
+
+
 class Engine(_Summaries):
     def __init__(self, n_chains, n_params, n_functions=1, device=0, seed=0, chain_offset=0,
                  adapt_mode=capi.ADAPT_FAITHFUL, history_capacity=0, poisson_logfact_double=False):
@@ -306,6 +326,15 @@ class Engine(_Summaries):
         else:
             sa, sp = capi.as_f64(np.broadcast_to(np.asarray(sigma, dtype=np.float64), xa.shape))
         capi.check(capi.lib().mhx_set_dataset(self._h, k, xp, yp, sp, xa.size, likelihood))
+
+    def set_dataset_planes(self, k, x, y, sigma=None, sigma_kind=capi.SIGMA_NONE,
+                           likelihood=capi.LIK_NORMAL):
+        """a dataset per walker (mhx_set_dataset_planes): x [n] shared, y [n_chains][n], sigma None,
+        [n], [n_chains] or [n_chains][n] as sigma_kind says"""
+        keep, (xp, yp, sp) = _planes_args(self.n_chains, x, y, sigma, sigma_kind)
+        self.__dict__.setdefault("_datasets", {})[int(k)] = (int(keep[0].size), 1)
+        capi.check(capi.lib().mhx_set_dataset_planes(self._h, k, xp, yp, sp, sigma_kind, keep[0].size,
+                                                     likelihood))
 
     def set_bounds(self, k, idx, lo, hi):
         ix, ixp = capi.as_i32(list(idx))
@@ -625,6 +654,14 @@ class Group(_Summaries):
         if sigma is not None:
             sa, sp = capi.as_f64(np.broadcast_to(np.asarray(sigma, dtype=np.float64), xa.shape))
         capi.check(capi.lib().mhx_group_set_dataset(self._h, k, xp, yp, sp, xa.size, likelihood))
+
+    def set_dataset_planes(self, k, x, y, sigma=None, sigma_kind=capi.SIGMA_NONE,
+                           likelihood=capi.LIK_NORMAL):
+        """mhx_group_set_dataset_planes: y (and a per-walker sigma) cover all chains of the group"""
+        keep, (xp, yp, sp) = _planes_args(self.n_chains, x, y, sigma, sigma_kind)
+        self.__dict__.setdefault("_datasets", {})[int(k)] = (int(keep[0].size), 1)
+        capi.check(capi.lib().mhx_group_set_dataset_planes(self._h, k, xp, yp, sp, sigma_kind,
+                                                           keep[0].size, likelihood))
 
     def set_bounds(self, k, idx, lo, hi):
         ix, ixp = capi.as_i32(list(idx))

@@ -24,6 +24,10 @@ library, or without a gfx950 device, walker-create signals MHX-ERROR."
 (defconstant +lik-normal-cutoff+ 1)
 (defconstant +lik-poisson+ 2)
 (defconstant +lik-expr+ 3)
+(defconstant +sigma-none+ 0)
+(defconstant +sigma-shared+ 1)
+(defconstant +sigma-per-chain+ 2)
+(defconstant +sigma-per-point+ 3)
 (defconstant +chain-running+ 0)
 (defconstant +chain-done+ 1)
 (defconstant +chain-fp-trap+ 2)
@@ -59,6 +63,9 @@ library, or without a gfx950 device, walker-create signals MHX-ERROR."
   (param-index :pointer) (n-index :int))
 (cffi:defcfun ("mhx_set_dataset" %mhx-set-dataset) :int
   (e :pointer) (k :int) (x :pointer) (y :pointer) (sigma :pointer) (n :size) (likelihood :int))
+(cffi:defcfun ("mhx_set_dataset_planes" %mhx-set-dataset-planes) :int
+  (e :pointer) (k :int) (x :pointer) (y :pointer) (sigma :pointer) (sigma-kind :int) (n :size)
+  (likelihood :int))
 (cffi:defcfun ("mhx_set_dataset_cols" %mhx-set-dataset-cols) :int
   (e :pointer) (k :int) (xcols :pointer) (n-cols :int) (y :pointer) (sigma :pointer) (n :size)
   (likelihood :int))
@@ -140,6 +147,9 @@ library, or without a gfx950 device, walker-create signals MHX-ERROR."
   (param-index :pointer) (n-index :int))
 (cffi:defcfun ("mhx_group_set_dataset" %mhx-group-set-dataset) :int
   (g :pointer) (k :int) (x :pointer) (y :pointer) (sigma :pointer) (n :size) (likelihood :int))
+(cffi:defcfun ("mhx_group_set_dataset_planes" %mhx-group-set-dataset-planes) :int
+  (g :pointer) (k :int) (x :pointer) (y :pointer) (sigma :pointer) (sigma-kind :int) (n :size)
+  (likelihood :int))
 (cffi:defcfun ("mhx_group_set_dataset_cols" %mhx-group-set-dataset-cols) :int
   (g :pointer) (k :int) (xcols :pointer) (n-cols :int) (y :pointer) (sigma :pointer) (n :size)
   (likelihood :int))

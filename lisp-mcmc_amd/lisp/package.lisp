@@ -13,7 +13,7 @@
    #:walker-data #:walker-data-error #:walker-log-liklihood #:walker-log-prior
    #:walker-length #:walker-age #:walker-last-step #:walker-most-likely-step #:walker-walk
    #:walker-step #:make-walker-step #:walker-step-prob #:walker-step-params
-   #:walker-create #:mcmc-fit
+   #:walker-create #:mcmc-fit #:walker-set-create #:data-separated
    #:walker-adaptive-steps #:walker-adaptive-steps-full #:walker-many-steps
    #:walker-take-step #:walker-take-step-injected #:walker-get #:walker-set-get #:walker-modify
    #:walker-destroy

@@ -26,7 +26,16 @@ variable.")
   (log-liklihood nil :type list)
   (log-prior nil :type list)
   (n-chains 1 :type integer)
-  (n-params 0 :type integer))
+  (n-params 0 :type integer)
+  ;; walker-set-create: ((y stddev) ...) of function 0, one entry per walker, whose DATA and
+  ;; DATA-ERROR hold walker 0's; nil: every walker fits DATA
+  (planes nil :type list))
+
+(defvar *walker-set-planes* nil
+  "Bound by walker-set-create around its call of walker-create: (ys sigma sigma-kind thetas) - the
+y column of every walker, the stddevs as mhx_set_dataset_planes takes them for SIGMA-KIND (nil:
+none), and the starting vector of every walker.  walker-create then hands function 0 its dataset
+through mhx_set_dataset_planes and every walker its own first step.")
 
 (defun force-list (item) (if (consp item) item (list item))) ; M:755-759
 
@@ -82,6 +91,18 @@ structure is taken as is; anything else broadcasts its first element."
           do (unless (member k keys) (push k keys)))
     (nreverse keys)))
 
+(defun %dataset-of (walker fn-number chain)
+  "the dataset (x y) function FN-NUMBER of walker CHAIN fits"
+  (let ((data (elt (walker-data walker) fn-number)))
+    (if (and (walker-planes walker) (zerop fn-number))
+        (list (first data) (first (elt (walker-planes walker) chain)))
+        data)))
+
+(defun %stddev-of (walker fn-number chain)
+  (if (and (walker-planes walker) (zerop fn-number))
+      (second (elt (walker-planes walker) chain))
+      (elt (walker-data-error walker) fn-number)))
+
 (defun grouped-p (walker)
   (not (cffi:null-pointer-p (walker-group walker))))
 
@@ -114,6 +135,23 @@ structure is taken as is; anything else broadcasts its first element."
                         :operation 'walker-take-step :operands (list :chain (+ first c))))))))
 
 ;;; ------------------------------------------------------------------ walker-create
+(defun %set-planes (walker k cx n lik)
+  "function K's dataset of a walker set (*walker-set-planes*): the shared x in CX, N points"
+  (destructuring-bind (ys sigma sigma-kind thetas) *walker-set-planes*
+    (declare (ignore thetas))
+    (let ((c (length ys)))
+      (cffi:with-foreign-objects ((cy :double (* c n)) (cs :double (max 1 (length sigma))))
+        (fill-doubles cy (loop for y in ys append y))
+        (fill-doubles cs sigma)
+        (with-c-call
+          (check (if (grouped-p walker)
+                     (%mhx-group-set-dataset-planes (walker-group walker) k cx cy
+                                                    (if sigma cs (cffi:null-pointer))
+                                                    sigma-kind n lik)
+                     (%mhx-set-dataset-planes (walker-engine walker) k cx cy
+                                              (if sigma cs (cffi:null-pointer))
+                                              sigma-kind n lik))))))))
+
 (defun %define-problem (walker set-function set-function-expr set-dataset set-dataset-cols
                         set-bounds set-prior-expr set-likelihood-expr)
   "walker-create's per-function work (M:1138-1147), through the seven setters of one engine or of
@@ -244,7 +282,10 @@ the adaptive proposal covariance over all chains (one RCCL all-reduce per 200 st
                 walker
                 (lambda (k &rest a) (with-c-call (check (apply #'%mhx-group-set-function g k a))))
                 (lambda (k &rest a) (with-c-call (check (apply #'%mhx-group-set-function-expr g k a))))
-                (lambda (k &rest a) (with-c-call (check (apply #'%mhx-group-set-dataset g k a))))
+                (lambda (k &rest a)
+                  (if *walker-set-planes*
+                      (%set-planes walker k (first a) (fourth a) (fifth a))
+                      (with-c-call (check (apply #'%mhx-group-set-dataset g k a)))))
                 (lambda (k &rest a) (with-c-call (check (apply #'%mhx-group-set-dataset-cols g k a))))
                 (lambda (k &rest a) (with-c-call (check (apply #'%mhx-group-set-bounds g k a))))
                 (lambda (k &rest a) (with-c-call (check (apply #'%mhx-group-set-prior-expr g k a))))
@@ -253,20 +294,88 @@ the adaptive proposal covariance over all chains (one RCCL all-reduce per 200 st
                 walker
                 (lambda (k &rest a) (with-c-call (check (apply #'%mhx-set-function e k a))))
                 (lambda (k &rest a) (with-c-call (check (apply #'%mhx-set-function-expr e k a))))
-                (lambda (k &rest a) (with-c-call (check (apply #'%mhx-set-dataset e k a))))
+                (lambda (k &rest a)
+                  (if *walker-set-planes*
+                      (%set-planes walker k (first a) (fourth a) (fifth a))
+                      (with-c-call (check (apply #'%mhx-set-dataset e k a)))))
                 (lambda (k &rest a) (with-c-call (check (apply #'%mhx-set-dataset-cols e k a))))
                 (lambda (k &rest a) (with-c-call (check (apply #'%mhx-set-bounds e k a))))
                 (lambda (k &rest a) (with-c-call (check (apply #'%mhx-set-prior-expr e k a))))
                 (lambda (k &rest a) (with-c-call (check (apply #'%mhx-set-likelihood-expr e k a))))))
-           (cffi:with-foreign-object (th :double d)
-             (fill-doubles th values)
-             (with-c-call (check (if grouped
-                                     (%mhx-group-init-chains g th 1)
-                                     (%mhx-init-chains e th 1)))))
+           (let ((thetas (fourth *walker-set-planes*)))  ; (a starting vector per walker)
+             (cffi:with-foreign-object (th :double (if thetas (* n-chains d) d))
+               (fill-doubles th (if thetas (loop for v in thetas append v) values))
+               (with-c-call (check (if grouped
+                                       (%mhx-group-init-chains g th (if thetas 0 1))
+                                       (%mhx-init-chains e th (if thetas 0 1)))))))
            (setf ok t))
       (unless ok (walker-destroy walker)))
     (signal-if-trapped walker)
     walker))
+
+(defun data-separated (data)
+  "The columns of one file, x first, as one dataset (x y) per remaining column: what the
+reference's NV tools make of a frequency sweep before they create one walker per dataset."
+  (let ((x (elt data 0)))
+    (map 'list (lambda (column) (list x column)) (subseq data 1))))
+
+(defun walker-set-create (&key function datasets params data-error log-liklihood log-prior
+                            (device 0) devices (seed 0) (chain-offset 0) (history-capacity 0))
+  "A walker set in which every walker fits a dataset of its own over a shared x.  DATASETS: a list
+of (x y), one per walker, every x the same numbers; PARAMS: one plist for all walkers or a list of
+one plist per walker with the same keys in the same order; DATA-ERROR: nil, one number, one number
+per walker, one list per point, or one list per point per walker.  One function, the normal
+likelihood.  The result is an ordinary walker of (length DATASETS) chains that walk in one launch:
+walker c does what a single walker on dataset c would do."
+  (let* ((c (length datasets))
+         (x (map 'list (lambda (v) (coerce v 'double-float)) (first (first datasets))))
+         (n (length x))
+         (ys (loop for ds in datasets
+                   for i from 0
+                   do (unless (and (= (length (first ds)) n)
+                                   (every (lambda (a b) (eql (coerce a 'double-float) b))
+                                          (first ds) x))
+                        (error "walker-set-create: walker ~d: its x differs from walker 0's" i))
+                      (unless (= (length (second ds)) n)
+                        (error "walker-set-create: walker ~d: y must be as long as x" i))
+                   collect (coerce (second ds) 'list)))
+         (plists (if (keywordp (first params)) (make-list c :initial-element params) params))
+         (keys (plist-keys (first plists)))
+         (thetas (loop for pl in plists
+                       for i from 0
+                       do (unless (equal (plist-keys pl) keys)
+                            (error "walker-set-create: walker ~d: its params have other keys, or another order, than walker 0's" i))
+                       collect (mapcar (lambda (k) (coerce (getf pl k) 'double-float)) keys))))
+    (unless (= (length plists) c)
+      (error "walker-set-create: ~d parameter lists for ~d walkers" (length plists) c))
+    (multiple-value-bind (sigma kind rows)
+        (cond ((null data-error)
+               (values nil +sigma-none+
+                       (make-list c :initial-element (make-list n :initial-element 1))))
+              ((numberp data-error)
+               (values (make-list c :initial-element data-error) +sigma-per-chain+
+                       (make-list c :initial-element (make-list n :initial-element data-error))))
+              ((and (= (length data-error) c) (every #'numberp data-error))
+               (values (coerce data-error 'list) +sigma-per-chain+
+                       (map 'list (lambda (s) (make-list n :initial-element s)) data-error)))
+              ((and (= (length data-error) n) (every #'numberp data-error))
+               (values (coerce data-error 'list) +sigma-shared+
+                       (make-list c :initial-element (coerce data-error 'list))))
+              ((and (= (length data-error) c)
+                    (every (lambda (s) (and (not (numberp s)) (= (length s) n))) data-error))
+               (values (loop for s in (coerce data-error 'list) append (coerce s 'list))
+                       +sigma-per-point+
+                       (map 'list (lambda (s) (coerce s 'list)) data-error)))
+              (t (error "walker-set-create: :data-error must be nil, a number, one number per walker, one list per point, or one list per point per walker")))
+      (let* ((*walker-set-planes* (list ys sigma kind thetas))
+             (walker (walker-create :function function :data (list x (first ys))
+                                    :params (first plists) :data-error (first rows)
+                                    :log-liklihood log-liklihood :log-prior log-prior
+                                    :n-chains c :device device :devices devices :seed seed
+                                    :chain-offset chain-offset
+                                    :history-capacity history-capacity)))
+        (setf (walker-planes walker) (mapcar #'list ys rows))
+        walker))))
 
 (defun walker-destroy (walker)
   (cond ((grouped-p walker)
@@ -924,7 +1033,7 @@ when the chains' windows differ in length or hold fewer than four steps."
   "-> (x-fit y-fit x-data y-data params): the fit on 1000 points between the data's least and
 greatest x at the chosen solution"
   (let* ((take (%clamped-take walker take chain))
-         (data (elt (walker-data walker) fn-number))
+         (data (%dataset-of walker fn-number chain))
          (x-data (elt data x-column))
          (y-data (elt data y-column))
          (x-fit (%even-grid (reduce #'min x-data) (reduce #'max x-data) 1000))
@@ -979,10 +1088,10 @@ model value at every x-fit over the (ceiling (* 0.66 take)) most probable steps 
   "-> (x-data residuals stddev): the model at the median parameters minus the data, at the
 data's own x - what walker-plot-residuals draws"
   (let* ((take (%clamped-take walker take chain))
-         (data (elt (walker-data walker) fn-number))
+         (data (%dataset-of walker fn-number chain))
          (x-data (elt data x-column))
          (y-data (elt data y-column))
-         (stddev (elt (walker-data-error walker) fn-number))
+         (stddev (%stddev-of walker fn-number chain))
          (stddev (if (= 1 (length stddev))
                      (make-list (length x-data) :initial-element (elt stddev 0))
                      stddev))
@@ -1105,6 +1214,9 @@ window), :stddev-normal (the 84.1 point minus the median), :values (newest first
 (defun walker-save (walker filename &optional take (chain 0))
   "(walker-save walker filename &optional take): the newest TAKE steps (all of them by default)
 of chain CHAIN with the data they were walked on."
+  (when (walker-planes walker)
+    (error 'mhx-error :code -5
+                      :message "walker-save of a walker set with a dataset per walker (walker-set-create): the file holds one dataset per function"))
   (let ((form (list :fn (mapcar #'%designator-name (walker-function walker))
                     :data (walker-data walker)
                     :param-keys (walker-param-keys walker)

@@ -47,6 +47,10 @@ def _name(obj):
 def walker_save(walker, filename, take=None, chain=0):
     """(walker-save walker filename &optional take) M:980-985"""
     from .walker import walker_get
+    if getattr(walker, "planes", None) is not None:
+        from ._capi import EUNSUPPORTED, MhxError
+        raise MhxError(EUNSUPPORTED, "walker-save of a walker set with a dataset per walker "
+                       "(walker_set_create): the file format holds one dataset per function")
     steps = walker_get(walker, get=":steps", take=take, chain=chain)
     keys = walker.param_keys
     out = ["(:FN (%s)" % " ".join(_name(f) for f in walker.function),

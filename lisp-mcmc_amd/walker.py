@@ -207,6 +207,22 @@ class Walker:
         self.log_liklihood = log_liklihood
         self.log_prior = log_prior
         self.n_chains = engine.n_chains
+        # walker_set_create: {"y": [n_chains][n], "sigma": [n_chains][n]} of function 0, whose
+        # self.data / self.data_error hold walker 0's; None: every walker fits self.data
+        self.planes = None
+
+    def data_of(self, fn_number=0, chain=0):
+        """the dataset [x, y] function fn_number of walker `chain` fits"""
+        data = self.data[fn_number]
+        if self.planes is not None and fn_number == 0:
+            return [data[0], self.planes["y"][chain]]
+        return data
+
+    def data_error_of(self, fn_number=0, chain=0):
+        """... and its stddev per point"""
+        if self.planes is not None and fn_number == 0:
+            return self.planes["sigma"][chain]
+        return self.data_error[fn_number]
 
     # struct accessors (exported M:480)
     def _step(self, th, pr):
@@ -300,6 +316,134 @@ def walker_create(function=None, data=None, params=None, data_error=None, log_li
                                 ":log-prior must be None (log-prior-flat) or prior_bounds(...)")
     eng.init_chains(vals if theta0 is None else np.asarray(theta0, dtype=np.float64))
     w = Walker(eng, fns, keys, dsets, sig, liks, pris)
+    w._raise_on_trap()
+    return w
+
+
+def data_separated(columns):
+    """nv-data->separated (nv-specific.lisp:5-6): the columns of one file, x first, as one
+    dataset [x, y] per remaining column"""
+    cols = list(columns)
+    return [[cols[0], c] for c in cols[1:]]
+
+
+def _is_number(v):
+    return isinstance(v, (int, float, np.floating, np.integer))
+
+
+def planes_layout(datasets, params, data_error=None):
+    """The arrays of a walker set with one dataset per walker (Engine.set_dataset_planes), from what
+    walker_set_create is given; no engine, no device.
+      datasets    a list of [x, y], one per walker; every x equal bit for bit (ValueError names
+                  the first walker whose x differs)
+      params      one plist for all walkers, or a list of one plist per walker with the same keys
+                  in the same order
+      data_error  None (SIGMA_NONE), one number (SIGMA_PER_CHAIN, the same for every walker), one
+                  number per walker (SIGMA_PER_CHAIN), one list per point (SIGMA_SHARED), or one
+                  list per point per walker (SIGMA_PER_POINT).  A list of numbers as long as the
+                  walkers is taken per walker (nv-data-std-dev) even when the points are as many.
+    Returns a dict: x [n], y [C][n], sigma (None or the array of its kind), sigma_kind, keys,
+    theta0 [C][d] and sigma_rows [C][n] (every walker's stddev per point, for the read-outs)."""
+    dsets = [list(ds) for ds in datasets]
+    if not dsets or any(len(ds) != 2 for ds in dsets):
+        raise ValueError("datasets must be a non-empty list of [x, y], one per walker")
+    C_ = len(dsets)
+    x = np.ascontiguousarray(dsets[0][0], dtype=np.float64)
+    if x.ndim != 1 or x.size == 0:
+        raise ValueError("x must be one column of at least one point")
+    y = np.empty((C_, x.size))
+    for c, (xc, yc) in enumerate(dsets):
+        xc = np.ascontiguousarray(xc, dtype=np.float64)
+        if xc.shape != x.shape or xc.tobytes() != x.tobytes():
+            raise ValueError("walker %d: its x differs from walker 0's (a walker set shares one x)" % c)
+        yc = np.asarray(yc, dtype=np.float64)
+        if yc.shape != x.shape:
+            raise ValueError("walker %d: y must be as long as x" % c)
+        y[c] = yc
+    n = x.size
+    if data_error is None:
+        kind, sigma, rows = capi.SIGMA_NONE, None, np.ones((C_, n))
+    elif _is_number(data_error):
+        kind, sigma = capi.SIGMA_PER_CHAIN, np.full(C_, float(data_error))
+        rows = np.full((C_, n), float(data_error))
+    else:
+        de = list(data_error)
+        if len(de) == C_ and all(_is_number(v) for v in de):
+            kind, sigma = capi.SIGMA_PER_CHAIN, np.asarray(de, dtype=np.float64)
+            rows = np.repeat(sigma[:, None], n, axis=1)
+        elif len(de) == n and all(_is_number(v) for v in de):
+            kind, sigma = capi.SIGMA_SHARED, np.asarray(de, dtype=np.float64)
+            rows = np.repeat(sigma[None, :], C_, axis=0)
+        elif len(de) == C_ and all(not _is_number(v) and len(v) == n for v in de):
+            kind, sigma = capi.SIGMA_PER_POINT, np.ascontiguousarray(de, dtype=np.float64)
+            rows = sigma
+        else:
+            raise ValueError("data_error must be None, a number, one number per walker, one list "
+                             "per point, or one list per point per walker")
+    if isinstance(params, dict) or (len(params) and isinstance(list(params)[0], str)):
+        keys, vals = _plist(params)
+        theta0 = np.repeat(vals[None, :], C_, axis=0)
+    else:
+        pl = [_plist(q) for q in params]
+        if len(pl) != C_:
+            raise ValueError("params: one plist, or one per walker (%d given for %d walkers)" % (len(pl), C_))
+        keys = pl[0][0]
+        for c, (kc, _) in enumerate(pl):
+            if kc != keys:
+                raise ValueError("walker %d: its params have other keys, or another order, than walker 0's" % c)
+        theta0 = np.array([v for _, v in pl], dtype=np.float64)
+    return {"x": x, "y": y, "sigma": sigma, "sigma_kind": kind, "keys": keys, "theta0": theta0,
+            "sigma_rows": rows}
+
+
+def walker_set_create(function=None, datasets=None, params=None, data_error=None, log_prior=None,
+                      log_liklihood=None, device=0, seed=0, chain_offset=0, history_capacity=0):
+    """A walker set in which every walker fits a dataset of its own over a shared x - what
+    nv-specific.lisp:50-66 builds one walker at a time (file->nv-walkers): `datasets` as
+    data_separated returns them, one starting guess for all or one per walker, one stddev for all
+    or one per walker.  ONE function, the normal likelihood (#'log-liklihood-normal or None).  The
+    result is an ordinary Walker of len(datasets) chains that walk in one launch: walker c does what
+    a single walker on dataset c would do with chain_id c."""
+    if isinstance(function, (list, tuple)):
+        if len(function) != 1:
+            raise capi.MhxError(capi.EUNSUPPORTED, "walker_set_create takes one function")
+        function = function[0]
+    if not isinstance(function, Model):
+        raise TypeError(":function must be a model designator (lisp_mcmc_amd.models)")
+    lk = log_liklihood.lstrip("#':").lower() if isinstance(log_liklihood, str) else log_liklihood
+    if lk not in _LIKS or _LIKS[lk] != capi.LIK_NORMAL:
+        raise capi.MhxError(capi.EUNSUPPORTED, "walker_set_create: a dataset per walker takes the "
+                            "normal likelihood only, not %r" % (log_liklihood,))
+    lay = planes_layout(datasets, params, data_error)
+    keys, f = lay["keys"], function
+    missing = [q for q in f.keys if q not in keys]
+    if missing:
+        raise KeyError("the function reads keys %s that :params does not supply" % (missing,))
+    eng = Engine(len(lay["y"]), len(keys), 1, device=device, seed=seed, chain_offset=chain_offset,
+                 history_capacity=history_capacity)
+    if getattr(f, "as_written", False):
+        eng.set_expr_recognition(False)
+    if f.model_id == capi.MODEL_EXPR:
+        eng.set_function_expr(0, f.expr, f.keys, [keys.index(q) for q in f.keys])
+    else:
+        eng.set_function(0, f.model_id, f.shape, [keys.index(q) for q in f.keys])
+    eng.set_dataset_planes(0, lay["x"], lay["y"], lay["sigma"], lay["sigma_kind"])
+    if log_prior is None:
+        eng.set_bounds(0, [], [], [])
+    elif isinstance(log_prior, PriorBounds):
+        pr = log_prior
+        eng.set_bounds(0, [keys.index(q) if q in keys else -1 for q, _, _ in pr.bounds],
+                       [lo for _, lo, _ in pr.bounds], [hi for _, _, hi in pr.bounds])
+        if pr.body:
+            from . import sexpr
+            eng.set_prior_expr(0, sexpr.prior_body_to_expr(pr.body), keys, range(len(keys)))
+    else:
+        raise capi.MhxError(capi.EUNSUPPORTED,
+                            ":log-prior must be None (log-prior-flat) or prior_bounds(...)")
+    eng.init_chains(lay["theta0"])
+    w = Walker(eng, [f], keys, [[lay["x"], lay["y"][0]]], [lay["sigma_rows"][0]], [log_liklihood],
+               [log_prior])
+    w.planes = {"y": lay["y"], "sigma": lay["sigma_rows"]}
     w._raise_on_trap()
     return w
 
@@ -565,9 +709,9 @@ def fit_linspace(lo, hi, n=1000):
     return np.array([float(start + i * step) for i in range(n)])
 
 
-def _fit_inputs(walker, take, x_column, y_column, fn_number):
-    """what M:1232-1241 binds: the data columns and x-fit of one function"""
-    data = walker.data[fn_number]
+def _fit_inputs(walker, take, x_column, y_column, fn_number, chain=0):
+    """what M:1232-1241 binds: the data columns and x-fit of one function (of walker `chain`)"""
+    data = walker.data_of(fn_number, chain)
     x_data = np.asarray(data[x_column], dtype=np.float64)
     y_data = np.asarray(data[y_column], dtype=np.float64)
     if x_data.ndim != 1:
@@ -612,7 +756,7 @@ def walker_get_data_and_fit_no_stddev(walker, take=1000, x_column=0, y_column=1,
     model is evaluated by the device's own code (mhx_eval_function)."""
     cap = walker.length(chain)
     take = cap if take is None or take > cap else int(take)
-    x_data, y_data, x_fit = _fit_inputs(walker, take, x_column, y_column, fn_number)
+    x_data, y_data, x_fit = _fit_inputs(walker, take, x_column, y_column, fn_number, chain)
     plists, th = _fit_solution(walker, which_solution, take, chain)
     y_fit = walker.engine.eval_function(fn_number, th[0], x_fit)
     return [_shift(x_fit, x_shift), _shift(y_fit, y_shift), _shift(x_data, x_shift),
@@ -640,6 +784,8 @@ def _data_and_fit(walker, take, x_column, y_column, fn_number, which_solution, x
     ys = 0 if y_shift is None else y_shift  # (+ (if y-shift y-shift 0) ...) M:1252-1253
     out = []
     for i, c in enumerate(which):
+        if walker.planes is not None:  # (a dataset per walker: walker c's own columns)
+            x_data, y_data, _ = _fit_inputs(walker, take, x_column, y_column, fn_number, c)
         out.append([_shift(x_fit, x_shift), [ys + float(v) for v in ymax[c]],
                     [ys + float(v) for v in ymin[c]], _shift(y_fit[i], y_shift),
                     _shift(x_data, x_shift), _shift(y_data, y_shift), plists[i]])
@@ -673,10 +819,10 @@ def walker_get_residuals(walker, take=1000, x_column=0, y_column=1, fn_number=0,
     device already; a stddev of one number is spread over the points (M:1280)."""
     cap = walker.length(chain)
     take = cap if take is None or take > cap else int(take)
-    data = walker.data[fn_number]
+    data = walker.data_of(fn_number, chain)
     x_data = np.asarray(data[x_column], dtype=np.float64)
     y_data = np.asarray(data[y_column], dtype=np.float64)
-    sd = np.asarray(walker.data_error[fn_number], dtype=np.float64).reshape(-1)
+    sd = np.asarray(walker.data_error_of(fn_number, chain), dtype=np.float64).reshape(-1)
     if sd.size == 1:
         sd = np.full(len(y_data), sd[0])
     _, th = _fit_solution(walker, ":median", take, chain)
