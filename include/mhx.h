@@ -701,6 +701,55 @@ int mhx_group_get_autocorr(mhx_group* g, int take, const int32_t* cols, int n_co
 int mhx_split_rhat(const double* half_mean, const double* half_var, const int32_t* n_used,
                    int64_t n_chains, int n_cols, double* rhat);
 
+/* ---- ensemble percentiles: ONE posterior from all chains of a walker set.  On a set whose chains
+ * sample the same posterior (one shared dataset) the user wants one median and one 95 % interval
+ * drawn from every step of every chain, not one per chain.  The reference has no walker-set
+ * reduction; the definition is this library's own and fixes every bit.
+ *   window   chain c contributes its newest t_c = min(take, walker-length, steps held) steps: the
+ *            window of mhx_get_percentiles.  n_used[c] = t_c, and 0 for an excluded chain
+ *   pool     for column p the multiset of x[c][s][p] over all included chains c and s < t_c
+ *   size     N = the sum of the t_c, an int64: *n_pooled
+ *   rank     mhx_percentile_rank(N, num, den) gives pos and between
+ *   value    the element at pos of the pool in ascending order by the order of
+ *            mhx_get_percentiles: a NaN sorts last whatever its sign; -0 and +0 compare equal and
+ *            either may stand for the other
+ *   between  the IEEE (e[pos] + e[pos+1]) / 2
+ * that is nth-percentile (M:1495-1506) on the concatenation of the chains' :param lists.  Exact
+ * whatever n_chains and take are: a most-significant-digit-first radix selection over the whole
+ * device - eight passes of 8-bit digits over the 64-bit order keys and, where a `between` rank is
+ * the last of its run of equal values, one pass for the successor: at most nine launches, no
+ * sort, no history moved; only integer counts cross to the host, so the result does not depend
+ * on thread order, workgroup order or the split of the chains over devices.
+ * Arguments: cols[n_cols] distinct parameter indices in [0, d), 1 <= n_cols <= d, in any order
+ * (the outputs follow that order); include[n_chains] (NULL: every chain) leaves out the chains
+ * whose byte is 0 - those that never converged, which show up as stuck in split R-hat or through
+ * a poor most-likely step; 0 <= n_pct <= MHX_MAX_PERCENTILES (0 writes only the counts); take in
+ * [1, history_capacity].  out [n_pct][n_cols]; status [n_cols]: 1 when the pool's column holds a
+ * NaN.  Any output may be NULL.  MHX_ESTATE before mhx_init_chains; MHX_EINVAL for bad arguments
+ * and for an include that leaves no chain; the outputs stay untouched on error.  A chain in
+ * MHX_CHAIN_FP_TRAP is served from the history it has.  The device scratch (the counters of at
+ * most 1008 tasks, 2 KiB each, the task list, the mask, n_used) does not depend on take;
+ * mhx_get_summary_timing covers the kernels of all passes.  ("Ensemble" because mhx_get_pooled
+ * already means the pooled adaptation.) */
+int mhx_get_ensemble_percentiles(mhx_engine* e, int take, const int32_t* cols, int n_cols,
+                                 const uint8_t* include, const int32_t* pct_num,
+                                 const int32_t* pct_den, int n_pct, double* out, int64_t* n_pooled,
+                                 int32_t* n_used, int32_t* status);
+/* The same over a group: include and n_used in global chain order.  Every engine runs each pass
+ * over its own chains, every device's launch enqueued before any is waited for; the host adds the
+ * engines' counters (exact integers), picks once and hands every engine the same next tasks, and
+ * takes the least of the engines' successors. */
+int mhx_group_get_ensemble_percentiles(mhx_group* g, int take, const int32_t* cols, int n_cols,
+                                       const uint8_t* include, const int32_t* pct_num,
+                                       const int32_t* pct_den, int n_pct, double* out,
+                                       int64_t* n_pooled, int32_t* n_used, int32_t* status);
+/* One step of that selection on the host (needs no engine and no device): of counts[n_bins], the
+ * smallest *digit whose cumulative count exceeds rank, the rank within that bin and the bin's
+ * count.  MHX_EINVAL unless n_bins >= 1 and 0 <= rank < the sum of the counts.  Any output may
+ * be NULL. */
+int mhx_ensemble_pick(const uint64_t* counts, int n_bins, int64_t rank, int32_t* digit,
+                      int64_t* rank_in_bin, int64_t* bin_count);
+
 /* Restore a saved walk (walker-load, sketched in the comments M:987-1001): prob[n], theta[n][d]
  * NEWEST FIRST, as walker-save would have written them.  Sets the ring (newest
  * min(n, history_capacity) steps), last-step, length, age = n and the most-likely step. */

@@ -11,7 +11,7 @@ importlib.import_module("lisp-mcmc_amd").
 """
 from . import _capi as capi  # noqa: F401
 from ._capi import MhxError  # noqa: F401
-from .engine import Engine, Group, band_count, comm_unique_id, partition, split_rhat  # noqa: F401
+from .engine import Engine, Group, band_count, comm_unique_id, partition, split_rhat, ensemble_pick  # noqa: F401
 from . import models  # noqa: F401
 from . import sexpr  # noqa: F401
 from . import distributed  # noqa: F401
@@ -27,7 +27,7 @@ from .walker import (  # noqa: F401
     walker_with_exp, walker_exp_get, walker_set_with_exp, walker_set_exp_get,
     make_histo, make_histo_x, histo_edges, walker_param_histo, walker_set_param_histo,
     walker_set_corner_grid,
-    autocorr, walker_autocorr, walker_set_autocorr, walker_set_rhat,
+    autocorr, walker_autocorr, walker_set_autocorr, walker_set_rhat, walker_set_ensemble_get,
 )
 
 __all__ = ["capi", "MhxError", "Engine", "Group", "comm_unique_id", "partition", "models", "Walker", "WalkerStep", "walker_create",
@@ -40,4 +40,5 @@ __all__ = ["capi", "MhxError", "Engine", "Group", "comm_unique_id", "partition",
            "walker_with_exp", "walker_exp_get", "walker_set_with_exp", "walker_set_exp_get",
            "make_histo", "make_histo_x", "histo_edges", "walker_param_histo", "walker_set_param_histo",
            "walker_set_corner_grid",
-           "autocorr", "walker_autocorr", "walker_set_autocorr", "walker_set_rhat", "split_rhat"]
+           "autocorr", "walker_autocorr", "walker_set_autocorr", "walker_set_rhat", "split_rhat",
+           "walker_set_ensemble_get", "ensemble_pick"]

@@ -157,6 +157,11 @@ SIGNATURES = {
     "mhx_group_get_autocorr": (C.c_int, [C.c_void_p, C.c_int, i32p, C.c_int, C.c_int, f64p, f64p, f64p,
                                          f64p, f64p, i32p, i32p, i32p]),
     "mhx_split_rhat": (C.c_int, [f64p, f64p, i32p, C.c_int64, C.c_int, f64p]),
+    "mhx_get_ensemble_percentiles": (C.c_int, [C.c_void_p, C.c_int, i32p, C.c_int, u8p, i32p, i32p, C.c_int,
+                                               f64p, i64p, i32p, i32p]),
+    "mhx_group_get_ensemble_percentiles": (C.c_int, [C.c_void_p, C.c_int, i32p, C.c_int, u8p, i32p, i32p,
+                                                     C.c_int, f64p, i64p, i32p, i32p]),
+    "mhx_ensemble_pick": (C.c_int, [u64p, C.c_int, C.c_int64, i32p, i64p, i64p]),
 }
 
 _lib = None

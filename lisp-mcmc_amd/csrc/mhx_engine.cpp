@@ -19,6 +19,7 @@
 
 #include <memory>
 
+#include "mhx_ensemble.hpp"
 #include "mhx_launch.hpp"
 #include "mhx_plan.hpp"
 #include "mhx_rtc.hpp"
@@ -3120,6 +3121,173 @@ int mhx_get_autocorr(mhx_engine* e, int take, const int32_t* cols, int n_cols, i
   return rc != MHX_OK ? rc : run_portions(e, q);
 }
 
+// ---- ensemble percentiles: ONE posterior from all chains of a walker set (k_ensemble_digits;
+// include/mhx.h has the definitions, mhx_ensemble.hpp the bookkeeping).  Eight count passes and,
+// where a `between` rank is the last of its run, one successor pass.  Per pass and engine: the
+// task list goes up, the counters are cleared, one launch over all the engine's chains, tasks x
+// 2 KiB of counters come back.  The host adds the engines' counters (exact integers), picks every
+// target's digit once and hands every engine the same next tasks.  The scratch does not depend
+// on `take` or grow with the pool: no portions.
+extern "C++" {
+static int ensemble_run(const std::vector<mhx_engine*>& engs, const int64_t* first, int take,
+                        const int32_t* cols, int n_cols, const uint8_t* include, const int32_t* pct_num,
+                        const int32_t* pct_den, int n_pct, double* out, int64_t* n_pooled, int32_t* n_used,
+                        int32_t* status) {
+  static_assert(kEnsMaxTasks == 1008, "63 columns x 16 percentiles");
+  int rc = MHX_OK;
+  for (const mhx_engine* e : engs)
+    if ((rc = window_check(e, take)) != MHX_OK) return rc;
+  const int d = engs[0]->P.d;
+  if (n_cols < 1 || n_cols > d || !cols) return fail(MHX_EINVAL, "n_cols must be in [1, d = %d]", d);
+  ColList cl{};
+  PctList pc{};
+  if ((rc = fill_cols(&cl, cols, n_cols, d)) != MHX_OK || (rc = fill_pcts(&pc, pct_num, pct_den, n_pct)) != MHX_OK)
+    return rc;
+  const size_t E = engs.size();
+  int64_t total = 0;
+  std::vector<int64_t> at(E);
+  for (size_t i = 0; i < E; ++i) {
+    if (engs[i]->P.d != d) return fail(MHX_EINVAL, "the engines' parameter counts differ");
+    at[i] = first ? first[i] : 0;
+    total += engs[i]->cfg.n_chains;
+  }
+  if (include) {
+    bool any = false;
+    for (int64_t c = 0; c < total && !any; ++c) any = include[c] != 0;
+    if (!any) return fail(MHX_EINVAL, "include leaves no chain");
+  }
+  const int max_tasks = ensemble_max_tasks(n_cols, n_pct);
+  std::vector<EnsemblePieces> pieces(E);
+  auto give_up = [&](int code) {
+    for (mhx_engine* e : engs) drain(e);
+    return code;
+  };
+  // the scratch, cleared; the mask of the engine's own chains
+  auto prepare = [&](size_t i) -> int {
+    mhx_engine* e = engs[i];
+    Carver cv;
+    pieces[i] = carve_ensemble(cv, max_tasks, n_cols, e->cfg.n_chains);
+    int r = use_device(e);
+    if (r != MHX_OK || (r = ensure_stage(e, cv.bytes())) != MHX_OK) return r;
+    e->summary_ms = 0.0;
+    HIP_TRY(hipMemsetAsync(e->stage.p, 0, cv.bytes(), e->stream));
+    if (include)
+      HIP_TRY(hipMemcpyAsync(e->stage.p + pieces[i].include, include + at[i], (size_t)e->cfg.n_chains,
+                             hipMemcpyHostToDevice, e->stream));
+    return MHX_OK;
+  };
+  for (size_t i = 0; i < E; ++i)
+    if ((rc = prepare(i)) != MHX_OK) return give_up(rc);
+
+  std::vector<EnsTask> tasks((size_t)max_tasks);
+  std::vector<uint64_t> sum, part;
+  // One pass: `nt` tasks of `words` counters each, cleared to `fill` bytes; every engine's launch
+  // is enqueued before any is waited for; sum[] gathers the engines' counters by `join`.
+  auto enqueue = [&](size_t i, int mode, int nt, size_t words, int fill) -> int {
+    mhx_engine* e = engs[i];
+    const EnsemblePieces& s = pieces[i];
+    const int r = use_device(e);
+    if (r != MHX_OK) return r;
+    HIP_TRY(hipMemcpyAsync(e->stage.p + s.tasks, tasks.data(), (size_t)nt * sizeof(EnsTask), hipMemcpyHostToDevice,
+                           e->stream));
+    HIP_TRY(hipMemsetAsync(e->stage.p + s.counters, fill, (size_t)nt * words * sizeof(uint64_t), e->stream));
+    HIP_TRY(hipEventRecord(e->ev0, e->stream));
+    const bool lds = !e->knobs.ensemble_no_lds && ensemble_lds_bytes(take, cl.n, true) <= kPctLdsBudget;
+    HIP_TRY(launch_ensemble_digits(e->stream, e->S, e->cfg.n_chains, take, cl,
+                                   include ? stage_at<uint8_t>(e, s.include) : nullptr,
+                                   stage_at<EnsTask>(e, s.tasks), nt, mode, lds, stage_at<uint64_t>(e, s.counters),
+                                   stage_at<int32_t>(e, s.n_used), stage_at<int32_t>(e, s.status)));
+    HIP_TRY(hipEventRecord(e->ev1, e->stream));
+    return MHX_OK;
+  };
+  auto collect = [&](size_t i, size_t n_words, bool least) -> int {
+    mhx_engine* e = engs[i];
+    const int r = use_device(e);
+    if (r != MHX_OK) return r;
+    HIP_TRY(hipEventSynchronize(e->ev1));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
+    e->summary_ms += (double)ms;
+    HIP_TRY(hipMemcpy(part.data(), e->stage.p + pieces[i].counters, n_words * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < n_words; ++k) sum[k] = least ? std::min(sum[k], part[k]) : sum[k] + part[k];
+    return MHX_OK;
+  };
+  auto pass = [&](int mode, int nt) -> int {
+    const bool least = mode == ENS_SUCCESSOR;
+    const size_t words = least ? 1 : (size_t)kEnsBins, n_words = (size_t)nt * words;
+    sum.assign(n_words, least ? ~(uint64_t)0 : 0);
+    part.resize(n_words);
+    int r = MHX_OK;
+    for (size_t i = 0; i < E; ++i)
+      if ((r = enqueue(i, mode, nt, words, least ? 0xFF : 0)) != MHX_OK) return r;
+    for (size_t i = 0; i < E; ++i)
+      if ((r = collect(i, n_words, least)) != MHX_OK) return r;
+    return MHX_OK;
+  };
+
+  // pass 0 counts every column whole: the pool's size comes with it
+  const int n_targets = n_cols * n_pct;
+  std::vector<EnsTarget> targets((size_t)n_targets);
+  if ((rc = pass(ENS_COUNT_FIRST, ensemble_first_tasks(n_cols, tasks.data()))) != MHX_OK) return give_up(rc);
+  int64_t pooled = 0;
+  for (int b = 0; b < kEnsBins; ++b) pooled += (int64_t)sum[(size_t)b];
+  if (pooled < 1) return fail(MHX_ESTATE, "the included chains hold no step");
+  ensemble_targets(pooled, pc, n_cols, targets.data());
+  for (int p = 0; p < kEnsPasses && n_targets > 0; ++p) {
+    const int shift = ensemble_shift(p);
+    if (p > 0 && (rc = pass(ENS_COUNT, ensemble_tasks(targets.data(), n_targets, shift, tasks.data()))) != MHX_OK)
+      return give_up(rc);
+    if (!ensemble_advance(targets.data(), n_targets, shift, sum.data()))
+      return fail(MHX_EDEVICE, "ensemble percentiles: pass %d's counts do not hold a rank", p);
+  }
+  const int n_succ = ensemble_successor_tasks(targets.data(), n_targets, tasks.data());
+  if (n_succ > 0) {
+    if ((rc = pass(ENS_SUCCESSOR, n_succ)) != MHX_OK) return give_up(rc);
+    ensemble_take_successors(targets.data(), n_targets, sum.data());
+  }
+  // the counts; then the outputs, which nothing can fail any more
+  std::vector<int32_t> used((size_t)total), flags((size_t)n_cols, 0), flag_part((size_t)n_cols);
+  auto counts_of = [&](size_t i) -> int {
+    mhx_engine* e = engs[i];
+    const int r = use_device(e);
+    if (r != MHX_OK) return r;
+    HIP_TRY(hipMemcpy(used.data() + at[i], e->stage.p + pieces[i].n_used, (size_t)e->cfg.n_chains * sizeof(int32_t),
+                      hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(flag_part.data(), e->stage.p + pieces[i].status, (size_t)n_cols * sizeof(int32_t),
+                      hipMemcpyDeviceToHost));
+    for (int c = 0; c < n_cols; ++c) flags[(size_t)c] |= flag_part[(size_t)c] ? 1 : 0;
+    return MHX_OK;
+  };
+  for (size_t i = 0; i < E; ++i)
+    if ((rc = counts_of(i)) != MHX_OK) return give_up(rc);
+  if (out)
+    for (int k = 0; k < n_targets; ++k) out[k] = ensemble_value(targets[(size_t)k]);
+  if (n_pooled) *n_pooled = pooled;
+  if (n_used) std::copy(used.begin(), used.end(), n_used);
+  if (status) std::copy(flags.begin(), flags.end(), status);
+  return MHX_OK;
+}
+}  // extern "C++"
+
+int mhx_get_ensemble_percentiles(mhx_engine* e, int take, const int32_t* cols, int n_cols, const uint8_t* include,
+                                 const int32_t* pct_num, const int32_t* pct_den, int n_pct, double* out,
+                                 int64_t* n_pooled, int32_t* n_used, int32_t* status) {
+  if (!e) return fail(MHX_EINVAL, "engine is NULL");
+  return ensemble_run({e}, nullptr, take, cols, n_cols, include, pct_num, pct_den, n_pct, out, n_pooled, n_used, status);
+}
+int mhx_ensemble_pick(const uint64_t* counts, int n_bins, int64_t rank, int32_t* digit, int64_t* rank_in_bin,
+                      int64_t* bin_count) {
+  if (!counts || n_bins < 1) return fail(MHX_EINVAL, "mhx_ensemble_pick: n_bins must be >= 1 and counts given");
+  int32_t dg = 0;
+  int64_t rb = 0, bc = 0;
+  if (!ensemble_pick(counts, n_bins, rank, &dg, &rb, &bc))
+    return fail(MHX_EINVAL, "mhx_ensemble_pick: rank %lld is outside [0, the sum of the counts)", (long long)rank);
+  if (digit) *digit = dg;
+  if (rank_in_bin) *rank_in_bin = rb;
+  if (bin_count) *bin_count = bc;
+  return MHX_OK;
+}
+
 // Split R-hat from the half moments of mhx_get_autocorr: host arithmetic only, every sum serial
 // from its first term (include/mhx.h).
 int mhx_split_rhat(const double* half_mean, const double* half_var, const int32_t* n_used, int64_t n_chains,
@@ -3739,6 +3907,14 @@ int mhx_group_get_autocorr(mhx_group* g, int take, const int32_t* cols, int n_co
   AutocorrCall q;
   const int rc = q.prepare(g->eng, take, cols, n_cols, max_lag, tau, ess, acf, half_mean, half_var, n_lags, n_used, status);
   return rc != MHX_OK ? rc : run_portions(g, q);
+}
+
+int mhx_group_get_ensemble_percentiles(mhx_group* g, int take, const int32_t* cols, int n_cols,
+                                       const uint8_t* include, const int32_t* pct_num, const int32_t* pct_den,
+                                       int n_pct, double* out, int64_t* n_pooled, int32_t* n_used, int32_t* status) {
+  if (!g) return fail(MHX_EINVAL, "group is NULL");
+  return ensemble_run(g->eng, g->first.data(), take, cols, n_cols, include, pct_num, pct_den, n_pct, out, n_pooled,
+                      n_used, status);
 }
 
 }  // extern "C"

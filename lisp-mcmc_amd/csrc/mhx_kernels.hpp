@@ -3539,6 +3539,112 @@ __global__ __launch_bounds__(kPctThreads) void k_autocorr(
     autocorr_body<false>(ring, cl, t, L, max_lag + 1, tpad, i, acf, tau, ess, half_mean, half_var, status);
 }
 
+// mhx_get_ensemble_percentiles: one pass of the radix selection over the POOL of all included
+// chains' windows (include/mhx.h has the definitions, mhx_ensemble.hpp the host's half).  One
+// workgroup of kPctThreads per chain of the engine; an excluded chain's workgroup returns at once.
+//   1 the window's rows - t x d contiguous doubles, two runs when the ring has wrapped - are read
+//     ONCE, coalesced, as k_percentiles and k_autocorr read them; the requested columns are laid
+//     down in LDS as order keys, one column of `tpad` keys each
+//   2 wave w takes the tasks w, w + kPctWaves, ...: it walks the task's column, keeps the keys
+//     whose bits above the task's digit equal the task's prefix, and adds 1 to the digit's bin of
+//     its own 256-bin uint32 histogram in LDS (a window holds at most ring-capacity steps)
+//   3 every non-zero bin goes to the task's uint64 counters in memory with one integer atomic add
+// ENS_COUNT_FIRST (pass 0, whose tasks are one per column with no prefix) also writes n_used and
+// flags the columns that hold a NaN (the only value whose key is all ones).
+// ENS_SUCCESSOR: a task's prefix is a whole key; the wave finds the least key of the column above
+// it (one masked min-reduction, as select_percentile's) and hands it to the task's counter with
+// one integer atomic min.
+// Integer additions and minima only: thread order, workgroup order and the split of the chains
+// over devices cannot change a bit.  No workgroup waits for another.
+// use_lds = 0 (the columns do not fit, or MHX_ENSEMBLE_NO_LDS): every pass reads the column from
+// ring.theta with stride d; only the histograms are in LDS.
+template <bool kLds>
+__device__ __forceinline__ void ensemble_body(const Ring& ring, const ColList& cl, int t, int tpad,
+                                              const EnsTask* __restrict__ tasks, int n_tasks, int mode,
+                                              unsigned long long* counters, int32_t* nan_flag) {
+  const int d = ring.d, nc = cl.n, tid = threadIdx.x, w = wave_in_group(), l = lane_id();
+  unsigned long long* col = reinterpret_cast<unsigned long long*>(mhx_lds_raw);
+  unsigned int* hist = reinterpret_cast<unsigned int*>(col + (kLds ? (size_t)nc * tpad : 0)) + w * kEnsBins;
+  if (kLds) {  // 1: element f = s d + p of the window, oldest row first
+    const int64_t oldest = ring.nh - t;
+    const int ds = kPctThreads / d, dp = kPctThreads - ds * d;
+    int s = tid / d, p = tid - s * d;
+    for (int f = tid; f < t * d; f += kPctThreads) {
+      const int c = cl.of_param[p];
+      if (c >= 0) {
+        const int64_t slot = (oldest + s) & (int64_t)ring.mask;
+        col[(size_t)c * tpad + s] = order_key(ring.theta[slot * d + p]);
+      }
+      s += ds;
+      p += dp;
+      if (p >= d) {
+        p -= d;
+        ++s;
+      }
+    }
+    __syncthreads();
+  }
+  auto key_at = [&](int c, int s) -> unsigned long long {
+    return kLds ? col[(size_t)c * tpad + s] : order_key(ring.theta[(int64_t)ring.slot(s) * d + cl.idx[c]]);
+  };
+  // every wave goes round as often as the busiest, so that the barriers are the workgroup's
+  for (int T0 = 0; T0 < n_tasks; T0 += kPctWaves) {
+    const int T = T0 + w;
+    const bool mine = T < n_tasks;
+    const EnsTask tk = tasks[mine ? T : 0];
+    const int c = tk.col;
+    if (mode == ENS_SUCCESSOR) {
+      if (!mine) continue;
+      unsigned long long m = ~0ULL;
+      for (int s = l; s < t; s += kWave) {
+        const unsigned long long key = key_at(c, s);
+        if (key > tk.prefix && key < m) m = key;
+      }
+      m = wave_min_u64(m);
+      // the counter only ever falls: a chain whose least key is not below what it reads there has
+      // nothing to hand in (a stale read only costs a minimum that changes nothing), which spares
+      // most of the workgroups an atomic on an address they all share
+      if (l == 0 && m < __hip_atomic_load(&counters[T], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+        atomicMin(&counters[T], m);
+      continue;
+    }
+    for (int b = l; b < kEnsBins; b += kWave) hist[b] = 0;
+    __syncthreads();
+    if (mine) {
+      const unsigned long long mask = tk.shift >= 56 ? 0ULL : ~0ULL << (tk.shift + 8);
+      bool nan = false;
+      for (int s = l; s < t; s += kWave) {
+        const unsigned long long key = key_at(c, s);
+        if ((key & mask) == tk.prefix) atomicAdd(&hist[(unsigned)(key >> tk.shift) & (kEnsBins - 1)], 1u);
+        nan = nan || key == ~0ULL;
+      }
+      if (mode == ENS_COUNT_FIRST && nan) atomicOr(&nan_flag[c], 1);
+    }
+    __syncthreads();
+    if (mine)
+      for (int b = l; b < kEnsBins; b += kWave) {
+        const unsigned int h = hist[b];
+        if (h != 0) atomicAdd(&counters[(size_t)T * kEnsBins + b], (unsigned long long)h);
+      }
+  }
+}
+// tasks [n_tasks]; counters [n_tasks][kEnsBins] zeroed (ENS_SUCCESSOR: [n_tasks], all ones);
+// include [chains] or NULL; n_used [chains] and nan_flag [cl.n] zeroed ahead of ENS_COUNT_FIRST
+__global__ __launch_bounds__(kPctThreads) void k_ensemble_digits(
+    ChainState S, int take, ColList cl, const uint8_t* __restrict__ include,
+    const EnsTask* __restrict__ tasks, int n_tasks, int mode, int use_lds, int tpad,
+    unsigned long long* counters, int32_t* __restrict__ n_used, int32_t* nan_flag) {
+  const int64_t i = blockIdx.x;
+  if (include && include[i] == 0) return;
+  const Ring ring = ring_of(S, i);
+  const int t = ring_held(ring, take);
+  if (mode == ENS_COUNT_FIRST && threadIdx.x == 0) n_used[i] = t;
+  if (use_lds)
+    ensemble_body<true>(ring, cl, t, tpad, tasks, n_tasks, mode, counters, nan_flag);
+  else
+    ensemble_body<false>(ring, cl, t, tpad, tasks, n_tasks, mode, counters, nan_flag);
+}
+
 // mhx_get_derived, second half: the posterior summaries of the values mhx_user_derived left in
 // the portion's staging buffer, vals [n][ne][pitch] newest first.  One workgroup of kPctWaves
 // wavefronts per chain, as k_percentiles, the expressions in the parameters' place.

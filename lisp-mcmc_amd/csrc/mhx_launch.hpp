@@ -135,6 +135,18 @@ hipError_t launch_autocorr(hipStream_t st, const ChainState& S, int64_t c0, int6
                            const ColList& cl, int max_lag, bool use_lds, double* acf, double* tau,
                            double* ess, double* half_mean, double* half_var, int32_t* n_lags,
                            int32_t* n_used, int32_t* status);
+// mhx_get_ensemble_percentiles (k_ensemble_digits): one pass over ALL the engine's chains.  The
+// LDS a workgroup needs: nc columns of keys at the pitch of k_percentiles where use_lds, and a
+// 256-bin uint32 histogram for each of its four waves.  Above kPctLdsBudget, or with use_lds =
+// false, the columns stay in memory.
+inline size_t ensemble_lds_bytes(int take, int nc, bool use_lds) {
+  return (use_lds ? (size_t)nc * pct_column_pitch(take, nc) * sizeof(uint64_t) : 0) +
+         (size_t)4 * kEnsBins * sizeof(uint32_t);
+}
+hipError_t launch_ensemble_digits(hipStream_t st, const ChainState& S, int64_t n, int take,
+                                  const ColList& cl, const uint8_t* include, const EnsTask* tasks,
+                                  int n_tasks, int mode, bool use_lds, uint64_t* counters,
+                                  int32_t* n_used, int32_t* nan_flag);
 hipError_t launch_covariances(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
                               int* uniq, double* cov, int32_t* n_unique, int32_t* status);
 hipError_t launch_l_matrices(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,

@@ -273,6 +273,9 @@ hipError_t summary_configure() {
   if (e == hipSuccess)
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_autocorr),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPctLdsBudget);
+  if (e == hipSuccess)
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ensemble_digits),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPctLdsBudget);
   return e;
 }
 hipError_t launch_percentiles(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
@@ -331,6 +334,20 @@ hipError_t launch_autocorr(hipStream_t st, const ChainState& S, int64_t c0, int6
   k_autocorr<<<dim3((unsigned)n), dim3(kPctThreads), lds, st>>>(
       S, c0, take, cl, max_lag, use_lds ? 1 : 0, pct_column_pitch(take, cl.n), acf, tau, ess,
       half_mean, half_var, n_lags, n_used, status);
+  return hipGetLastError();
+}
+hipError_t launch_ensemble_digits(hipStream_t st, const ChainState& S, int64_t n, int take,
+                                  const ColList& cl, const uint8_t* include, const EnsTask* tasks,
+                                  int n_tasks, int mode, bool use_lds, uint64_t* counters,
+                                  int32_t* n_used, int32_t* nan_flag) {
+  static_assert(kPctWaves == 4, "ensemble_lds_bytes counts four histograms");
+  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the counters are 64-bit");
+  if (n <= 0 || n_tasks <= 0) return hipSuccess;
+  const size_t lds = ensemble_lds_bytes(take, cl.n, use_lds);
+  if (lds > kPctLdsBudget) return hipErrorInvalidValue;
+  k_ensemble_digits<<<dim3((unsigned)n), dim3(kPctThreads), lds, st>>>(
+      S, take, cl, include, tasks, n_tasks, mode, use_lds ? 1 : 0, pct_column_pitch(take, cl.n),
+      reinterpret_cast<unsigned long long*>(counters), n_used, nan_flag);
   return hipGetLastError();
 }
 hipError_t launch_covariances(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,

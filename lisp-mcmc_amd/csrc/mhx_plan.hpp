@@ -37,6 +37,7 @@ struct EngineKnobs {
   bool summary_no_lds = false;      // MHX_SUMMARY_NO_LDS: k_percentiles reads its columns from memory even where they fit LDS
   bool histo_no_lds = false;        // MHX_HISTO_NO_LDS: k_histograms / k_pair_grids count straight into memory even where LDS would hold them
   bool autocorr_no_lds = false;     // MHX_AUTOCORR_NO_LDS: k_autocorr reads the window from memory even where its columns fit LDS
+  bool ensemble_no_lds = false;     // MHX_ENSEMBLE_NO_LDS: k_ensemble_digits reads its columns from memory in every pass even where they fit LDS
   bool planes_no_lds = false;       // MHX_PLANES_NO_LDS: a dataset per walker is streamed from memory even where it fits LDS
 #ifdef MHX_DEBUG_HOOKS
   bool test_lose_sweepers = false;  // MHX_TEST_LOSE_SWEEPERS: k_persist's sweep workgroups never come (test library)
@@ -54,7 +55,7 @@ inline EngineKnobs read_knobs() {
       {"MHX_NO_COMPACT", &EngineKnobs::no_compact}, {"MHX_COMPACT_ALWAYS", &EngineKnobs::compact_always},
       {"MHX_NO_GRAPH", &EngineKnobs::no_graph}, {"MHX_SUMMARY_NO_LDS", &EngineKnobs::summary_no_lds},
       {"MHX_HISTO_NO_LDS", &EngineKnobs::histo_no_lds}, {"MHX_AUTOCORR_NO_LDS", &EngineKnobs::autocorr_no_lds},
-      {"MHX_PLANES_NO_LDS", &EngineKnobs::planes_no_lds},
+      {"MHX_PLANES_NO_LDS", &EngineKnobs::planes_no_lds}, {"MHX_ENSEMBLE_NO_LDS", &EngineKnobs::ensemble_no_lds},
 #ifdef MHX_DEBUG_HOOKS
       {"MHX_TEST_LOSE_SWEEPERS", &EngineKnobs::test_lose_sweepers},
 #endif

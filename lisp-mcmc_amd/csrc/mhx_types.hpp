@@ -186,6 +186,17 @@ struct ColList {
   int32_t idx[MHX_MAX_PARAMS + 1], of_param[MHX_MAX_PARAMS + 1];
 };
 
+// one task of a pass of mhx_get_ensemble_percentiles (k_ensemble_digits reads a list of them):
+// count, by their 8-bit digit at `shift`, the keys of column `col` (a place in the call's
+// ColList) whose bits above the digit equal `prefix`; in the successor pass `prefix` is a whole
+// key and the task asks for the least key above it
+struct EnsTask {
+  uint64_t prefix;
+  int32_t col, shift;
+};
+constexpr int kEnsBins = 256;  // counters of a task: one per value of a digit
+enum { ENS_COUNT_FIRST = 0, ENS_COUNT = 1, ENS_SUCCESSOR = 2 };  // k_ensemble_digits' modes
+
 // walker-get-data-and-fit's count of enveloped steps, (ceiling (* 0.66 take)) M:1250
 // (include/mhx.h: mhx_band_count): 0.66 is a single float and so is the product.
 #ifndef __HIPCC_RTC__

@@ -184,6 +184,48 @@ class _Summaries:
             *(out[k].ctypes.data_as(capi.i32p) for k in ("n_lags", "n_used", "status"))))
         return out
 
+    def ensemble_percentiles(self, take, pcts, cols=None, include=None):
+        """ONE posterior from all chains (mhx_get_ensemble_percentiles, which has the definitions):
+        nth-percentile of the pool of every included chain's newest `take` steps, for the
+        parameters `cols` (None: all, in order).  include: [n_chains] truth values, None: every
+        chain.  A dict of out [len(pcts), n_cols], n_pooled (the pool's size), n_used [n_chains]
+        (0 for an excluded chain) and status [n_cols] (1: the pool's column holds a NaN).  pcts:
+        numbers or (num, den) pairs, as for percentiles()."""
+        rat = [p if isinstance(p, tuple) else percentile_ratio(p) for p in pcts]
+        num, nump = capi.as_i32([r[0] for r in rat] or [0])
+        den, denp = capi.as_i32([r[1] for r in rat] or [1])
+        cols = list(range(self.d)) if cols is None else [int(c) for c in cols]
+        ca, colp = capi.as_i32(cols or [0])
+        incp = None
+        if include is not None:
+            inc = np.ascontiguousarray(np.asarray(include).astype(bool), dtype=np.uint8)
+            if inc.shape != (self.n_chains,):
+                raise ValueError("include must be [n_chains = %d], not %r" % (self.n_chains, inc.shape))
+            incp = inc.ctypes.data_as(capi.u8p)
+        out = {"out": np.zeros((len(rat), len(cols))), "n_used": np.zeros(self.n_chains, dtype=np.int32),
+               "status": np.zeros(len(cols), dtype=np.int32)}
+        pooled = C.c_int64(0)
+        capi.check(self._summary("ensemble_percentiles")(
+            self._h, int(take), colp, len(cols), incp, nump, denp, len(rat),
+            out["out"].ctypes.data_as(capi.f64p), C.byref(pooled), out["n_used"].ctypes.data_as(capi.i32p),
+            out["status"].ctypes.data_as(capi.i32p)))
+        out["n_pooled"] = pooled.value
+        return out
+
+
+def ensemble_pick(counts, rank):
+    """(digit, rank in its bin, the bin's count) of `rank` among the bins `counts`
+    (mhx_ensemble_pick: host arithmetic, no device): the smallest digit whose cumulative count
+    exceeds rank.  ValueError, with the library's message, unless 0 <= rank < sum(counts)."""
+    ca = np.ascontiguousarray(counts, dtype=np.uint64).reshape(-1)
+    digit, rb, bc = C.c_int32(0), C.c_int64(0), C.c_int64(0)
+    rc = capi.lib().mhx_ensemble_pick(ca.ctypes.data_as(capi.u64p), int(ca.size), int(rank),
+                                      C.byref(digit), C.byref(rb), C.byref(bc))
+    if rc == capi.EINVAL:
+        raise ValueError(capi.lib().mhx_last_error().decode())
+    capi.check(rc)
+    return digit.value, rb.value, bc.value
+
 
 def split_rhat(half_mean, half_var, n_used):
     """split R-hat of every column (mhx_split_rhat: host arithmetic, no device) from the half

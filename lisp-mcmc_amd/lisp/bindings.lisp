@@ -248,6 +248,18 @@ library, or without a gfx950 device, walker-create signals MHX-ERROR."
 (cffi:defcfun ("mhx_split_rhat" %mhx-split-rhat) :int
   (half-mean :pointer) (half-var :pointer) (n-used :pointer) (n-chains :int64) (n-cols :int)
   (rhat :pointer))
+;; ensemble percentiles: one posterior from all chains of a walker set; one step of its selection
+(cffi:defcfun ("mhx_get_ensemble_percentiles" %mhx-get-ensemble-percentiles) :int
+  (e :pointer) (take :int) (cols :pointer) (n-cols :int) (include :pointer) (pct-num :pointer)
+  (pct-den :pointer) (n-pct :int) (out :pointer) (n-pooled :pointer) (n-used :pointer)
+  (status :pointer))
+(cffi:defcfun ("mhx_group_get_ensemble_percentiles" %mhx-group-get-ensemble-percentiles) :int
+  (g :pointer) (take :int) (cols :pointer) (n-cols :int) (include :pointer) (pct-num :pointer)
+  (pct-den :pointer) (n-pct :int) (out :pointer) (n-pooled :pointer) (n-used :pointer)
+  (status :pointer))
+(cffi:defcfun ("mhx_ensemble_pick" %mhx-ensemble-pick) :int
+  (counts :pointer) (n-bins :int) (rank :int64) (digit :pointer) (rank-in-bin :pointer)
+  (bin-count :pointer))
 
 (defmacro with-c-call (&body body)
   "HIP/RCCL runtime code may raise inexact/invalid flags that SBCL turns into conditions;

@@ -21,7 +21,7 @@
    #:walker-with-exp #:walker-exp-get #:walker-set-exp-get
    #:make-histo #:make-histo-x #:walker-param-histo #:walker-set-param-histo
    #:walker-set-corner-grid
-   #:walker-set-autocorr #:walker-set-rhat
+   #:walker-set-autocorr #:walker-set-rhat #:walker-set-ensemble-get
    #:walker-save #:walker-load #:diagonal-covariance
    #:mfit-walker-estop #:request-stop
    ;; likelihood / prior designators

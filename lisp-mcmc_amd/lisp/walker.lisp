@@ -984,6 +984,46 @@ when the chains' windows differ in length or hold fewer than four steps."
             for j from 0
             append (list k (cffi:mem-aref rhat :double j))))))
 
+;;; ------------------------------------------------------------------ one posterior for the set
+;;; On a set whose chains sample the same posterior the steps of all chains make ONE sample.  The
+;;; reference has no walker-set reduction (walker-set-get answers per chain); this is an exact
+;;; selection over the pool on the device (mhx_get_ensemble_percentiles, whose comment in
+;;; include/mhx.h has the definitions).
+(defun walker-set-ensemble-get (walker &key (get :median-params) (take 1000) keys include)
+  "GET of the pool of every chain's newest TAKE steps, the plist (key value ...) over KEYS (nil:
+all), from one device call.  GET: :median-params, :95cr (a list low high), :iqr, :stddev-normal
+(the 84.1 point minus the median) or (:percentile n).  INCLUDE: a sequence with one generalised
+boolean per chain that leaves out the chains marked nil (those that never converged); nil: all."
+  (let* ((n (walker-n-chains walker))
+         (cols (%key-columns walker keys))
+         (names (or keys (walker-param-keys walker)))
+         (nc (length cols))
+         (selector (if (consp get) (first get) get))
+         (points (%exp-percentiles (if (eq get :median-params) :median get)))
+         (n-pct (length points))
+         (window (%bin-window walker take "walker-set-ensemble-get"))
+         (none (cffi:null-pointer)))
+    (unless (and points (member selector '(:median-params :95cr :iqr :stddev-normal :percentile)))
+      (error "unknown :get ~s" get))
+    (when (and include (/= (length include) n))
+      (error ":include must hold one entry per chain (~d), not ~d" n (length include)))
+    (cffi:with-foreign-objects ((colp :int32 nc) (num :int32 n-pct) (den :int32 n-pct)
+                                (mask :uint8 n) (out :double (* n-pct nc)))
+      (fill-int32s colp cols)
+      (fill-int32s num (mapcar #'car points))
+      (fill-int32s den (mapcar #'cdr points))
+      (let ((i 0))
+        (map nil (lambda (v) (setf (cffi:mem-aref mask :uint8 i) (if v 1 0)) (incf i)) include))
+      (%set-call walker #'%mhx-get-ensemble-percentiles #'%mhx-group-get-ensemble-percentiles
+                 window colp nc (if include mask none) num den n-pct out none none none)
+      (loop for k in names
+            for j from 0
+            append (list k (flet ((point (q) (cffi:mem-aref out :double (+ (* q nc) j))))
+                             (ecase selector
+                               ((:median-params :percentile) (point 0))
+                               (:95cr (list (point 0) (point 1)))
+                               ((:iqr :stddev-normal) (- (point 1) (point 0))))))))))
+
 ;;; ------------------------------------------------------------------ data and fit M:1208-1283
 ;;; The numbers behind the reference's plots.  The :function lives on the device, so the fit
 ;;; curve is mhx_eval_function and the envelope of the model over the most probable two thirds of

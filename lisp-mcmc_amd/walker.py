@@ -1122,6 +1122,45 @@ def walker_set_rhat(walker, keys=None, take=1000):
     return dict(zip(names, (float(v) for v in split_rhat(r["half_mean"], r["half_var"], r["n_used"]))))
 
 
+_ENSEMBLE_PERCENTILES = {"median-params": (50,), "95cr": (2.5, 97.5), "iqr": (25, 75),
+                         "stddev-normal": (50, 84.1)}
+
+
+def walker_set_ensemble_get(walker, get=":median-params", take=1000, keys=None, include=None):
+    """ONE posterior for the whole set: the chains' newest `take` steps pooled, and for every key
+    (None: all) a point of that pool - one device call (mhx_get_ensemble_percentiles), no history
+    moved, exact whatever the set's size.  get: :median-params, :95cr (a [lo, hi] pair), :iqr,
+    :stddev-normal (the 84.1 point minus the median, M:1529-1535) or (":percentile", n); the
+    points and result shapes are walker_exp_get's.  include: one truth value per chain, to leave
+    out chains that never converged (walker_set_rhat, a poor :most-likely-step); None: all.
+    Returns {key: value}.  The reference has no counterpart: walker-set-get answers per chain."""
+    arg = None
+    if isinstance(get, (tuple, list)):
+        if len(get) != 2:
+            raise ValueError("unknown :get %r" % (get,))
+        get, arg = get
+    g = str(get).lstrip(":").lower()
+    if (g not in _ENSEMBLE_PERCENTILES and g != "percentile") or (g == "percentile") != (arg is not None):
+        raise ValueError("unknown :get %r" % (get,))
+    if g == "percentile":
+        _, pcts = exp_selector((":percentile", arg))
+    else:
+        pcts = _ENSEMBLE_PERCENTILES[g]
+    names, cols = _key_columns(walker, keys)
+    window = _bin_window(walker, take, "walker-set-ensemble-get")
+    p = walker.engine.ensemble_percentiles(window, pcts, cols, include)["out"]
+    out = {}
+    for j, k in enumerate(names):
+        v = [float(x) for x in p[:, j]]
+        if g in ("median-params", "percentile"):
+            out[k] = v[0]
+        elif g == "95cr":  # M:1508-1509
+            out[k] = [v[0], v[1]]
+        else:  # iqr M:1511-1513; stddev-normal M:1529-1535
+            out[k] = v[1] - v[0]
+    return out
+
+
 def walker_modify(walker, modify=None, **kw):
     """(walker-modify ...) M:547-580: only :add-step is on the accelerated path and it is
     performed by the device inside walker-take-step; the list-surgery actions are host-side
