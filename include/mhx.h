@@ -480,7 +480,7 @@ int mhx_get_window_best(mhx_engine* e, int take, double* prob, double* theta);
  * not below mhx_config.history_capacity and the adaptation window). */
 int mhx_get_history_capacity(mhx_engine* e, int32_t* capacity);
 /* HIP-event milliseconds the kernels of the engine's last mhx_get_percentiles / _covariances /
- * _proposal_factors / _window_best / _fit_bands / _derived / _histograms / _pair_grids or
+ * _proposal_factors / _window_best / _fit_bands / _derived / _histograms / _pair_grids / _waic or
  * mhx_eval_function call ran (all portions; copies excluded). */
 int mhx_get_summary_timing(mhx_engine* e, double* kernel_ms);
 /* The same for a group, gathered in global chain order like mhx_group_get_state; every
@@ -749,6 +749,75 @@ int mhx_group_get_ensemble_percentiles(mhx_group* g, int take, const int32_t* co
  * be NULL. */
 int mhx_ensemble_pick(const uint64_t* counts, int n_bins, int64_t rank, int32_t* digit,
                       int64_t* rank_in_bin, int64_t* bin_count);
+
+/* ---- which model to have fitted: WAIC (Watanabe; Gelman, Hwang and Vehtari 2014), the pointwise
+ * predictive accuracy of every chain, on the device ring.  The reference has no such function
+ * (walker-plot-residuals is what it offers): the definition is this library's own and fixes the
+ * results operation by operation.  All arithmetic is plain IEEE binary64 multiply, add, subtract
+ * and divide, never fused.  `fn` is one function of a global fit, N its point count, x_i the
+ * dataset's own x.
+ *   window   the newest n = min(take, walker-length, steps held) steps theta_0 (newest) ...
+ *            theta_{n-1}: the window of mhx_get_percentiles.  n_used[c] = n
+ *   value    v_is = function fn at x_i for theta_s, the very bits mhx_eval_function returns
+ *   term     l_is, by the dataset's likelihood, from the numbers mhx_set_dataset forms:
+ *            w_i = 1 / sigma_i, ys_i = y_i * w_i, c_i = -1/2 log(2 pi) + (-1 * log sigma_i) for the
+ *            normal forms (sigma NULL: 1); c_i = -log-factorial(y_i) for Poisson, in the form
+ *            mhx_config.poisson_logfact_double selects (the addends of the sweep's constant)
+ *              MHX_LIK_NORMAL         a = v * w_i;  r = ys_i - a;  h = 0.5 * r;  q = h * r;
+ *                                     l = c_i - q
+ *              MHX_LIK_NORMAL_CUTOFF  the same, then l > -5000 ? l : -5000
+ *              MHX_LIK_POISSON        l = ((y_i * tlog_rate(v)) - v) + c_i, tlog_rate the sweep's
+ *                                     table logarithm (NaN unless v is a positive normal number)
+ *              MHX_LIK_EXPR           l = the likelihood expression at (y_i, v, error_i); no constant
+ *   over s   for s = 0 .. n-1 in that order, k = s + 1, q_k = 1.0 / k (one division):
+ *              Welford      delta = l - mean;  mean = mean + delta * q_k;
+ *                           M2 = M2 + delta * (l - mean)            from mean = 0, M2 = 0
+ *              log-sum-exp  s = 0: M = l, S = 1.  Then with up = l > M,
+ *                           g = exp(up ? M - l : l - M)  (the engine's exp, < 1 ulp),
+ *                           S = up ? S * g + 1 : S + g,  M = up ? l : M
+ *   point    pw_acc[c][i] = {M, S, mean, M2}
+ *            pw_p[c][i]    = M2 / (n - 1)       (n = 1: the IEEE 0/0, as mhx_get_derived's
+ *                                               standard deviation of one step)
+ *            pw_lppd[c][i] = M + log(S / n)     (the engine's log, < 1 ulp; S / n one division)
+ *   chain    the points go in blocks of MHX_WAIC_BLOCK: block b holds points b MHX_WAIC_BLOCK ..
+ *            A block's sum of a pointwise quantity t: lane j = i mod 64 of the block adds its
+ *            points serially in ascending i to a sum that starts at 0.0 (a point beyond N adds
+ *            0.0), then the 64 lane sums are added pairwise, lanes 32 apart first, then 16, 8, 4,
+ *            2, 1 (u_j = u_j + u_{j xor m}).  lppd[c] and p_waic[c] are the blocks' sums of
+ *            pw_lppd and pw_p, added serially in ascending b to a sum that starts at 0.0.
+ *            elpd[c] = lppd[c] - p_waic[c], one subtraction (waic = -2 elpd is the caller's).
+ *            n_high[c] = the exact count of points with pw_p > 0.4 (where the variance
+ *            approximation is known to be unreliable)
+ *   status   a sum of
+ *              MHX_WAIC_NONFINITE  a v_is or l_is of the chain is not finite (the reference would
+ *                                  have trapped): the chain's numbers are unspecified; no other
+ *                                  chain is touched by it
+ *              MHX_WAIC_ONE_STEP   n = 1: pw_p and p_waic are NaN
+ *            An empty window (n = 0: a walk that :burn-walks emptied) has no mean to take:
+ *            n_used[c] = 0, status[c] = MHX_WAIC_NONFINITE, the chain's numbers are unspecified.
+ * The results are the same bits from call to call, whatever portions the call is worked through
+ * in and however a group's chains are split over its engines.
+ * elpd, lppd, p_waic [n_chains]; n_high, n_used, status [n_chains]; pw_lppd, pw_p [n_chains][N];
+ * pw_acc [n_chains][N][4].  Any output may be NULL.  take in [1, history_capacity], fn a function
+ * of the problem, else MHX_EINVAL; MHX_ESTATE before mhx_init_chains; MHX_EUNSUPPORTED for an
+ * engine with a dataset per walker (mhx_set_dataset_planes: its per-point constants are per
+ * walker and not on the device).  The outputs stay untouched on error.  A chain in
+ * MHX_CHAIN_FP_TRAP is served from the history it has.  Serves every model the engine can walk.
+ * Worked through in portions whose device scratch stays below 64 MiB; mhx_get_summary_timing
+ * covers the call. */
+#define MHX_WAIC_BLOCK 256 /* points of one block of mhx_get_waic's sums */
+enum {
+  MHX_WAIC_NONFINITE = 1,
+  MHX_WAIC_ONE_STEP = 2
+};
+int mhx_get_waic(mhx_engine* e, int fn, int take, double* elpd, double* lppd, double* p_waic,
+                 int32_t* n_high, double* pw_lppd, double* pw_p, double* pw_acc, int32_t* n_used,
+                 int32_t* status);
+/* The same for a group, in global chain order; every device's work is enqueued before any is
+ * waited for. */
+int mhx_group_get_waic(mhx_group* g, int fn, int take, double* elpd, double* lppd, double* p_waic,
+                       int32_t* n_high, double* pw_lppd, double* pw_p, double* pw_acc,
+                       int32_t* n_used, int32_t* status);
 
 /* Restore a saved walk (walker-load, sketched in the comments M:987-1001): prob[n], theta[n][d]
  * NEWEST FIRST, as walker-save would have written them.  Sets the ring (newest

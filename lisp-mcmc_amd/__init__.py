@@ -28,6 +28,7 @@ from .walker import (  # noqa: F401
     make_histo, make_histo_x, histo_edges, walker_param_histo, walker_set_param_histo,
     walker_set_corner_grid,
     autocorr, walker_autocorr, walker_set_autocorr, walker_set_rhat, walker_set_ensemble_get,
+    walker_set_waic, walker_waic, waic_compare, waic_merge,
 )
 
 __all__ = ["capi", "MhxError", "Engine", "Group", "comm_unique_id", "partition", "models", "Walker", "WalkerStep", "walker_create",
@@ -41,4 +42,5 @@ __all__ = ["capi", "MhxError", "Engine", "Group", "comm_unique_id", "partition",
            "make_histo", "make_histo_x", "histo_edges", "walker_param_histo", "walker_set_param_histo",
            "walker_set_corner_grid",
            "autocorr", "walker_autocorr", "walker_set_autocorr", "walker_set_rhat", "split_rhat",
-           "walker_set_ensemble_get", "ensemble_pick"]
+           "walker_set_ensemble_get", "ensemble_pick",
+           "walker_set_waic", "walker_waic", "waic_compare", "waic_merge"]

@@ -26,6 +26,7 @@ SIGMA_NONE, SIGMA_SHARED, SIGMA_PER_CHAIN, SIGMA_PER_POINT = 0, 1, 2, 3
 CHAIN_RUNNING, CHAIN_DONE, CHAIN_FP_TRAP, CHAIN_STOPPED = 0, 1, 2, 3
 L_OK, L_CAUGHT, L_INVALID, L_EMPTY = 0, 1, 2, 3
 AUTOCORR_NONFINITE, AUTOCORR_CONSTANT, AUTOCORR_OPEN, MAX_AUTOCORR_LAG = 1, 2, 4, 1023
+WAIC_NONFINITE, WAIC_ONE_STEP, WAIC_BLOCK = 1, 2, 256
 
 
 class Config(C.Structure):
@@ -162,6 +163,10 @@ SIGNATURES = {
     "mhx_group_get_ensemble_percentiles": (C.c_int, [C.c_void_p, C.c_int, i32p, C.c_int, u8p, i32p, i32p,
                                                      C.c_int, f64p, i64p, i32p, i32p]),
     "mhx_ensemble_pick": (C.c_int, [u64p, C.c_int, C.c_int64, i32p, i64p, i64p]),
+    "mhx_get_waic": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f64p, f64p, f64p, i32p, f64p, f64p, f64p,
+                               i32p, i32p]),
+    "mhx_group_get_waic": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f64p, f64p, f64p, i32p, f64p, f64p,
+                                     f64p, i32p, i32p]),
 }
 
 _lib = None

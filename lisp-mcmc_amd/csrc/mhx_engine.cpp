@@ -78,6 +78,9 @@ struct Dataset {
   DevBuf<double> x, y, w, c, txlo, txhi, tgh;
   std::vector<double> hx;  // host copy of the padded x: tile ranges are formed per kernel family
   size_t n = 0;            // data points (hx holds the pads too)
+  // mhx_get_waic's per-point constants where the device's c array does not hold them (Poisson:
+  // -log-factorial(y_i); a normal likelihood with a second column of x, which takes c's place)
+  std::vector<double> hconst;
   bool no_rec = false;     // MHX_NO_RECURRENCE=1 when the dataset was set
   bool set = false;
   // a dataset per walker (mhx_set_dataset_planes): x (and a shared 1/sigma) above, the walkers'
@@ -1409,7 +1412,8 @@ int mhx_create(const mhx_config* cfg, mhx_engine** out) {
       break;
     }
     if (family_w8().configure() != hipSuccess || family_w16().configure() != hipSuccess ||
-        summary_configure() != hipSuccess || fit_configure() != hipSuccess) {
+        summary_configure() != hipSuccess || fit_configure() != hipSuccess ||
+        waic_configure() != hipSuccess) {
       rc = fail(MHX_EDEVICE, "hipFuncSetAttribute(max dynamic LDS = %zu / %zu) failed",
                 family_w8().lds_bytes, family_w16().lds_bytes);
       break;
@@ -1491,6 +1495,7 @@ static int set_dataset_impl(mhx_engine* e, int k, const double* x, const double*
   long double csum = 0.0L;
   const double half_log_2pi = -0.5 * std::log(2.0 * M_PI);  // (* -1/2 (log (* 2 pi))) M:377
   std::vector<float> lf_cache;
+  std::vector<double> hconst(likelihood == MHX_LIK_POISSON || (x1 && likelihood == MHX_LIK_NORMAL) ? n : 0);
   for (size_t i = 0; i < n; ++i) {
     hx[i] = x[i];
     hy[i] = y[i];
@@ -1499,8 +1504,8 @@ static int set_dataset_impl(mhx_engine* e, int k, const double* x, const double*
         return fail(MHX_EINVAL, "poisson count y[%zu] = %g is not a non-negative integer", i, y[i]);
       hw[i] = 0.0;
       hc[i] = 0.0;
-      csum -= (long double)log_factorial_ref((long)y[i], e->cfg.poisson_logfact_double != 0,
-                                             lf_cache);
+      hconst[i] = -log_factorial_ref((long)y[i], e->cfg.poisson_logfact_double != 0, lf_cache);
+      csum += (long double)hconst[i];
     } else if (likelihood == MHX_LIK_EXPR) {
       hw[i] = sigma ? sigma[i] : 1.0;  // handed to the expression as `error`, untouched
       hc[i] = 0.0;
@@ -1520,6 +1525,7 @@ static int set_dataset_impl(mhx_engine* e, int k, const double* x, const double*
     hw[i] = 0.0;
     hc[i] = 0.0;
   }
+  if (x1 && likelihood == MHX_LIK_NORMAL) std::copy(hc.begin(), hc.begin() + n, hconst.begin());
   if (x1)  // (the c array is read by the cutoff likelihood only, which was refused above)
     for (size_t i = 0; i < np; ++i) hc[i] = n ? x1[i < n ? i : n - 1] : 0.0;
   Dataset& D = e->data[k];
@@ -1539,6 +1545,7 @@ static int set_dataset_impl(mhx_engine* e, int k, const double* x, const double*
   f.n = (int64_t)n;
   f.n_tiles = 0;
   D.hx.swap(hx);
+  D.hconst.swap(hconst);
   f.lik = likelihood;
   f.lik_const = (double)csum;
   f.xmin = f.xmax = n ? x[0] : 0.0;
@@ -2631,6 +2638,121 @@ int mhx_eval_function(mhx_engine* e, int fn, const double* theta, int64_t n, con
 int mhx_get_fit_bands(mhx_engine* e, int fn, int take, const double* xcols, int n_cols, int64_t m,
                       double* ymax, double* ymin, int32_t* n_selected, int32_t* status) {
   return run_portions(e, FitCall(fn, take, -1, nullptr, xcols, n_cols, m, ymax, ymin, n_selected, status));
+}
+
+// ---- WAIC (include/mhx.h has the definition): every chain's pointwise log-sum-exp and Welford
+// moments of the log-likelihood terms of function fn over its window (k_waic), and their totals
+// (k_waic_totals).  An item is a chain; the function's points go in chunks of kFitChunkPoints, a
+// whole number of MHX_WAIC_BLOCK blocks, so a block is the same points whatever the split.  The
+// blocks' partial sums of all chunks stay in the stage; the totals are taken on the last chunk.
+struct WaicCall {
+  int fn = 0, take = 0, want = 0;
+  int64_t m = 0, nb_total = 0;
+  enum { ELPD, LPPD, P_WAIC, N_HIGH, N_USED, STATUS, PW_LPPD, PW_P, PW_ACC, N_DST };
+  HostDst dst[N_DST];
+  static_assert(kFitChunkPoints % MHX_WAIC_BLOCK == 0, "a chunk of points is whole blocks");
+
+  WaicCall(int fn_, int take_, double* elpd, double* lppd, double* p_waic, int32_t* n_high,
+           double* pw_lppd, double* pw_p, double* pw_acc, int32_t* n_used, int32_t* status)
+      : fn(fn_), take(take_) {
+    dst[ELPD] = {elpd, sizeof(double)}, dst[LPPD] = {lppd, sizeof(double)};
+    dst[P_WAIC] = {p_waic, sizeof(double)}, dst[N_HIGH] = {n_high, sizeof(int32_t)};
+    dst[N_USED] = {n_used, sizeof(int32_t)}, dst[STATUS] = {status, sizeof(int32_t)};
+    dst[PW_LPPD].p = pw_lppd, dst[PW_P].p = pw_p, dst[PW_ACC].p = pw_acc;
+    want = (pw_lppd ? WAIC_WANT_LPPD : 0) | (pw_p ? WAIC_WANT_P : 0) | (pw_acc ? WAIC_WANT_ACC : 0);
+  }
+  int check(mhx_engine* e) {
+    int rc = window_check(e, take);
+    if (rc != MHX_OK || (rc = use_device(e)) != MHX_OK || (rc = finalize_problem(e)) != MHX_OK) return rc;
+    if (fn < 0 || fn >= e->P.K) return fail(MHX_EINVAL, "function %d out of range", fn);
+    for (int k = 0; k < e->P.K; ++k)
+      if (e->data[k].planes)
+        return fail(MHX_EUNSUPPORTED, "mhx_get_waic on an engine with a dataset per walker "
+                                      "(mhx_set_dataset_planes): the planes' per-point constants "
+                                      "live per walker and are not on the device");
+    m = e->P.fn[fn].n;
+    if (m < 1) return fail(MHX_EINVAL, "function %d has no data points", fn);
+    nb_total = waic_blocks(m);
+    dst[PW_LPPD].item_bytes = dst[PW_P].item_bytes = (size_t)m * sizeof(double);
+    dst[PW_ACC].item_bytes = (size_t)m * 4 * sizeof(double);
+    return MHX_OK;
+  }
+  int64_t items(const mhx_engine* e) const { return e->cfg.n_chains; }
+  int64_t points() const { return m; }
+  WaicPieces carve(const mhx_engine*, Carver& c, int64_t n_items, int64_t m_points) const {
+    return carve_waic(c, nb_total, want, n_items, m_points);
+  }
+  // the per-point constants of the chunk: on the device (the normal forms' c array), on the host
+  // (Dataset::hconst), or none (MHX_LIK_EXPR)
+  int upload(mhx_engine* e, const Portion& p) const {
+    Carver c;
+    const WaicPieces s = carve(e, c, p.n, p.m);
+    const Dataset& D = e->data[fn];
+    if (!D.hconst.empty())
+      HIP_TRY(hipMemcpyAsync(stage_at<double>(e, s.cst), D.hconst.data() + p.m0, (size_t)p.m * sizeof(double),
+                             hipMemcpyHostToDevice, e->stream));
+    if (p.m0 == 0)
+      HIP_TRY(hipMemsetAsync(stage_at<int32_t>(e, s.status), 0, (size_t)p.n * sizeof(int32_t), e->stream));
+    return MHX_OK;
+  }
+  int launch(mhx_engine* e, const Portion& p) const {
+    Carver c;
+    const WaicPieces s = carve(e, c, p.n, p.m);
+    const FnDesc& f = e->P.fn[fn];
+    const bool on_host = !e->data[fn].hconst.empty();
+    WaicArgs A{};
+    A.c0 = p.i0, A.n = p.n;
+    A.take = take, A.fn = fn;
+    A.n_blocks = (int32_t)waic_blocks(p.m);
+    A.blk0 = p.m0 / MHX_WAIC_BLOCK, A.nb_total = nb_total, A.m = p.m;
+    A.x0 = f.x + p.m0;
+    A.x1 = f.n_xcols > 1 ? f.c + p.m0 : nullptr;
+    A.y = f.y + p.m0;
+    A.w = f.w + p.m0;
+    A.c = on_host ? stage_at<double>(e, s.cst) : f.lik == MHX_LIK_EXPR ? nullptr : f.c + p.m0;
+    A.pw_lppd = (want & WAIC_WANT_LPPD) ? stage_at<double>(e, s.pw_lppd) : nullptr;
+    A.pw_p = (want & WAIC_WANT_P) ? stage_at<double>(e, s.pw_p) : nullptr;
+    A.pw_acc = (want & WAIC_WANT_ACC) ? stage_at<double>(e, s.pw_acc) : nullptr;
+    A.part_lppd = stage_at<double>(e, s.part_lppd);
+    A.part_p = stage_at<double>(e, s.part_p);
+    A.part_high = stage_at<int32_t>(e, s.part_high);
+    A.status = stage_at<int32_t>(e, s.status);
+    HIP_TRY(e->spec == SPEC_USER ? rtc_launch_waic(*e->user_prog, e->stream, e->dP.p, e->S, A)
+                                 : launch_waic(e->spec, e->stream, e->dP.p, e->S, A));
+    if (p.m0 + p.m >= m)
+      HIP_TRY(launch_waic_totals(e->stream, e->S, p.i0, p.n, take, nb_total, A.part_lppd, A.part_p, A.part_high,
+                                 stage_at<double>(e, s.elpd), stage_at<double>(e, s.lppd),
+                                 stage_at<double>(e, s.p_waic), stage_at<int32_t>(e, s.n_high),
+                                 stage_at<int32_t>(e, s.n_used), A.status));
+    e->launches++;
+    return MHX_OK;
+  }
+  int collect(mhx_engine* e, const Portion& p) const {
+    Carver c;
+    const WaicPieces s = carve(e, c, p.n, p.m);
+    const size_t pw[3] = {s.pw_lppd, s.pw_p, s.pw_acc};
+    for (int k = 0; k < 3; ++k) {
+      const HostDst& h = dst[PW_LPPD + k];
+      const size_t per = (k == 2 ? 4 : 1) * sizeof(double);  // bytes of a point
+      if (h.p)
+        HIP_TRY(hipMemcpy2D(static_cast<unsigned char*>(h.at(p.i0)) + (size_t)p.m0 * per, (size_t)m * per,
+                            e->stage.p + pw[k], (size_t)p.m * per, (size_t)p.m * per, (size_t)p.n,
+                            hipMemcpyDeviceToHost));
+    }
+    if (p.m0 + p.m < m) return MHX_OK;  // (the totals come with the last chunk of points)
+    const size_t off[6] = {s.elpd, s.lppd, s.p_waic, s.n_high, s.n_used, s.status};
+    for (int k = 0; k < 6; ++k) {
+      const int rc = copy_back(dst[k], p.i0, p.n, e->stage.p + off[k]);
+      if (rc != MHX_OK) return rc;
+    }
+    return MHX_OK;
+  }
+};
+
+int mhx_get_waic(mhx_engine* e, int fn, int take, double* elpd, double* lppd, double* p_waic,
+                 int32_t* n_high, double* pw_lppd, double* pw_p, double* pw_acc, int32_t* n_used,
+                 int32_t* status) {
+  return run_portions(e, WaicCall(fn, take, elpd, lppd, p_waic, n_high, pw_lppd, pw_p, pw_acc, n_used, status));
 }
 
 // ---- walker-with-exp (M:1052-1064) and the posterior of the expression: derived quantities of
@@ -3867,6 +3989,12 @@ int mhx_group_get_fit_bands(mhx_group* g, int fn, int take, const double* xcols,
   if (!g) return fail(MHX_EINVAL, "group is NULL");
   if (m < 1) return fail(MHX_EINVAL, "m must be >= 1");
   return run_portions(g, FitCall(fn, take, -1, nullptr, xcols, n_cols, m, ymax, ymin, n_selected, status));
+}
+
+int mhx_group_get_waic(mhx_group* g, int fn, int take, double* elpd, double* lppd, double* p_waic,
+                       int32_t* n_high, double* pw_lppd, double* pw_p, double* pw_acc,
+                       int32_t* n_used, int32_t* status) {
+  return run_portions(g, WaicCall(fn, take, elpd, lppd, p_waic, n_high, pw_lppd, pw_p, pw_acc, n_used, status));
 }
 
 int mhx_group_get_derived(mhx_group* g, const char* const* exprs, int n_expr,

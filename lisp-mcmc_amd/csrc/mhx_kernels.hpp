@@ -1049,6 +1049,10 @@ struct FixedSpec {
                                                 double (&v)[PTS]) {
     model_values<Model, PTS>(f, pf, scratch, x0, x1, v);
   }
+  // MHX_LIK_EXPR's per-point term (k_waic_body): only run-time compiled programs have one
+  static __device__ __forceinline__ double lik_term(const FnDesc&, double, double, double) {
+    return __builtin_nan("");
+  }
 };
 
 // Anything else: wave-uniform dispatch on (model, shape, likelihood)
@@ -1139,6 +1143,9 @@ struct GenericSpec {
       default:
         return model_values<PVoigt2Model, PTS>(f, pf, scratch, x0, x1, v);
     }
+  }
+  static __device__ __forceinline__ double lik_term(const FnDesc&, double, double, double) {
+    return __builtin_nan("");
   }
 };
 
@@ -1598,6 +1605,23 @@ struct Ring {
   }
   __device__ __forceinline__ int slot(int s) const { return (int)((nh - 1 - s) & mask); }
 };
+// (here, not with the read-outs below: k_waic_body is compiled at run time too)
+__device__ __forceinline__ Ring ring_of(const ChainState& S, int64_t c) {
+  Ring r;
+  r.prob = S.hist_prob + c * S.R;
+  r.theta = S.hist_theta + c * S.R * S.d;
+  r.mask = S.R - 1;
+  r.d = S.d;
+  r.nh = uniform_i64(S.n_hist[c]);
+  r.length = uniform_i64(S.length[c]);
+  return r;
+}
+// steps a window of `take` (<= R) holds: what mhx_get_trace would deliver
+__device__ __forceinline__ int ring_held(const Ring& r, int take) {
+  int64_t t = r.length < r.nh ? r.length : r.nh;
+  if (t > (int64_t)take) t = take;
+  return (int)(t < 0 ? 0 : t);
+}
 
 __device__ __forceinline__ unsigned long long bits_of(double v) {
   return (unsigned long long)__double_as_longlong(v);
@@ -3028,22 +3052,6 @@ __global__ __launch_bounds__(kThreads) void k_acceptance(ChainState S, int take,
 // indexed by the chain's place in the portion.
 // ------------------------------------------------------------------------------------------
 #if defined(MHX_FAMILY_PRIMARY) && !defined(__HIPCC_RTC__)
-__device__ __forceinline__ Ring ring_of(const ChainState& S, int64_t c) {
-  Ring r;
-  r.prob = S.hist_prob + c * S.R;
-  r.theta = S.hist_theta + c * S.R * S.d;
-  r.mask = S.R - 1;
-  r.d = S.d;
-  r.nh = uniform_i64(S.n_hist[c]);
-  r.length = uniform_i64(S.length[c]);
-  return r;
-}
-// steps a window of `take` (<= R) holds: what mhx_get_trace would deliver
-__device__ __forceinline__ int ring_held(const Ring& r, int take) {
-  int64_t t = r.length < r.nh ? r.length : r.nh;
-  if (t > (int64_t)take) t = take;
-  return (int)(t < 0 ? 0 : t);
-}
 
 // order-preserving 64-bit key of a double: all bits of a negative flipped, the sign bit of the
 // others set.  -0 < +0 as keys (they compare equal as numbers: either may stand for the other);
@@ -3979,6 +3987,175 @@ __device__ __forceinline__ void k_fit_body(const ProblemDesc* __restrict__ Pp, F
 template <class Spec>
 __global__ __launch_bounds__(kThreads) void k_fit(const ProblemDesc* __restrict__ Pp, FitArgs A) {
   k_fit_body<Spec>(Pp, A);
+}
+#endif
+
+// mhx_get_waic (include/mhx.h has the definition, operation by operation): k_fit's shape with the
+// likelihood behind it.  Wave g serves chain g / n_blocks of the launch and block g % n_blocks of
+// its points: kWaicPts points per lane, whose x, ys, w, c and the four accumulators {M, S, mean,
+// M2} stay in registers.  The window's steps are addressed by ring slot, newest first - no
+// selection pass; each step's parameter vector goes through the wave's LDS row with the next
+// step's load in flight, then ONE Spec::values (the bits of mhx_eval_function), the term of the
+// function's likelihood (wave-uniform) and the two accumulations.  Every product and sum below
+// is rounded on its own (the unit is compiled without contraction; no fma is written here).  The
+// block's sums of pw_lppd and pw_p and its count of pw_p > 0.4 go to part_*[chain][block]:
+// k_waic_totals adds them in block order.
+template <class Spec>
+__device__ __forceinline__ void k_waic_body(const ProblemDesc* __restrict__ Pp, ChainState S,
+                                            WaicArgs A) {
+  FitLds& lds = *reinterpret_cast<FitLds*>(mhx_lds_raw);
+  lds_tables_begin();
+  __syncthreads();  // (the only barrier: waves without work leave behind it)
+  const int w = wave_in_group(), l = lane_id();
+  const int64_t g = (int64_t)blockIdx.x * kWavesPerGroup + w;
+  if (g >= A.n * A.n_blocks) return;
+  const int64_t i = g / A.n_blocks;
+  const int64_t blk = g - i * A.n_blocks;
+  const int64_t p0 = blk * (int64_t)(kWave * kWaicPts) + l;
+  const FnDesc& f = Pp->fn[A.fn];
+  const int d = Pp->d;
+  const int lik = __builtin_amdgcn_readfirstlane(f.lik);
+  double x0[kWaicPts], x1[kWaicPts], ys[kWaicPts], wi[kWaicPts], ci[kWaicPts];
+  double aM[kWaicPts], aS[kWaicPts], mean[kWaicPts], m2[kWaicPts];
+#pragma unroll
+  for (int j = 0; j < kWaicPts; ++j) {
+    const int64_t p = p0 + (int64_t)j * kWave;
+    const int64_t q = p < A.m ? p : A.m - 1;  // (beyond m: the last point once more, never stored)
+    x0[j] = A.x0[q];
+    x1[j] = A.x1 ? A.x1[q] : 0.0;
+    ys[j] = A.y[q];
+    wi[j] = A.w[q];
+    ci[j] = A.c ? A.c[q] : 0.0;
+    aM[j] = aS[j] = mean[j] = m2[j] = 0.0;
+  }
+  const Ring r = ring_of(S, A.c0 + i);
+  const int n = ring_held(r, A.take);
+  double* th = lds.th[w];
+  double thn = 0.0;
+  if (n > 0 && l < d) thn = r.theta[(int64_t)r.slot(0) * d + l];
+  bool bad = false;
+  for (int s = 0; s < n; ++s) {
+    if (l < d) th[l] = thn;
+    __builtin_amdgcn_wave_barrier();
+    if (s + 1 < n && l < d) thn = r.theta[(int64_t)r.slot(s + 1) * d + l];
+    auto pf = [&](int j) -> double { return th[f.idx[j]]; };
+    double v[kWaicPts], t[kWaicPts];
+    Spec::template values<kWaicPts>(f, pf, lds.scr[w], x0, x1, v);
+    if (lik == MHX_LIK_POISSON) {
+#pragma unroll
+      for (int j = 0; j < kWaicPts; ++j) {
+        const double a = ys[j] * tlog_rate(v[j]);
+        const double b = a - v[j];
+        t[j] = b + ci[j];
+      }
+    } else if (lik == MHX_LIK_EXPR) {
+#pragma unroll
+      for (int j = 0; j < kWaicPts; ++j) t[j] = Spec::lik_term(f, ys[j], v[j], wi[j]);
+    } else {
+      const bool cut = lik == MHX_LIK_NORMAL_CUTOFF;
+#pragma unroll
+      for (int j = 0; j < kWaicPts; ++j) {
+        const double a = v[j] * wi[j];
+        const double rr = ys[j] - a;
+        const double h = 0.5 * rr;
+        const double q = h * rr;
+        const double e = ci[j] - q;
+        t[j] = cut ? (e > -5000.0 ? e : -5000.0) : e;
+      }
+    }
+    const double qk = 1.0 / (double)(s + 1);
+#pragma unroll
+    for (int j = 0; j < kWaicPts; ++j) {
+      const double e = t[j];
+      bad = bad || !finite_f64(v[j]) || !finite_f64(e);
+      const double dl = e - mean[j];
+      mean[j] = mean[j] + dl * qk;
+      m2[j] = m2[j] + dl * (e - mean[j]);
+      const bool up = e > aM[j];
+      const double ge = gexp(up ? aM[j] - e : e - aM[j]);
+      const double sn = up ? aS[j] * ge + 1.0 : aS[j] + ge;
+      aS[j] = s == 0 ? 1.0 : sn;
+      aM[j] = (s == 0 || up) ? e : aM[j];
+    }
+  }
+  const double nm1 = (double)(n - 1), nd = (double)n;
+  double sl = 0.0, sp = 0.0;
+  int nh = 0;
+#pragma unroll
+  for (int j = 0; j < kWaicPts; ++j) {
+    const int64_t p = p0 + (int64_t)j * kWave;
+    const double pp = m2[j] / nm1;
+    const double lp = aM[j] + tlog(aS[j] / nd);
+    const bool in = p < A.m;
+    sl = sl + (in ? lp : 0.0);
+    sp = sp + (in ? pp : 0.0);
+    nh += (in && pp > 0.4) ? 1 : 0;
+    if (in) {
+      const int64_t o = i * A.m + p;
+      if (A.pw_lppd) A.pw_lppd[o] = lp;
+      if (A.pw_p) A.pw_p[o] = pp;
+      if (A.pw_acc) {
+        A.pw_acc[o * 4 + 0] = aM[j];
+        A.pw_acc[o * 4 + 1] = aS[j];
+        A.pw_acc[o * 4 + 2] = mean[j];
+        A.pw_acc[o * 4 + 3] = m2[j];
+      }
+    }
+  }
+  sl = wave_sum(sl);
+  sp = wave_sum(sp);
+  nh = wave_sum_i(nh);
+  const bool any_bad = __ballot(bad) != 0ULL;
+  if (l == 0) {
+    const int64_t o = i * A.nb_total + A.blk0 + blk;
+    A.part_lppd[o] = sl;
+    A.part_p[o] = sp;
+    A.part_high[o] = nh;
+    if (any_bad) A.status[i] = MHX_WAIC_NONFINITE;
+  }
+}
+#ifndef __HIPCC_RTC__
+template <class Spec>
+__global__ __launch_bounds__(kThreads) void k_waic(const ProblemDesc* __restrict__ Pp, ChainState S,
+                                                   WaicArgs A) {
+  k_waic_body<Spec>(Pp, S, A);
+}
+#endif
+#if defined(MHX_FAMILY_PRIMARY) && !defined(__HIPCC_RTC__)
+// mhx_get_waic, the totals: one thread per chain adds the blocks' partial sums in block order
+// (whatever launches wrote them), takes the one subtraction and completes n_used and the status
+// (a one-step window; an empty one, whose 0/0 quotient is flagged as not finite).
+__global__ __launch_bounds__(kThreads) void k_waic_totals(ChainState S, int64_t c0, int64_t n, int take,
+                                                          int64_t nb_total,
+                                                          const double* __restrict__ part_lppd,
+                                                          const double* __restrict__ part_p,
+                                                          const int32_t* __restrict__ part_high,
+                                                          double* __restrict__ elpd,
+                                                          double* __restrict__ lppd,
+                                                          double* __restrict__ p_waic,
+                                                          int32_t* __restrict__ n_high,
+                                                          int32_t* __restrict__ n_used,
+                                                          int32_t* __restrict__ status) {
+  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  const int64_t c = c0 + i;
+  int64_t t = S.length[c] < S.n_hist[c] ? S.length[c] : S.n_hist[c];
+  if (t > (int64_t)take) t = take;
+  if (t < 0) t = 0;
+  double sl = 0.0, sp = 0.0;
+  int nh = 0;
+  for (int64_t b = 0; b < nb_total; ++b) {
+    sl = sl + part_lppd[i * nb_total + b];
+    sp = sp + part_p[i * nb_total + b];
+    nh += part_high[i * nb_total + b];
+  }
+  lppd[i] = sl;
+  p_waic[i] = sp;
+  elpd[i] = sl - sp;
+  n_high[i] = nh;
+  n_used[i] = (int32_t)t;
+  if (t == 1) status[i] = status[i] | MHX_WAIC_ONE_STEP;
+  if (t == 0) status[i] = status[i] | MHX_WAIC_NONFINITE;  // (an empty walk: nothing to average)
 }
 #endif
 

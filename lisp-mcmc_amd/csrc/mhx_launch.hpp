@@ -164,4 +164,16 @@ hipError_t launch_band_select(hipStream_t st, const ChainState& S, int64_t c0, i
                               int32_t* sel, int32_t* n_sel);
 hipError_t launch_fit(int spec, hipStream_t st, const ProblemDesc* P, const FitArgs& A);
 
+// mhx_get_waic: the pointwise accumulation and the blocks' partial sums (WaicArgs, mhx_types.hpp)
+// for the ahead-of-time specs - run-time compiled problems go through rtc_launch_waic - and the
+// totals of n chains from the partials of all nb_total blocks.
+inline int64_t waic_blocks(int64_t m) { return (m + MHX_WAIC_BLOCK - 1) / MHX_WAIC_BLOCK; }
+hipError_t waic_configure();
+hipError_t launch_waic(int spec, hipStream_t st, const ProblemDesc* P, const ChainState& S,
+                       const WaicArgs& A);
+hipError_t launch_waic_totals(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
+                              int64_t nb_total, const double* part_lppd, const double* part_p,
+                              const int32_t* part_high, double* elpd, double* lppd, double* p_waic,
+                              int32_t* n_high, int32_t* n_used, int32_t* status);
+
 }  // namespace mhx

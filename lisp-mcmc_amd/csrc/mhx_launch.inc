@@ -397,6 +397,35 @@ hipError_t launch_fit(int spec, hipStream_t st, const ProblemDesc* P, const FitA
   return hipGetLastError();
 }
 
+// mhx_get_waic (k_waic, k_waic_totals): as k_fit, compiled in this family only
+hipError_t waic_configure() {
+  hipError_t e = hipSuccess;
+  for (int s = 0; s < SPEC__COUNT; ++s)
+    for_spec(s, [&](auto sp) {
+      using SpecT = decltype(sp);
+      if (e == hipSuccess) e = no_static_lds(&k_waic<SpecT>);
+    });
+  return e;
+}
+hipError_t launch_waic(int spec, hipStream_t st, const ProblemDesc* P, const ChainState& S,
+                       const WaicArgs& A) {
+  if (A.n <= 0 || A.m <= 0) return hipSuccess;
+  for_spec(spec, [&](auto sp) {
+    using SpecT = decltype(sp);
+    k_waic<SpecT><<<grid_for(A.n * A.n_blocks), dim3(kThreads), fit_lds_bytes(kWavesPerGroup), st>>>(P, S, A);
+  });
+  return hipGetLastError();
+}
+hipError_t launch_waic_totals(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
+                              int64_t nb_total, const double* part_lppd, const double* part_p,
+                              const int32_t* part_high, double* elpd, double* lppd, double* p_waic,
+                              int32_t* n_high, int32_t* n_used, int32_t* status) {
+  if (n <= 0) return hipSuccess;
+  k_waic_totals<<<dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, st>>>(
+      S, c0, n, take, nb_total, part_lppd, part_p, part_high, elpd, lppd, p_waic, n_high, n_used, status);
+  return hipGetLastError();
+}
+
 const char* spec_name(int spec) {
   static const char* names[] = {"generic",      "gauss22_normal", "gauss15_poisson",
                                            "pvoigt2_normal", "poly2_normal",   "poly8_normal",

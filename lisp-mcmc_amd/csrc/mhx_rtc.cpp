@@ -307,6 +307,14 @@ static std::string generate(const std::vector<UserExpr>& models,
             ? "      default: return GenericSpec::values<PTS>(f, pf, scratch, x0, x1, v);\n"
             : "      default: (void)scratch; return;  // every function has a slot\n")
     << "    }\n  }\n"
+       // the per-point term of an expression likelihood (k_waic_body)
+       "  static __device__ __forceinline__ double lik_term(const FnDesc& f, double y, double model,\n"
+       "                                                    double error) {\n"
+       "    switch (f.user_slot) {\n";
+  for (size_t m = 0; m < models.size(); ++m)
+    if (models[m].builtin.empty() && !models[m].dispatch && !models[m].lik_expr.empty())
+      s << "      case " << m << ": return UserModel" << m << "::lik_term(y, model, error);\n";
+  s << "      default: (void)y; (void)model; (void)error; return __builtin_nan(\"\");\n    }\n  }\n"
        "  static __device__ __forceinline__ double logprior(const FnDesc& f, const double* th,\n"
        "                                                    double bounds_total) {\n"
        "    switch (f.prior_slot) {\n";
@@ -331,6 +339,9 @@ static std::string generate(const std::vector<UserExpr>& models,
        "extern \"C\" __global__ __launch_bounds__(MHX_USER_THREADS) void mhx_user_fit(\n"
        "    const ProblemDesc* P, FitArgs A) {\n"
        "  k_fit_body<UserSpec>(P, A);\n}\n"
+       "extern \"C\" __global__ __launch_bounds__(MHX_USER_THREADS) void mhx_user_waic(\n"
+       "    const ProblemDesc* P, ChainState S, WaicArgs A) {\n"
+       "  k_waic_body<UserSpec>(P, S, A);\n}\n"
        "extern \"C\" __global__ __launch_bounds__(MHX_USER_THREADS) void mhx_user_init(const ProblemDesc* P,\n"
        "                                                              ChainState S) {\n"
        "  k_init_body<UserSpec>(P, S);\n}\n"
@@ -582,6 +593,12 @@ static int build_once(const std::vector<UserExpr>& models, const std::vector<Use
                             : std::string("module function mhx_user_fit has static LDS");
     return -1;
   }
+  he = hipModuleGetFunction(&prog->f_waic, prog->module, "mhx_user_waic");
+  if (he != hipSuccess || static_lds(prog->f_waic) != 0) {
+    *err = he != hipSuccess ? std::string("module function mhx_user_waic: ") + hipGetErrorString(he)
+                            : std::string("module function mhx_user_waic has static LDS");
+    return -1;
+  }
   prog->has_split = false;
   if (with_split) {
     he = hipModuleGetFunction(&prog->f_split_sweep, prog->module, "mhx_user_split_sweep");
@@ -695,6 +712,15 @@ hipError_t rtc_launch_fit(const UserProgram& p, hipStream_t st, const ProblemDes
   FitArgs a = A;
   void* args[] = {(void*)&P, (void*)&a};
   return hipModuleLaunchKernel(p.f_fit, grid_for(p, A.n * A.n_chunks), 1, 1, (unsigned)p.fam->threads,
+                               1, 1, fit_lds_bytes(p.fam->waves_per_group), st, args, nullptr);
+}
+hipError_t rtc_launch_waic(const UserProgram& p, hipStream_t st, const ProblemDesc* P,
+                           const ChainState& S, const WaicArgs& A) {
+  if (A.n <= 0 || A.m <= 0) return hipSuccess;
+  ChainState s = S;
+  WaicArgs a = A;
+  void* args[] = {(void*)&P, (void*)&s, (void*)&a};
+  return hipModuleLaunchKernel(p.f_waic, grid_for(p, A.n * A.n_blocks), 1, 1, (unsigned)p.fam->threads,
                                1, 1, fit_lds_bytes(p.fam->waves_per_group), st, args, nullptr);
 }
 hipError_t rtc_launch_init(const UserProgram& p, hipStream_t st, const ProblemDesc* P,

@@ -175,6 +175,34 @@ inline AutocorrPieces carve_autocorr(Carver& c, int nc_, int max_lag, int64_t n_
   s.status = c.take(n * nc * sizeof(int32_t));
   return s;
 }
+// WAIC of n chains at m points of a function of nb_total blocks: what depends on the chains alone
+// comes first and keeps its place from one chunk of points to the next - status, n_used, n_high
+// [n], the totals elpd, lppd, p_waic [n], the blocks' partial sums [n][nb_total] (two double
+// arrays, one int) - then the chunk's per-point constants [m] and the pointwise results the caller
+// asked for: pw_lppd, pw_p [n][m], pw_acc [n][m][4] (want bits 1, 2, 4; a piece not asked for is
+// empty and the kernel does not write it).
+enum { WAIC_WANT_LPPD = 1, WAIC_WANT_P = 2, WAIC_WANT_ACC = 4 };
+struct WaicPieces {
+  size_t status, n_used, n_high, elpd, lppd, p_waic, part_lppd, part_p, part_high, cst, pw_lppd, pw_p, pw_acc;
+};
+inline WaicPieces carve_waic(Carver& c, int64_t nb_total, int want, int64_t n_, int64_t m_) {
+  const size_t n = (size_t)n_, m = (size_t)m_, nb = (size_t)nb_total;
+  WaicPieces s;
+  s.status = c.take(n * sizeof(int32_t));
+  s.n_used = c.take(n * sizeof(int32_t));
+  s.n_high = c.take(n * sizeof(int32_t));
+  s.elpd = c.take(n * sizeof(double));
+  s.lppd = c.take(n * sizeof(double));
+  s.p_waic = c.take(n * sizeof(double));
+  s.part_lppd = c.take(n * nb * sizeof(double));
+  s.part_p = c.take(n * nb * sizeof(double));
+  s.part_high = c.take(n * nb * sizeof(int32_t));
+  s.cst = c.take(m * sizeof(double));
+  s.pw_lppd = c.take((want & WAIC_WANT_LPPD) ? n * m * sizeof(double) : 0);
+  s.pw_p = c.take((want & WAIC_WANT_P) ? n * m * sizeof(double) : 0);
+  s.pw_acc = c.take((want & WAIC_WANT_ACC) ? n * m * 4 * sizeof(double) : 0);
+  return s;
+}
 // Whether ONE item of a piece list fits the budget at all, by portion_of's own accounting
 // (portion_of answers 1 either way: a read-out that must not outgrow the budget asks first).
 template <class Carve>

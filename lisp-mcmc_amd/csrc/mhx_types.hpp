@@ -234,6 +234,44 @@ constexpr unsigned fit_lds_bytes(int wpg) {
   return 6144u + (unsigned)wpg * (MHX_MAX_PARAMS + 1 + MHX_MAX_FN_PARAMS + 4) * 8u;
 }
 
+// k_waic (mhx_get_waic): per data point of function `fn`, the log-sum-exp and the Welford moments
+// of the log-likelihood terms over the window of each of n chains from c0 on.  A wave serves one
+// chain and one block of MHX_WAIC_BLOCK = kWave x kWaicPts points; n_blocks blocks cover the m
+// points of this launch, which are blocks blk0 .. of the function's nb_total.  The dataset's
+// arrays come offset to the launch's first point: y and w as the sweep reads them (y/sigma and
+// 1/sigma for the normal forms), c the per-point constants (nullptr: none, MHX_LIK_EXPR).
+// kWaicPts = 4: a lane keeps nine doubles per point (x0, x1, ys, w, c, M, S, mean, M2) where
+// k_fit keeps four: 72 VGPRs before the model has one.  The kernel runs in workgroups of 8 waves
+// (two per SIMD), so what counts is how many WHOLE workgroups the registers leave a CU: two up to
+// 128 VGPRs (4 waves per SIMD), one above (2 waves per SIMD, whatever the compiler's "3" says).
+// As compiled for gfx950 with 4 points no instance uses scratch; config 2's two-peak kernel takes
+// 117 VGPRs and the polynomials 114: two workgroups a CU, as their k_fit.  The five-peak Poisson,
+// pvoigt2 and lorder instances take 136 to 143 and the generic kernel 185: one workgroup a CU
+// (pvoigt2's and the generic k_fit are there already; Poisson's and lorder's k_fit, at 126 and
+// 124, still fit two).  With 8 points the arrays alone are 144 VGPRs: EVERY instance, the flagship
+// included, would fall to one workgroup a CU, for the sake of halving a per-step prepare that
+// 256 points share already.  MHX_WAIC_BLOCK must divide kFitChunkPoints, so the choice is among
+// powers of two.
+constexpr int kWaicPts = MHX_WAIC_BLOCK / kWave;
+static_assert(kWaicPts * kWave == MHX_WAIC_BLOCK && kWaicPts == 4, "MHX_WAIC_BLOCK (include/mhx.h)");
+struct WaicArgs {
+  int64_t c0, n;
+  int32_t take, fn, n_blocks, pad_;
+  int64_t blk0, nb_total, m;
+  const double* x0;
+  const double* x1;  // the second column of x, or nullptr
+  const double* y;
+  const double* w;
+  const double* c;
+  double* pw_lppd;     // [n][m] or nullptr
+  double* pw_p;        // [n][m] or nullptr
+  double* pw_acc;      // [n][m][4] or nullptr
+  double* part_lppd;   // [n][nb_total] the blocks' sums of pw_lppd
+  double* part_p;      // [n][nb_total] ... of pw_p
+  int32_t* part_high;  // [n][nb_total] points of the block with pw_p > 0.4
+  int32_t* status;     // [n] MHX_WAIC_NONFINITE is stored where a value or a term is not finite
+};
+
 // mhx_user_derived (mhx_get_derived, mhx_derived.hpp): the expressions of one run-time compiled
 // module over the windows of the n chains from c0 on.  idx[j] = the place in theta of the j-th
 // name; values [n][n_expr][pitch] newest first, at_best [n][n_expr] (the most-likely step).

@@ -212,6 +212,32 @@ class _Summaries:
         out["n_pooled"] = pooled.value
         return out
 
+    def waic(self, fn, take, pointwise=False, accumulators=False):
+        """WAIC of every chain for function `fn` over the newest `take` steps (mhx_get_waic, which
+        has the definition): a dict of elpd, lppd, p_waic [n_chains] (waic = -2 elpd), n_high
+        [n_chains] (points whose variance term exceeds 0.4), n_used and status [n_chains]
+        (WAIC_NONFINITE 1, WAIC_ONE_STEP 2).  pointwise=True adds pw_lppd and pw_p [n_chains, N];
+        accumulators=True adds pw_acc [n_chains, N, 4], the (M, S, mean, M2) waic_merge pools."""
+        n = self.n_chains
+        pts = getattr(self, "_datasets", {}).get(int(fn), (0, 1))[0]
+        if (pointwise or accumulators) and pts < 1:
+            raise ValueError("waic: function %d has no dataset set through this object" % int(fn))
+        out = {"elpd": np.zeros(n), "lppd": np.zeros(n), "p_waic": np.zeros(n),
+               "n_high": np.zeros(n, dtype=np.int32), "n_used": np.zeros(n, dtype=np.int32),
+               "status": np.zeros(n, dtype=np.int32)}
+        if pointwise:
+            out["pw_lppd"] = np.zeros((n, pts))
+            out["pw_p"] = np.zeros((n, pts))
+        if accumulators:
+            out["pw_acc"] = np.zeros((n, pts, 4))
+        capi.check(self._summary("waic")(
+            self._h, int(fn), int(take),
+            *(out[k].ctypes.data_as(capi.f64p) for k in ("elpd", "lppd", "p_waic")),
+            out["n_high"].ctypes.data_as(capi.i32p),
+            *(out[k].ctypes.data_as(capi.f64p) if k in out else None for k in ("pw_lppd", "pw_p", "pw_acc")),
+            out["n_used"].ctypes.data_as(capi.i32p), out["status"].ctypes.data_as(capi.i32p)))
+        return out
+
 
 def ensemble_pick(counts, rank):
     """(digit, rank in its bin, the bin's count) of `rank` among the bins `counts`
@@ -691,7 +717,8 @@ class Group(_Summaries):
     def set_dataset(self, k, x, y, sigma=None, likelihood=capi.LIK_NORMAL):
         xa, xp = capi.as_f64(x)
         ya, yp = capi.as_f64(y)
-        self.__dict__.setdefault("_datasets", {})[int(k)] = (int(ya.size), 1)
+        for owner in [self] + self.engines:      # (what waic / eval_function / fit_bands size x=None by)
+            owner.__dict__.setdefault("_datasets", {})[int(k)] = (int(ya.size), 1)
         sp = None
         if sigma is not None:
             sa, sp = capi.as_f64(np.broadcast_to(np.asarray(sigma, dtype=np.float64), xa.shape))
@@ -701,7 +728,8 @@ class Group(_Summaries):
                            likelihood=capi.LIK_NORMAL):
         """mhx_group_set_dataset_planes: y (and a per-walker sigma) cover all chains of the group"""
         keep, (xp, yp, sp) = _planes_args(self.n_chains, x, y, sigma, sigma_kind)
-        self.__dict__.setdefault("_datasets", {})[int(k)] = (int(keep[0].size), 1)
+        for owner in [self] + self.engines:
+            owner.__dict__.setdefault("_datasets", {})[int(k)] = (int(keep[0].size), 1)
         capi.check(capi.lib().mhx_group_set_dataset_planes(self._h, k, xp, yp, sp, sigma_kind,
                                                            keep[0].size, likelihood))
 

@@ -260,6 +260,17 @@ library, or without a gfx950 device, walker-create signals MHX-ERROR."
 (cffi:defcfun ("mhx_ensemble_pick" %mhx-ensemble-pick) :int
   (counts :pointer) (n-bins :int) (rank :int64) (digit :pointer) (rank-in-bin :pointer)
   (bin-count :pointer))
+;; WAIC: the pointwise predictive accuracy of every chain (status: a sum of the two constants)
+(defconstant +waic-nonfinite+ 1)
+(defconstant +waic-one-step+ 2)
+(cffi:defcfun ("mhx_get_waic" %mhx-get-waic) :int
+  (e :pointer) (fn :int) (take :int) (elpd :pointer) (lppd :pointer) (p-waic :pointer)
+  (n-high :pointer) (pw-lppd :pointer) (pw-p :pointer) (pw-acc :pointer) (n-used :pointer)
+  (status :pointer))
+(cffi:defcfun ("mhx_group_get_waic" %mhx-group-get-waic) :int
+  (g :pointer) (fn :int) (take :int) (elpd :pointer) (lppd :pointer) (p-waic :pointer)
+  (n-high :pointer) (pw-lppd :pointer) (pw-p :pointer) (pw-acc :pointer) (n-used :pointer)
+  (status :pointer))
 
 (defmacro with-c-call (&body body)
   "HIP/RCCL runtime code may raise inexact/invalid flags that SBCL turns into conditions;

@@ -22,6 +22,7 @@
    #:make-histo #:make-histo-x #:walker-param-histo #:walker-set-param-histo
    #:walker-set-corner-grid
    #:walker-set-autocorr #:walker-set-rhat #:walker-set-ensemble-get
+   #:walker-set-waic #:walker-waic
    #:walker-save #:walker-load #:diagonal-covariance
    #:mfit-walker-estop #:request-stop
    ;; likelihood / prior designators

@@ -1024,6 +1024,57 @@ boolean per chain that leaves out the chains marked nil (those that never conver
                                (:95cr (list (point 0) (point 1)))
                                ((:iqr :stddev-normal) (- (point 1) (point 0))))))))))
 
+;;; ------------------------------------------------------------------ which model to have fitted
+;;; The reference compares models by eye (walker-plot-residuals).  WAIC (Watanabe; Gelman, Hwang and
+;;; Vehtari 2014) from the device ring, every chain in one call per function of a global fit
+;;; (mhx_get_waic, whose comment in include/mhx.h has the definition).
+(defun walker-set-waic (walker &key (take 1000))
+  "For every chain of the set the plist (:elpd :lppd :p-waic :waic :n-high :n-used :status) over its
+newest TAKE steps, summed over the functions of a global fit: lppd - p-waic, the log pointwise
+predictive density, the effective number of parameters, -2 elpd, the points whose variance term
+exceeds 0.4, the window, and 0 or +waic-one-step+.  FLOATING-POINT-INVALID-OPERATION where a model
+value or a likelihood term of a window is not finite: the reference would have trapped there."
+  (let* ((n (walker-n-chains walker))
+         (k-fns (length (walker-function walker)))
+         (window (%bin-window walker take "walker-set-waic"))
+         (none (cffi:null-pointer))
+         (lppd-sum (make-array n :element-type 'double-float :initial-element 0d0))
+         (p-sum (make-array n :element-type 'double-float :initial-element 0d0))
+         (high (make-array n :element-type 'fixnum :initial-element 0))
+         (used (make-array n :element-type 'fixnum :initial-element 0))
+         (flags (make-array n :element-type 'fixnum :initial-element 0)))
+    (cffi:with-foreign-objects ((lppd :double n) (p :double n) (nh :int32 n) (nu :int32 n)
+                                (st :int32 n))
+      (dotimes (fn k-fns)
+        (%set-call walker #'%mhx-get-waic #'%mhx-group-get-waic
+                   fn window none lppd p nh none none none nu st)
+        (dotimes (c n)
+          (incf (aref lppd-sum c) (cffi:mem-aref lppd :double c))
+          (incf (aref p-sum c) (cffi:mem-aref p :double c))
+          (incf (aref high c) (cffi:mem-aref nh :int32 c))
+          (setf (aref used c) (cffi:mem-aref nu :int32 c))
+          ;; (the two status bits, function after function: a bit set once stays set)
+          (let ((now (cffi:mem-aref st :int32 c))
+                (before (aref flags c)))
+            (setf (aref flags c)
+                  (+ (if (or (oddp now) (oddp before)) +waic-nonfinite+ 0)
+                     (if (or (>= now +waic-one-step+) (>= before +waic-one-step+))
+                         +waic-one-step+
+                         0)))))))
+    (loop for c below n
+          do (when (oddp (aref flags c))
+               (error 'floating-point-invalid-operation
+                      :operation 'walker-set-waic :operands (list :chain c)))
+          collect (let ((elpd (- (aref lppd-sum c) (aref p-sum c))))
+                    (list :elpd elpd :lppd (aref lppd-sum c) :p-waic (aref p-sum c)
+                          :waic (* -2d0 elpd) :n-high (aref high c) :n-used (aref used c)
+                          :status (aref flags c))))))
+
+(defun walker-waic (walker &key (chain 0) (take 1000))
+  "One chain's entry of walker-set-waic.  The device call is the whole set's: for more than a few
+chains call walker-set-waic once and take its elements."
+  (elt (walker-set-waic walker :take take) chain))
+
 ;;; ------------------------------------------------------------------ data and fit M:1208-1283
 ;;; The numbers behind the reference's plots.  The :function lives on the device, so the fit
 ;;; curve is mhx_eval_function and the envelope of the model over the most probable two thirds of

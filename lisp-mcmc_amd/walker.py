@@ -1161,6 +1161,102 @@ def walker_set_ensemble_get(walker, get=":median-params", take=1000, keys=None, 
     return out
 
 
+def _waic(walker, take, pointwise, chains, who):
+    e = walker.engine
+    window = _bin_window(walker, take, who)
+    parts = [e.waic(k, window, pointwise=pointwise) for k in range(e.K)]
+    status = np.bitwise_or.reduce([r["status"] for r in parts])
+    which = range(e.n_chains) if chains is None else [chains]
+    bad = [c for c in which if status[c] & capi.WAIC_NONFINITE]
+    if bad:
+        raise FloatingPointError(
+            "%s: a model value or a likelihood term is not finite at a step of walker(s) %s: the "
+            "reference would have signalled a floating-point trap here" % (who, bad[:8]))
+    out = []
+    for c in which:
+        lppd, p = _serial_sum([r["lppd"][c] for r in parts]), _serial_sum([r["p_waic"][c] for r in parts])
+        elpd = lppd - p if len(parts) > 1 else parts[0]["elpd"][c]
+        entry = {"elpd": float(elpd), "lppd": float(lppd), "p-waic": float(p), "waic": float(-2.0 * elpd),
+                 "n-high": int(sum(int(r["n_high"][c]) for r in parts)),
+                 "n-used": int(parts[0]["n_used"][c]), "status": int(status[c])}
+        if pointwise:
+            pw = np.concatenate([r["pw_lppd"][c] - r["pw_p"][c] for r in parts])
+            entry["pointwise"] = pw
+            with np.errstate(all="ignore"):
+                entry["se"] = float(np.sqrt(pw.size * np.var(pw, ddof=1))) if pw.size > 1 else float("nan")
+        out.append(entry)
+    return out
+
+
+def walker_set_waic(walker, take=1000, pointwise=False):
+    """Which model should have been fitted: WAIC (Watanabe; Gelman, Hwang and Vehtari 2014) of
+    every chain of the set over its newest `take` steps - one device call per function of a global
+    fit (mhx_get_waic, which has the definition), no history moved.  A list with, chain by chain,
+    {"elpd": the expected log pointwise predictive density lppd - p_waic, "lppd", "p-waic": the
+    effective number of parameters, "waic": -2 elpd, "n-high": the points whose variance term
+    exceeds 0.4 (the approximation is unreliable there), "n-used": the window, "status": 0 or
+    WAIC_ONE_STEP}, the totals summed over the functions.  pointwise=True adds "pointwise", the
+    elpd_i of all functions' points one after another, and "se" = sqrt(N var(elpd_i)) (the
+    variance with N - 1): what waic_compare takes.  Raises FloatingPointError where a model value
+    or a likelihood term of a window is not finite: the reference would have trapped there.  The
+    reference has no counterpart: it compares models by eye (walker-plot-residuals)."""
+    return _waic(walker, take, pointwise, None, "walker-set-waic")
+
+
+def walker_waic(walker, chain=0, take=1000, pointwise=False):
+    """One chain's entry of walker_set_waic (and only that chain's trap).  The device call is the
+    whole set's - there is no per-chain form of mhx_get_waic - and with pointwise=True the
+    pointwise arrays of every chain come back before one is picked: for more than a few chains
+    call walker_set_waic once and index its result."""
+    return _waic(walker, take, pointwise, int(chain), "walker-waic")[0]
+
+
+def waic_compare(a, b):
+    """Two models on the SAME data, from two pointwise results of walker_waic (host arithmetic):
+    {"elpd-diff": sum(a_i - b_i), positive where a predicts better, "se": sqrt(N var(a_i - b_i)),
+    the standard error of that difference (the variance with N - 1)}.  ValueError unless both
+    hold the same number of points."""
+    pa = np.asarray(a["pointwise"] if isinstance(a, dict) else a, dtype=np.float64).reshape(-1)
+    pb = np.asarray(b["pointwise"] if isinstance(b, dict) else b, dtype=np.float64).reshape(-1)
+    if pa.size != pb.size or pa.size < 1:
+        raise ValueError("waic_compare: the two results hold %d and %d points: WAIC compares models "
+                         "on the same data" % (pa.size, pb.size))
+    diff = pa - pb
+    with np.errstate(all="ignore"):
+        se = float(np.sqrt(diff.size * np.var(diff, ddof=1))) if diff.size > 1 else float("nan")
+    return {"elpd-diff": float(np.sum(diff)), "se": se}
+
+
+def waic_merge(acc, n_used):
+    """ONE WAIC from the chains of a set that share their data: pools the accumulators pw_acc
+    [n_chains, N, 4] = (M, S, mean, M2) of Engine.waic(..., accumulators=True) over the chains,
+    n_used [n_chains] their windows.  (mean, M2) merge by Chan's pairwise update, chain after
+    chain; (M, S) by shifting every chain's S to the greatest M.  Host arithmetic in numpy, NOT
+    bit-defined: it agrees with one accumulation over the concatenated windows to rounding.  A
+    dict of elpd, lppd, p_waic, n (the pooled steps), pw_lppd and pw_p [N]."""
+    acc = np.asarray(acc, dtype=np.float64)
+    n_used = np.asarray(n_used, dtype=np.int64).reshape(-1)
+    if acc.ndim != 3 or acc.shape[2] != 4 or acc.shape[0] != n_used.size or n_used.size < 1:
+        raise ValueError("acc must be [n_chains, N, 4] and n_used [n_chains]")
+    if (n_used < 1).any():
+        raise ValueError("every chain must bring at least one step")
+    M = acc[:, :, 0].max(axis=0)
+    with np.errstate(all="ignore"):
+        S = (acc[:, :, 1] * np.exp(acc[:, :, 0] - M[None, :])).sum(axis=0)
+        n, mean, m2 = float(n_used[0]), acc[0, :, 2].copy(), acc[0, :, 3].copy()
+        for c in range(1, n_used.size):
+            nb = float(n_used[c])
+            delta = acc[c, :, 2] - mean
+            tot = n + nb
+            mean = mean + delta * (nb / tot)
+            m2 = m2 + acc[c, :, 3] + delta * delta * (n * nb / tot)
+            n = tot
+        pw_p = m2 / (n - 1.0)
+        pw_lppd = M + np.log(S / n)
+    lppd, p = float(np.sum(pw_lppd)), float(np.sum(pw_p))
+    return {"elpd": lppd - p, "lppd": lppd, "p_waic": p, "n": int(n), "pw_lppd": pw_lppd, "pw_p": pw_p}
+
+
 def walker_modify(walker, modify=None, **kw):
     """(walker-modify ...) M:547-580: only :add-step is on the accelerated path and it is
     performed by the device inside walker-take-step; the list-surgery actions are host-side
