@@ -480,8 +480,8 @@ int mhx_get_window_best(mhx_engine* e, int take, double* prob, double* theta);
  * not below mhx_config.history_capacity and the adaptation window). */
 int mhx_get_history_capacity(mhx_engine* e, int32_t* capacity);
 /* HIP-event milliseconds the kernels of the engine's last mhx_get_percentiles / _covariances /
- * _proposal_factors / _window_best / _fit_bands / _derived / _histograms / _pair_grids / _waic or
- * mhx_eval_function call ran (all portions; copies excluded). */
+ * _proposal_factors / _window_best / _fit_bands / _derived / _histograms / _pair_grids / _waic /
+ * _traces or mhx_eval_function call ran (all portions; copies excluded). */
 int mhx_get_summary_timing(mhx_engine* e, double* kernel_ms);
 /* The same for a group, gathered in global chain order like mhx_group_get_state; every
  * device's launch is enqueued before any is waited for. */
@@ -818,6 +818,63 @@ int mhx_get_waic(mhx_engine* e, int fn, int take, double* elpd, double* lppd, do
 int mhx_group_get_waic(mhx_group* g, int fn, int take, double* elpd, double* lppd, double* p_waic,
                        int32_t* n_high, double* pw_lppd, double* pw_p, double* pw_acc,
                        int32_t* n_used, int32_t* status);
+
+/* ---- batched traces: the steps of EVERY chain, filtered and thinned on the device -------------
+ * What (mapcar (lambda (w) (walker-get w :get :steps / :unique-steps / :forward-steps / :params /
+ * :param / :log-liklihoods :take take)) walkers) reads (M:490-510, M:540) - the data behind
+ * walker-catepillar-plots (M:1294-1309), walker-liklihood-plot (M:1313-1320) and
+ * walker-plot-one-corner (M:1322-1331) - in one call: only the columns asked for, only every
+ * stride-th kept step, optionally with the extremes of what lies between.  No arithmetic is done:
+ * every number returned is a number of the ring, bit for bit.
+ *   window    chain c's window is exactly what mhx_get_trace(e, c, take, ...) delivers, newest
+ *             first: steps s = 0 .. t-1 with t = n_used[c] = min(take, walker-length, steps the
+ *             ring holds).  take in [1, history_capacity].
+ *   filter    gives the KEPT LIST, newest first; n_kept[c] is its length.
+ *               MHX_TRACE_STEPS    every step
+ *               MHX_TRACE_UNIQUE   (M:492-496) step s when s == t-1 or the bits of prob[s] differ
+ *                                  from the bits of prob[s+1]: the oldest step is always kept, a
+ *                                  NaN equals a NaN of the same bits, -0 differs from +0
+ *               MHX_TRACE_FORWARD  (M:497-502) step s when s < t-1 and !(prob[s] <= prob[s+1]):
+ *                                  the oldest step is never kept, a NaN on either side keeps s
+ *             (the predicates of mhx_get_covariances and mhx_get_proposal_factors)
+ *   thinning  `thin` (M:149-157) of the kept list: row r is kept item i = start + r stride;
+ *             rows = mhx_trace_rows(n_kept[c], stride, start) = 0 when n_kept <= start, else
+ *             ceil((n_kept - start) / stride); n_out[c] = min(rows, max_out).
+ *             values[c][r][j] = column cols[j] of that step's parameter vector, or the step's prob
+ *             where cols[j] == MHX_TRACE_PROB.  Rows n_out[c] .. max_out-1 of values, lo and hi
+ *             are all-bits-zero.
+ *   envelope  computed only when lo or hi is given.  Row r's bucket is the kept items i in
+ *             [start + r stride, min(start + (r+1) stride, n_kept)), visited in that order.  lo
+ *             and hi both start as the bucket's first value (= values[c][r][j]); for each later
+ *             value v: if (v < lo) lo = v; if (v > hi) hi = v;  So a NaN that is not first is
+ *             ignored, a first NaN stays, and of -0.0 / +0.0 the earlier one stays.  With stride 1
+ *             lo == hi == values.
+ * values, lo, hi [n_chains][max_out][n_cols]; n_out, n_kept, n_used [n_chains]; any output may be
+ * NULL.  MHX_EINVAL unless filter is one of the three, 1 <= stride <= history_capacity,
+ * 0 <= start < stride, 1 <= n_cols, cols is non-NULL and every cols[j] lies in [-1, d) (a column
+ * may be named more than once), 1 <= max_out <= history_capacity; also when the pieces of ONE
+ * chain (up to three arrays of max_out n_cols doubles) exceed the 64 MiB of a portion.  MHX_ESTATE
+ * before mhx_init_chains; a chain in MHX_CHAIN_FP_TRAP is read from the history it has.  Worked
+ * through in portions whose device scratch stays below 64 MiB; mhx_get_summary_timing covers the
+ * call. */
+enum {
+  MHX_TRACE_STEPS = 0,
+  MHX_TRACE_UNIQUE = 1,
+  MHX_TRACE_FORWARD = 2
+};
+#define MHX_TRACE_PROB (-1) /* a "column" that is the step's prob */
+int mhx_get_traces(mhx_engine* e, int take, int filter, int stride, int start,
+                   const int32_t* cols, int n_cols, int max_out, double* values, double* lo,
+                   double* hi, int32_t* n_out, int32_t* n_kept, int32_t* n_used);
+/* The same for a group, in global chain order; every device's work is enqueued before any is
+ * waited for. */
+int mhx_group_get_traces(mhx_group* g, int take, int filter, int stride, int start,
+                         const int32_t* cols, int n_cols, int max_out, double* values, double* lo,
+                         double* hi, int32_t* n_out, int32_t* n_kept, int32_t* n_used);
+/* *rows = the rows `thin` (M:149-157) leaves of a list of n_kept items: those at start,
+ * start + stride, ...  Host only: needs no engine and no device.  MHX_EINVAL unless n_kept >= 0,
+ * stride >= 1, 0 <= start < stride. */
+int mhx_trace_rows(int64_t n_kept, int32_t stride, int32_t start, int64_t* rows);
 
 /* Restore a saved walk (walker-load, sketched in the comments M:987-1001): prob[n], theta[n][d]
  * NEWEST FIRST, as walker-save would have written them.  Sets the ring (newest

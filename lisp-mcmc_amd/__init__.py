@@ -11,7 +11,7 @@ importlib.import_module("lisp-mcmc_amd").
 """
 from . import _capi as capi  # noqa: F401
 from ._capi import MhxError  # noqa: F401
-from .engine import Engine, Group, band_count, comm_unique_id, partition, split_rhat, ensemble_pick  # noqa: F401
+from .engine import Engine, Group, band_count, comm_unique_id, partition, split_rhat, ensemble_pick, trace_rows  # noqa: F401
 from . import models  # noqa: F401
 from . import sexpr  # noqa: F401
 from . import distributed  # noqa: F401
@@ -29,6 +29,7 @@ from .walker import (  # noqa: F401
     walker_set_corner_grid,
     autocorr, walker_autocorr, walker_set_autocorr, walker_set_rhat, walker_set_ensemble_get,
     walker_set_waic, walker_waic, waic_compare, waic_merge,
+    walker_set_trace, walker_set_catepillar,
 )
 
 __all__ = ["capi", "MhxError", "Engine", "Group", "comm_unique_id", "partition", "models", "Walker", "WalkerStep", "walker_create",
@@ -43,4 +44,5 @@ __all__ = ["capi", "MhxError", "Engine", "Group", "comm_unique_id", "partition",
            "walker_set_corner_grid",
            "autocorr", "walker_autocorr", "walker_set_autocorr", "walker_set_rhat", "split_rhat",
            "walker_set_ensemble_get", "ensemble_pick",
-           "walker_set_waic", "walker_waic", "waic_compare", "waic_merge"]
+           "walker_set_waic", "walker_waic", "waic_compare", "waic_merge",
+           "trace_rows", "walker_set_trace", "walker_set_catepillar"]

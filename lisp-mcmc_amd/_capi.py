@@ -27,6 +27,7 @@ CHAIN_RUNNING, CHAIN_DONE, CHAIN_FP_TRAP, CHAIN_STOPPED = 0, 1, 2, 3
 L_OK, L_CAUGHT, L_INVALID, L_EMPTY = 0, 1, 2, 3
 AUTOCORR_NONFINITE, AUTOCORR_CONSTANT, AUTOCORR_OPEN, MAX_AUTOCORR_LAG = 1, 2, 4, 1023
 WAIC_NONFINITE, WAIC_ONE_STEP, WAIC_BLOCK = 1, 2, 256
+TRACE_STEPS, TRACE_UNIQUE, TRACE_FORWARD, TRACE_PROB = 0, 1, 2, -1
 
 
 class Config(C.Structure):
@@ -167,6 +168,11 @@ SIGNATURES = {
                                i32p, i32p]),
     "mhx_group_get_waic": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f64p, f64p, f64p, i32p, f64p, f64p,
                                      f64p, i32p, i32p]),
+    "mhx_get_traces": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, i32p, C.c_int, C.c_int,
+                                 f64p, f64p, f64p, i32p, i32p, i32p]),
+    "mhx_group_get_traces": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, i32p, C.c_int,
+                                       C.c_int, f64p, f64p, f64p, i32p, i32p, i32p]),
+    "mhx_trace_rows": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, i64p]),
 }
 
 _lib = None

@@ -2508,6 +2508,101 @@ int mhx_get_summary_timing(mhx_engine* e, double* kernel_ms) {
   return MHX_OK;
 }
 
+// ---- batched traces: every chain's steps, filtered and thinned on the device (k_traces).  A
+// portion's pieces: the column list, the rows and their envelopes, the three counts, and the list
+// of kept ring slots (`take` ints per chain).
+extern "C++" {
+// rows `thin` (M:149-157) leaves of a list of n_kept: the items start, start + stride, ...
+static int64_t trace_rows_of(int64_t n_kept, int64_t stride, int64_t start) {
+  return n_kept <= start ? 0 : (n_kept - start + stride - 1) / stride;
+}
+}  // extern "C++"
+struct TraceCall {
+  int take = 0, filter = 0, stride = 0, start = 0, n_cols = 0, max_out = 0;
+  bool cols_null = false, envelope = false;
+  std::vector<int32_t> cols;
+  enum { VALUES, LO, HI, N_OUT, N_KEPT, N_USED };
+  HostDst dst[6];
+
+  TraceCall(int take_, int filter_, int stride_, int start_, const int32_t* cols_, int n_cols_, int max_out_,
+            double* values, double* lo, double* hi, int32_t* n_out, int32_t* n_kept, int32_t* n_used)
+      : take(take_), filter(filter_), stride(stride_), start(start_), n_cols(n_cols_), max_out(max_out_),
+        cols_null(!cols_), envelope(lo || hi) {
+    if (cols_ && n_cols >= 1) cols.assign(cols_, cols_ + n_cols);
+    dst[VALUES].p = values, dst[LO].p = lo, dst[HI].p = hi;
+    dst[N_OUT].p = n_out, dst[N_KEPT].p = n_kept, dst[N_USED].p = n_used;
+  }
+  int check(mhx_engine* e) {
+    const int rc = window_check(e, take);
+    if (rc != MHX_OK) return rc;
+    const int R = e->S.R, d = e->P.d;
+    if (filter != MHX_TRACE_STEPS && filter != MHX_TRACE_UNIQUE && filter != MHX_TRACE_FORWARD)
+      return fail(MHX_EINVAL, "filter must be MHX_TRACE_STEPS, _UNIQUE or _FORWARD, not %d", filter);
+    if (stride < 1 || stride > R) return fail(MHX_EINVAL, "stride must be in [1, history_capacity = %d]", R);
+    if (start < 0 || start >= stride) return fail(MHX_EINVAL, "start must be in [0, stride = %d)", stride);
+    if (n_cols < 1) return fail(MHX_EINVAL, "n_cols must be >= 1");
+    if (cols_null) return fail(MHX_EINVAL, "cols is NULL");
+    for (int j = 0; j < n_cols; ++j)
+      if (cols[j] < MHX_TRACE_PROB || cols[j] >= d)
+        return fail(MHX_EINVAL, "cols[%d] = %d outside [-1,%d)", j, cols[j], d);
+    if (max_out < 1 || max_out > R) return fail(MHX_EINVAL, "max_out must be in [1, history_capacity = %d]", R);
+    if (!one_item_fits([&](Carver& c, int64_t n) { carve(e, c, n, 1); }))
+      return fail(MHX_EINVAL, "the pieces of ONE chain exceed the stage budget of %zu bytes", kStageBudget);
+    const size_t row = (size_t)max_out * (size_t)n_cols * sizeof(double);
+    dst[VALUES].item_bytes = dst[LO].item_bytes = dst[HI].item_bytes = row;
+    dst[N_OUT].item_bytes = dst[N_KEPT].item_bytes = dst[N_USED].item_bytes = sizeof(int32_t);
+    return MHX_OK;
+  }
+  int64_t items(const mhx_engine* e) const { return e->cfg.n_chains; }
+  int64_t points() const { return 1; }
+  TracePieces carve(const mhx_engine*, Carver& c, int64_t n, int64_t) const {
+    return carve_traces(c, n_cols, max_out, take, envelope ? 1 : 0, n);
+  }
+  int upload(mhx_engine* e, const Portion& p) const {
+    Carver c;
+    const TracePieces s = carve(e, c, p.n, p.m);
+    // the outputs, which lie together: rows from n_out on stay all-bits-zero
+    HIP_TRY(hipMemsetAsync(e->stage.p + s.values, 0, s.kept - s.values, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->stage.p + s.cols, cols.data(), cols.size() * sizeof(int32_t), hipMemcpyHostToDevice,
+                           e->stream));
+    return MHX_OK;
+  }
+  int launch(mhx_engine* e, const Portion& p) const {
+    Carver c;
+    const TracePieces s = carve(e, c, p.n, p.m);
+    HIP_TRY(launch_traces(e->stream, e->S, p.i0, p.n, take, filter, stride, start, n_cols, max_out,
+                          stage_at<int32_t>(e, s.cols), stage_at<int32_t>(e, s.kept), stage_at<double>(e, s.values),
+                          dst[LO].p ? stage_at<double>(e, s.lo) : nullptr,
+                          dst[HI].p ? stage_at<double>(e, s.hi) : nullptr, stage_at<int32_t>(e, s.n_out),
+                          stage_at<int32_t>(e, s.n_kept), stage_at<int32_t>(e, s.n_used)));
+    return MHX_OK;
+  }
+  int collect(mhx_engine* e, const Portion& p) const {
+    Carver c;
+    const TracePieces s = carve(e, c, p.n, p.m);
+    const size_t off[6] = {s.values, s.lo, s.hi, s.n_out, s.n_kept, s.n_used};
+    for (int k = 0; k < 6; ++k) {
+      const int rc = copy_back(dst[k], p.i0, p.n, e->stage.p + off[k]);
+      if (rc != MHX_OK) return rc;
+    }
+    return MHX_OK;
+  }
+};
+
+int mhx_trace_rows(int64_t n_kept, int32_t stride, int32_t start, int64_t* rows) {
+  if (n_kept < 0) return fail(MHX_EINVAL, "n_kept must be >= 0");
+  if (stride < 1) return fail(MHX_EINVAL, "stride must be >= 1");
+  if (start < 0 || start >= stride) return fail(MHX_EINVAL, "start must be in [0, stride = %d)", stride);
+  if (rows) *rows = trace_rows_of(n_kept, stride, start);
+  return MHX_OK;
+}
+int mhx_get_traces(mhx_engine* e, int take, int filter, int stride, int start, const int32_t* cols, int n_cols,
+                   int max_out, double* values, double* lo, double* hi, int32_t* n_out, int32_t* n_kept,
+                   int32_t* n_used) {
+  return run_portions(e, TraceCall(take, filter, stride, start, cols, n_cols, max_out, values, lo, hi, n_out,
+                                   n_kept, n_used));
+}
+
 // ---- walker-get-data-and-fit (M:1230-1255): model values and credible bands on the device
 // (k_band_select, k_fit).  An ITEM is a parameter vector (mhx_eval_function) or a chain
 // (mhx_get_fit_bands).  Items and points are worked through in portions: at most
@@ -3995,6 +4090,13 @@ int mhx_group_get_waic(mhx_group* g, int fn, int take, double* elpd, double* lpp
                        int32_t* n_high, double* pw_lppd, double* pw_p, double* pw_acc,
                        int32_t* n_used, int32_t* status) {
   return run_portions(g, WaicCall(fn, take, elpd, lppd, p_waic, n_high, pw_lppd, pw_p, pw_acc, n_used, status));
+}
+
+int mhx_group_get_traces(mhx_group* g, int take, int filter, int stride, int start, const int32_t* cols,
+                         int n_cols, int max_out, double* values, double* lo, double* hi, int32_t* n_out,
+                         int32_t* n_kept, int32_t* n_used) {
+  return run_portions(g, TraceCall(take, filter, stride, start, cols, n_cols, max_out, values, lo, hi, n_out,
+                                   n_kept, n_used));
 }
 
 int mhx_group_get_derived(mhx_group* g, const char* const* exprs, int n_expr,

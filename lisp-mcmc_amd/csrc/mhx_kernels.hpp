@@ -3796,6 +3796,86 @@ __global__ __launch_bounds__(kThreads) void k_covariances(ChainState S, int64_t 
   }
 }
 
+// mhx_get_traces: the steps of every chain's window, filtered (MHX_TRACE_*: :steps, :unique-steps
+// M:492-496, :forward-steps M:497-502) and thinned (`thin` M:149-157), one wavefront per chain.
+// 1. compact: blocks of 64 steps, newest first; a ballot and a prefix count give every kept step
+//    its place in kept [n][take] (ring slots), as in ring_forward_list.  MHX_TRACE_STEPS keeps
+//    every step: item i is slot(i) and the list is not written.
+// 2. gather: (row r, column j) is flattened over the lanes, so a row's n_cols values are written
+//    side by side and read from one theta[slot][0 .. d) line.  The lane that owns (r, j) walks its
+//    bucket - kept items start + r stride .. - in order and carries lo / hi in registers: the
+//    sequential definition of include/mhx.h, no reduction.  lo / hi may be nullptr, each alone.
+// cols [n_cols]: a parameter, or MHX_TRACE_PROB.  values, lo, hi [n][max_out][n_cols] and the
+// counts come zeroed from the host: rows from n_out on are left as they are.
+__global__ __launch_bounds__(kThreads) void k_traces(ChainState S, int64_t c0, int64_t n, int take,
+                                                    int filter, int stride, int start, int n_cols,
+                                                    int max_out, const int32_t* __restrict__ cols,
+                                                    int* __restrict__ kept_all,
+                                                    double* __restrict__ values_all,
+                                                    double* __restrict__ lo_all,
+                                                    double* __restrict__ hi_all,
+                                                    int32_t* __restrict__ n_out,
+                                                    int32_t* __restrict__ n_kept,
+                                                    int32_t* __restrict__ n_used) {
+  const int w = wave_in_group(), l = lane_id(), d = S.d;
+  const int64_t i = (int64_t)blockIdx.x * kWavesPerGroup + w;
+  if (i >= n) return;
+  const Ring r = ring_of(S, c0 + i);
+  const int t = ring_held(r, take);
+  int* kept = kept_all + i * take;
+  int nk = t;
+  if (filter != MHX_TRACE_STEPS) {
+    const bool uniq = filter == MHX_TRACE_UNIQUE;
+    nk = 0;
+    for (int base = 0; base < t; base += kWave) {
+      const int s = base + l;
+      bool f = false;
+      if (s < t) {
+        const bool last = s == t - 1;
+        const double a = r.prob[r.slot(s)];
+        const double b = last ? 0.0 : r.prob[r.slot(s + 1)];
+        f = uniq ? (last || bits_of(a) != bits_of(b)) : (!last && !(a <= b));
+      }
+      const unsigned long long m = __ballot(f);
+      const int pos = nk + __popcll(m & ((1ULL << l) - 1ULL));
+      if (f) kept[pos] = r.slot(s);
+      nk += __popcll(m);
+    }
+    __threadfence();
+  }
+  const int rows = nk <= start ? 0 : (nk - start + stride - 1) / stride;
+  const int no = rows < max_out ? rows : max_out;
+  if (l == 0) {
+    n_out[i] = no;
+    n_kept[i] = nk;
+    n_used[i] = t;
+  }
+  const bool envelope = lo_all != nullptr || hi_all != nullptr;
+  const int64_t at = i * (int64_t)max_out * n_cols;
+  auto slot_of = [&](int k) { return filter == MHX_TRACE_STEPS ? r.slot(k) : kept[k]; };
+  for (int e = l; e < no * n_cols; e += kWave) {
+    const int row = e / n_cols, j = e - row * n_cols, col = cols[j];
+    auto value_of = [&](int k) {
+      const int slot = slot_of(k);
+      return col < 0 ? r.prob[slot] : r.theta[(int64_t)slot * d + col];
+    };
+    const int k0 = start + row * stride;
+    const double first = value_of(k0);
+    values_all[at + e] = first;
+    if (envelope) {
+      const int k1 = k0 + stride < nk ? k0 + stride : nk;
+      double lo = first, hi = first;
+      for (int k = k0 + 1; k < k1; ++k) {
+        const double v = value_of(k);
+        if (v < lo) lo = v;
+        if (v > hi) hi = v;
+      }
+      if (lo_all) lo_all[at + e] = lo;
+      if (hi_all) hi_all[at + e] = hi;
+    }
+  }
+}
+
 // mhx_get_proposal_factors: ring_l_matrix - the code k_l_matrix and the controller run - for
 // every chain.  fwd [n][take], cov / out [n][d][d] (zeroed by the host, as for k_l_matrix).
 __global__ __launch_bounds__(kThreads) void k_l_matrices(ChainState S, int64_t c0, int64_t n,

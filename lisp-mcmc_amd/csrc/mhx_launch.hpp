@@ -149,6 +149,12 @@ hipError_t launch_ensemble_digits(hipStream_t st, const ChainState& S, int64_t n
                                   int32_t* n_used, int32_t* nan_flag);
 hipError_t launch_covariances(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
                               int* uniq, double* cov, int32_t* n_unique, int32_t* status);
+// mhx_get_traces (k_traces): cols [n_cols] on the device, kept [n][take] scratch, values / lo / hi
+// [n][max_out][n_cols] zeroed by the caller (lo, hi: nullptr where not asked for)
+hipError_t launch_traces(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
+                         int filter, int stride, int start, int n_cols, int max_out,
+                         const int32_t* cols, int* kept, double* values, double* lo, double* hi,
+                         int32_t* n_out, int32_t* n_kept, int32_t* n_used);
 hipError_t launch_l_matrices(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
                              int* fwd, double* cov, double* out, int32_t* status,
                              int32_t* n_forward);

@@ -356,6 +356,16 @@ hipError_t launch_covariances(hipStream_t st, const ChainState& S, int64_t c0, i
   k_covariances<<<grid_for(n), dim3(kThreads), 0, st>>>(S, c0, n, take, uniq, cov, n_unique, status);
   return hipGetLastError();
 }
+hipError_t launch_traces(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
+                         int filter, int stride, int start, int n_cols, int max_out,
+                         const int32_t* cols, int* kept, double* values, double* lo, double* hi,
+                         int32_t* n_out, int32_t* n_kept, int32_t* n_used) {
+  if (n <= 0) return hipSuccess;
+  k_traces<<<grid_for(n), dim3(kThreads), 0, st>>>(S, c0, n, take, filter, stride, start, n_cols,
+                                                  max_out, cols, kept, values, lo, hi, n_out, n_kept,
+                                                  n_used);
+  return hipGetLastError();
+}
 hipError_t launch_l_matrices(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
                              int* fwd, double* cov, double* out, int32_t* status,
                              int32_t* n_forward) {

@@ -203,6 +203,27 @@ inline WaicPieces carve_waic(Carver& c, int64_t nb_total, int want, int64_t n_, 
   s.pw_acc = c.take((want & WAIC_WANT_ACC) ? n * m * 4 * sizeof(double) : 0);
   return s;
 }
+// batched traces: the caller's column list [n_cols] - it does not grow with n and comes first -
+// the rows values [n][max_out][n_cols], their envelopes lo and hi of the same shape (envelope 0:
+// both empty, the kernel does not write them), n_out, n_kept, n_used [n], and the kept-index
+// scratch [n][take]: the ring slots of the steps that passed the filter, newest first.  The
+// outputs lie together, values .. n_used, so that one clear zeroes them.
+struct TracePieces {
+  size_t cols, values, lo, hi, n_out, n_kept, n_used, kept;
+};
+inline TracePieces carve_traces(Carver& c, int n_cols_, int max_out_, int take, int envelope, int64_t n_) {
+  const size_t n = (size_t)n_, rows = (size_t)max_out_ * (size_t)n_cols_;
+  TracePieces s;
+  s.cols = c.take((size_t)n_cols_ * sizeof(int32_t));
+  s.values = c.take(n * rows * sizeof(double));
+  s.lo = c.take(envelope ? n * rows * sizeof(double) : 0);
+  s.hi = c.take(envelope ? n * rows * sizeof(double) : 0);
+  s.n_out = c.take(n * sizeof(int32_t));
+  s.n_kept = c.take(n * sizeof(int32_t));
+  s.n_used = c.take(n * sizeof(int32_t));
+  s.kept = c.take(n * (size_t)take * sizeof(int32_t));
+  return s;
+}
 // Whether ONE item of a piece list fits the budget at all, by portion_of's own accounting
 // (portion_of answers 1 either way: a read-out that must not outgrow the budget asks first).
 template <class Carve>

@@ -238,6 +238,47 @@ class _Summaries:
             out["n_used"].ctypes.data_as(capi.i32p), out["status"].ctypes.data_as(capi.i32p)))
         return out
 
+    TRACE_FILTERS = {"steps": capi.TRACE_STEPS, "unique": capi.TRACE_UNIQUE, "forward": capi.TRACE_FORWARD}
+
+    def traces(self, take, cols=None, filter="steps", stride=1, start=0, max_out=None, envelope=False):
+        """every chain's steps, filtered and thinned on the device (mhx_get_traces, which has the
+        definitions).  cols: parameter indices, capi.TRACE_PROB (-1) for a step's prob; None:
+        [TRACE_PROB, 0 .. d-1].  filter: "steps", "unique" or "forward" (or a capi.TRACE_*);
+        stride, start: every stride-th kept step from the start-th on, newest first; max_out: rows
+        to return, None: trace_rows(take, stride, start), all there can be.  A dict of values
+        [n_chains, max_out, n_cols] (rows from n_out on are zero), n_out, n_kept, n_used
+        [n_chains] and, with envelope=True, lo and hi as values: the extremes of each row's
+        bucket of `stride` kept steps."""
+        cols = [capi.TRACE_PROB] + list(range(self.d)) if cols is None else [int(c) for c in cols]
+        flt = self.TRACE_FILTERS.get(str(filter).lstrip(":").lower().replace("-steps", ""), filter)
+        if max_out is None:  # (arguments the library will refuse are left for it to name)
+            ok = int(take) >= 0 and int(stride) >= 1 and 0 <= int(start) < int(stride)
+            max_out = max(trace_rows(int(take), stride, start), 1) if ok else 1
+        ca, colp = capi.as_i32(cols or [0])
+        n, nc, rows = self.n_chains, len(cols), max(int(max_out), 0)
+        out = {"values": np.zeros((n, rows, nc))}
+        if envelope:
+            out["lo"], out["hi"] = np.zeros((n, rows, nc)), np.zeros((n, rows, nc))
+        for k in ("n_out", "n_kept", "n_used"):
+            out[k] = np.zeros(n, dtype=np.int32)
+        capi.check(self._summary("traces")(
+            self._h, int(take), int(flt), int(stride), int(start), colp, nc, int(max_out),
+            *(out[k].ctypes.data_as(capi.f64p) if k in out else None for k in ("values", "lo", "hi")),
+            *(out[k].ctypes.data_as(capi.i32p) for k in ("n_out", "n_kept", "n_used"))))
+        return out
+
+
+def trace_rows(n_kept, stride=1, start=0):
+    """rows `thin` (M:149-157) leaves of a list of n_kept items: those at start, start + stride,
+    ... (mhx_trace_rows: host arithmetic, no device).  ValueError, with the library's message,
+    unless n_kept >= 0, stride >= 1 and 0 <= start < stride."""
+    rows = C.c_int64(0)
+    rc = capi.lib().mhx_trace_rows(int(n_kept), int(stride), int(start), C.byref(rows))
+    if rc == capi.EINVAL:
+        raise ValueError(capi.lib().mhx_last_error().decode())
+    capi.check(rc)
+    return rows.value
+
 
 def ensemble_pick(counts, rank):
     """(digit, rank in its bin, the bin's count) of `rank` among the bins `counts`

@@ -271,6 +271,16 @@ library, or without a gfx950 device, walker-create signals MHX-ERROR."
   (g :pointer) (fn :int) (take :int) (elpd :pointer) (lppd :pointer) (p-waic :pointer)
   (n-high :pointer) (pw-lppd :pointer) (pw-p :pointer) (pw-acc :pointer) (n-used :pointer)
   (status :pointer))
+(cffi:defcfun ("mhx_get_traces" %mhx-get-traces) :int
+  (e :pointer) (take :int) (filter :int) (stride :int) (start :int) (cols :pointer) (n-cols :int)
+  (max-out :int) (values :pointer) (lo :pointer) (hi :pointer) (n-out :pointer) (n-kept :pointer)
+  (n-used :pointer))
+(cffi:defcfun ("mhx_group_get_traces" %mhx-group-get-traces) :int
+  (g :pointer) (take :int) (filter :int) (stride :int) (start :int) (cols :pointer) (n-cols :int)
+  (max-out :int) (values :pointer) (lo :pointer) (hi :pointer) (n-out :pointer) (n-kept :pointer)
+  (n-used :pointer))
+(cffi:defcfun ("mhx_trace_rows" %mhx-trace-rows) :int
+  (n-kept :int64) (stride :int32) (start :int32) (rows :pointer))
 
 (defmacro with-c-call (&body body)
   "HIP/RCCL runtime code may raise inexact/invalid flags that SBCL turns into conditions;

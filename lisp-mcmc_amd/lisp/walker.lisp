@@ -699,7 +699,8 @@ vectors of (x_i - mean_i)(x_j - mean_j) / n, the division inside the sum."
 ;;; ------------------------------------------------------------------ walker-set-get M:1029-1030
 ;;; walker-get mapped over the set.  The summarising selectors are ONE batched device call for all
 ;;; chains (mhx_get_percentiles / _covariances / _proposal_factors / _window_best, or their
-;;; mhx_group_get_* forms): no history crosses to the host.
+;;; mhx_group_get_* forms): no history crosses to the host.  The list-valued selectors are ONE
+;;; mhx_get_traces call: the device filters, and only the columns the selector reads come back.
 (defun %set-call (walker engine-fn group-fn &rest args)
   "ENGINE-FN on the walker's engine or GROUP-FN on its group, ARGS after the handle"
   (with-c-call
@@ -722,6 +723,37 @@ vectors of (x_i - mean_i)(x_j - mean_j) / n, the division inside the sum."
     (1 (error 'division-by-zero :operation 'cholesky-decomp :operands nil))
     (2 (error 'floating-point-invalid-operation :operation 'cholesky-decomp :operands nil))
     (t (make-array '(0 0) :element-type 'double-float))))
+
+(defun %set-traces (walker window filter stride start cols envelope)
+  "mhx_get_traces for every chain of the set: the columns COLS (places in the parameter vector, -1
+the step's prob) of every STRIDE-th step FILTER (0 every step, 1 :unique-steps, 2 :forward-steps)
+keeps of the newest WINDOW, from the START-th on.  Values: the rows ROWS carved per chain, the
+vectors VALUES, LO and HI [n][rows][n-cols] (LO and HI nil without ENVELOPE) and the lists n-out,
+n-kept, n-used."
+  (let* ((n (walker-n-chains walker))
+         (nc (length cols))
+         (rows (max 1 (cffi:with-foreign-object (r :int64)
+                        (with-c-call (check (%mhx-trace-rows window stride start r)))
+                        (cffi:mem-ref r :int64))))
+         (count (* n rows nc))
+         (vals (cffi:foreign-alloc :double :count count))
+         (lo (if envelope (cffi:foreign-alloc :double :count count) (cffi:null-pointer)))
+         (hi (if envelope (cffi:foreign-alloc :double :count count) (cffi:null-pointer))))
+    (unwind-protect
+         (cffi:with-foreign-objects ((colp :int32 nc) (n-out :int32 n) (n-kept :int32 n)
+                                     (n-used :int32 n))
+           (fill-int32s colp cols)
+           (%set-call walker #'%mhx-get-traces #'%mhx-group-get-traces
+                      window filter stride start colp nc rows vals lo hi n-out n-kept n-used)
+           (flet ((doubles (ptr)
+                    (if (cffi:null-pointer-p ptr) nil (read-doubles ptr count)))
+                  (ints (ptr)
+                    (loop for c below n collect (cffi:mem-aref ptr :int32 c))))
+             (values rows (doubles vals) (doubles lo) (doubles hi)
+                     (ints n-out) (ints n-kept) (ints n-used))))
+      (cffi:foreign-free vals)
+      (unless (cffi:null-pointer-p lo) (cffi:foreign-free lo))
+      (unless (cffi:null-pointer-p hi) (cffi:foreign-free hi)))))
 
 (defun walker-set-get (walker &key (get :steps) take param)
   "(walker-set-get the-walker-set &key get take param) M:1029-1030 over a batched walker: a list
@@ -752,7 +784,41 @@ condition is signalled for the first chain walker-get would signal it for, as ma
              (let ((a (make-array (list d d) :element-type 'double-float)))
                (dotimes (i d a)
                  (dotimes (j d)
-                   (setf (aref a i j) (cffi:mem-aref ptr :double (+ offset (* i d) j))))))))
+                   (setf (aref a i j) (cffi:mem-aref ptr :double (+ offset (* i d) j)))))))
+           (listed ()
+             ;; M:490-502, M:509-510, M:540: the steps themselves, filtered on the device
+             (let* ((every (loop for j below d collect j))
+                    (column (and (eq get :param) (position param keys)))
+                    (cols (case get
+                            (:steps (cons -1 every))
+                            (:log-liklihoods (list -1))
+                            (:param (list (or column -1)))
+                            (t every)))
+                    (nc (length cols)))
+               (multiple-value-bind (rows v lo hi n-out n-kept n-used)
+                   (%set-traces walker window
+                                (case get (:unique-steps 1) (:forward-steps 2) (t 0))
+                                1 0 cols nil)
+                 (declare (ignore lo hi n-kept))
+                 (when (some (lambda (used len) (< used (if take (min take len) len)))
+                             n-used lengths)
+                   (warn "walker-set-get ~s :take ~d: the device history ring holds the newest ~d steps of a walk; create the walker with :history-capacity >= the walks' length to keep them all"
+                         get wanted ring))
+                 (flet ((plist-from (at)
+                          (loop for k in keys
+                                for j from at
+                                append (list k (aref v j)))))
+                   (loop for c below n
+                         for held in n-out
+                         collect (loop for r below held
+                                       collect (let ((at (* nc (+ (* c rows) r))))
+                                                 (case get
+                                                   (:steps (make-walker-step
+                                                            :prob (aref v at)
+                                                            :params (plist-from (1+ at))))
+                                                   (:log-liklihoods (aref v at))
+                                                   (:param (and column (aref v at)))
+                                                   (t (plist-from at)))))))))))
       (case get
         (:median-params                 ; nth-percentile 50 of every parameter, M:516-523
          (cffi:with-foreign-objects ((num :int32) (den :int32) (out :double (* n d)))
@@ -792,6 +858,10 @@ condition is signalled for the first chain walker-get would signal it for, as ma
                                        (loop for k in keys
                                              for i from 0
                                              append (list k (aref l i i))))))))))
+        ((:steps :params :param :log-liklihoods :unique-steps :forward-steps)
+         (if (and take (< take 1))
+             (per-chain)                ; no window the device could be asked for
+             (listed)))
         (t (per-chain))))))
 
 ;;; ------------------------------------------------------------------ histograms M:1361-1369, M:1541-1564
@@ -935,6 +1005,65 @@ whole walk."
                                               (cffi:mem-aref counts :int32
                                                              (+ (* bins bins (+ (* c np) q)) (* i bins) j)))))
                                     (list (list (elt names a) (elt names b)) grid)))))))
+
+;;; ------------------------------------------------------------------ traces as arrays
+;;; What walker-catepillar-plots M:1294-1309, walker-liklihood-plot M:1313-1320 and
+;;; walker-plot-one-corner M:1322-1331 draw, for every walker of a set, as arrays: one
+;;; mhx_get_traces call, thinned on the device with the reference's `thin` M:149-157.
+(defun walker-set-trace (walker &key keys take (thin 1) (start 0) (which :steps) envelope (prob t))
+  "The steps of every chain of the set as arrays [n-chains][rows], newest first: a plist of
+:values (key array ...) for KEYS (nil: all), :prob (the steps' log-posteriors, nil unless PROB),
+:n-out, :n-kept and :n-used (lists: rows written, steps WHICH kept, steps the window held; the
+rows of chain c beyond its n-out are zero) and, with ENVELOPE, :lo and :hi (key array ...),
+:prob-lo and :prob-hi: the smallest and greatest value among the THIN kept steps a row stands
+for.  WHICH: :steps, :unique-steps or :forward-steps; THIN, START: (thin list thin start) of what
+WHICH keeps; TAKE nil: every walk whole."
+  (let* ((n (walker-n-chains walker))
+         (names (or keys (walker-param-keys walker)))
+         (cols (append (if prob (list -1) nil) (%key-columns walker keys)))
+         (nc (length cols))
+         (lead (if prob 1 0))
+         (window (%bin-window walker take "walker-set-trace")))
+    (multiple-value-bind (rows v lo hi n-out n-kept n-used)
+        (%set-traces walker window
+                     (ecase which (:steps 0) (:unique-steps 1) (:forward-steps 2))
+                     thin start cols envelope)
+      (labels ((column (vec j)
+                 (let ((a (make-array (list n rows) :element-type 'double-float)))
+                   (dotimes (c n a)
+                     (dotimes (r rows)
+                       (setf (aref a c r) (aref vec (+ (* nc (+ (* c rows) r)) j)))))))
+               (per-key (vec)
+                 (loop for k in names
+                       for j from lead
+                       append (list k (column vec j)))))
+        (append (list :values (per-key v)
+                      :prob (and prob (column v 0))
+                      :n-out n-out :n-kept n-kept :n-used n-used)
+                (and envelope
+                     (list :lo (per-key lo) :hi (per-key hi)
+                           :prob-lo (and prob (column lo 0))
+                           :prob-hi (and prob (column hi 0)))))))))
+
+(defun walker-set-catepillar (walker &key take points)
+  "The numbers behind walker-catepillar-plots and walker-liklihood-plot for every walker of the
+set.  POINTS nil: every step of the newest TAKE (nil: the whole walks).  POINTS p: buckets of
+stride = (ceiling window p) steps, and of each bucket its first value and its extremes, so that no
+excursion is lost to the thinning.  A plist of :stride, :n-out (rows of each chain, newest first),
+:params (key (:first array [:lo array :hi array]) ...) and :log-liklihoods (:first array ...);
+the arrays are [n-chains][rows]."
+  (let* ((window (%bin-window walker take "walker-set-catepillar"))
+         (stride (if points (max 1 (ceiling window points)) 1))
+         (r (walker-set-trace walker :take window :thin stride :envelope (and points t))))
+    (flet ((sides (first lo hi)
+             (append (list :first first) (and points (list :lo lo :hi hi)))))
+      (list :stride stride
+            :n-out (getf r :n-out)
+            :params (loop for k in (walker-param-keys walker)
+                          append (list k (sides (getf (getf r :values) k)
+                                                (getf (getf r :lo) k)
+                                                (getf (getf r :hi) k))))
+            :log-liklihoods (sides (getf r :prob) (getf r :prob-lo) (getf r :prob-hi))))))
 
 ;;; ------------------------------------------------------------------ what a window is worth
 ;;; The reference judges convergence by eye (walker-catepillar-plots M:1294-1310); these are the

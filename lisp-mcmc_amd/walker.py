@@ -631,7 +631,9 @@ def walker_set_get(walker, get=":steps", take=None, param=None):
     The summarising selectors (:median-params :stddev-params :l-matrix :covariance-matrix
     :most-likely-step :most-likely-params :acceptance) are served by ONE batched device call for
     all chains (include/mhx.h, mhx_get_percentiles and its kin): no history crosses to the host.
-    The list-valued selectors read one trace per chain, the lengths once.  A condition is raised
+    The list-valued selectors (:steps :params :param :log-liklihoods :unique-steps :forward-steps)
+    take ONE mhx_get_traces call for the set: the device filters, and only the columns the
+    selector reads come back.  A condition is raised
     for the first chain (in chain order) that walker_get would raise it for, as mapcar would;
     HistoryTruncated is warned once per call when any chain's window reached past its ring."""
     e = walker.engine
@@ -689,14 +691,40 @@ def walker_set_get(walker, get=":steps", take=None, param=None):
         if past:
             truncated(ring, widest, past)
         return [walker._step(th[c], pr[c]) for c in range(n)]
-    out, short = [], 0
-    for c in range(n):
-        prob, th = e.trace(c, int(t[c]))
-        short += len(prob) < t[c]
-        steps = [walker._step(th[i], prob[i]) for i in range(len(prob))]
-        out.append(_list_selector(g, steps, prob, param))
+    if take is not None and int(take) < 1:  # (no window the device could be asked for)
+        out, short = [], 0
+        for c in range(n):
+            prob, th = e.trace(c, int(t[c]))
+            short += len(prob) < t[c]
+            steps = [walker._step(th[i], prob[i]) for i in range(len(prob))]
+            out.append(_list_selector(g, steps, prob, param))
+        if short:
+            truncated(ring, widest, short)
+        return out
+    # ONE device call for the whole set: the selector's filter, only the columns it reads
+    every = list(range(len(keys)))
+    if g == "param":
+        k = _key(param)
+        cols = [list(keys).index(k)] if k in keys else [capi.TRACE_PROB]
+    else:
+        cols = {"steps": [capi.TRACE_PROB] + every, "log-liklihoods": [capi.TRACE_PROB]}.get(g, every)
+    r = e.traces(window, cols, filter={"unique-steps": "unique", "forward-steps": "forward"}.get(g, "steps"))
+    short = int((r["n_used"] < t).sum())
     if short:
         truncated(ring, widest, short)
+    out = []
+    for c in range(n):
+        rows = r["values"][c, :int(r["n_out"][c])]
+        if g == "steps":
+            out.append([walker._step(v[1:], v[0]) for v in rows])
+        elif g == "log-liklihoods":  # M:540
+            out.append(rows[:, 0].tolist())
+        elif g == "param":
+            if k not in keys and len(rows):
+                raise KeyError(k)  # (what the first step's plist answers in walker_get)
+            out.append(rows[:, 0].tolist())
+        else:  # :params, :unique-steps M:492-496, :forward-steps M:497-502
+            out.append([dict(zip(keys, v.tolist())) for v in rows])
     return out
 
 
@@ -1021,6 +1049,51 @@ def walker_set_param_histo(walker, keys=None, take=10000, bins=20):
     counts = walker.engine.histograms(window, cols, edges)["counts"]
     return [{k: (_histo_x(lo[c, j], hi[c, j], int(bins)), counts[c, j].tolist())
              for j, k in enumerate(names)} for c in range(counts.shape[0])]
+
+
+def walker_set_trace(walker, keys=None, take=None, thin=1, start=0, which=":steps", envelope=False,
+                     prob=True):
+    """the steps of every chain of the set as ARRAYS, for sets too large for lists of objects: one
+    mhx_get_traces call.  keys: the parameters wanted (None: all); take: the window (None: every
+    walk whole); which: :steps, :unique-steps or :forward-steps; thin, start: the reference's
+    (thin list thin start) M:149-157 of what `which` keeps, newest first.  A dict of
+      values   {key: [n_chains, rows]}, the rows of chain c beyond n_out[c] are zero
+      prob     [n_chains, rows] the steps' log-posteriors (None with prob=False)
+      n_out, n_kept, n_used  [n_chains]: rows written, steps `which` kept, steps the window held
+    and with envelope=True lo and hi {key: [n_chains, rows]}, prob_lo and prob_hi: the smallest and
+    greatest value among the `thin` kept steps a row stands for (include/mhx.h has the rule)."""
+    names, cols = _key_columns(walker, keys)
+    window = _bin_window(walker, take, "walker-set-trace")
+    lead = [capi.TRACE_PROB] if prob else []
+    r = walker.engine.traces(window, lead + cols, filter=which, stride=int(thin), start=int(start),
+                             envelope=envelope)
+    at = len(lead)
+    out = {"values": {k: r["values"][:, :, at + j].copy() for j, k in enumerate(names)},
+           "prob": r["values"][:, :, 0].copy() if prob else None,
+           "n_out": r["n_out"], "n_kept": r["n_kept"], "n_used": r["n_used"]}
+    if envelope:
+        for side in ("lo", "hi"):
+            out[side] = {k: r[side][:, :, at + j].copy() for j, k in enumerate(names)}
+            out["prob_" + side] = r[side][:, :, 0].copy() if prob else None
+    return out
+
+
+def walker_set_catepillar(walker, take=None, points=None):
+    """the numbers behind walker-catepillar-plots M:1294-1309 and walker-liklihood-plot M:1313-1320
+    for every walker of the set, without the plots.  points None: every step - each key's :param
+    list and the :log-liklihoods, as arrays.  points p: at most about p rows a walk, for a plot p
+    pixels wide: stride = ceil(window / p), and for every bucket of `stride` steps its first
+    value and its extremes, so that no excursion is lost to the thinning.  A dict of stride,
+    n_out [n_chains] (rows of each chain, newest first; the rest are zero), params {key: {"first":
+    [n_chains, rows]}} and log_liklihoods {"first": ...}, with "lo" and "hi" beside "first" when
+    points is given."""
+    window = _bin_window(walker, take, "walker-set-catepillar")
+    stride = 1 if points is None else max(1, -(-window // int(points)))
+    r = walker_set_trace(walker, None, take=window, thin=stride, envelope=points is not None)
+    sides = [("first", "values", "prob")] + ([("lo", "lo", "prob_lo"), ("hi", "hi", "prob_hi")] if points is not None else [])
+    return {"stride": stride, "n_out": r["n_out"],
+            "params": {k: {s: r[v][k] for s, v, _ in sides} for k in r["values"]},
+            "log_liklihoods": {s: r[p] for s, _, p in sides}}
 
 
 def permute_params(params):
