@@ -508,7 +508,20 @@ int mhx_band_count(int64_t take, int64_t* k);
  * expression model that names xcol1, else 1).  xcols == NULL: the function's own dataset x, which
  * is on the device already; m must then be its point count (pads are not included).  Every value
  * is the model's direct form at that x: no likelihood, no prior, no recurrence, no tile
- * skipping.  Serves every model the engine can walk (ahead-of-time kernels, the generic one,
+ * skipping.  Accuracy, per value: within 1e-12 * sum |terms| of the reference's formula (the terms:
+ * the background's monomials and the peaks, in absolute value) PLUS THE ARGUMENT TERM of the models
+ * that form their argument otherwise than the reference does.  Peaks (Gaussian, Lorentzian,
+ * pseudo-Voigt): t = fma(x, iw, c) with c = fl(-mu * iw) is the reference's (x - mu) / w at a centre
+ * moved by at most delta = |mu| * 2^-53 - half an ulp of mu -, so a value differs by at most
+ * 2 * sum_k |A_k| * |dg_k/dx| * delta_k more (|dg/dx| = 2 |u| / |w| * g for a Gaussian,
+ * 2 |u| / |w| / (1 + u^2)^2 for a Lorentzian, u = (x - mu) / w; the factor 2 stands for iw's own
+ * rounding and the final rounding of t).  Nothing near the origin; up to 8e-12 of a peak's height
+ * at x ~ mu ~ 2000, w = 0.05 (1.72 * |mu| / |w| * 2^-53, on the flanks).  The sweep's uniform-grid recurrence adds the grid's tolerated departure,
+ * 8 ulp of the window's max |x|, to delta.  Sinusoid: |A| * (|om x| + |ph|) * 2^-53 (also doubled);
+ * exp-decay: |x / tau| * 2^-52 relative on the exponential.  Polynomials, MHX_MODEL_LORDER_MIXED and
+ * expression models form their arguments as the reference does: 1e-12 * sum |terms| alone.  Centre x
+ * (subtract a constant near the peaks from x and from the centres) when |mu| / w is beyond about 1e4.
+ * Serves every model the engine can walk (ahead-of-time kernels, the generic one,
  * run-time compiled expression and specialised problems).  Worked through in portions whose
  * device scratch stays below 64 MiB whatever n and m are.  mhx_get_summary_timing covers it. */
 int mhx_eval_function(mhx_engine* e, int fn, const double* theta, int64_t n, const double* xcols,

@@ -647,9 +647,24 @@ struct PeaksModel {
   // most 31 steps away from an exactly evaluated one: r_j = r_0 q^j carries (j + 1) roundings,
   // g_m = g_0 r_0 ... r_(m-1)  m + sum_j (j + 1) <= 527 of them -> |g_m / g(t_m) - 1| <=
   // 560 * 2^-53 = 6.2e-14, plus the grid's own departure from x_0 + i h (checked <= 8 ulp of
-  // max |x| when the dataset is set: 2 |t| iw 8 ulp).  Both are far inside the stated tolerance
-  // 1e-12 sum |term| (tests/test_gpu_recurrence.py measures them against the direct path and the
-  // oracle).  A seed costs two table exps per peak: 1.6 instructions per point at 32 points per
+  // max |x| when the dataset is set: 2 |t| iw 8 ulp).  The first is far inside the stated
+  // 1e-12 sum |term| (tests/test_gpu_recurrence.py measures it against the direct path and the
+  // oracle); the second is a shift of the ARGUMENT and belongs to the argument term:
+  //   THE ARGUMENT OF A PEAK.  t = fma(x, iw, c) with iw = fl(g / w) and c = fl(-mu iw) (prepare()
+  //   below) is iw (x - mu - mu e) (1 + e'), |e|, |e'| <= 2^-53: c's rounding moves the CENTRE by up
+  //   to |mu| 2^-53, half an ulp of mu.  As a backward error that is nothing; as a forward error a
+  //   peak's value is the reference formula's at an argument moved by at most
+  //       delta = |mu| 2^-53                                  (direct form, every peaks model)
+  //       delta = |mu| 2^-53 + 8 ulp(max |x| of the window)   (a window swept by the recurrence)
+  //   and differs from it by at most  2 |A| |dg/dx| delta  ON TOP OF 1e-12 sum |term|
+  //   (|dg/dx| = 2 |u| / |w| g for a Gaussian, 2 |u| / |w| / (1 + u^2)^2 for a Lorentzian,
+  //   u = (x - mu) / w; the one factor 2 stands for iw's own rounding inside c and the final
+  //   rounding of t).  Near the origin the term vanishes next to 1e-12 sum |term|; at
+  //   x ~ mu ~ 2000 it is up to 8e-12 of the peak's height for w = 0.05 (its greatest, on the
+  //   flanks: 1.72 |mu| / |w| 2^-53) and 8e-9 for w = 5e-5 (DESIGN 3.1;
+  //   tests/offset_cases.py restates it, tests/test_gpu_offset.py holds the kernels to it against
+  //   high precision).  Data with |mu| / w beyond about 1e4 are better centred by the caller.
+  // A seed costs two table exps per peak: 1.6 instructions per point at 32 points per
   // seed next to the 9 of the two-peak loop itself (3.3 at 16, which round 2 started with).
   // Preconditions, per step and PEAK (else that peak keeps the direct form): the fast path,
   // 32 |D| <= 1 - a seed that underflows to 0 (|t| > 33.8) then stays beyond |t| = 32.8 for its
@@ -1376,6 +1391,8 @@ struct ExpDecayModel {
     return p;
   }
   static __device__ __forceinline__ double eval(const Prep& p, double x) {
+    // (x * fl(1 / tau) where the reference divides: two roundings on the argument, |x / tau| 2^-52
+    // relative on the exponential - the argument term of this model)
     return __builtin_fma(p.A, gexp(-(x * p.itau)), p.c);  // < 1 ulp for any argument
   }
 };
@@ -1392,6 +1409,8 @@ struct SinusoidModel {
     return p;
   }
   static __device__ __forceinline__ double eval(const Prep& p, double x) {
+    // (om x + ph may contract to one fma where the reference rounds twice: the argument differs
+    // by up to (|om x| + |ph|) 2^-53, the value by |A| times that - the argument term of this model)
     return __builtin_fma(p.A, sin(p.om * x + p.ph), p.c);
   }
 };
@@ -1400,6 +1419,9 @@ struct PVoigt2Model {
   // per peak: u = x*iw + c (c = -mu*iw); Lorentzian eta/(1+u^2) by frcp; Gaussian
   // (1-eta) exp(-u^2) = (1-eta) 2^(-t^2), t = x*(iw g) + c g, g = sqrt(log2 e).  Fast path (the
   // low-dword exponent trick of mexp2_negsq) when |t| < kFastT over the dataset's x range.
+  // The argument term (PeaksModel, "THE ARGUMENT OF A PEAK"): u and the guarded t = u g move the
+  // centre by delta = |mu| 2^-53; the fast path's t rounds iw g and c g separately, two roundings
+  // more: delta = (|x| + 2 |mu|) 2^-53 for its Gaussians.
   static constexpr bool kHasFast = true;
   struct Prep {
     double A, b0, b1, c1, iw1, eta1, om1, c2p, iw2, eta2, om2, rho, c2;

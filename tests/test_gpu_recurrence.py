@@ -105,9 +105,11 @@ def test_not_a_grid_means_direct_form(mhx, orc):
         os.environ.pop("MHX_NO_WINDOW_GRIDS", None)
     a.close()
     b.close()
-    # a grid far from the origin, negative spacing direction excluded (x must ascend to be found
-    # sorted by tile skipping, but the recurrence does not care): x = 2000 + i * 0.25
-    s3 = pb.lorder()  # not a peaks model: nothing changes either way
+    # a model that is not made of peaks: the switch changes nothing.  (lorder's x = 2000 ... 2997
+    # is far from the origin, but its kernel forms (x - x0) * ilw as the reference does; PEAKS on
+    # grids far from the origin, where t = fma(x, iw, c) shifts the centre by half an ulp of mu and
+    # the recurrence adds the grid's departure, are tests/test_gpu_offset.py's)
+    s3 = pb.lorder()
     a, b = engines(mhx, s3, 1)
     t3 = pb.perturbed(s3.theta_star, 4, 0.01, seed=1)
     assert np.array_equal(a.logpost(t3), b.logpost(t3))
