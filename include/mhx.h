@@ -481,7 +481,7 @@ int mhx_get_window_best(mhx_engine* e, int take, double* prob, double* theta);
 int mhx_get_history_capacity(mhx_engine* e, int32_t* capacity);
 /* HIP-event milliseconds the kernels of the engine's last mhx_get_percentiles / _covariances /
  * _proposal_factors / _window_best / _fit_bands / _derived / _histograms / _pair_grids / _waic /
- * _traces or mhx_eval_function call ran (all portions; copies excluded). */
+ * _traces / _fit_percentiles or mhx_eval_function call ran (all portions; copies excluded). */
 int mhx_get_summary_timing(mhx_engine* e, double* kernel_ms);
 /* The same for a group, gathered in global chain order like mhx_group_get_state; every
  * device's launch is enqueued before any is waited for. */
@@ -831,6 +831,70 @@ int mhx_get_waic(mhx_engine* e, int fn, int take, double* elpd, double* lppd, do
 int mhx_group_get_waic(mhx_group* g, int fn, int take, double* elpd, double* lppd, double* p_waic,
                        int32_t* n_high, double* pw_lppd, double* pw_p, double* pw_acc,
                        int32_t* n_used, int32_t* status);
+
+/* ---- credible bands: the pointwise posterior of the fit curve, of every chain, on the device ring.
+ * mhx_get_fit_bands is the reference's envelope - the extremes of the model over the most probable
+ * steps, a plotting device whose width depends on take.  This is the posterior statement: at each
+ * x the percentiles, the mean and the standard deviation of f(x; theta_s) over the window.  The
+ * reference has no such function: the definition is this library's own and fixes the results
+ * operation by operation.  All arithmetic is plain IEEE binary64, never fused.
+ *   window      the newest n = min(take, walker-length, steps held) steps theta_0 (newest) ...
+ *               theta_{n-1}: the window of mhx_get_percentiles and mhx_get_waic, NOT the candidate
+ *               set of mhx_get_fit_bands.  n_used[c] = n
+ *   value       v_js = function fn at point j for theta_s, the very bits mhx_eval_function returns.
+ *               xcols, n_cols, m as for mhx_eval_function (NULL: the function's own x; two columns
+ *               where the function reads two)
+ *   percentile  pct[c][q][j] = nth-percentile (M:1495-1506) of the n values {v_js}_s at
+ *               pct_num[q] / pct_den[q] per cent: mhx_percentile_rank(n, ...) gives pos and
+ *               between; the result is the element at pos of the ascending order, or
+ *               (e[pos] + e[pos+1]) / 2 - one IEEE add, one IEEE divide - when between.  The order
+ *               is that of mhx_get_percentiles: -0 before +0 (they compare equal as numbers: either
+ *               may be returned), a NaN last whatever its sign.  Exact for any take: a radix
+ *               selection over the 64-bit order keys, nothing approximated
+ *   moments     over s = 0 .. n-1 in that order, k = s + 1, q_k = 1.0 / k (one division):
+ *                 delta = v - mean;  mean = mean + delta * q_k;  M2 = M2 + delta * (v - mean)
+ *               from mean = 0, M2 = 0 (mhx_get_waic's Welford recurrence).  mean[c][j] = the final
+ *               mean; stddev[c][j] = sqrt(M2 / (n - 1)): one IEEE divide, a correctly rounded
+ *               square root (n = 1: the IEEE 0/0, as mhx_get_derived)
+ *   status      a sum of
+ *                 MHX_FITPCT_NONFINITE  some v_js of the chain is not finite: the percentiles still
+ *                                       follow the order above, the moments are whatever IEEE
+ *                                       gives; no other chain is touched by it
+ *                 MHX_FITPCT_ONE_STEP   n = 1
+ *                 MHX_FITPCT_EMPTY      n = 0: the chain's numbers are unspecified, n_used[c] = 0
+ * pct [n_chains][n_pct][m]; mean, stddev [n_chains][m]; n_used, status [n_chains].  Any output
+ * may be NULL.  take in [1, history_capacity], fn a function of the problem, m >= 1, n_cols the
+ * function's, 0 <= n_pct <= MHX_MAX_PERCENTILES (0: the moments only), else MHX_EINVAL;
+ * MHX_ESTATE before mhx_init_chains; the outputs stay untouched on error.  A chain in
+ * MHX_CHAIN_FP_TRAP is served from the history it has.  Serves every model the engine can walk,
+ * an engine with a dataset per walker (mhx_set_dataset_planes) included: the call reads the model,
+ * the shared x and the ring only.  The results are the same bits from call to call, whatever
+ * portions the call is worked through in, whether the selection reads its columns from LDS or
+ * from memory (MHX_FITPCT_NO_LDS=1), and however a group's chains are split over its engines.
+ * Device scratch: the window's values of a portion are staged, take doubles per chain and point,
+ * and the points go in chunks of whole blocks of MHX_FITPCT_BLOCK so that a portion stays below
+ * 64 MiB whatever n_chains and m are.  ONE chain's smallest chunk - p = min(m, MHX_FITPCT_BLOCK)
+ * points - must fit: 8 p take bytes of values, 8 p (n_pct + 4) of x and results, 8 for the two
+ * counts and 2 KiB of alignment within 64 MiB: take <= 65529 - n_pct at m >= 128, more at fewer
+ * points (a ring of 65536 is served whole at m <= 127).  Beyond that the call is refused with
+ * MHX_EUNSUPPORTED and mhx_last_error names the greatest take that fits.
+ * mhx_get_summary_timing covers the call. */
+#define MHX_FITPCT_BLOCK 128 /* points of one block of mhx_get_fit_percentiles' value kernel */
+enum {
+  MHX_FITPCT_NONFINITE = 1,
+  MHX_FITPCT_ONE_STEP = 2,
+  MHX_FITPCT_EMPTY = 4
+};
+int mhx_get_fit_percentiles(mhx_engine* e, int fn, int take, const double* xcols, int n_cols,
+                            int64_t m, const int32_t* pct_num, const int32_t* pct_den, int n_pct,
+                            double* pct, double* mean, double* stddev, int32_t* n_used,
+                            int32_t* status);
+/* The same for a group, in global chain order; every device's work is enqueued before any is
+ * waited for. */
+int mhx_group_get_fit_percentiles(mhx_group* g, int fn, int take, const double* xcols, int n_cols,
+                                  int64_t m, const int32_t* pct_num, const int32_t* pct_den,
+                                  int n_pct, double* pct, double* mean, double* stddev,
+                                  int32_t* n_used, int32_t* status);
 
 /* ---- batched traces: the steps of EVERY chain, filtered and thinned on the device -------------
  * What (mapcar (lambda (w) (walker-get w :get :steps / :unique-steps / :forward-steps / :params /

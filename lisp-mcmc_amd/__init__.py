@@ -23,7 +23,7 @@ from .walker import (  # noqa: F401
     walker_adaptive_steps_full, walker_many_steps, walker_take_step, walker_get, walker_set_get,
     walker_modify, prior_bounds, log_prior_flat, request_stop, create_log_liklihood_function,
     walker_get_data_and_fit, walker_get_data_and_fit_no_stddev, walker_get_residuals,
-    walker_set_get_data_and_fit, fit_linspace,
+    walker_set_get_data_and_fit, fit_linspace, walker_get_fit_credible, walker_set_get_fit_credible,
     walker_with_exp, walker_exp_get, walker_set_with_exp, walker_set_exp_get,
     make_histo, make_histo_x, histo_edges, walker_param_histo, walker_set_param_histo,
     walker_set_corner_grid,
@@ -39,6 +39,7 @@ __all__ = ["capi", "MhxError", "Engine", "Group", "comm_unique_id", "partition",
            "prior_bounds", "log_prior_flat", "request_stop", "create_log_liklihood_function",
            "band_count", "walker_get_data_and_fit", "walker_get_data_and_fit_no_stddev",
            "walker_get_residuals", "walker_set_get_data_and_fit", "fit_linspace",
+           "walker_get_fit_credible", "walker_set_get_fit_credible",
            "walker_with_exp", "walker_exp_get", "walker_set_with_exp", "walker_set_exp_get",
            "make_histo", "make_histo_x", "histo_edges", "walker_param_histo", "walker_set_param_histo",
            "walker_set_corner_grid",

@@ -1413,7 +1413,7 @@ int mhx_create(const mhx_config* cfg, mhx_engine** out) {
     }
     if (family_w8().configure() != hipSuccess || family_w16().configure() != hipSuccess ||
         summary_configure() != hipSuccess || fit_configure() != hipSuccess ||
-        waic_configure() != hipSuccess) {
+        waic_configure() != hipSuccess || fitpct_configure() != hipSuccess) {
       rc = fail(MHX_EDEVICE, "hipFuncSetAttribute(max dynamic LDS = %zu / %zu) failed",
                 family_w8().lds_bytes, family_w16().lds_bytes);
       break;
@@ -2322,6 +2322,18 @@ static int fill_pcts(PctList* pc, const int32_t* num, const int32_t* den, int n_
   return MHX_OK;
 }
 
+// The cursor of call c on engine e: the call's own where it has one (c.cursor(e): a read-out whose
+// chunk of points depends on its arguments), else portion_cursor's over c.items and c.points.
+template <class Q>
+static auto cursor_for(const Q& c, const mhx_engine* e, int) -> decltype(c.cursor(e)) {
+  return c.cursor(e);
+}
+template <class Q>
+static PortionCursor cursor_for(const Q& c, const mhx_engine* e, long) {
+  return portion_cursor(c.items(e), c.points(),
+                        [&](Carver& cv, int64_t n, int64_t m) { c.carve(e, cv, n, m); });
+}
+
 // Call q on every engine of engs, engine i's results landing at item first[i] of the caller's
 // arrays (first NULL: one engine, item 0).  Round by round, every engine's portion is enqueued
 // before any is waited for; summary_ms gathers the kernels' time over the portions.
@@ -2339,8 +2351,7 @@ static int run_portions(const std::vector<mhx_engine*>& engs, const int64_t* fir
     for (HostDst& h : c.dst)
       if (h.p && first) h.p = h.at(first[i]);
     e->summary_ms = 0.0;
-    at[i] = portion_cursor(c.items(e), c.points(),
-                           [&](Carver& cv, int64_t n, int64_t m) { c.carve(e, cv, n, m); });
+    at[i] = cursor_for(c, e, 0);
   }
   auto give_up = [&](int code) {
     for (mhx_engine* e : engs) drain(e);
@@ -2848,6 +2859,124 @@ int mhx_get_waic(mhx_engine* e, int fn, int take, double* elpd, double* lppd, do
                  int32_t* n_high, double* pw_lppd, double* pw_p, double* pw_acc, int32_t* n_used,
                  int32_t* status) {
   return run_portions(e, WaicCall(fn, take, elpd, lppd, p_waic, n_high, pw_lppd, pw_p, pw_acc, n_used, status));
+}
+
+// ---- credible bands (include/mhx.h has the definition): every chain's pointwise percentiles and
+// moments of function fn over its window (k_fitpct_values, then the model-free k_fitpct_select).
+// An item is a chain.  The window's values of a portion are staged, `take` doubles per chain and
+// point, so the chunk of points is the call's own (fitpct_cursor, mhx_stage.hpp): whole blocks of
+// the value kernel, as many as let one chain fit the budget.
+struct FitPctCall {
+  int fn = 0, take = 0, n_cols = 1;
+  int64_t m = 0;
+  const double* xcols = nullptr;  // [n_cols][m] on the host, or NULL: the function's dataset
+  PctList pc{};
+  enum { PCT, MEAN, STDDEV, N_USED, STATUS };
+  HostDst dst[5];
+  static_assert(kFitPctBlock == MHX_FITPCT_BLOCK, "MHX_FITPCT_BLOCK (include/mhx.h)");
+
+  FitPctCall(int fn_, int take_, const double* xcols_, int n_cols_, int64_t m_, double* pct, double* mean,
+             double* stddev, int32_t* n_used, int32_t* status)
+      : fn(fn_), take(take_), n_cols(n_cols_), m(m_), xcols(xcols_) {
+    const size_t row = (size_t)std::max<int64_t>(m, 0) * sizeof(double);
+    dst[PCT].p = pct, dst[MEAN] = {mean, row}, dst[STDDEV] = {stddev, row};
+    dst[N_USED] = {n_used, sizeof(int32_t)}, dst[STATUS] = {status, sizeof(int32_t)};
+  }
+  int check(mhx_engine* e) {
+    int rc = window_check(e, take);
+    if (rc != MHX_OK || (rc = use_device(e)) != MHX_OK || (rc = finalize_problem(e)) != MHX_OK) return rc;
+    if (fn < 0 || fn >= e->P.K) return fail(MHX_EINVAL, "function %d out of range", fn);
+    if (n_cols != FitCall::fn_cols(e, fn))
+      return fail(MHX_EINVAL, "function %d reads %d column(s) of x, n_cols is %d", fn, FitCall::fn_cols(e, fn),
+                  n_cols);
+    if (!xcols && m != e->P.fn[fn].n)
+      return fail(MHX_EINVAL, "xcols is NULL: m must be the dataset's %lld points", (long long)e->P.fn[fn].n);
+    if (m < 1) return fail(MHX_EINVAL, "m must be >= 1");
+    if (cursor(e).chunk < 1)
+      return fail(MHX_EUNSUPPORTED, "mhx_get_fit_percentiles: the %d staged values of each of a chain's first %lld "
+                                    "points do not fit the 64 MiB of a portion: the greatest take that fits is %d",
+                  take, (long long)std::min<int64_t>(m, kFitPctBlock), fitpct_max_take(m, pc.n));
+    dst[PCT].item_bytes = (size_t)pc.n * (size_t)m * sizeof(double);
+    return MHX_OK;
+  }
+  int64_t items(const mhx_engine* e) const { return e->cfg.n_chains; }
+  int64_t points() const { return m; }
+  PortionCursor cursor(const mhx_engine* e) const { return fitpct_cursor(items(e), m, take, pc.n); }
+  FitPctPieces carve(const mhx_engine*, Carver& c, int64_t n_items, int64_t m_points) const {
+    return carve_fitpct(c, take, pc.n, n_items, m_points);
+  }
+  // chains [i0, i0 + n) at points [m0, m0 + m): the status gathers over the chunks of points
+  int upload(mhx_engine* e, const Portion& p) const {
+    Carver c;
+    const FitPctPieces s = carve(e, c, p.n, p.m);
+    const size_t mb = (size_t)p.m * sizeof(double);
+    if (xcols) {
+      HIP_TRY(hipMemcpyAsync(stage_at<double>(e, s.x0), xcols + p.m0, mb, hipMemcpyHostToDevice, e->stream));
+      if (n_cols > 1)
+        HIP_TRY(hipMemcpyAsync(stage_at<double>(e, s.x1), xcols + m + p.m0, mb, hipMemcpyHostToDevice, e->stream));
+    }
+    if (p.m0 == 0)
+      HIP_TRY(hipMemsetAsync(stage_at<int32_t>(e, s.status), 0, (size_t)p.n * sizeof(int32_t), e->stream));
+    return MHX_OK;
+  }
+  int launch(mhx_engine* e, const Portion& p) const {
+    Carver c;
+    const FitPctPieces s = carve(e, c, p.n, p.m);
+    const FnDesc& f = e->P.fn[fn];
+    const bool step_fastest = e->knobs.fitpct_step_fastest;
+    FitPctArgs A{};
+    A.c0 = p.i0, A.n = p.n;
+    A.take = take, A.fn = fn;
+    A.n_blocks = (int32_t)fitpct_blocks(p.m);
+    A.m = p.m;
+    A.vs_step = step_fastest ? 1 : p.m, A.vs_point = step_fastest ? take : 1;
+    if (xcols) {
+      A.x0 = stage_at<double>(e, s.x0);
+      A.x1 = n_cols > 1 ? stage_at<double>(e, s.x1) : nullptr;
+    } else {
+      A.x0 = f.x + p.m0;
+      A.x1 = f.n_xcols > 1 ? f.c + p.m0 : nullptr;
+    }
+    A.values = stage_at<double>(e, s.values);
+    A.mean = stage_at<double>(e, s.mean);
+    A.stddev = stage_at<double>(e, s.stddev);
+    A.status = stage_at<int32_t>(e, s.status);
+    HIP_TRY(e->spec == SPEC_USER ? rtc_launch_fitpct(*e->user_prog, e->stream, e->dP.p, e->S, A)
+                                 : launch_fitpct_values(e->spec, e->stream, e->dP.p, e->S, A));
+    // (no percentile asked for: the selection only completes n_used and the status - no column is laid down)
+    const bool lds = pc.n > 0 && !e->knobs.fitpct_no_lds && fitpct_cols(take) > 0;
+    HIP_TRY(launch_fitpct_select(e->stream, e->S, p.i0, p.n, take, p.m, A.vs_step, A.vs_point, pc, lds,
+                                 !e->knobs.fitpct_select_singly, A.values,
+                                 stage_at<double>(e, s.pct), stage_at<int32_t>(e, s.n_used), A.status));
+    e->launches++;
+    return MHX_OK;
+  }
+  int collect(mhx_engine* e, const Portion& p) const {
+    Carver c;
+    const FitPctPieces s = carve(e, c, p.n, p.m);
+    const size_t dv[3] = {s.pct, s.mean, s.stddev};
+    for (int k = 0; k < 3; ++k) {
+      const size_t rows = (size_t)p.n * (k == PCT ? (size_t)pc.n : 1);  // (pct: a row per chain and percentile)
+      if (dst[k].p && rows > 0)
+        HIP_TRY(hipMemcpy2D(static_cast<double*>(dst[k].at(p.i0)) + p.m0, (size_t)m * sizeof(double),
+                            stage_at<double>(e, dv[k]), (size_t)p.m * sizeof(double),
+                            (size_t)p.m * sizeof(double), rows, hipMemcpyDeviceToHost));
+    }
+    if (p.m0 + p.m < m) return MHX_OK;  // (the status gathers over the chunks of points)
+    int rc = copy_back(dst[N_USED], p.i0, p.n, stage_at<int32_t>(e, s.n_used));
+    if (rc != MHX_OK || (rc = copy_back(dst[STATUS], p.i0, p.n, stage_at<int32_t>(e, s.status))) != MHX_OK)
+      return rc;
+    return MHX_OK;
+  }
+};
+
+int mhx_get_fit_percentiles(mhx_engine* e, int fn, int take, const double* xcols, int n_cols, int64_t m,
+                            const int32_t* pct_num, const int32_t* pct_den, int n_pct, double* pct,
+                            double* mean, double* stddev, int32_t* n_used, int32_t* status) {
+  FitPctCall q(fn, take, xcols, n_cols, m, pct, mean, stddev, n_used, status);
+  int rc = window_check(e, take);
+  if (rc != MHX_OK || (rc = fill_pcts(&q.pc, pct_num, pct_den, n_pct)) != MHX_OK) return rc;
+  return run_portions(e, q);
 }
 
 // ---- walker-with-exp (M:1052-1064) and the posterior of the expression: derived quantities of
@@ -4086,6 +4215,15 @@ int mhx_group_get_fit_bands(mhx_group* g, int fn, int take, const double* xcols,
   return run_portions(g, FitCall(fn, take, -1, nullptr, xcols, n_cols, m, ymax, ymin, n_selected, status));
 }
 
+int mhx_group_get_fit_percentiles(mhx_group* g, int fn, int take, const double* xcols, int n_cols, int64_t m,
+                                  const int32_t* pct_num, const int32_t* pct_den, int n_pct, double* pct,
+                                  double* mean, double* stddev, int32_t* n_used, int32_t* status) {
+  FitPctCall q(fn, take, xcols, n_cols, m, pct, mean, stddev, n_used, status);
+  if (!g || g->eng.empty()) return fail(MHX_EINVAL, "group is NULL");
+  int rc = window_check(g->eng[0], take);
+  if (rc != MHX_OK || (rc = fill_pcts(&q.pc, pct_num, pct_den, n_pct)) != MHX_OK) return rc;
+  return run_portions(g, q);
+}
 int mhx_group_get_waic(mhx_group* g, int fn, int take, double* elpd, double* lppd, double* p_waic,
                        int32_t* n_high, double* pw_lppd, double* pw_p, double* pw_acc,
                        int32_t* n_used, int32_t* status) {

@@ -4239,6 +4239,216 @@ __global__ __launch_bounds__(kThreads) void k_waic_totals(ChainState S, int64_t 
 }
 #endif
 
+// mhx_get_fit_percentiles, first half (include/mhx.h has the definition): k_waic's walk over the
+// window with nothing behind the model.  Wave g serves chain g / n_blocks of the launch and block
+// g % n_blocks of its points: kFitPctPts points per lane, whose x and Welford pair {mean, M2} stay
+// in registers.  The window's steps are addressed by ring slot, newest first; each step's
+// parameter vector goes through the wave's LDS row with the next step's load in flight, then ONE
+// Spec::values (the bits of mhx_eval_function), the recurrence, and the values' stores into the
+// portion's stage piece (FitPctArgs has the layout).  Every product and sum is rounded on its own
+// (the unit is compiled without contraction; no fma is written here).
+template <class Spec>
+__device__ __forceinline__ void k_fitpct_values_body(const ProblemDesc* __restrict__ Pp, ChainState S,
+                                                     FitPctArgs A) {
+  FitLds& lds = *reinterpret_cast<FitLds*>(mhx_lds_raw);
+  lds_tables_begin();
+  __syncthreads();  // (the only barrier: waves without work leave behind it)
+  const int w = wave_in_group(), l = lane_id();
+  const int64_t g = (int64_t)blockIdx.x * kWavesPerGroup + w;
+  if (g >= A.n * A.n_blocks) return;
+  const int64_t i = g / A.n_blocks;
+  const int64_t p0 = (g - i * A.n_blocks) * (int64_t)(kWave * kFitPctPts) + l;
+  const FnDesc& f = Pp->fn[A.fn];
+  const int d = Pp->d;
+  double x0[kFitPctPts], x1[kFitPctPts], mean[kFitPctPts], m2[kFitPctPts];
+#pragma unroll
+  for (int j = 0; j < kFitPctPts; ++j) {
+    const int64_t p = p0 + (int64_t)j * kWave;
+    const int64_t q = p < A.m ? p : A.m - 1;  // (beyond m: the last point once more, never stored)
+    x0[j] = A.x0[q];
+    x1[j] = A.x1 ? A.x1[q] : 0.0;
+    mean[j] = m2[j] = 0.0;
+  }
+  const Ring r = ring_of(S, A.c0 + i);
+  const int n = ring_held(r, A.take);
+  double* th = lds.th[w];
+  double* const out = A.values + i * ((int64_t)A.take * A.m) + p0 * A.vs_point;
+  double thn = 0.0;
+  if (n > 0 && l < d) thn = r.theta[(int64_t)r.slot(0) * d + l];
+  bool bad = false;
+  for (int s = 0; s < n; ++s) {
+    if (l < d) th[l] = thn;
+    __builtin_amdgcn_wave_barrier();
+    if (s + 1 < n && l < d) thn = r.theta[(int64_t)r.slot(s + 1) * d + l];
+    auto pf = [&](int j) -> double { return th[f.idx[j]]; };
+    double v[kFitPctPts];
+    Spec::template values<kFitPctPts>(f, pf, lds.scr[w], x0, x1, v);
+    const double qk = 1.0 / (double)(s + 1);
+    double* const row = out + (int64_t)s * A.vs_step;
+#pragma unroll
+    for (int j = 0; j < kFitPctPts; ++j) {
+      const double e = v[j];
+      bad = bad || !finite_f64(e);
+      const double dl = e - mean[j];
+      mean[j] = mean[j] + dl * qk;
+      m2[j] = m2[j] + dl * (e - mean[j]);
+      if (p0 + (int64_t)j * kWave < A.m) row[(int64_t)j * kWave * A.vs_point] = e;
+    }
+  }
+  const double nm1 = (double)(n - 1);
+#pragma unroll
+  for (int j = 0; j < kFitPctPts; ++j) {
+    const int64_t p = p0 + (int64_t)j * kWave;
+    if (p < A.m) {
+      A.mean[i * A.m + p] = mean[j];
+      A.stddev[i * A.m + p] = __builtin_sqrt(m2[j] / nm1);
+    }
+  }
+  if (__ballot(bad) != 0ULL && l == 0) atomicOr(&A.status[i], (int32_t)MHX_FITPCT_NONFINITE);
+}
+#ifndef __HIPCC_RTC__
+template <class Spec>
+__global__ __launch_bounds__(kThreads) void k_fitpct_values(const ProblemDesc* __restrict__ Pp,
+                                                            ChainState S, FitPctArgs A) {
+  k_fitpct_values_body<Spec>(Pp, S, A);
+}
+#endif
+#if defined(MHX_FAMILY_PRIMARY) && !defined(__HIPCC_RTC__)
+// select_percentile for up to kSelTogether ranks of ONE column in the same 64 passes: a pass reads
+// every key once and tests it against each rank's prefix; a rank's count is the popcount of the
+// wave's ballot, kept in scalar registers - no per-lane counter, no reduction.  The passes a
+// column costs no longer grow with the percentiles asked for.  Each rank follows
+// select_percentile's own decisions bit by bit, so the results are its bits.  pos, between, out
+// [nq], nq <= kSelTogether; all lanes hold the same out.
+constexpr int kSelTogether = 4;
+template <class KeyAt>
+__device__ __forceinline__ void select_percentiles_together(KeyAt key_at, int n, int nq, const int* pos,
+                                                            const bool* between, double* out) {
+  const int l = lane_id();
+  unsigned long long prefix[kSelTogether], mask = 0;
+  int k[kSelTogether], cand[kSelTogether];
+#pragma unroll
+  for (int q = 0; q < kSelTogether; ++q) prefix[q] = 0, k[q] = q < nq ? pos[q] : 0, cand[q] = n;
+  for (int b = 63; b >= 0; --b) {
+    const unsigned long long bit = 1ULL << b, upto = mask | bit;
+    int cnt[kSelTogether] = {0, 0, 0, 0};
+    for (int s0 = 0; s0 < n; s0 += kWave) {
+      const bool in = s0 + l < n;
+      const unsigned long long key = in ? key_at(s0 + l) & upto : 0ULL;
+#pragma unroll
+      for (int q = 0; q < kSelTogether; ++q)  // (a candidate whose bit is 0: its bits down to b are the prefix)
+        if (q < nq) cnt[q] += (int)__popcll(__ballot(in && key == prefix[q]));
+    }
+#pragma unroll
+    for (int q = 0; q < kSelTogether; ++q) {
+      if (k[q] < cnt[q]) {
+        cand[q] = cnt[q];
+      } else {
+        k[q] -= cnt[q];
+        cand[q] -= cnt[q];
+        prefix[q] |= bit;
+      }
+    }
+    mask |= bit;
+  }
+#pragma unroll
+  for (int q = 0; q < kSelTogether; ++q) {
+    if (q >= nq) continue;
+    const double lo = key_value(prefix[q]);
+    if (!between[q]) {
+      out[q] = lo;
+      continue;
+    }
+    unsigned long long up = prefix[q];
+    if (k[q] + 1 >= cand[q]) {  // (the last of its run of equal keys: the smallest key above it)
+      unsigned long long m = ~0ULL;
+      for (int s = l; s < n; s += kWave) {
+        const unsigned long long key = key_at(s);
+        if (key > prefix[q] && key < m) m = key;
+      }
+      up = wave_min_u64(m);
+    }
+    out[q] = (lo + key_value(up)) / 2.0;
+  }
+}
+
+// mhx_get_fit_percentiles, second half: the percentiles of the staged values, model-free.  One
+// workgroup of kPctWaves wavefronts serves chain i and `cols` neighbouring points; wave w takes
+// the points w, w + kPctWaves, ... of them and reruns the selection for every percentile.
+//   use_lds = 1: the t values of each of the workgroup's points are laid down as keys, one column
+//     of `tpad` slots a point - read once; with a step's points side by side in memory the read is
+//     the transposing one of k_percentiles (tpad staggers the columns over the banks)
+//   use_lds = 0 (not even one column fits, or MHX_FITPCT_NO_LDS=1): every pass reads the stage
+// together = 1: a column's percentiles share their passes, kSelTogether at a time
+// (select_percentiles_together); 0 (MHX_FITPCT_SELECT_SINGLY=1): select_percentile once for each.
+// The workgroup of a chain's first points also completes the chain's n_used and status.
+// pct [n][n_pct][m].
+__global__ __launch_bounds__(kPctThreads) void k_fitpct_select(
+    ChainState S, int64_t c0, int take, int64_t m, int cols, int n_groups, int64_t vs_step,
+    int64_t vs_point, PctList pc, int use_lds, int together, int tpad, const double* __restrict__ vals,
+    double* __restrict__ pct, int32_t* __restrict__ n_used, int32_t* __restrict__ status) {
+  unsigned long long* col = reinterpret_cast<unsigned long long*>(mhx_lds_raw);
+  const int w = wave_in_group(), l = lane_id();
+  const int64_t i = blockIdx.x / n_groups;
+  const int64_t p0 = (int64_t)(blockIdx.x - i * n_groups) * cols;
+  const int nc = (int)(m - p0 < cols ? m - p0 : cols);
+  const Ring ring = ring_of(S, c0 + i);
+  const int t = ring_held(ring, take);
+  const double* v = vals + i * ((int64_t)take * m) + p0 * vs_point;
+  if (p0 == 0 && threadIdx.x == 0) {
+    n_used[i] = t;
+    if (t == 1) atomicOr(&status[i], (int32_t)MHX_FITPCT_ONE_STEP);
+    if (t == 0) atomicOr(&status[i], (int32_t)MHX_FITPCT_EMPTY);
+  }
+  if (use_lds) {
+    if (vs_point == 1) {
+      for (int f = threadIdx.x; f < t * cols; f += kPctThreads) {
+        const int s = f / cols, q = f - s * cols;
+        if (q < nc) col[(size_t)q * tpad + s] = order_key(v[(int64_t)s * vs_step + q]);
+      }
+    } else {
+      for (int q = 0; q < nc; ++q)
+        for (int s = threadIdx.x; s < t; s += kPctThreads)
+          col[(size_t)q * tpad + s] = order_key(v[(int64_t)s * vs_step + (int64_t)q * vs_point]);
+    }
+    __syncthreads();
+  }
+  for (int q = w; q < nc; q += kPctWaves) {
+    const unsigned long long* cp = col + (size_t)q * tpad;
+    const double* vp = v + (int64_t)q * vs_point;
+    for (int k0 = 0; k0 < pc.n; k0 += together ? kSelTogether : 1) {
+      const int nq = together ? (pc.n - k0 < kSelTogether ? pc.n - k0 : kSelTogether) : 1;
+      double r[kSelTogether] = {0.0, 0.0, 0.0, 0.0};
+      if (t > 0) {
+        int pos[kSelTogether] = {0, 0, 0, 0};
+        bool between[kSelTogether] = {false, false, false, false};
+#pragma unroll
+        for (int j = 0; j < kSelTogether; ++j)
+          if (j < nq) {
+            int64_t at;
+            int32_t half;
+            percentile_rank_of(t, pc.num[k0 + j], pc.den[k0 + j], &at, &half);
+            pos[j] = (int)at, between[j] = half != 0;
+          }
+        if (!together) {
+          r[0] = use_lds ? select_percentile([&](int s) { return cp[s]; }, t, pos[0], between[0])
+                         : select_percentile([&](int s) { return order_key(vp[(int64_t)s * vs_step]); }, t,
+                                             pos[0], between[0]);
+        } else if (use_lds) {
+          select_percentiles_together([&](int s) { return cp[s]; }, t, nq, pos, between, r);
+        } else {
+          select_percentiles_together([&](int s) { return order_key(vp[(int64_t)s * vs_step]); }, t, nq, pos,
+                                      between, r);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < kSelTogether; ++j)
+        if (j < nq && l == 0) pct[(i * pc.n + k0 + j) * m + p0 + q] = r[j];
+    }
+  }
+}
+#endif
+
 }  // inline namespace MHX_FAMILY
 }  // namespace mhx
 

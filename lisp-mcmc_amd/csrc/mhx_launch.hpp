@@ -182,4 +182,25 @@ hipError_t launch_waic_totals(hipStream_t st, const ChainState& S, int64_t c0, i
                               const int32_t* part_high, double* elpd, double* lppd, double* p_waic,
                               int32_t* n_high, int32_t* n_used, int32_t* status);
 
+// mhx_get_fit_percentiles: the values and moments (FitPctArgs, mhx_types.hpp) for the
+// ahead-of-time specs - run-time compiled problems go through rtc_launch_fitpct - and the
+// model-free selection over the staged values.  fitpct_cols: the neighbouring points one
+// selection workgroup takes - the most of 8, 4, 2, 1 whose key columns fit kPctLdsBudget (two
+// workgroups a CU), 0 where not even one column does: the selection then reads the stage.
+// together: a column's percentiles share their passes (select_percentiles_together).
+inline int64_t fitpct_blocks(int64_t m) { return (m + MHX_FITPCT_BLOCK - 1) / MHX_FITPCT_BLOCK; }
+inline int fitpct_cols(int take) {
+  for (int c = 8; c >= 1; c >>= 1)
+    if (pct_lds_bytes(take, c) <= kPctLdsBudget) return c;
+  return 0;
+}
+constexpr int kFitPctMemCols = 4;  // ... a workgroup's points on the memory path: one per wave
+hipError_t fitpct_configure();
+hipError_t launch_fitpct_values(int spec, hipStream_t st, const ProblemDesc* P, const ChainState& S,
+                                const FitPctArgs& A);
+hipError_t launch_fitpct_select(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
+                                int64_t m, int64_t vs_step, int64_t vs_point, const PctList& pc,
+                                bool use_lds, bool together, const double* vals, double* pct,
+                                int32_t* n_used, int32_t* status);
+
 }  // namespace mhx

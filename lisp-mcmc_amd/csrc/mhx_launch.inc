@@ -436,6 +436,42 @@ hipError_t launch_waic_totals(hipStream_t st, const ChainState& S, int64_t c0, i
   return hipGetLastError();
 }
 
+// mhx_get_fit_percentiles (k_fitpct_values, k_fitpct_select): as k_waic, compiled in this family only
+hipError_t fitpct_configure() {
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fitpct_select),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPctLdsBudget);
+  for (int s = 0; s < SPEC__COUNT; ++s)
+    for_spec(s, [&](auto sp) {
+      using SpecT = decltype(sp);
+      if (e == hipSuccess) e = no_static_lds(&k_fitpct_values<SpecT>);
+    });
+  return e;
+}
+hipError_t launch_fitpct_values(int spec, hipStream_t st, const ProblemDesc* P, const ChainState& S,
+                                const FitPctArgs& A) {
+  if (A.n <= 0 || A.m <= 0) return hipSuccess;
+  for_spec(spec, [&](auto sp) {
+    using SpecT = decltype(sp);
+    k_fitpct_values<SpecT><<<grid_for(A.n * A.n_blocks), dim3(kThreads), fit_lds_bytes(kWavesPerGroup), st>>>(P, S, A);
+  });
+  return hipGetLastError();
+}
+hipError_t launch_fitpct_select(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
+                                int64_t m, int64_t vs_step, int64_t vs_point, const PctList& pc,
+                                bool use_lds, bool together, const double* vals, double* pct,
+                                int32_t* n_used, int32_t* status) {
+  if (n <= 0 || m <= 0) return hipSuccess;
+  const int cols = use_lds ? fitpct_cols(take) : kFitPctMemCols;
+  if (cols <= 0) return hipErrorInvalidValue;
+  const size_t lds = use_lds ? pct_lds_bytes(take, cols) : 0;
+  const int64_t n_groups = (m + cols - 1) / cols;
+  if (lds > kPctLdsBudget || n * n_groups > (int64_t)0x7fffffff) return hipErrorInvalidValue;
+  k_fitpct_select<<<dim3((unsigned)(n * n_groups)), dim3(kPctThreads), lds, st>>>(
+      S, c0, take, m, cols, (int)n_groups, vs_step, vs_point, pc, use_lds ? 1 : 0, together ? 1 : 0,
+      pct_column_pitch(take, cols), vals, pct, n_used, status);
+  return hipGetLastError();
+}
+
 const char* spec_name(int spec) {
   static const char* names[] = {"generic",      "gauss22_normal", "gauss15_poisson",
                                            "pvoigt2_normal", "poly2_normal",   "poly8_normal",

@@ -269,4 +269,63 @@ PortionCursor portion_cursor(int64_t items, int64_t points, Carve&& carve) {
   return at;
 }
 
+// ---- pointwise percentiles of the fit (mhx_get_fit_percentiles): n chains at m points.  What
+// depends on the chains alone comes first and keeps its place from one chunk of points to the
+// next - status, n_used [n] - then x0, x1 [m], the staged values [n][take][m] (a chain's window
+// step by step, the points of a step side by side) and the results pct [n][n_pct][m], mean,
+// stddev [n][m].
+constexpr int64_t kFitPctBlock = 128;  // points of a block of the value kernel (MHX_FITPCT_BLOCK)
+static_assert(kFitChunkPoints % kFitPctBlock == 0, "a chunk of points is whole blocks");
+struct FitPctPieces {
+  size_t status, n_used, x0, x1, values, pct, mean, stddev;
+};
+inline FitPctPieces carve_fitpct(Carver& c, int take, int n_pct, int64_t n_, int64_t m_) {
+  const size_t n = (size_t)n_, m = (size_t)m_;
+  FitPctPieces s;
+  s.status = c.take(n * sizeof(int32_t));
+  s.n_used = c.take(n * sizeof(int32_t));
+  s.x0 = c.take(m * sizeof(double));
+  s.x1 = c.take(m * sizeof(double));
+  s.values = c.take(n * m * (size_t)take * sizeof(double));
+  s.pct = c.take(n * (size_t)n_pct * m * sizeof(double));
+  s.mean = c.take(n * m * sizeof(double));
+  s.stddev = c.take(n * m * sizeof(double));
+  return s;
+}
+// whether ONE chain's pieces at m points fit the budget
+inline bool fitpct_fits(int take, int n_pct, int64_t m) {
+  return one_item_fits([&](Carver& c, int64_t n) { carve_fitpct(c, take, n_pct, n, m); });
+}
+// The cursor of the call.  portion_cursor's fixed chunk would ask 1 GB of one chain at take 1000:
+// here the chunk of points is all of `points` where one chain fits the budget with them (and they
+// are at most kFitChunkPoints), else the largest whole number of blocks, at most kFitChunkPoints,
+// with which one chain fits.  chunk == 0: not even one block fits - the caller refuses the call.
+inline PortionCursor fitpct_cursor(int64_t items, int64_t points, int take, int n_pct) {
+  PortionCursor at;
+  at.items = items;
+  at.points = points;
+  if (points <= kFitChunkPoints && fitpct_fits(take, n_pct, points)) {
+    at.chunk = points;
+  } else {
+    int64_t lo = 0, hi = std::min(points, kFitChunkPoints) / kFitPctBlock;  // blocks: lo fits, hi + 1 does not
+    while (lo < hi) {
+      const int64_t mid = (lo + hi + 1) / 2;
+      if (fitpct_fits(take, n_pct, mid * kFitPctBlock)) lo = mid; else hi = mid - 1;
+    }
+    at.chunk = lo * kFitPctBlock;
+  }
+  at.per_portion = at.chunk > 0 ? portion_of([&](Carver& c, int64_t n) { carve_fitpct(c, take, n_pct, n, at.chunk); }) : 1;
+  return at;
+}
+// the greatest take at which one chain's smallest chunk of `points` fits (0: none does)
+inline int fitpct_max_take(int64_t points, int n_pct) {
+  const int64_t m = std::min(points, kFitPctBlock);
+  int lo = 0, hi = 1 << 30;
+  while (lo < hi) {
+    const int mid = lo + (hi - lo + 1) / 2;
+    if (fitpct_fits(mid, n_pct, m)) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
 }  // namespace mhx

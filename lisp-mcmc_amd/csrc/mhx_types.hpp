@@ -272,6 +272,37 @@ struct WaicArgs {
   int32_t* status;     // [n] MHX_WAIC_NONFINITE is stored where a value or a term is not finite
 };
 
+// k_fitpct_values (mhx_get_fit_percentiles): the model of function `fn` at m points for every step
+// of the window of each of n chains from c0 on, and the Welford moments of those values per point.
+// A wave serves one chain and one block of MHX_FITPCT_BLOCK = kWave x kFitPctPts points; n_blocks
+// blocks cover m.  The value of point p at the step s-th from newest goes to
+// values[i * take * m + s * vs_step + p * vs_point]: vs_step = m, vs_point = 1 lays a step's
+// points side by side (the stores of a wave are whole lines; the selection transposes on its way
+// into LDS), vs_step = 1, vs_point = take lays a point's steps side by side.
+// kFitPctPts = 2.  Registers would allow k_fit's 8: a lane keeps four doubles per point (x0, x1,
+// mean, M2), what k_fit keeps (x0, x1, max, min), and as compiled for gfx950 with 8 points the
+// two-peak instance took 118 VGPRs and none used scratch.  But the values are staged, `take`
+// doubles per chain and point, and the stage budget (mhx_stage.hpp: 64 MiB) bounds the points in
+// flight, not the registers: at take 1000 a portion is 8 388 (chain, point) pairs, which is 16
+// waves of 512 points - two workgroups on a GPU of 256 CUs - or 66 waves of 128.  A wave's time
+// is its window's steps, one after the other, whatever it holds; fewer points per lane shorten
+// the step and spread the portion over more CUs.  Below 2 a step is shorter than the latency of
+// the next step's parameter row, which is the only load in flight.  MHX_FITPCT_BLOCK must divide
+// kFitChunkPoints, so the choice is among powers of two.
+constexpr int kFitPctPts = MHX_FITPCT_BLOCK / kWave;
+static_assert(kFitPctPts * kWave == MHX_FITPCT_BLOCK && kFitPctPts == 2, "MHX_FITPCT_BLOCK (include/mhx.h)");
+struct FitPctArgs {
+  int64_t c0, n;
+  int32_t take, fn, n_blocks, pad_;
+  int64_t m, vs_step, vs_point;
+  const double* x0;  // [m]
+  const double* x1;  // [m] the second column of x, or nullptr
+  double* values;    // [n][take * m]
+  double* mean;      // [n][m]
+  double* stddev;    // [n][m]
+  int32_t* status;   // [n] MHX_FITPCT_NONFINITE is or-ed in where a value is not finite
+};
+
 // mhx_user_derived (mhx_get_derived, mhx_derived.hpp): the expressions of one run-time compiled
 // module over the windows of the n chains from c0 on.  idx[j] = the place in theta of the j-th
 // name; values [n][n_expr][pitch] newest first, at_best [n][n_expr] (the most-likely step).

@@ -82,6 +82,28 @@ class _Summaries:
                                               st.ctypes.data_as(capi.i32p)))
         return ymax, ymin, nsel, st
 
+    def fit_percentiles(self, fn, take, xs=None, pcts=((5, 2), (50, 1), (195, 2)), m=None):
+        """the pointwise posterior of the fit curve of every chain (mhx_get_fit_percentiles, which
+        has the definition): at each of the points xs ([m] or [n_cols, m]; None: the function's
+        own dataset x, `m` its point count) the percentiles pcts - numbers or (num, den) pairs, by
+        default the 2.5, 50 and 97.5 per cent points - the mean and the standard deviation of
+        function `fn` over each chain's newest `take` steps.  Returns pct [n_chains, len(pcts), m],
+        mean and stddev [n_chains, m], n_used [n_chains] and status [n_chains] (a sum of
+        FITPCT_NONFINITE 1, FITPCT_ONE_STEP 2, FITPCT_EMPTY 4)."""
+        xa, xp, n_cols, m = _x_columns(self, fn, xs, m)
+        rat = [p if isinstance(p, tuple) else percentile_ratio(p) for p in pcts]
+        num, nump = capi.as_i32([r[0] for r in rat] or [0])
+        den, denp = capi.as_i32([r[1] for r in rat] or [1])
+        pct = np.zeros((self.n_chains, len(rat), m))
+        mean, sd = np.zeros((self.n_chains, m)), np.zeros((self.n_chains, m))
+        used = np.zeros(self.n_chains, dtype=np.int32)
+        st = np.zeros(self.n_chains, dtype=np.int32)
+        capi.check(self._summary("fit_percentiles")(
+            self._h, int(fn), int(take), xp, n_cols, m, nump, denp, len(rat),
+            pct.ctypes.data_as(capi.f64p), mean.ctypes.data_as(capi.f64p), sd.ctypes.data_as(capi.f64p),
+            used.ctypes.data_as(capi.i32p), st.ctypes.data_as(capi.i32p)))
+        return pct, mean, sd, used, st
+
     def derived(self, exprs, names, index, take, percentiles=(), values=False):
         """walker-with-exp for every step of every chain, and its posterior (mhx_get_derived): the
         C-syntax expressions `exprs` over names[i] = theta[index[i]] (and `prob`) on each chain's

@@ -271,6 +271,18 @@ library, or without a gfx950 device, walker-create signals MHX-ERROR."
   (g :pointer) (fn :int) (take :int) (elpd :pointer) (lppd :pointer) (p-waic :pointer)
   (n-high :pointer) (pw-lppd :pointer) (pw-p :pointer) (pw-acc :pointer) (n-used :pointer)
   (status :pointer))
+;; credible bands: pointwise percentiles and moments of the fit (status: a sum of the three constants)
+(defconstant +fitpct-nonfinite+ 1)
+(defconstant +fitpct-one-step+ 2)
+(defconstant +fitpct-empty+ 4)
+(cffi:defcfun ("mhx_get_fit_percentiles" %mhx-get-fit-percentiles) :int
+  (e :pointer) (fn :int) (take :int) (xcols :pointer) (n-cols :int) (m :int64) (pct-num :pointer)
+  (pct-den :pointer) (n-pct :int) (pct :pointer) (mean :pointer) (stddev :pointer)
+  (n-used :pointer) (status :pointer))
+(cffi:defcfun ("mhx_group_get_fit_percentiles" %mhx-group-get-fit-percentiles) :int
+  (g :pointer) (fn :int) (take :int) (xcols :pointer) (n-cols :int) (m :int64) (pct-num :pointer)
+  (pct-den :pointer) (n-pct :int) (pct :pointer) (mean :pointer) (stddev :pointer)
+  (n-used :pointer) (status :pointer))
 (cffi:defcfun ("mhx_get_traces" %mhx-get-traces) :int
   (e :pointer) (take :int) (filter :int) (stride :int) (start :int) (cols :pointer) (n-cols :int)
   (max-out :int) (values :pointer) (lo :pointer) (hi :pointer) (n-out :pointer) (n-kept :pointer)

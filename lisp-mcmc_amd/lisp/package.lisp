@@ -18,6 +18,7 @@
    #:walker-take-step #:walker-take-step-injected #:walker-get #:walker-set-get #:walker-modify
    #:walker-destroy
    #:walker-get-data-and-fit #:walker-get-data-and-fit-no-stddev #:walker-get-residuals
+   #:walker-get-fit-credible #:walker-set-get-fit-credible
    #:walker-with-exp #:walker-exp-get #:walker-set-exp-get
    #:make-histo #:make-histo-x #:walker-param-histo #:walker-set-param-histo
    #:walker-set-corner-grid

@@ -1303,6 +1303,76 @@ model value at every x-fit over the (ceiling (* 0.66 take)) most probable steps 
         (cffi:foreign-free ymax)
         (cffi:foreign-free ymin)))))
 
+;;; ------------------------------------------------------------------ credible bands of the fit
+;;; walker-get-data-and-fit's max-ys / min-ys are the reference's envelope, whose width depends on
+;;; :take.  The pointwise posterior of the curve - percentiles, mean and standard deviation of the
+;;; model at each x over the window - is mhx_get_fit_percentiles (include/mhx.h has the
+;;; definition): every walker of a set in one device call, no history moved.
+(defun %credible-points (band who)
+  "the (num . den) per cent points (low median high) of BAND: :95cr, :iqr or (:percentile low high)"
+  (flet ((ratio (n) (cons (round (* 1000 n)) 1000)))
+    (cond ((and (consp band) (eq (first band) :percentile) (= 3 (length band))
+                (<= 0 (second band) (third band) 100))
+           (list (ratio (second band)) '(50 . 1) (ratio (third band))))
+          ((eq band :95cr) '((5 . 2) (50 . 1) (195 . 2)))
+          ((eq band :iqr) '((25 . 1) (50 . 1) (75 . 1)))
+          (t (error 'mhx-error :code -1
+                               :message (format nil "~a: a band is :95cr, :iqr or (:percentile low high), not ~s"
+                                                who band))))))
+
+(defun %fit-credible (walker take points band x-column fn-number chains who)
+  "the entries (x-fit hi lo median mean stddev) of the walkers CHAINS from one device call"
+  (let* ((n (walker-n-chains walker))
+         (m points)
+         (x-data (elt (elt (walker-data walker) fn-number) x-column))
+         (x-fit (%even-grid (reduce #'min x-data) (reduce #'max x-data) m))
+         (window (%bin-window walker take who))
+         (per-cent (%credible-points band who))
+         (pct (cffi:foreign-alloc :double :count (* n 3 m)))
+         (mean (cffi:foreign-alloc :double :count (* n m)))
+         (sd (cffi:foreign-alloc :double :count (* n m))))
+    (unwind-protect
+         (cffi:with-foreign-objects ((xp :double m) (num :int32 3) (den :int32 3) (st :int32 n))
+           (fill-doubles xp x-fit)
+           (fill-int32s num (mapcar #'car per-cent))
+           (fill-int32s den (mapcar #'cdr per-cent))
+           (%set-call walker #'%mhx-get-fit-percentiles #'%mhx-group-get-fit-percentiles
+                      fn-number window xp 1 m num den 3 pct mean sd (cffi:null-pointer) st)
+           (loop for c in chains
+                 do (when (oddp (cffi:mem-aref st :int32 c))
+                      (error 'floating-point-invalid-operation
+                             :operation who :operands (list :chain c)))
+                 collect (flet ((row (ptr offset)
+                                  (loop for i below m
+                                        collect (cffi:mem-aref ptr :double (+ offset i)))))
+                           (list x-fit
+                                 (row pct (* (+ (* c 3) 2) m))
+                                 (row pct (* (* c 3) m))
+                                 (row pct (* (+ (* c 3) 1) m))
+                                 (row mean (* c m))
+                                 (row sd (* c m))))))
+      (cffi:foreign-free pct)
+      (cffi:foreign-free mean)
+      (cffi:foreign-free sd))))
+
+(defun walker-get-fit-credible (walker &key (take 1000) (points 1000) (band :95cr) (x-column 0)
+                                         (fn-number 0) (chain 0))
+  "-> (x-fit hi lo median mean stddev): at POINTS points between the data's least and greatest x
+the BAND - :95cr, :iqr or (:percentile low high) - the median, the mean and the standard deviation
+of function FN-NUMBER over the walk's newest TAKE steps, computed on the device.
+FLOATING-POINT-INVALID-OPERATION where a model value of the window is not finite.  The device call
+is the whole set's: for more than a few walkers call walker-set-get-fit-credible once."
+  (first (%fit-credible walker take points band x-column fn-number (list chain)
+                        'walker-get-fit-credible)))
+
+(defun walker-set-get-fit-credible (walker &key (take 1000) (points 1000) (band :95cr) (x-column 0)
+                                             (fn-number 0))
+  "walker-get-fit-credible for every walker of the set, from ONE device call: a list with one entry
+per chain"
+  (%fit-credible walker take points band x-column fn-number
+                 (loop for c below (walker-n-chains walker) collect c)
+                 'walker-set-get-fit-credible))
+
 (defun walker-get-residuals (walker &key (take 1000) (x-column 0) (y-column 1) (fn-number 0)
                                       (chain 0))
   "-> (x-data residuals stddev): the model at the median parameters minus the data, at the

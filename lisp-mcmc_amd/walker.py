@@ -841,6 +841,67 @@ def walker_set_get_data_and_fit(walker, take=1000, x_column=0, y_column=1, fn_nu
                          y_shift, None, "walker-set-get-data-and-fit")
 
 
+def _credible_pcts(band, who):
+    """the (lo, median, hi) percentiles of a band: ':95cr', ':iqr' or (':percentile', lo, hi)"""
+    if isinstance(band, (tuple, list)):
+        if len(band) != 3 or str(band[0]).lstrip(":").lower() != "percentile":
+            raise ValueError("%s: a band is ':95cr', ':iqr' or (':percentile', lo, hi), not %r" % (who, band))
+        lo, hi = band[1], band[2]
+    else:
+        pair = {"95cr": (2.5, 97.5), "iqr": (25, 75)}.get(str(band).lstrip(":").lower())
+        if pair is None:
+            raise ValueError("%s: a band is ':95cr', ':iqr' or (':percentile', lo, hi), not %r" % (who, band))
+        lo, hi = pair
+    if not 0 <= lo <= hi <= 100:
+        raise ValueError("%s: the band's percentiles must satisfy 0 <= lo <= hi <= 100, not %r, %r" % (who, lo, hi))
+    return [lo, 50, hi]
+
+
+def _fit_credible(walker, take, points, band, x_column, fn_number, chains, who):
+    e = walker.engine
+    lengths = e.state()["length"].astype(np.int64)
+    data = walker.data_of(fn_number, 0)
+    x_data = np.asarray(data[x_column], dtype=np.float64)
+    if x_data.ndim != 1:
+        raise capi.MhxError(capi.EUNSUPPORTED, "%s draws one column of x: a vector-valued x has no min "
+                            "and max (use Engine.fit_percentiles)" % who)
+    x_fit = fit_linspace(x_data.min(), x_data.max(), int(points))
+    which = range(e.n_chains) if chains is None else [chains]
+    big = int(lengths.max()) if take is None else int(take)
+    pct, mean, sd, _, status = e.fit_percentiles(
+        fn_number, _band_take(walker, big, lengths[list(which)], who), x_fit, _credible_pcts(band, who))
+    bad = [c for c in which if status[c] & capi.FITPCT_NONFINITE]
+    if bad:
+        raise FloatingPointError(
+            "%s: the model is not finite at a step of walker(s) %s: the reference would have "
+            "signalled a floating-point trap here" % (who, bad[:8]))
+    return [[list(x_fit), list(pct[c, 2]), list(pct[c, 0]), list(pct[c, 1]), list(mean[c]), list(sd[c])]
+            for c in which]
+
+
+def walker_get_fit_credible(walker, take=1000, points=1000, band=":95cr", x_column=0, fn_number=0,
+                            chain=0):
+    """The credible band of the fit: [x_fit, hi, lo, median, mean, stddev], the pointwise
+    posterior of function fn_number over the walk's newest `take` steps at `points` points between
+    the data's least and greatest x (fit_linspace, as walker_get_data_and_fit), computed on the
+    device (mhx_get_fit_percentiles, which has the definition).  band: ':95cr' (the 2.5 and 97.5
+    per cent points), ':iqr' (25, 75) or (':percentile', lo, hi); the median is the 50 per cent
+    point; stddev is NaN for a walk of one step.  Where walker_get_data_and_fit's max_ys / min_ys
+    are the reference's envelope - whose width depends on take - these are percentiles with a
+    coverage meaning.  Raises FloatingPointError where a model value of the window is not finite.
+    The device call is the whole set's: for more than a few walkers call
+    walker_set_get_fit_credible once."""
+    return _fit_credible(walker, take, points, band, x_column, fn_number, int(chain),
+                         "walker-get-fit-credible")[0]
+
+
+def walker_set_get_fit_credible(walker, take=1000, points=1000, band=":95cr", x_column=0, fn_number=0):
+    """walker_get_fit_credible mapped over the set: entry c is what
+    walker_get_fit_credible(..., chain=c) returns, from ONE device call per function."""
+    return _fit_credible(walker, take, points, band, x_column, fn_number, None,
+                         "walker-set-get-fit-credible")
+
+
 def walker_get_residuals(walker, take=1000, x_column=0, y_column=1, fn_number=0, chain=0):
     """the data of walker-plot-residuals M:1271-1283 without the plot: [x_data, y_fit - y_data,
     stddev] at the median parameters over `take`; y_fit at the dataset's own x, which is on the
