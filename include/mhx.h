@@ -481,7 +481,7 @@ int mhx_get_window_best(mhx_engine* e, int take, double* prob, double* theta);
 int mhx_get_history_capacity(mhx_engine* e, int32_t* capacity);
 /* HIP-event milliseconds the kernels of the engine's last mhx_get_percentiles / _covariances /
  * _proposal_factors / _window_best / _fit_bands / _derived / _histograms / _pair_grids / _waic /
- * _traces / _fit_percentiles or mhx_eval_function call ran (all portions; copies excluded). */
+ * _traces / _fit_percentiles / _residuals or mhx_eval_function call ran (all portions; copies excluded). */
 int mhx_get_summary_timing(mhx_engine* e, double* kernel_ms);
 /* The same for a group, gathered in global chain order like mhx_group_get_state; every
  * device's launch is enqueued before any is waited for. */
@@ -895,6 +895,68 @@ int mhx_group_get_fit_percentiles(mhx_group* g, int fn, int take, const double* 
                                   int64_t m, const int32_t* pct_num, const int32_t* pct_den,
                                   int n_pct, double* pct, double* mean, double* stddev,
                                   int32_t* n_used, int32_t* status);
+
+/* ---- which walkers fit badly: walker-plot-residuals (M:1271-1292) without the plotting, for EVERY
+ * walker of a set, with the goodness-of-fit statistics of the standardized residuals reduced on the
+ * device.  For each chain c function `fn` is evaluated at ONE parameter vector over the chain's own
+ * data; the fit values and the residuals themselves come back only when asked for.  The definition
+ * fixes the results operation by operation; all arithmetic is plain IEEE binary64 multiply, add,
+ * subtract, divide and square root, never fused.  N is the function's point count.
+ *   theta    [n_chains][d], the caller's vectors (the medians mhx_get_percentiles returned, say);
+ *            NULL: each chain's most-likely parameters, which are on the device
+ *   data     the function's shared dataset, or chain c's own plane where the engine was given a
+ *            dataset per walker (mhx_set_dataset_planes; all four sigma_kinds), in the numbers the
+ *            engine formed when the dataset was set and holds on the device: w_i = 1 / sigma_i,
+ *            ys_i = y_i * w_i (MHX_SIGMA_PER_CHAIN: the walker's one w; MHX_SIGMA_NONE and a NULL
+ *            sigma: 1.0); for Poisson the raw counts y_i.  Nothing is uploaded per point.
+ *   value    v_i = function fn at the dataset's own x_i for theta_c, the very bits
+ *            mhx_eval_function returns.  fit[c][i] = v_i
+ *   z        the standardized residual, fit minus data as the reference has it (M:1283):
+ *              MHX_LIK_NORMAL, MHX_LIK_NORMAL_CUTOFF   a = v_i * w_i;  z_i = a - ys_i
+ *              MHX_LIK_POISSON (Pearson)               dl = v_i - y_i;  rt = sqrt(v_i) (correctly
+ *                                                      rounded);  z_i = dl / rt (one division)
+ *              MHX_LIK_EXPR                            refused (MHX_EUNSUPPORTED): an expression
+ *                                                      likelihood's `error` need not be a sigma
+ *            z[c][i] = z_i
+ *   point    in dataset order i = 0 .. N-1:  t_chi = z_i * z_i;  t_dw = 0.0 at i = 0, else
+ *            dd = z_i - z_{i-1}, t_dw = dd * dd;  s_i = (z_i > 0.0) - zero, -0 and NaN are "not
+ *            positive"
+ *   sums     chi2[c], sum_z[c], dw[c] = the sums of t_chi, z_i, t_dw by mhx_get_waic's rule with
+ *            blocks of MHX_RESID_BLOCK points: lane j = i mod 64 of a block adds its points serially
+ *            in ascending i to a sum that starts at 0.0 (a point beyond N adds 0.0), the 64 lane
+ *            sums are added pairwise, lanes 32 apart first, then 16, 8, 4, 2, 1
+ *            (u_j = u_j + u_{j xor m}), and the blocks' sums are added serially in ascending block
+ *            order to a sum that starts at 0.0.  (Durbin and Watson's statistic is dw / chi2, the
+ *            caller's division.)
+ *   counts   exact integers: n_pos[c] = #{i : s_i};  n_runs[c] = 1 + #{i >= 1 : s_i != s_{i-1}}, the
+ *            runs of equal sign (Wald and Wolfowitz);  n_out[c] = #{i : |z_i| > z_limit}
+ *   extreme  from m = -1.0, idx = -1: for ascending i, where |z_i| > m take (m, idx) = (|z_i|, i).
+ *            A NaN never compares greater and is passed over; ties keep the earliest i.
+ *            max_abs_z[c] = m, max_index[c] = idx
+ *   status   MHX_RESID_NONFINITE where some v_i or z_i of the chain is not finite: the chain's three
+ *            sums are then unspecified; its counts and extreme still follow the rules above, and
+ *            no other chain is touched by it
+ * The results are the same bits from call to call, whatever portions the call is worked through in,
+ * however the points are split into chunks and however a group's chains are split over its engines.
+ * fit, z [n_chains][N]; chi2, sum_z, dw, max_abs_z [n_chains]; max_index [n_chains]; n_pos, n_runs,
+ * n_out, status [n_chains].  Any output may be NULL.  fn a function of the problem and z_limit not a
+ * NaN, else MHX_EINVAL; MHX_ESTATE before mhx_init_chains; the outputs stay untouched on error.
+ * Serves every model the engine can walk.  Worked through in portions whose device scratch stays
+ * below 64 MiB; mhx_get_summary_timing covers the call. */
+#define MHX_RESID_BLOCK 256 /* points of one block of mhx_get_residuals' sums */
+enum {
+  MHX_RESID_NONFINITE = 1
+};
+int mhx_get_residuals(mhx_engine* e, int fn, const double* theta, double z_limit, double* fit,
+                      double* z, double* chi2, double* sum_z, double* dw, double* max_abs_z,
+                      int64_t* max_index, int32_t* n_pos, int32_t* n_runs, int32_t* n_out,
+                      int32_t* status);
+/* The same for a group, in global chain order (theta too); every device's work is enqueued before
+ * any is waited for. */
+int mhx_group_get_residuals(mhx_group* g, int fn, const double* theta, double z_limit, double* fit,
+                            double* z, double* chi2, double* sum_z, double* dw, double* max_abs_z,
+                            int64_t* max_index, int32_t* n_pos, int32_t* n_runs, int32_t* n_out,
+                            int32_t* status);
 
 /* ---- batched traces: the steps of EVERY chain, filtered and thinned on the device -------------
  * What (mapcar (lambda (w) (walker-get w :get :steps / :unique-steps / :forward-steps / :params /

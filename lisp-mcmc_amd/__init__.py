@@ -30,6 +30,7 @@ from .walker import (  # noqa: F401
     autocorr, walker_autocorr, walker_set_autocorr, walker_set_rhat, walker_set_ensemble_get,
     walker_set_waic, walker_waic, waic_compare, waic_merge,
     walker_set_trace, walker_set_catepillar,
+    walker_set_get_residuals, walker_set_goodness_of_fit, walker_goodness_of_fit, runs_z,
 )
 
 __all__ = ["capi", "MhxError", "Engine", "Group", "comm_unique_id", "partition", "models", "Walker", "WalkerStep", "walker_create",
@@ -46,4 +47,5 @@ __all__ = ["capi", "MhxError", "Engine", "Group", "comm_unique_id", "partition",
            "autocorr", "walker_autocorr", "walker_set_autocorr", "walker_set_rhat", "split_rhat",
            "walker_set_ensemble_get", "ensemble_pick",
            "walker_set_waic", "walker_waic", "waic_compare", "waic_merge",
-           "trace_rows", "walker_set_trace", "walker_set_catepillar"]
+           "trace_rows", "walker_set_trace", "walker_set_catepillar",
+           "walker_set_get_residuals", "walker_set_goodness_of_fit", "walker_goodness_of_fit", "runs_z"]

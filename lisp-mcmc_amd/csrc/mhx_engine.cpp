@@ -1413,7 +1413,8 @@ int mhx_create(const mhx_config* cfg, mhx_engine** out) {
     }
     if (family_w8().configure() != hipSuccess || family_w16().configure() != hipSuccess ||
         summary_configure() != hipSuccess || fit_configure() != hipSuccess ||
-        waic_configure() != hipSuccess || fitpct_configure() != hipSuccess) {
+        waic_configure() != hipSuccess || fitpct_configure() != hipSuccess ||
+        resid_configure() != hipSuccess) {
       rc = fail(MHX_EDEVICE, "hipFuncSetAttribute(max dynamic LDS = %zu / %zu) failed",
                 family_w8().lds_bytes, family_w16().lds_bytes);
       break;
@@ -2861,6 +2862,140 @@ int mhx_get_waic(mhx_engine* e, int fn, int take, double* elpd, double* lppd, do
   return run_portions(e, WaicCall(fn, take, elpd, lppd, p_waic, n_high, pw_lppd, pw_p, pw_acc, n_used, status));
 }
 
+// ---- residuals (include/mhx.h has the definition): function fn at one parameter vector per chain
+// over the chain's own data, and the block partials of the standardized residuals (k_resid), then
+// their totals (k_resid_totals).  An item is a chain; the function's points go in chunks of
+// kFitChunkPoints, a whole number of MHX_RESID_BLOCK blocks, so a block is the same points whatever
+// the split.  The partials of all chunks stay in the stage; the totals are taken on the last chunk.
+// The data are read where the engine holds them: the shared arrays, or the planes of a dataset per
+// walker (PlaneDesc) by the pitches ResidArgs describes.
+struct ResidCall {
+  int fn = 0, want = 0;
+  double z_limit = 0.0;
+  int64_t m = 0, nb_total = 0;
+  enum { CHI2, SUM_Z, DW, MAX_ABS_Z, MAX_INDEX, N_POS, N_RUNS, N_OUT, STATUS, FIT, Z, THETA, N_DST };
+  HostDst dst[N_DST];  // (THETA is read, not written: it lies here to move with a group's chains)
+  static_assert(kFitChunkPoints % MHX_RESID_BLOCK == 0, "a chunk of points is whole blocks");
+
+  ResidCall(int fn_, const double* theta, double z_limit_, double* fit, double* z, double* chi2,
+            double* sum_z, double* dw, double* max_abs_z, int64_t* max_index, int32_t* n_pos,
+            int32_t* n_runs, int32_t* n_out, int32_t* status)
+      : fn(fn_), z_limit(z_limit_) {
+    dst[CHI2] = {chi2, sizeof(double)}, dst[SUM_Z] = {sum_z, sizeof(double)};
+    dst[DW] = {dw, sizeof(double)}, dst[MAX_ABS_Z] = {max_abs_z, sizeof(double)};
+    dst[MAX_INDEX] = {max_index, sizeof(int64_t)}, dst[N_POS] = {n_pos, sizeof(int32_t)};
+    dst[N_RUNS] = {n_runs, sizeof(int32_t)}, dst[N_OUT] = {n_out, sizeof(int32_t)};
+    dst[STATUS] = {status, sizeof(int32_t)};
+    dst[FIT].p = fit, dst[Z].p = z, dst[THETA].p = const_cast<double*>(theta);
+    want = (fit ? RESID_WANT_FIT : 0) | (z ? RESID_WANT_Z : 0);
+  }
+  int check(mhx_engine* e) {
+    if (!e) return fail(MHX_EINVAL, "engine is NULL");
+    if (!e->chains_ready) return fail(MHX_ESTATE, "mhx_init_chains has not been called");
+    int rc = use_device(e);
+    if (rc != MHX_OK || (rc = finalize_problem(e)) != MHX_OK) return rc;
+    if (fn < 0 || fn >= e->P.K) return fail(MHX_EINVAL, "function %d out of range", fn);
+    if (z_limit != z_limit) return fail(MHX_EINVAL, "z_limit is not a number");
+    if (e->P.fn[fn].lik == MHX_LIK_EXPR)
+      return fail(MHX_EUNSUPPORTED, "mhx_get_residuals with MHX_LIK_EXPR: an expression likelihood's "
+                                    "`error` need not be a sigma to divide a residual by");
+    m = e->P.fn[fn].n;
+    if (m < 1) return fail(MHX_EINVAL, "function %d has no data points", fn);
+    nb_total = resid_blocks(m);
+    dst[FIT].item_bytes = dst[Z].item_bytes = (size_t)m * sizeof(double);
+    dst[THETA].item_bytes = (size_t)e->P.d * sizeof(double);
+    return MHX_OK;
+  }
+  int64_t items(const mhx_engine* e) const { return e->cfg.n_chains; }
+  int64_t points() const { return m; }
+  ResidPieces carve(const mhx_engine* e, Carver& c, int64_t n_items, int64_t m_points) const {
+    return carve_resid(c, nb_total, e->P.d, dst[THETA].p ? 1 : 0, want, n_items, m_points);
+  }
+  // what depends on the chains alone is done on the portion's first chunk of points
+  int upload(mhx_engine* e, const Portion& p) const {
+    if (p.m0 != 0) return MHX_OK;
+    Carver c;
+    const ResidPieces s = carve(e, c, p.n, p.m);
+    if (dst[THETA].p)
+      HIP_TRY(hipMemcpyAsync(stage_at<double>(e, s.theta), dst[THETA].at(p.i0), (size_t)p.n * dst[THETA].item_bytes,
+                             hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemsetAsync(stage_at<int32_t>(e, s.status), 0, (size_t)p.n * sizeof(int32_t), e->stream));
+    return MHX_OK;
+  }
+  int launch(mhx_engine* e, const Portion& p) const {
+    Carver c;
+    const ResidPieces s = carve(e, c, p.n, p.m);
+    const FnDesc& f = e->P.fn[fn];
+    const Dataset& D = e->data[fn];
+    ResidArgs A{};
+    A.c0 = p.i0, A.n = p.n;
+    A.fn = fn;
+    A.n_blocks = (int32_t)resid_blocks(p.m);
+    A.blk0 = p.m0 / MHX_RESID_BLOCK, A.nb_total = nb_total, A.m = p.m, A.p_first = p.m0;
+    A.z_limit = z_limit;
+    A.theta = dst[THETA].p ? stage_at<double>(e, s.theta) : nullptr;
+    A.x0 = f.x + p.m0;
+    A.x1 = f.n_xcols > 1 ? f.c + p.m0 : nullptr;
+    if (D.planes) {  // row c of the planes is the engine's chain c
+      A.y = D.pd.y + p.m0, A.y_pitch = D.pd.pitch;
+      switch (D.pd.w_kind) {
+        case kPlaneWShared: A.w = f.w + p.m0, A.w_pitch = 0, A.w_step = 1; break;
+        case kPlaneWScalar: A.w = D.pd.w, A.w_pitch = 1, A.w_step = 0; break;
+        default: A.w = D.pd.w + p.m0, A.w_pitch = D.pd.pitch, A.w_step = 1; break;
+      }
+    } else {
+      A.y = f.y + p.m0, A.y_pitch = 0;
+      A.w = f.w + p.m0, A.w_pitch = 0, A.w_step = 1;
+    }
+    A.fit = (want & RESID_WANT_FIT) ? stage_at<double>(e, s.fit) : nullptr;
+    A.z = (want & RESID_WANT_Z) ? stage_at<double>(e, s.z) : nullptr;
+    A.part_chi2 = stage_at<double>(e, s.part_chi2);
+    A.part_sumz = stage_at<double>(e, s.part_sumz);
+    A.part_dw = stage_at<double>(e, s.part_dw);
+    A.part_max = stage_at<double>(e, s.part_max);
+    A.part_idx = stage_at<int64_t>(e, s.part_idx);
+    A.part_cnt = stage_at<int32_t>(e, s.part_cnt);
+    A.status = stage_at<int32_t>(e, s.status);
+    HIP_TRY(e->spec == SPEC_USER ? rtc_launch_resid(*e->user_prog, e->stream, e->dP.p, e->S, A)
+                                 : launch_resid(e->spec, e->stream, e->dP.p, e->S, A));
+    if (p.m0 + p.m >= m)
+      HIP_TRY(launch_resid_totals(e->stream, p.n, nb_total, A, stage_at<double>(e, s.chi2),
+                                  stage_at<double>(e, s.sum_z), stage_at<double>(e, s.dw),
+                                  stage_at<double>(e, s.max_abs_z), stage_at<int64_t>(e, s.max_index),
+                                  stage_at<int32_t>(e, s.n_pos), stage_at<int32_t>(e, s.n_runs),
+                                  stage_at<int32_t>(e, s.n_out)));
+    e->launches++;
+    return MHX_OK;
+  }
+  int collect(mhx_engine* e, const Portion& p) const {
+    Carver c;
+    const ResidPieces s = carve(e, c, p.n, p.m);
+    const size_t pw[2] = {s.fit, s.z};
+    for (int k = 0; k < 2; ++k) {
+      const HostDst& h = dst[FIT + k];
+      if (h.p)
+        HIP_TRY(hipMemcpy2D(static_cast<double*>(h.at(p.i0)) + p.m0, (size_t)m * sizeof(double),
+                            e->stage.p + pw[k], (size_t)p.m * sizeof(double), (size_t)p.m * sizeof(double),
+                            (size_t)p.n, hipMemcpyDeviceToHost));
+    }
+    if (p.m0 + p.m < m) return MHX_OK;  // (the totals come with the last chunk of points)
+    const size_t off[9] = {s.chi2, s.sum_z, s.dw, s.max_abs_z, s.max_index, s.n_pos, s.n_runs, s.n_out, s.status};
+    for (int k = 0; k < 9; ++k) {
+      const int rc = copy_back(dst[k], p.i0, p.n, e->stage.p + off[k]);
+      if (rc != MHX_OK) return rc;
+    }
+    return MHX_OK;
+  }
+};
+
+int mhx_get_residuals(mhx_engine* e, int fn, const double* theta, double z_limit, double* fit,
+                      double* z, double* chi2, double* sum_z, double* dw, double* max_abs_z,
+                      int64_t* max_index, int32_t* n_pos, int32_t* n_runs, int32_t* n_out,
+                      int32_t* status) {
+  return run_portions(e, ResidCall(fn, theta, z_limit, fit, z, chi2, sum_z, dw, max_abs_z, max_index, n_pos,
+                                   n_runs, n_out, status));
+}
+
 // ---- credible bands (include/mhx.h has the definition): every chain's pointwise percentiles and
 // moments of function fn over its window (k_fitpct_values, then the model-free k_fitpct_select).
 // An item is a chain.  The window's values of a portion are staged, `take` doubles per chain and
@@ -4228,6 +4363,14 @@ int mhx_group_get_waic(mhx_group* g, int fn, int take, double* elpd, double* lpp
                        int32_t* n_high, double* pw_lppd, double* pw_p, double* pw_acc,
                        int32_t* n_used, int32_t* status) {
   return run_portions(g, WaicCall(fn, take, elpd, lppd, p_waic, n_high, pw_lppd, pw_p, pw_acc, n_used, status));
+}
+
+int mhx_group_get_residuals(mhx_group* g, int fn, const double* theta, double z_limit, double* fit,
+                            double* z, double* chi2, double* sum_z, double* dw, double* max_abs_z,
+                            int64_t* max_index, int32_t* n_pos, int32_t* n_runs, int32_t* n_out,
+                            int32_t* status) {
+  return run_portions(g, ResidCall(fn, theta, z_limit, fit, z, chi2, sum_z, dw, max_abs_z, max_index, n_pos,
+                                   n_runs, n_out, status));
 }
 
 int mhx_group_get_traces(mhx_group* g, int take, int filter, int stride, int start, const int32_t* cols,

@@ -4239,6 +4239,172 @@ __global__ __launch_bounds__(kThreads) void k_waic_totals(ChainState S, int64_t 
 }
 #endif
 
+// mhx_get_residuals (include/mhx.h has the definition, operation by operation): k_waic's shape with
+// one parameter vector in place of a window - no loop over steps.  Wave g serves chain
+// g / n_blocks of the launch and block g % n_blocks of its points, kResidPts points per lane; the
+// chain's vector (the caller's, or ChainState::best_theta) goes to the wave's LDS row, then ONE
+// Spec::values (the bits of mhx_eval_function) over the lane's four points and, in a fifth slot,
+// the point before the block - the neighbour z_{i-1} of the block's first point belongs to another
+// wave, perhaps of another launch, so it is computed again from the same inputs (every lane forms
+// it; lane 0 uses it).  Within the block the neighbour of lane l > 0 is lane l - 1 of the same row
+// of 64 points and that of lane 0 is lane 63 of the row before.  Points beyond m take the last
+// point's inputs and contribute nothing: no term, no change of sign, no extreme.  Every product and
+// sum below is rounded on its own (the unit is compiled without contraction; no fma is written
+// here).  The block's three sums, three counts and (max, index) go to part_*[chain][block]:
+// k_resid_totals adds them in block order.
+template <class Spec>
+__device__ __forceinline__ void k_resid_body(const ProblemDesc* __restrict__ Pp, ChainState S,
+                                             ResidArgs A) {
+  FitLds& lds = *reinterpret_cast<FitLds*>(mhx_lds_raw);
+  lds_tables_begin();
+  __syncthreads();  // (the only barrier: waves without work leave behind it)
+  const int w = wave_in_group(), l = lane_id();
+  const int64_t g = (int64_t)blockIdx.x * kWavesPerGroup + w;
+  if (g >= A.n * A.n_blocks) return;
+  const int64_t i = g / A.n_blocks;
+  const int64_t blk = g - i * A.n_blocks;
+  const int64_t p0 = blk * (int64_t)(kWave * kResidPts) + l;
+  const FnDesc& f = Pp->fn[A.fn];
+  const int d = Pp->d;
+  const int lik = __builtin_amdgcn_readfirstlane(f.lik);
+  const int64_t row = A.c0 + i;
+  const double* yr = A.y + row * A.y_pitch;
+  const double* wr = A.w + row * A.w_pitch;
+  constexpr int kN = kResidPts;  // the neighbour's slot
+  double x0[kResidPts + 1], x1[kResidPts + 1], ys[kResidPts + 1], wi[kResidPts + 1];
+  // the point before the block's first: index -1 of a later launch is the launch before's last
+  const int64_t pn = blk * (int64_t)(kWave * kResidPts) - 1;
+  const int64_t qn = A.p_first + pn >= 0 ? pn : 0;  // (the dataset's first point has no neighbour)
+#pragma unroll
+  for (int j = 0; j <= kResidPts; ++j) {
+    const int64_t p = p0 + (int64_t)j * kWave;
+    const int64_t q = j == kN ? qn : (p < A.m ? p : A.m - 1);  // (beyond m: the last point once more)
+    x0[j] = A.x0[q];
+    x1[j] = A.x1 ? A.x1[q] : 0.0;
+    ys[j] = yr[q];
+    wi[j] = wr[q * A.w_step];
+  }
+  const double* src = A.theta ? A.theta + i * d : S.best_theta + row * d;
+  double* th = lds.th[w];
+  if (l < d) th[l] = src[l];
+  __builtin_amdgcn_wave_barrier();
+  auto pf = [&](int j) -> double { return th[f.idx[j]]; };
+  double v[kResidPts + 1], z[kResidPts + 1];
+  Spec::template values<kResidPts + 1>(f, pf, lds.scr[w], x0, x1, v);
+  if (lik == MHX_LIK_POISSON) {
+#pragma unroll
+    for (int j = 0; j <= kResidPts; ++j) {
+      const double dl = v[j] - ys[j];
+      const double rt = __builtin_sqrt(v[j]);
+      z[j] = dl / rt;
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j <= kResidPts; ++j) {
+      const double a = v[j] * wi[j];
+      z[j] = a - ys[j];
+    }
+  }
+  double sc = 0.0, sz = 0.0, sd = 0.0, mx = -1.0;
+  int64_t mi = -1;
+  int np = 0, nc = 0, no = 0;
+  bool bad = false;
+#pragma unroll
+  for (int j = 0; j < kResidPts; ++j) {
+    const int64_t p = p0 + (int64_t)j * kWave;
+    const bool in = p < A.m;
+    const double left = __shfl(z[j], (l + kWave - 1) & (kWave - 1), kWave);
+    const double edge = j == 0 ? z[kN] : readlane_f64(z[j - 1], kWave - 1);
+    const double prev = l == 0 ? edge : left;
+    const bool has = in && A.p_first + p >= 1;
+    const double dd = z[j] - prev;
+    const double az = __builtin_fabs(z[j]);
+    const bool pos = z[j] > 0.0;
+    sc = sc + (in ? z[j] * z[j] : 0.0);
+    sz = sz + (in ? z[j] : 0.0);
+    sd = sd + (has ? dd * dd : 0.0);
+    np += (in && pos) ? 1 : 0;
+    nc += (has && pos != (prev > 0.0)) ? 1 : 0;
+    no += (in && az > A.z_limit) ? 1 : 0;
+    if (in && az > mx) mx = az, mi = A.p_first + p;
+    bad = bad || (in && (!finite_f64(v[j]) || !finite_f64(z[j])));
+    if (in) {
+      const int64_t o = i * A.m + p;
+      if (A.fit) A.fit[o] = v[j];
+      if (A.z) A.z[o] = z[j];
+    }
+  }
+  sc = wave_sum(sc);
+  sz = wave_sum(sz);
+  sd = wave_sum(sd);
+  np = wave_sum_i(np);
+  nc = wave_sum_i(nc);
+  no = wave_sum_i(no);
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {  // the greatest |z|; among equals the earliest point
+    const double om = __shfl_xor(mx, m, kWave);
+    const int64_t oi = (int64_t)__shfl_xor((long long)mi, m, kWave);
+    const bool take = om > mx || (om == mx && oi < mi);
+    mx = take ? om : mx;
+    mi = take ? oi : mi;
+  }
+  const bool any_bad = __ballot(bad) != 0ULL;
+  if (l == 0) {
+    const int64_t o = i * A.nb_total + A.blk0 + blk;
+    A.part_chi2[o] = sc;
+    A.part_sumz[o] = sz;
+    A.part_dw[o] = sd;
+    A.part_max[o] = mx;
+    A.part_idx[o] = mi;
+    A.part_cnt[o * 3 + 0] = np;
+    A.part_cnt[o * 3 + 1] = nc;
+    A.part_cnt[o * 3 + 2] = no;
+    if (any_bad) A.status[i] = MHX_RESID_NONFINITE;
+  }
+}
+#ifndef __HIPCC_RTC__
+template <class Spec>
+__global__ __launch_bounds__(kThreads) void k_resid(const ProblemDesc* __restrict__ Pp, ChainState S,
+                                                    ResidArgs A) {
+  k_resid_body<Spec>(Pp, S, A);
+}
+#endif
+#if defined(MHX_FAMILY_PRIMARY) && !defined(__HIPCC_RTC__)
+// mhx_get_residuals, the totals: one thread per chain adds the blocks' partial sums and counts in
+// block order (whatever launches wrote them) and keeps the first of the blocks' greatest |z|.
+__global__ __launch_bounds__(kThreads) void k_resid_totals(
+    int64_t n, int64_t nb_total, const double* __restrict__ part_chi2, const double* __restrict__ part_sumz,
+    const double* __restrict__ part_dw, const double* __restrict__ part_max,
+    const int64_t* __restrict__ part_idx, const int32_t* __restrict__ part_cnt, double* __restrict__ chi2,
+    double* __restrict__ sum_z, double* __restrict__ dw, double* __restrict__ max_abs_z,
+    int64_t* __restrict__ max_index, int32_t* __restrict__ n_pos, int32_t* __restrict__ n_runs,
+    int32_t* __restrict__ n_out) {
+  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  double sc = 0.0, sz = 0.0, sd = 0.0, mx = -1.0;
+  int64_t mi = -1;
+  int np = 0, nc = 0, no = 0;
+  for (int64_t b = 0; b < nb_total; ++b) {
+    const int64_t o = i * nb_total + b;
+    sc = sc + part_chi2[o];
+    sz = sz + part_sumz[o];
+    sd = sd + part_dw[o];
+    np += part_cnt[o * 3 + 0];
+    nc += part_cnt[o * 3 + 1];
+    no += part_cnt[o * 3 + 2];
+    if (part_max[o] > mx) mx = part_max[o], mi = part_idx[o];
+  }
+  chi2[i] = sc;
+  sum_z[i] = sz;
+  dw[i] = sd;
+  max_abs_z[i] = mx;
+  max_index[i] = mi;
+  n_pos[i] = np;
+  n_runs[i] = 1 + nc;
+  n_out[i] = no;
+}
+#endif
+
 // mhx_get_fit_percentiles, first half (include/mhx.h has the definition): k_waic's walk over the
 // window with nothing behind the model.  Wave g serves chain g / n_blocks of the launch and block
 // g % n_blocks of its points: kFitPctPts points per lane, whose x and Welford pair {mean, M2} stay

@@ -203,4 +203,16 @@ hipError_t launch_fitpct_select(hipStream_t st, const ChainState& S, int64_t c0,
                                 bool use_lds, bool together, const double* vals, double* pct,
                                 int32_t* n_used, int32_t* status);
 
+// mhx_get_residuals: the residuals' block sums, counts and extremes (ResidArgs, mhx_types.hpp) for
+// the ahead-of-time specs - run-time compiled problems, every engine with a dataset per walker among
+// them, go through rtc_launch_resid - and the totals of n chains from the partials of all nb_total
+// blocks.
+inline int64_t resid_blocks(int64_t m) { return (m + MHX_RESID_BLOCK - 1) / MHX_RESID_BLOCK; }
+hipError_t resid_configure();
+hipError_t launch_resid(int spec, hipStream_t st, const ProblemDesc* P, const ChainState& S,
+                        const ResidArgs& A);
+hipError_t launch_resid_totals(hipStream_t st, int64_t n, int64_t nb_total, const ResidArgs& A,
+                               double* chi2, double* sum_z, double* dw, double* max_abs_z,
+                               int64_t* max_index, int32_t* n_pos, int32_t* n_runs, int32_t* n_out);
+
 }  // namespace mhx

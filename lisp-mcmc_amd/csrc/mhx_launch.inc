@@ -436,6 +436,35 @@ hipError_t launch_waic_totals(hipStream_t st, const ChainState& S, int64_t c0, i
   return hipGetLastError();
 }
 
+// mhx_get_residuals (k_resid, k_resid_totals): as k_waic, compiled in this family only
+hipError_t resid_configure() {
+  hipError_t e = hipSuccess;
+  for (int s = 0; s < SPEC__COUNT; ++s)
+    for_spec(s, [&](auto sp) {
+      using SpecT = decltype(sp);
+      if (e == hipSuccess) e = no_static_lds(&k_resid<SpecT>);
+    });
+  return e;
+}
+hipError_t launch_resid(int spec, hipStream_t st, const ProblemDesc* P, const ChainState& S,
+                        const ResidArgs& A) {
+  if (A.n <= 0 || A.m <= 0) return hipSuccess;
+  for_spec(spec, [&](auto sp) {
+    using SpecT = decltype(sp);
+    k_resid<SpecT><<<grid_for(A.n * A.n_blocks), dim3(kThreads), fit_lds_bytes(kWavesPerGroup), st>>>(P, S, A);
+  });
+  return hipGetLastError();
+}
+hipError_t launch_resid_totals(hipStream_t st, int64_t n, int64_t nb_total, const ResidArgs& A,
+                               double* chi2, double* sum_z, double* dw, double* max_abs_z,
+                               int64_t* max_index, int32_t* n_pos, int32_t* n_runs, int32_t* n_out) {
+  if (n <= 0) return hipSuccess;
+  k_resid_totals<<<dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, st>>>(
+      n, nb_total, A.part_chi2, A.part_sumz, A.part_dw, A.part_max, A.part_idx, A.part_cnt, chi2, sum_z, dw,
+      max_abs_z, max_index, n_pos, n_runs, n_out);
+  return hipGetLastError();
+}
+
 // mhx_get_fit_percentiles (k_fitpct_values, k_fitpct_select): as k_waic, compiled in this family only
 hipError_t fitpct_configure() {
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fitpct_select),

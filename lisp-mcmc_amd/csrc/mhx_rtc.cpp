@@ -342,6 +342,9 @@ static std::string generate(const std::vector<UserExpr>& models,
        "extern \"C\" __global__ __launch_bounds__(MHX_USER_THREADS) void mhx_user_waic(\n"
        "    const ProblemDesc* P, ChainState S, WaicArgs A) {\n"
        "  k_waic_body<UserSpec>(P, S, A);\n}\n"
+       "extern \"C\" __global__ __launch_bounds__(MHX_USER_THREADS) void mhx_user_resid(\n"
+       "    const ProblemDesc* P, ChainState S, ResidArgs A) {\n"
+       "  k_resid_body<UserSpec>(P, S, A);\n}\n"
        "extern \"C\" __global__ __launch_bounds__(MHX_USER_THREADS) void mhx_user_fitpct(\n"
        "    const ProblemDesc* P, ChainState S, FitPctArgs A) {\n"
        "  k_fitpct_values_body<UserSpec>(P, S, A);\n}\n"
@@ -602,6 +605,12 @@ static int build_once(const std::vector<UserExpr>& models, const std::vector<Use
                             : std::string("module function mhx_user_waic has static LDS");
     return -1;
   }
+  he = hipModuleGetFunction(&prog->f_resid, prog->module, "mhx_user_resid");
+  if (he != hipSuccess || static_lds(prog->f_resid) != 0) {
+    *err = he != hipSuccess ? std::string("module function mhx_user_resid: ") + hipGetErrorString(he)
+                            : std::string("module function mhx_user_resid has static LDS");
+    return -1;
+  }
   he = hipModuleGetFunction(&prog->f_fitpct, prog->module, "mhx_user_fitpct");
   if (he != hipSuccess || static_lds(prog->f_fitpct) != 0) {
     *err = he != hipSuccess ? std::string("module function mhx_user_fitpct: ") + hipGetErrorString(he)
@@ -730,6 +739,15 @@ hipError_t rtc_launch_waic(const UserProgram& p, hipStream_t st, const ProblemDe
   WaicArgs a = A;
   void* args[] = {(void*)&P, (void*)&s, (void*)&a};
   return hipModuleLaunchKernel(p.f_waic, grid_for(p, A.n * A.n_blocks), 1, 1, (unsigned)p.fam->threads,
+                               1, 1, fit_lds_bytes(p.fam->waves_per_group), st, args, nullptr);
+}
+hipError_t rtc_launch_resid(const UserProgram& p, hipStream_t st, const ProblemDesc* P,
+                            const ChainState& S, const ResidArgs& A) {
+  if (A.n <= 0 || A.m <= 0) return hipSuccess;
+  ChainState s = S;
+  ResidArgs a = A;
+  void* args[] = {(void*)&P, (void*)&s, (void*)&a};
+  return hipModuleLaunchKernel(p.f_resid, grid_for(p, A.n * A.n_blocks), 1, 1, (unsigned)p.fam->threads,
                                1, 1, fit_lds_bytes(p.fam->waves_per_group), st, args, nullptr);
 }
 hipError_t rtc_launch_fitpct(const UserProgram& p, hipStream_t st, const ProblemDesc* P,

@@ -203,6 +203,42 @@ inline WaicPieces carve_waic(Carver& c, int64_t nb_total, int want, int64_t n_, 
   s.pw_acc = c.take((want & WAIC_WANT_ACC) ? n * m * 4 * sizeof(double) : 0);
   return s;
 }
+// Residuals of n chains at m points of a function of nb_total blocks: what depends on the chains
+// alone comes first and keeps its place from one chunk of points to the next - status, the counts
+// n_pos, n_runs, n_out [n], max_index [n], the totals chi2, sum_z, dw, max_abs_z [n], the caller's
+// parameter vectors theta [n][d] (with_theta 0: empty, the device's most-likely ones are read), the
+// blocks' partials [n][nb_total] (four double arrays, one of 64-bit indices, one of three ints) -
+// then the pointwise results the caller asked for: fit, z [n][m] (want bits 1, 2; a piece not asked
+// for is empty and the kernel does not write it).
+enum { RESID_WANT_FIT = 1, RESID_WANT_Z = 2 };
+struct ResidPieces {
+  size_t status, n_pos, n_runs, n_out, max_index, chi2, sum_z, dw, max_abs_z, theta, part_chi2, part_sumz,
+      part_dw, part_max, part_idx, part_cnt, fit, z;
+};
+inline ResidPieces carve_resid(Carver& c, int64_t nb_total, int d, int with_theta, int want, int64_t n_,
+                               int64_t m_) {
+  const size_t n = (size_t)n_, m = (size_t)m_, nb = (size_t)nb_total;
+  ResidPieces s;
+  s.status = c.take(n * sizeof(int32_t));
+  s.n_pos = c.take(n * sizeof(int32_t));
+  s.n_runs = c.take(n * sizeof(int32_t));
+  s.n_out = c.take(n * sizeof(int32_t));
+  s.max_index = c.take(n * sizeof(int64_t));
+  s.chi2 = c.take(n * sizeof(double));
+  s.sum_z = c.take(n * sizeof(double));
+  s.dw = c.take(n * sizeof(double));
+  s.max_abs_z = c.take(n * sizeof(double));
+  s.theta = c.take(with_theta ? n * (size_t)d * sizeof(double) : 0);
+  s.part_chi2 = c.take(n * nb * sizeof(double));
+  s.part_sumz = c.take(n * nb * sizeof(double));
+  s.part_dw = c.take(n * nb * sizeof(double));
+  s.part_max = c.take(n * nb * sizeof(double));
+  s.part_idx = c.take(n * nb * sizeof(int64_t));
+  s.part_cnt = c.take(n * nb * 3 * sizeof(int32_t));
+  s.fit = c.take((want & RESID_WANT_FIT) ? n * m * sizeof(double) : 0);
+  s.z = c.take((want & RESID_WANT_Z) ? n * m * sizeof(double) : 0);
+  return s;
+}
 // batched traces: the caller's column list [n_cols] - it does not grow with n and comes first -
 // the rows values [n][max_out][n_cols], their envelopes lo and hi of the same shape (envelope 0:
 // both empty, the kernel does not write them), n_out, n_kept, n_used [n], and the kept-index

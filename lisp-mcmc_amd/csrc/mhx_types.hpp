@@ -303,6 +303,46 @@ struct FitPctArgs {
   int32_t* status;   // [n] MHX_FITPCT_NONFINITE is or-ed in where a value is not finite
 };
 
+// k_resid (mhx_get_residuals): function `fn` at ONE parameter vector per chain over the chain's own
+// data, for each of n chains from c0 on, and the block sums, counts and extreme of the standardized
+// residuals.  A wave serves one chain and one block of MHX_RESID_BLOCK = kWave x kResidPts points;
+// n_blocks blocks cover the m points of this launch, which are blocks blk0 .. of the function's
+// nb_total and begin at point p_first of the dataset.  x0, x1, y, w come offset to the launch's
+// first point, and the data are on the device in full: index -1 is the point before it, which the
+// first block of a later chunk reads for its neighbour.  Chain c reads
+//   ys_i = y[c * y_pitch + i]               y_pitch 0: the shared dataset; a plane's pitch else
+//   w_i  = w[c * w_pitch + i * w_step]      (0, 1) the shared 1/sigma; (1, 0) one per walker;
+//                                           (pitch, 1) a plane of them
+// so that one kernel serves shared datasets and all three PlaneDesc::w_kinds; c counts from the
+// engine's chain 0, as the planes' rows do.  theta [n][d] is the launch's (nullptr:
+// ChainState::best_theta).  A lane keeps five points - its four and, in a fifth slot, the block's
+// neighbour (the last point of the block before, recomputed from the same inputs: the same bits) -
+// so that ONE Spec::values with one prepare serves both.
+constexpr int kResidPts = MHX_RESID_BLOCK / kWave;
+static_assert(kResidPts * kWave == MHX_RESID_BLOCK && kResidPts == 4, "MHX_RESID_BLOCK (include/mhx.h)");
+static_assert(MHX_RESID_BLOCK == MHX_WAIC_BLOCK, "mhx_get_residuals' sums follow mhx_get_waic's rule");
+struct ResidArgs {
+  int64_t c0, n;
+  int32_t fn, n_blocks, w_step, pad_;
+  int64_t blk0, nb_total, m, p_first;
+  int64_t y_pitch, w_pitch;
+  double z_limit;
+  const double* theta;  // [n][d] or nullptr
+  const double* x0;
+  const double* x1;     // the second column of x, or nullptr
+  const double* y;
+  const double* w;
+  double* fit;          // [n][m] or nullptr
+  double* z;            // [n][m] or nullptr
+  double* part_chi2;    // [n][nb_total] the blocks' sums of z^2
+  double* part_sumz;    // [n][nb_total] ... of z
+  double* part_dw;      // [n][nb_total] ... of (z_i - z_{i-1})^2
+  double* part_max;     // [n][nb_total] the blocks' greatest |z| (-1.0: none)
+  int64_t* part_idx;    // [n][nb_total] ... and its place in the dataset (-1: none)
+  int32_t* part_cnt;    // [n][nb_total][3] z > 0, changes of sign, |z| > z_limit
+  int32_t* status;      // [n] MHX_RESID_NONFINITE is stored where a value or a residual is not finite
+};
+
 // mhx_user_derived (mhx_get_derived, mhx_derived.hpp): the expressions of one run-time compiled
 // module over the windows of the n chains from c0 on.  idx[j] = the place in theta of the j-th
 // name; values [n][n_expr][pitch] newest first, at_best [n][n_expr] (the most-likely step).

@@ -260,7 +260,40 @@ class _Summaries:
             out["n_used"].ctypes.data_as(capi.i32p), out["status"].ctypes.data_as(capi.i32p)))
         return out
 
-    TRACE_FILTERS = {"steps": capi.TRACE_STEPS, "unique": capi.TRACE_UNIQUE, "forward": capi.TRACE_FORWARD}
+    def residuals(self, fn, theta=None, z_limit=3.0, pointwise=False):
+        """Goodness of fit of every walker for function `fn` at one parameter vector each
+        (mhx_get_residuals, which has the definition): theta [n_chains, d], None: every chain's
+        most-likely parameters.  A dict of chi2, sum_z, dw (the sums of z^2, z and
+        (z_i - z_{i-1})^2 of the standardized residuals z, fit minus data), max_abs_z and
+        max_index (the greatest |z| and its point), n_pos, n_runs (the runs of equal sign), n_out
+        (points with |z| > z_limit) and status (RESID_NONFINITE 1), all [n_chains].
+        pointwise=True adds fit and z [n_chains, N]."""
+        n = self.n_chains
+        pts = getattr(self, "_datasets", {}).get(int(fn), (0, 1))[0]
+        if pointwise and pts < 1:
+            raise ValueError("residuals: function %d has no dataset set through this object" % int(fn))
+        thp = None
+        if theta is not None:
+            th = np.ascontiguousarray(theta, dtype=np.float64)
+            if th.shape != (n, self.d):
+                raise ValueError("residuals: theta must be [n_chains, d] = [%d, %d]" % (n, self.d))
+            thp = th.ctypes.data_as(capi.f64p)
+        out = {k: np.zeros(n) for k in ("chi2", "sum_z", "dw", "max_abs_z")}
+        out["max_index"] = np.zeros(n, dtype=np.int64)
+        for k in ("n_pos", "n_runs", "n_out", "status"):
+            out[k] = np.zeros(n, dtype=np.int32)
+        if pointwise:
+            out["fit"] = np.zeros((n, pts))
+            out["z"] = np.zeros((n, pts))
+        capi.check(self._summary("residuals")(
+            self._h, int(fn), thp, float(z_limit),
+            *(out[k].ctypes.data_as(capi.f64p) if k in out else None for k in ("fit", "z")),
+            *(out[k].ctypes.data_as(capi.f64p) for k in ("chi2", "sum_z", "dw", "max_abs_z")),
+            out["max_index"].ctypes.data_as(capi.i64p),
+            *(out[k].ctypes.data_as(capi.i32p) for k in ("n_pos", "n_runs", "n_out", "status"))))
+        return out
+
+    TRACE_FILTERS ={"steps": capi.TRACE_STEPS, "unique": capi.TRACE_UNIQUE, "forward": capi.TRACE_FORWARD}
 
     def traces(self, take, cols=None, filter="steps", stride=1, start=0, max_out=None, envelope=False):
         """every chain's steps, filtered and thinned on the device (mhx_get_traces, which has the

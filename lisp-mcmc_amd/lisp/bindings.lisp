@@ -283,6 +283,16 @@ library, or without a gfx950 device, walker-create signals MHX-ERROR."
   (g :pointer) (fn :int) (take :int) (xcols :pointer) (n-cols :int) (m :int64) (pct-num :pointer)
   (pct-den :pointer) (n-pct :int) (pct :pointer) (mean :pointer) (stddev :pointer)
   (n-used :pointer) (status :pointer))
+;; residuals: the goodness of fit of every walker at one parameter vector each (theta may be null)
+(defconstant +resid-nonfinite+ 1)
+(cffi:defcfun ("mhx_get_residuals" %mhx-get-residuals) :int
+  (e :pointer) (fn :int) (theta :pointer) (z-limit :double) (fit :pointer) (z :pointer)
+  (chi2 :pointer) (sum-z :pointer) (dw :pointer) (max-abs-z :pointer) (max-index :pointer)
+  (n-pos :pointer) (n-runs :pointer) (n-out :pointer) (status :pointer))
+(cffi:defcfun ("mhx_group_get_residuals" %mhx-group-get-residuals) :int
+  (g :pointer) (fn :int) (theta :pointer) (z-limit :double) (fit :pointer) (z :pointer)
+  (chi2 :pointer) (sum-z :pointer) (dw :pointer) (max-abs-z :pointer) (max-index :pointer)
+  (n-pos :pointer) (n-runs :pointer) (n-out :pointer) (status :pointer))
 (cffi:defcfun ("mhx_get_traces" %mhx-get-traces) :int
   (e :pointer) (take :int) (filter :int) (stride :int) (start :int) (cols :pointer) (n-cols :int)
   (max-out :int) (values :pointer) (lo :pointer) (hi :pointer) (n-out :pointer) (n-kept :pointer)

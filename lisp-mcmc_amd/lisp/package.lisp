@@ -24,6 +24,7 @@
    #:walker-set-corner-grid
    #:walker-set-autocorr #:walker-set-rhat #:walker-set-ensemble-get
    #:walker-set-waic #:walker-waic
+   #:walker-set-get-residuals #:walker-set-goodness-of-fit #:walker-goodness-of-fit #:runs-z
    #:walker-set-trace #:walker-set-catepillar
    #:walker-save #:walker-load #:diagonal-covariance
    #:mfit-walker-estop #:request-stop

@@ -1389,6 +1389,115 @@ data's own x - what walker-plot-residuals draws"
          (y-fit (%model-values walker fn-number params nil)))
     (list x-data (mapcar #'- y-fit y-data) stddev)))
 
+;;; ------------------------------------------------------------------ which walkers fit badly
+;;; walker-get-residuals for every walker of a set, and the goodness-of-fit statistics of the
+;;; standardized residuals, from ONE device call (mhx_get_residuals, whose comment in
+;;; include/mhx.h has the definition) at the medians - one mhx_get_percentiles call - or at the
+;;; most-likely parameters, which the device holds.
+(defun runs-z (n-pos n-neg runs)
+  "Wald and Wolfowitz's score of RUNS runs of equal sign among N-POS positive and N-NEG other
+residuals; nil where it is undefined"
+  (let ((total (+ n-pos n-neg)))
+    (when (>= total 2)
+      (let* ((mu (+ 1 (/ (* 2 n-pos n-neg) total)))
+             (var (/ (* (- mu 1) (- mu 2)) (- total 1))))
+        (when (plusp var)
+          (/ (- runs mu) (sqrt (coerce var 'double-float))))))))
+
+(defun %with-residuals (walker take fn-number which-solution z-limit pointwise consumer)
+  "CONSUMER on the foreign arrays (fit chi2 sum-z dw max-z max-index n-pos n-runs n-out status) of one
+mhx_get_residuals call for the set; fit is null unless POINTWISE"
+  (let* ((n (walker-n-chains walker))
+         (d (length (walker-param-keys walker)))
+         (m (length (first (elt (walker-data walker) fn-number))))
+         (none (cffi:null-pointer))
+         (fit (if pointwise (cffi:foreign-alloc :double :count (* n m)) none)))
+    (unwind-protect
+         (cffi:with-foreign-objects ((th :double (* n d)) (chi2 :double n) (sum-z :double n)
+                                     (dw :double n) (max-z :double n) (max-index :int64 n)
+                                     (n-pos :int32 n) (n-runs :int32 n) (n-out :int32 n)
+                                     (status :int32 n))
+           (unless (eq which-solution :most-likely)
+             (fill-doubles th (loop for plist in (walker-set-get walker :get :median-params
+                                                                        :take take)
+                                    append (%parameter-vector walker plist))))
+           (%set-call walker #'%mhx-get-residuals #'%mhx-group-get-residuals
+                      fn-number (if (eq which-solution :most-likely) none th)
+                      (coerce z-limit 'double-float) fit none chi2 sum-z dw max-z max-index
+                      n-pos n-runs n-out status)
+           (funcall consumer fit chi2 sum-z dw max-z max-index n-pos n-runs n-out status))
+      (when pointwise (cffi:foreign-free fit)))))
+
+(defun walker-set-get-residuals (walker &key (take 1000) (fn-number 0) (which-solution :median))
+  "walker-get-residuals for every walker of the set: a list with, walker by walker, (x-data
+residuals stddev) of the walker's own data, from one device call.  WHICH-SOLUTION: :median or
+:most-likely (the walker's most-likely parameters)."
+  (let ((n (walker-n-chains walker))
+        (m (length (first (elt (walker-data walker) fn-number)))))
+    (%with-residuals
+     walker take fn-number which-solution 3d0 t
+     (lambda (fit chi2 sum-z dw max-z max-index n-pos n-runs n-out status)
+       (declare (ignore chi2 sum-z dw max-z max-index n-pos n-runs n-out status))
+       (loop for c below n
+             collect (let* ((data (%dataset-of walker fn-number c))
+                            (x-data (elt data 0))
+                            (y-data (elt data 1))
+                            (stddev (%stddev-of walker fn-number c))
+                            (stddev (if (= 1 (length stddev))
+                                        (make-list (length x-data) :initial-element (elt stddev 0))
+                                        stddev))
+                            (y-fit (loop for i below m
+                                         collect (cffi:mem-aref fit :double (+ (* c m) i)))))
+                       (list x-data (mapcar #'- y-fit y-data) stddev)))))))
+
+(defun walker-set-goodness-of-fit (walker &key (take 1000) (fn-number 0) (which-solution :median)
+                                            (z-limit 3d0))
+  "For every walker of the set the plist (:chi2 :dof :reduced-chi2 :mean-z :durbin-watson :runs
+:n-pos :runs-z :max-z :max-z-index :n-out :status) of its standardized residuals (fit minus data over
+the point's error) at the medians over TAKE, or at the most-likely parameters: the sum of their
+squares, the points minus the distinct parameters the function reads, their quotient, the mean
+residual, sum (z_i - z_{i-1})^2 / chi2, the runs of equal sign, the positive residuals, runs-z of
+them, the greatest |z| and its point, the points with |z| > Z-LIMIT, and 0 or +resid-nonfinite+
+(the sums of such a walker mean nothing).  One device call; no fit values cross to the host."
+  (let* ((n (walker-n-chains walker))
+         (m (length (first (elt (walker-data walker) fn-number))))
+         (fn (elt (force-list (walker-function walker)) fn-number))
+         (dof (- m (length (remove-duplicates (model-keys fn))))))
+    (%with-residuals
+     walker take fn-number which-solution z-limit nil
+     (lambda (fit chi2 sum-z dw max-z max-index n-pos n-runs n-out status)
+       (declare (ignore fit))
+       (loop for c below n
+             collect (let ((chi (cffi:mem-aref chi2 :double c))
+                           (pos (cffi:mem-aref n-pos :int32 c))
+                           (runs (cffi:mem-aref n-runs :int32 c))
+                           (flag (cffi:mem-aref status :int32 c)))
+                       (list :chi2 chi :dof dof
+                             :reduced-chi2 (if (and (zerop flag) (plusp dof)) (/ chi dof) nil)
+                             :mean-z (if (zerop flag) (/ (cffi:mem-aref sum-z :double c) m) nil)
+                             :durbin-watson (if (and (zerop flag) (plusp chi))
+                                                (/ (cffi:mem-aref dw :double c) chi)
+                                                nil)
+                             :runs runs :n-pos pos :runs-z (runs-z pos (- m pos) runs)
+                             :max-z (cffi:mem-aref max-z :double c)
+                             :max-z-index (cffi:mem-aref max-index :int64 c)
+                             :n-out (cffi:mem-aref n-out :int32 c)
+                             :status flag)))))))
+
+(defun walker-goodness-of-fit (walker &key (chain 0) (take 1000) (fn-number 0)
+                                        (which-solution :median) (z-limit 3d0))
+  "One walker's entry of walker-set-goodness-of-fit.  FLOATING-POINT-INVALID-OPERATION where a model
+value or a residual of that walker is not finite.  The device call is the whole set's: for more
+than a few walkers call walker-set-goodness-of-fit once and take its elements."
+  (let ((entry (elt (walker-set-goodness-of-fit walker :take take :fn-number fn-number
+                                                       :which-solution which-solution
+                                                       :z-limit z-limit)
+                    chain)))
+    (unless (zerop (getf entry :status))
+      (error 'floating-point-invalid-operation
+             :operation 'walker-goodness-of-fit :operands (list :chain chain)))
+    entry))
+
 ;;; ------------------------------------------------------------------ save / load M:971-1001
 ;;; The plist the reference's (commented) walker-construct-print-list builds, written and read
 ;;; under with-standard-io-syntax; functions are only NAMED in the file, so walker-load wants

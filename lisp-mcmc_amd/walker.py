@@ -34,6 +34,7 @@ list of walkers sequentially, M:1029-1033); `chain=` selects a member on read-ba
 """
 from fractions import Fraction
 
+import math
 import warnings
 
 import numpy as np
@@ -902,21 +903,129 @@ def walker_set_get_fit_credible(walker, take=1000, points=1000, band=":95cr", x_
                          "walker-set-get-fit-credible")
 
 
-def walker_get_residuals(walker, take=1000, x_column=0, y_column=1, fn_number=0, chain=0):
-    """the data of walker-plot-residuals M:1271-1283 without the plot: [x_data, y_fit - y_data,
-    stddev] at the median parameters over `take`; y_fit at the dataset's own x, which is on the
-    device already; a stddev of one number is spread over the points (M:1280)."""
-    cap = walker.length(chain)
-    take = cap if take is None or take > cap else int(take)
+def _residual_solution(which_solution, who):
+    s = str(which_solution).lstrip(":").lower()
+    if s not in ("median", "most-likely"):
+        raise ValueError("%s: which_solution is ':median' or ':most-likely', not %r" % (who, which_solution))
+    return s
+
+
+def _residual_columns(walker, fn_number, chain, x_column=0, y_column=1):
+    """(x_data, y_data, stddev per point) of walker `chain`; a stddev of one number is spread over
+    the points (M:1280)"""
     data = walker.data_of(fn_number, chain)
     x_data = np.asarray(data[x_column], dtype=np.float64)
     y_data = np.asarray(data[y_column], dtype=np.float64)
     sd = np.asarray(walker.data_error_of(fn_number, chain), dtype=np.float64).reshape(-1)
     if sd.size == 1:
         sd = np.full(len(y_data), sd[0])
-    _, th = _fit_solution(walker, ":median", take, chain)
-    y_fit = walker.engine.eval_function(fn_number, th[0])
+    return x_data, y_data, sd
+
+
+def walker_get_residuals(walker, take=1000, x_column=0, y_column=1, fn_number=0, chain=0,
+                         which_solution=":median"):
+    """the data of walker-plot-residuals M:1271-1283 without the plot: [x_data, y_fit - y_data,
+    stddev] at the median parameters over `take` (which_solution ':most-likely': at the walker's
+    most-likely parameters); y_fit at the dataset's own x, which is on the device already; a
+    stddev of one number is spread over the points (M:1280)."""
+    cap = walker.length(chain)
+    take = cap if take is None or take > cap else int(take)
+    x_data, y_data, sd = _residual_columns(walker, fn_number, chain, x_column, y_column)
+    if _residual_solution(which_solution, "walker-get-residuals") == "median":
+        _, th = _fit_solution(walker, ":median", take, chain)
+        th = th[0]
+    else:
+        th = walker.engine.state()["best_theta"][chain]
+    y_fit = walker.engine.eval_function(fn_number, th)
     return [list(x_data), [float(a - b) for a, b in zip(y_fit, y_data)], list(sd)]
+
+
+def runs_z(n_pos, n_neg, runs):
+    """Wald and Wolfowitz's score of `runs` runs of equal sign among n_pos positive and n_neg other
+    residuals: (runs - mu) / sqrt(var) with N = n_pos + n_neg, mu = 2 n_pos n_neg / N + 1,
+    var = (mu - 1)(mu - 2) / (N - 1).  Far below zero: too few runs, the residuals are structured
+    (a peak is missing).  NaN where it is undefined (N < 2, or all residuals of one sign)."""
+    n_pos, n_neg, runs = float(n_pos), float(n_neg), float(runs)
+    N = n_pos + n_neg
+    if N < 2.0:
+        return float("nan")
+    mu = 2.0 * n_pos * n_neg / N + 1.0
+    var = (mu - 1.0) * (mu - 2.0) / (N - 1.0)
+    if not var > 0.0:
+        return float("nan")
+    return (runs - mu) / math.sqrt(var)
+
+
+def _residual_call(walker, take, fn_number, which_solution, z_limit, pointwise, who):
+    """ONE mhx_get_residuals call for the set, at the medians over `take` (one
+    mhx_get_percentiles call) or at the most-likely parameters (which the device holds)"""
+    e = walker.engine
+    theta = None
+    if _residual_solution(which_solution, who) == "median":
+        _, theta = _fit_solution(walker, ":median", take)
+    return e.residuals(fn_number, theta, z_limit=z_limit, pointwise=pointwise)
+
+
+def walker_set_get_residuals(walker, take=1000, fn_number=0, which_solution=":median"):
+    """walker_get_residuals mapped over the set: entry c is what walker_get_residuals(..., chain=c)
+    returns - [x_data, y_fit - y_data, stddev] of walker c's own data - from ONE
+    mhx_get_percentiles call (none for ':most-likely') and ONE mhx_get_residuals call, whose fit
+    values are mhx_eval_function's bits; the raw y is subtracted here, as walker_get_residuals
+    does."""
+    r = _residual_call(walker, take, fn_number, which_solution, 3.0, True, "walker-set-get-residuals")
+    out = []
+    for c in range(walker.engine.n_chains):
+        x_data, y_data, sd = _residual_columns(walker, fn_number, c)
+        out.append([list(x_data), [float(a - b) for a, b in zip(r["fit"][c], y_data)], list(sd)])
+    return out
+
+
+def _goodness_of_fit(walker, take, fn_number, which_solution, z_limit, chains, who):
+    r = _residual_call(walker, take, fn_number, which_solution, z_limit, False, who)
+    fns = _force_list(walker.function)
+    n_points = len(np.asarray(walker.data_of(fn_number, 0)[1]).reshape(-1))
+    dof = n_points - len(set(fns[fn_number].keys))
+    which = range(walker.engine.n_chains) if chains is None else [chains]
+    bad = [c for c in which if r["status"][c] & capi.RESID_NONFINITE]
+    if bad and chains is not None:
+        raise FloatingPointError(
+            "%s: a model value or a residual of walker(s) %s is not finite: the reference would have "
+            "signalled a floating-point trap here" % (who, bad[:8]))
+    out = []
+    for c in which:
+        chi2, n_pos = float(r["chi2"][c]), int(r["n_pos"][c])
+        with np.errstate(all="ignore"):
+            out.append({"chi2": chi2, "dof": dof,
+                        "reduced-chi2": float(np.float64(chi2) / np.float64(dof)),
+                        "mean-z": float(r["sum_z"][c] / np.float64(n_points)),
+                        "durbin-watson": float(r["dw"][c] / r["chi2"][c]),
+                        "runs": int(r["n_runs"][c]), "n-pos": n_pos,
+                        "runs-z": runs_z(n_pos, n_points - n_pos, int(r["n_runs"][c])),
+                        "max-z": float(r["max_abs_z"][c]), "max-z-index": int(r["max_index"][c]),
+                        "n-out": int(r["n_out"][c]), "status": int(r["status"][c])})
+    return out
+
+
+def walker_set_goodness_of_fit(walker, take=1000, fn_number=0, which_solution=":median", z_limit=3.0):
+    """Which walkers of the set fit badly: for every walker, from ONE mhx_get_residuals call (which
+    has the definitions) at the medians over `take` (':most-likely': at the most-likely
+    parameters), the dict {"chi2": the sum of the squared standardized residuals z (fit minus data
+    over the point's error), "dof": the points minus the distinct parameters function fn_number
+    reads, "reduced-chi2", "mean-z", "durbin-watson": sum (z_i - z_{i-1})^2 / chi2 (2 for
+    uncorrelated residuals, towards 0 for structured ones), "runs": the runs of equal sign,
+    "n-pos", "runs-z": runs_z of them, "max-z" and "max-z-index": the greatest |z| and its point,
+    "n-out": the points with |z| > z_limit, "status": 0 or RESID_NONFINITE (the sums of such a
+    walker mean nothing)}.  No fit values cross to the host."""
+    return _goodness_of_fit(walker, take, fn_number, which_solution, z_limit, None,
+                            "walker-set-goodness-of-fit")
+
+
+def walker_goodness_of_fit(walker, chain=0, take=1000, fn_number=0, which_solution=":median", z_limit=3.0):
+    """One walker's entry of walker_set_goodness_of_fit.  Raises FloatingPointError where a model
+    value or a residual of that walker is not finite, as walker_waic does.  The device call is the
+    whole set's: for more than a few walkers call walker_set_goodness_of_fit once."""
+    return _goodness_of_fit(walker, take, fn_number, which_solution, z_limit, int(chain),
+                            "walker-goodness-of-fit")[0]
 
 
 _EXP_PERCENTILES = {"median": (50,), "95cr": (2.5, 97.5), "iqr": (25, 75),
