@@ -481,7 +481,8 @@ int mhx_get_window_best(mhx_engine* e, int take, double* prob, double* theta);
 int mhx_get_history_capacity(mhx_engine* e, int32_t* capacity);
 /* HIP-event milliseconds the kernels of the engine's last mhx_get_percentiles / _covariances /
  * _proposal_factors / _window_best / _fit_bands / _derived / _histograms / _pair_grids / _waic /
- * _traces / _fit_percentiles / _residuals or mhx_eval_function call ran (all portions; copies excluded). */
+ * _traces / _fit_percentiles / _residuals / _normal_equations or mhx_eval_function call ran (all
+ * portions; copies excluded). */
 int mhx_get_summary_timing(mhx_engine* e, double* kernel_ms);
 /* The same for a group, gathered in global chain order like mhx_group_get_state; every
  * device's launch is enqueued before any is waited for. */
@@ -957,6 +958,74 @@ int mhx_group_get_residuals(mhx_group* g, int fn, const double* theta, double z_
                             double* z, double* chi2, double* sum_z, double* dw, double* max_abs_z,
                             int64_t* max_index, int32_t* n_pos, int32_t* n_runs, int32_t* n_out,
                             int32_t* status);
+
+/* ---- before the walk: the normal equations of EVERY walker's least-squares problem ------------
+ * What any least-squares tool forms from the Jacobian: the weighted residual vector u, the scaled
+ * Jacobian g by central differences, and their products F = g^T g (the Gauss-Newton / Fisher
+ * matrix, whose inverse is the classical covariance (J^T W J)^-1), b = g^T u (the step's right-hand
+ * side: F delta = b is the Gauss-Newton step that RAISES the likelihood) and chi2 = u^T u, for
+ * function `fn` at ONE parameter vector per chain over the chain's own data.  The definition fixes
+ * the results operation by operation; every operation is one IEEE binary64 rounding (add, subtract,
+ * multiply, divide, square root), nothing is fused, there is no fma.  N is the function's point
+ * count, d the length of the parameter vector.
+ *   theta    [n_chains][d], the caller's vectors; NULL: each chain's most-likely parameters, as
+ *            mhx_get_residuals
+ *   steps    the half-widths h of the central differences, one per place of theta: [d], or
+ *            [n_chains][d] when per_chain_steps != 0.  Each >= 0 and finite, else MHX_EINVAL.
+ *   data     as mhx_get_residuals: the numbers the engine formed when the dataset was set, w_i =
+ *            1 / sigma_i, ys_i = y_i * w_i (chain c's own row of a dataset per walker, all four
+ *            sigma_kinds); for Poisson the raw counts y_i
+ *   centre   v_i = function fn at x_i for theta_c, the very bits mhx_eval_function returns
+ *   column   for place t of theta (a GLOBAL index, 0 <= t < d) with h = steps[..][t]:
+ *            if h == 0, or function fn does not read theta_t (t is not in its gather map), the
+ *            column is exactly +0.0: g[c][t][.], jtr[c][t], and row and column t of jtj[c].  Else
+ *              tp = theta_t + h;  tm = theta_t - h;  dh = tp - tm
+ *              vp_i, vm_i = function fn at x_i for theta_c with theta_t replaced by tp, by tm - the
+ *                           very bits mhx_eval_function returns for those vectors
+ *              df = vp_i - vm_i;  J = df / dh
+ *   scaling  by the function's likelihood:
+ *              MHX_LIK_NORMAL, MHX_LIK_NORMAL_CUTOFF   g_it = J * w_i;  a = v_i * w_i;  u_i = ys_i - a
+ *                    (the cutoff's clamp is NOT differentiated: these are the normal likelihood's
+ *                    equations whatever the cutoff)
+ *              MHX_LIK_POISSON (Fisher scoring)        rt = sqrt(v_i) (correctly rounded);
+ *                    g_it = J / rt;  dl = y_i - v_i;  u_i = dl / rt
+ *              MHX_LIK_EXPR                            refused (MHX_EUNSUPPORTED), for
+ *                    mhx_get_residuals' reason: an expression likelihood's `error` need not be a sigma
+ *            u_i is the exact negation of mhx_get_residuals' z_i.  g[c][t][i] = g_it
+ *   sums     the points go in blocks of MHX_NORMEQ_BLOCK: block b holds points 1024 b ..
+ *            min(1024 b + 1023, N - 1).  Within a block each of
+ *              chi2 = sum u_i * u_i;  jtr[t] = sum g_it * u_i;  jtj[t][s] = sum g_it * g_is  (t <= s)
+ *            is formed serially in ascending i from 0.0: pr = (the product); sum = sum + pr.  A
+ *            point beyond N is skipped (not added as zero).  The blocks' sums are then added
+ *            serially in ascending b to a sum that starts at 0.0.  jtj[s][t] is a copy of
+ *            jtj[t][s]: both triangles are written.
+ *   status   MHX_NORMEQ_NONFINITE where any v_i, vp_i, vm_i, g_it or u_i of the chain is not
+ *            finite - dh == 0 with h != 0 among them, the IEEE 0/0 or x/0: the chain's numbers are
+ *            then unspecified, and no other chain is touched by it
+ * The results are the same bits from call to call, whatever portions the call is worked through in,
+ * however the points are split into chunks and however a group's chains are split over its engines.
+ * jtj [n_chains][d][d]; jtr [n_chains][d]; chi2, status [n_chains]; g [n_chains][d][N].  Any output
+ * may be NULL.  fn a function of the problem, else MHX_EINVAL; MHX_ESTATE before mhx_init_chains;
+ * the outputs stay untouched on error.  Serves every model the engine can walk.  Worked through in
+ * portions whose device scratch stays below 64 MiB (one chain's, where that alone is more);
+ * mhx_get_summary_timing covers the call.
+ * Measured (tools/normeq_timing.py, 4096 chains, one MI355X, medians of 9 warm calls): 8
+ * parameters on 1e5 shared points 44.5 ms wall, 43.9 ms of kernel (17 model values per point:
+ * 1.6e11 values/s) against 79 s by 17 mhx_eval_function calls and numpy per chain (64 chains
+ * timed, extrapolated); 4096 spectra of 334 points, a dataset per walker, 7 parameters: 0.38 ms
+ * wall, 0.17 ms of kernel, against 2.4 s. */
+#define MHX_NORMEQ_BLOCK 1024 /* points of one block of mhx_get_normal_equations' sums */
+enum {
+  MHX_NORMEQ_NONFINITE = 1
+};
+int mhx_get_normal_equations(mhx_engine* e, int fn, const double* theta, const double* steps,
+                             int per_chain_steps, double* jtj, double* jtr, double* chi2,
+                             double* g, int32_t* status);
+/* The same for a group, in global chain order (theta and per-chain steps too); every device's work
+ * is enqueued before any is waited for. */
+int mhx_group_get_normal_equations(mhx_group* g, int fn, const double* theta, const double* steps,
+                                   int per_chain_steps, double* jtj, double* jtr, double* chi2,
+                                   double* g_out, int32_t* status);
 
 /* ---- batched traces: the steps of EVERY chain, filtered and thinned on the device -------------
  * What (mapcar (lambda (w) (walker-get w :get :steps / :unique-steps / :forward-steps / :params /

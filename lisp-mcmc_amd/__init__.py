@@ -11,7 +11,7 @@ importlib.import_module("lisp-mcmc_amd").
 """
 from . import _capi as capi  # noqa: F401
 from ._capi import MhxError  # noqa: F401
-from .engine import Engine, Group, band_count, comm_unique_id, partition, split_rhat, ensemble_pick, trace_rows  # noqa: F401
+from .engine import Engine, Group, band_count, comm_unique_id, partition, split_rhat, ensemble_pick, trace_rows, normeq_steps  # noqa: F401
 from . import models  # noqa: F401
 from . import sexpr  # noqa: F401
 from . import distributed  # noqa: F401
@@ -31,6 +31,7 @@ from .walker import (  # noqa: F401
     walker_set_waic, walker_waic, waic_compare, waic_merge,
     walker_set_trace, walker_set_catepillar,
     walker_set_get_residuals, walker_set_goodness_of_fit, walker_goodness_of_fit, runs_z,
+    walker_set_laplace, walker_laplace, laplace_summary, least_squares, walker_set_least_squares,
 )
 
 __all__ = ["capi", "MhxError", "Engine", "Group", "comm_unique_id", "partition", "models", "Walker", "WalkerStep", "walker_create",
@@ -48,4 +49,6 @@ __all__ = ["capi", "MhxError", "Engine", "Group", "comm_unique_id", "partition",
            "walker_set_ensemble_get", "ensemble_pick",
            "walker_set_waic", "walker_waic", "waic_compare", "waic_merge",
            "trace_rows", "walker_set_trace", "walker_set_catepillar",
-           "walker_set_get_residuals", "walker_set_goodness_of_fit", "walker_goodness_of_fit", "runs_z"]
+           "walker_set_get_residuals", "walker_set_goodness_of_fit", "walker_goodness_of_fit", "runs_z",
+           "normeq_steps", "walker_set_laplace", "walker_laplace", "laplace_summary", "least_squares",
+           "walker_set_least_squares"]

@@ -28,6 +28,7 @@ L_OK, L_CAUGHT, L_INVALID, L_EMPTY = 0, 1, 2, 3
 AUTOCORR_NONFINITE, AUTOCORR_CONSTANT, AUTOCORR_OPEN, MAX_AUTOCORR_LAG = 1, 2, 4, 1023
 WAIC_NONFINITE, WAIC_ONE_STEP, WAIC_BLOCK = 1, 2, 256
 RESID_NONFINITE, RESID_BLOCK = 1, 256
+NORMEQ_NONFINITE, NORMEQ_BLOCK = 1, 1024
 FITPCT_NONFINITE, FITPCT_ONE_STEP, FITPCT_EMPTY, FITPCT_BLOCK = 1, 2, 4, 128
 TRACE_STEPS, TRACE_UNIQUE, TRACE_FORWARD, TRACE_PROB = 0, 1, 2, -1
 
@@ -174,6 +175,10 @@ SIGNATURES = {
                                     f64p, i64p, i32p, i32p, i32p, i32p]),
     "mhx_group_get_residuals": (C.c_int, [C.c_void_p, C.c_int, f64p, C.c_double, f64p, f64p, f64p, f64p,
                                           f64p, f64p, i64p, i32p, i32p, i32p, i32p]),
+    "mhx_get_normal_equations": (C.c_int, [C.c_void_p, C.c_int, f64p, f64p, C.c_int, f64p, f64p, f64p, f64p,
+                                           i32p]),
+    "mhx_group_get_normal_equations": (C.c_int, [C.c_void_p, C.c_int, f64p, f64p, C.c_int, f64p, f64p, f64p,
+                                                 f64p, i32p]),
     "mhx_get_fit_percentiles": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f64p, C.c_int, C.c_int64, i32p, i32p,
                                           C.c_int, f64p, f64p, f64p, i32p, i32p]),
     "mhx_group_get_fit_percentiles": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f64p, C.c_int, C.c_int64, i32p,

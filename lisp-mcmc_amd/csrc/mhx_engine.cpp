@@ -1414,7 +1414,7 @@ int mhx_create(const mhx_config* cfg, mhx_engine** out) {
     if (family_w8().configure() != hipSuccess || family_w16().configure() != hipSuccess ||
         summary_configure() != hipSuccess || fit_configure() != hipSuccess ||
         waic_configure() != hipSuccess || fitpct_configure() != hipSuccess ||
-        resid_configure() != hipSuccess) {
+        resid_configure() != hipSuccess || normeq_configure() != hipSuccess) {
       rc = fail(MHX_EDEVICE, "hipFuncSetAttribute(max dynamic LDS = %zu / %zu) failed",
                 family_w8().lds_bytes, family_w16().lds_bytes);
       break;
@@ -2996,6 +2996,154 @@ int mhx_get_residuals(mhx_engine* e, int fn, const double* theta, double z_limit
                                    n_runs, n_out, status));
 }
 
+// ---- normal equations (include/mhx.h has the definition): function fn and its central differences
+// at one parameter vector per chain over the chain's own data, the block partials of the products
+// (k_normeq), then their totals, scattered through the function's gather map (k_normeq_totals).
+// An item is a chain; the function's points go in chunks of kFitChunkPoints, a whole number of
+// MHX_NORMEQ_BLOCK blocks, so a block is the same points whatever the split.  The partials of all
+// chunks stay in the stage; the totals are taken on the last chunk.  g moves as ResidCall's fit.
+struct NormEqCall {
+  int fn = 0, per_chain = 0, p = 0, n_tasks = 0;
+  int32_t col[MHX_MAX_FN_PARAMS] = {};
+  int64_t m = 0, nb_total = 0;
+  int64_t n_all = 0;  // the chains of the caller's arrays: the engine's, or the whole group's
+  enum { JTJ, JTR, CHI2, STATUS, G, THETA, STEPS, N_DST };
+  HostDst dst[N_DST];  // (THETA and STEPS are read, not written: they lie here to move with a group's chains)
+  static_assert(kFitChunkPoints % MHX_NORMEQ_BLOCK == 0, "a chunk of points is whole blocks");
+
+  NormEqCall(int64_t n_all_, int fn_, const double* theta, const double* steps, int per_chain_steps,
+             double* jtj, double* jtr, double* chi2, double* g, int32_t* status)
+      : fn(fn_), per_chain(per_chain_steps != 0), n_all(n_all_) {
+    dst[JTJ].p = jtj, dst[JTR].p = jtr, dst[G].p = g;
+    dst[CHI2] = {chi2, sizeof(double)}, dst[STATUS] = {status, sizeof(int32_t)};
+    dst[THETA].p = const_cast<double*>(theta), dst[STEPS].p = const_cast<double*>(steps);
+  }
+  int check(mhx_engine* e) {
+    if (!e) return fail(MHX_EINVAL, "engine is NULL");
+    if (!e->chains_ready) return fail(MHX_ESTATE, "mhx_init_chains has not been called");
+    int rc = use_device(e);
+    if (rc != MHX_OK || (rc = finalize_problem(e)) != MHX_OK) return rc;
+    if (fn < 0 || fn >= e->P.K) return fail(MHX_EINVAL, "function %d out of range", fn);
+    const FnDesc& f = e->P.fn[fn];
+    if (f.lik == MHX_LIK_EXPR)
+      return fail(MHX_EUNSUPPORTED, "mhx_get_normal_equations with MHX_LIK_EXPR: an expression likelihood's "
+                                    "`error` need not be a sigma to weigh a residual by");
+    if (!dst[STEPS].p) return fail(MHX_EINVAL, "steps is NULL");
+    const int d = e->P.d;
+    // (checked before a group's calls move to their engines' chains: all of the caller's steps)
+    const double* hs = static_cast<const double*>(dst[STEPS].p);
+    const int64_t n_steps = per_chain ? n_all * (int64_t)d : d;
+    for (int64_t k = 0; k < n_steps; ++k)
+      if (!(hs[k] >= 0.0) || !std::isfinite(hs[k]))
+        return fail(MHX_EINVAL, "step %lld is negative or not finite", (long long)k);
+    m = f.n;
+    if (m < 1) return fail(MHX_EINVAL, "function %d has no data points", fn);
+    // the columns: the distinct places of theta the function reads, ascending
+    bool reads[MHX_MAX_PARAMS + 1] = {};
+    for (int j = 0; j < f.n_idx; ++j) reads[f.idx[j]] = true;
+    p = 0;
+    for (int t = 0; t < d; ++t)
+      if (reads[t]) col[p++] = t;
+    n_tasks = normeq_tasks(p);
+    nb_total = normeq_blocks(m);
+    dst[JTJ].item_bytes = (size_t)d * d * sizeof(double);
+    dst[JTR].item_bytes = dst[THETA].item_bytes = (size_t)d * sizeof(double);
+    dst[STEPS].item_bytes = per_chain ? (size_t)d * sizeof(double) : 0;
+    dst[G].item_bytes = (size_t)d * m * sizeof(double);
+    return MHX_OK;
+  }
+  int64_t items(const mhx_engine* e) const { return e->cfg.n_chains; }
+  int64_t points() const { return m; }
+  NormEqPieces carve(const mhx_engine* e, Carver& c, int64_t n_items, int64_t m_points) const {
+    return carve_normeq(c, nb_total, n_tasks, e->P.d, per_chain, dst[THETA].p ? 1 : 0, dst[G].p ? 1 : 0,
+                        n_items, m_points);
+  }
+  // what depends on the chains alone is done on the portion's first chunk of points
+  int upload(mhx_engine* e, const Portion& pn) const {
+    Carver c;
+    const NormEqPieces s = carve(e, c, pn.n, pn.m);
+    const size_t d = (size_t)e->P.d;
+    if (dst[G].p)
+      HIP_TRY(hipMemsetAsync(e->stage.p + s.g, 0, (size_t)pn.n * d * (size_t)pn.m * sizeof(double), e->stream));
+    if (pn.m0 != 0) return MHX_OK;
+    if (dst[THETA].p)
+      HIP_TRY(hipMemcpyAsync(stage_at<double>(e, s.theta), dst[THETA].at(pn.i0), (size_t)pn.n * d * sizeof(double),
+                             hipMemcpyHostToDevice, e->stream));
+    if (per_chain)
+      HIP_TRY(hipMemcpyAsync(stage_at<double>(e, s.chain_steps), dst[STEPS].at(pn.i0),
+                             (size_t)pn.n * d * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    else
+      HIP_TRY(hipMemcpyAsync(stage_at<double>(e, s.steps), dst[STEPS].p, d * sizeof(double),
+                             hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemsetAsync(stage_at<int32_t>(e, s.status), 0, (size_t)pn.n * sizeof(int32_t), e->stream));
+    HIP_TRY(hipMemsetAsync(e->stage.p + s.jtr, 0, (size_t)pn.n * d * sizeof(double), e->stream));
+    HIP_TRY(hipMemsetAsync(e->stage.p + s.jtj, 0, (size_t)pn.n * d * d * sizeof(double), e->stream));
+    return MHX_OK;
+  }
+  int launch(mhx_engine* e, const Portion& pn) const {
+    Carver c;
+    const NormEqPieces s = carve(e, c, pn.n, pn.m);
+    const FnDesc& f = e->P.fn[fn];
+    const Dataset& D = e->data[fn];
+    NormEqArgs A{};
+    A.c0 = pn.i0, A.n = pn.n;
+    A.fn = fn;
+    A.n_blocks = (int32_t)normeq_blocks(pn.m);
+    A.p = p, A.n_tasks = n_tasks, A.pitch = normeq_pitch(p);
+    A.steps_pitch = per_chain ? e->P.d : 0;
+    A.blk0 = pn.m0 / MHX_NORMEQ_BLOCK, A.nb_total = nb_total, A.m = pn.m;
+    for (int a = 0; a < p; ++a) A.col[a] = col[a];
+    A.theta = dst[THETA].p ? stage_at<double>(e, s.theta) : nullptr;
+    A.steps = stage_at<double>(e, per_chain ? s.chain_steps : s.steps);
+    A.x0 = f.x + pn.m0;
+    A.x1 = f.n_xcols > 1 ? f.c + pn.m0 : nullptr;
+    if (D.planes) {  // row c of the planes is the engine's chain c
+      A.y = D.pd.y + pn.m0, A.y_pitch = D.pd.pitch;
+      switch (D.pd.w_kind) {
+        case kPlaneWShared: A.w = f.w + pn.m0, A.w_pitch = 0, A.w_step = 1; break;
+        case kPlaneWScalar: A.w = D.pd.w, A.w_pitch = 1, A.w_step = 0; break;
+        default: A.w = D.pd.w + pn.m0, A.w_pitch = D.pd.pitch, A.w_step = 1; break;
+      }
+    } else {
+      A.y = f.y + pn.m0, A.y_pitch = 0;
+      A.w = f.w + pn.m0, A.w_pitch = 0, A.w_step = 1;
+    }
+    A.g = dst[G].p ? stage_at<double>(e, s.g) : nullptr;
+    A.part = stage_at<double>(e, s.part);
+    A.status = stage_at<int32_t>(e, s.status);
+    // (A.sub, the points of a sub-step, is the launcher's: it depends on the kernel's family)
+    HIP_TRY(e->spec == SPEC_USER ? rtc_launch_normeq(*e->user_prog, e->stream, e->dP.p, e->S, A)
+                                 : launch_normeq(e->spec, e->stream, e->dP.p, e->S, A));
+    if (pn.m0 + pn.m >= m)
+      HIP_TRY(launch_normeq_totals(e->stream, A, e->P.d, stage_at<double>(e, s.jtj), stage_at<double>(e, s.jtr),
+                                   stage_at<double>(e, s.chi2)));
+    e->launches++;
+    return MHX_OK;
+  }
+  int collect(mhx_engine* e, const Portion& pn) const {
+    Carver c;
+    const NormEqPieces s = carve(e, c, pn.n, pn.m);
+    if (dst[G].p)  // rows (chain, place) of pn.m points each, m apart at the caller's
+      HIP_TRY(hipMemcpy2D(static_cast<double*>(dst[G].at(pn.i0)) + pn.m0, (size_t)m * sizeof(double),
+                          e->stage.p + s.g, (size_t)pn.m * sizeof(double), (size_t)pn.m * sizeof(double),
+                          (size_t)pn.n * (size_t)e->P.d, hipMemcpyDeviceToHost));
+    if (pn.m0 + pn.m < m) return MHX_OK;  // (the totals come with the last chunk of points)
+    const size_t off[4] = {s.jtj, s.jtr, s.chi2, s.status};
+    for (int k = 0; k < 4; ++k) {
+      const int rc = copy_back(dst[k], pn.i0, pn.n, e->stage.p + off[k]);
+      if (rc != MHX_OK) return rc;
+    }
+    return MHX_OK;
+  }
+};
+
+int mhx_get_normal_equations(mhx_engine* e, int fn, const double* theta, const double* steps,
+                             int per_chain_steps, double* jtj, double* jtr, double* chi2, double* g,
+                             int32_t* status) {
+  return run_portions(e, NormEqCall(e ? e->cfg.n_chains : 0, fn, theta, steps, per_chain_steps, jtj, jtr, chi2,
+                                    g, status));
+}
+
 // ---- credible bands (include/mhx.h has the definition): every chain's pointwise percentiles and
 // moments of function fn over its window (k_fitpct_values, then the model-free k_fitpct_select).
 // An item is a chain.  The window's values of a portion are staged, `take` doubles per chain and
@@ -4371,6 +4519,15 @@ int mhx_group_get_residuals(mhx_group* g, int fn, const double* theta, double z_
                             int32_t* status) {
   return run_portions(g, ResidCall(fn, theta, z_limit, fit, z, chi2, sum_z, dw, max_abs_z, max_index, n_pos,
                                    n_runs, n_out, status));
+}
+
+int mhx_group_get_normal_equations(mhx_group* g, int fn, const double* theta, const double* steps,
+                                   int per_chain_steps, double* jtj, double* jtr, double* chi2,
+                                   double* g_out, int32_t* status) {
+  int64_t n_all = 0;
+  if (g)
+    for (int64_t c : g->count) n_all += c;
+  return run_portions(g, NormEqCall(n_all, fn, theta, steps, per_chain_steps, jtj, jtr, chi2, g_out, status));
 }
 
 int mhx_group_get_traces(mhx_group* g, int take, int filter, int stride, int start, const int32_t* cols,

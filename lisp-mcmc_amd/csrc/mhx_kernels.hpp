@@ -4405,6 +4405,208 @@ __global__ __launch_bounds__(kThreads) void k_resid_totals(
 }
 #endif
 
+// mhx_get_normal_equations (include/mhx.h has the definition, operation by operation; NormEqArgs,
+// mhx_types.hpp, the layout).  Wave g serves chain g / n_blocks of the launch and block
+// g % n_blocks of its points, in sub-steps of A.sub = kNormEqPts * A.lanes <= 256 points with two
+// phases each:
+//   1  lanes are points, kNormEqPts each (slot j of lane l is point j * A.lanes + l of the
+//      sub-step).  The chain's vector lies in the wave's LDS row; ONE Spec::values call site runs
+//      2 p + 1 times - at theta, then for each column with theta_t replaced by tp and by tm (lane 0
+//      writes the place, the wave's LDS operations are in order) - one prepare each, the bits of
+//      mhx_eval_function.  Four points a lane, as k_waic, and not one: a run-time compiled
+//      expression divides by reciprocal where a divisor repeats, so a call with ONE point rounds
+//      (x - mu) / w otherwise than mhx_eval_function's eight.  A column whose step is 0 is not
+//      evaluated.  The point's row {g_i0 .. g_i,p-1, u_i} goes to the wave's tile, point-major.
+//   2  lanes are tasks.  Lane l adds the products of tasks l, l + 64, ... over the sub-step's points
+//      in ascending i; its accumulators stay in registers across the block's sub-steps, so the sums
+//      are those of one serial pass over the block whatever A.sub is.
+// Points beyond m take the last point's inputs in phase 1 and are not read in phase 2.  Every
+// product and sum is rounded on its own (the unit is compiled without contraction; no fma is
+// written here).  The block's task sums go to part[chain][block][task].
+template <class Spec>
+__device__ __forceinline__ void k_normeq_body(const ProblemDesc* __restrict__ Pp, ChainState S,
+                                              NormEqArgs A) {
+  FitLds& lds = *reinterpret_cast<FitLds*>(mhx_lds_raw);
+  lds_tables_begin();
+  __syncthreads();  // (the only barrier: waves without work leave behind it)
+  const int w = wave_in_group(), l = lane_id();
+  const int64_t g = (int64_t)blockIdx.x * kWavesPerGroup + w;
+  if (g >= A.n * A.n_blocks) return;
+  const int64_t i = g / A.n_blocks;
+  const int64_t blk = g - i * A.n_blocks;
+  const FnDesc& f = Pp->fn[A.fn];
+  const int d = Pp->d;
+  const int lik = __builtin_amdgcn_readfirstlane(f.lik);
+  const int p = A.p, pitch = A.pitch, sub = A.sub, lanes = A.lanes;
+  const int64_t row = A.c0 + i;
+  const double* yr = A.y + row * A.y_pitch;
+  const double* wr = A.w + row * A.w_pitch;
+  const double* hs = A.steps + i * A.steps_pitch;
+  double* tile = reinterpret_cast<double*>(mhx_lds_raw + sizeof(FitLds)) + (size_t)w * sub * pitch;
+  const double* src = A.theta ? A.theta + i * d : S.best_theta + row * d;
+  double* th = lds.th[w];
+  if (l < d) th[l] = src[l];
+  __builtin_amdgcn_wave_barrier();
+  auto pf = [&](int j) -> double { return th[f.idx[j]]; };
+  // the lane's tasks: k = b (b + 1) / 2 + a, a <= b <= p
+  const int nq = (A.n_tasks + kWave - 1) / kWave;
+  int ta[kNormEqLaneTasks], tb[kNormEqLaneTasks];
+  double acc[kNormEqLaneTasks];
+#pragma unroll
+  for (int q = 0; q < kNormEqLaneTasks; ++q) {
+    const int k = l + q * kWave;
+    int b = 0;
+    while ((b + 1) * (b + 2) / 2 <= k && b < p) ++b;
+    const int a = k - b * (b + 1) / 2;
+    ta[q] = k < A.n_tasks ? a : 0;
+    tb[q] = k < A.n_tasks ? b : 0;
+    acc[q] = 0.0;
+  }
+  const int64_t b0 = blk * (int64_t)MHX_NORMEQ_BLOCK;
+  const int64_t b1 = b0 + MHX_NORMEQ_BLOCK < A.m ? b0 + MHX_NORMEQ_BLOCK : A.m;
+  bool bad = false;
+  for (int64_t s0 = b0; s0 < b1; s0 += sub) {
+    const int cnt = b1 - s0 < (int64_t)sub ? (int)(b1 - s0) : sub;
+    bool in[kNormEqPts];
+    int64_t pt[kNormEqPts];
+    double x0[kNormEqPts], x1[kNormEqPts], ys[kNormEqPts], wi[kNormEqPts], v[kNormEqPts];
+    double vp[kNormEqPts], rt[kNormEqPts];
+    double* mine[kNormEqPts];
+#pragma unroll
+    for (int j = 0; j < kNormEqPts; ++j) {
+      const int r = j * lanes + l;  // the point's row of the tile
+      in[j] = l < lanes && r < cnt;
+      pt[j] = in[j] ? s0 + r : b1 - 1;  // (beyond the sub-step: the block's last point, never stored)
+      x0[j] = A.x0[pt[j]];
+      x1[j] = A.x1 ? A.x1[pt[j]] : 0.0;
+      ys[j] = yr[pt[j]];
+      wi[j] = wr[pt[j] * A.w_step];
+      mine[j] = tile + (in[j] ? r : 0) * pitch;
+      vp[j] = 0.0, rt[j] = 1.0;
+    }
+    for (int k = 0; k <= 2 * p; ++k) {
+      const int a = (k - 1) >> 1;
+      const bool plus = (k & 1) != 0;
+      int t = 0;
+      double t0 = 0.0, tp = 0.0, tm = 0.0;
+      if (k > 0) {
+        t = __builtin_amdgcn_readfirstlane(A.col[a]);
+        const double h = hs[t];
+        if (h == 0.0) {  // (wave-uniform: the step is the chain's)
+          if (!plus) {
+#pragma unroll
+            for (int j = 0; j < kNormEqPts; ++j)
+              if (in[j]) mine[j][a] = 0.0;
+          }
+          continue;
+        }
+        t0 = src[t];
+        tp = t0 + h;
+        tm = t0 - h;
+        if (l == 0) th[t] = plus ? tp : tm;
+        __builtin_amdgcn_wave_barrier();
+      }
+      Spec::template values<kNormEqPts>(f, pf, lds.scr[w], x0, x1, v);
+      if (k == 0) {
+#pragma unroll
+        for (int j = 0; j < kNormEqPts; ++j) {
+          double u;
+          if (lik == MHX_LIK_POISSON) {
+            rt[j] = __builtin_sqrt(v[j]);
+            const double dl = ys[j] - v[j];
+            u = dl / rt[j];
+          } else {
+            const double av = v[j] * wi[j];
+            u = ys[j] - av;
+          }
+          if (in[j]) mine[j][p] = u;
+          bad = bad || (in[j] && (!finite_f64(v[j]) || !finite_f64(u)));
+        }
+      } else if (plus) {
+#pragma unroll
+        for (int j = 0; j < kNormEqPts; ++j) vp[j] = v[j];
+      } else {
+        const double dh = tp - tm;
+#pragma unroll
+        for (int j = 0; j < kNormEqPts; ++j) {
+          const double df = vp[j] - v[j];
+          const double J = df / dh;
+          const double gv = lik == MHX_LIK_POISSON ? J / rt[j] : J * wi[j];
+          if (in[j]) {
+            mine[j][a] = gv;
+            if (A.g) A.g[(i * d + t) * A.m + pt[j]] = gv;
+          }
+          bad = bad || (in[j] && (!finite_f64(vp[j]) || !finite_f64(v[j]) || !finite_f64(gv)));
+        }
+        if (l == 0) th[t] = t0;
+        __builtin_amdgcn_wave_barrier();
+      }
+    }
+    __builtin_amdgcn_wave_barrier();  // (the wave's own rows, written by other lanes)
+    for (int ii = 0; ii < cnt; ++ii) {
+      const double* r = tile + ii * pitch;
+#pragma unroll
+      for (int q = 0; q < kNormEqLaneTasks; ++q) {
+        if (q < nq) {
+          const double pr = r[ta[q]] * r[tb[q]];
+          acc[q] = acc[q] + pr;
+        }
+      }
+    }
+    __builtin_amdgcn_wave_barrier();  // (... which the next sub-step overwrites)
+  }
+  double* out = A.part + (i * A.nb_total + A.blk0 + blk) * (int64_t)A.n_tasks;
+#pragma unroll
+  for (int q = 0; q < kNormEqLaneTasks; ++q) {
+    const int k = l + q * kWave;
+    if (k < A.n_tasks) out[k] = acc[q];
+  }
+  if (__ballot(bad) != 0ULL && l == 0) A.status[i] = MHX_NORMEQ_NONFINITE;
+}
+#ifndef __HIPCC_RTC__
+template <class Spec>
+__global__ __launch_bounds__(kThreads) void k_normeq(const ProblemDesc* __restrict__ Pp, ChainState S,
+                                                     NormEqArgs A) {
+  k_normeq_body<Spec>(Pp, S, A);
+}
+#endif
+#if defined(MHX_FAMILY_PRIMARY) && !defined(__HIPCC_RTC__)
+// mhx_get_normal_equations, the totals: one thread per chain and task adds the blocks' partial sums
+// in block order (whatever launches wrote them) and scatters the total through the function's gather
+// map: task (a, b) to jtj[col a][col b] and its mirror, (a, p) to jtr[col a], (p, p) to chi2.  A
+// column whose step is 0 is +0.0 exactly; what the function does not read was zeroed by the host.
+__global__ __launch_bounds__(kThreads) void k_normeq_totals(NormEqArgs A, int d,
+                                                            double* __restrict__ jtj,
+                                                            double* __restrict__ jtr,
+                                                            double* __restrict__ chi2) {
+  const int64_t tid = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (tid >= A.n * A.n_tasks) return;
+  const int64_t i = tid / A.n_tasks;
+  const int k = (int)(tid - i * A.n_tasks);
+  int b = 0;
+  while ((b + 1) * (b + 2) / 2 <= k) ++b;
+  const int a = k - b * (b + 1) / 2;
+  const double* part = A.part + i * A.nb_total * (int64_t)A.n_tasks + k;
+  double s = 0.0;
+  for (int64_t blk = 0; blk < A.nb_total; ++blk) s = s + part[blk * (int64_t)A.n_tasks];
+  const double* hs = A.steps + i * A.steps_pitch;
+  const int p = A.p;
+  if (b == p) {
+    if (a == p) {
+      chi2[i] = s;
+    } else {
+      const int t = A.col[a];
+      jtr[i * d + t] = hs[t] == 0.0 ? 0.0 : s;
+    }
+  } else {
+    const int t = A.col[a], u = A.col[b];
+    const double v = (hs[t] == 0.0 || hs[u] == 0.0) ? 0.0 : s;
+    jtj[(i * d + t) * d + u] = v;
+    jtj[(i * d + u) * d + t] = v;
+  }
+}
+#endif
+
 // mhx_get_fit_percentiles, first half (include/mhx.h has the definition): k_waic's walk over the
 // window with nothing behind the model.  Wave g serves chain g / n_blocks of the launch and block
 // g % n_blocks of its points: kFitPctPts points per lane, whose x and Welford pair {mean, M2} stay

@@ -215,4 +215,15 @@ hipError_t launch_resid_totals(hipStream_t st, int64_t n, int64_t nb_total, cons
                                double* chi2, double* sum_z, double* dw, double* max_abs_z,
                                int64_t* max_index, int32_t* n_pos, int32_t* n_runs, int32_t* n_out);
 
+// mhx_get_normal_equations: the block sums of the products of the scaled Jacobian and the residual
+// (NormEqArgs, mhx_types.hpp) for the ahead-of-time specs - run-time compiled problems go through
+// rtc_launch_normeq - and the totals of A.n chains from the partials of all A.nb_total blocks,
+// scattered into jtj [n][d][d], jtr [n][d] (both zeroed by the caller) and chi2 [n].
+inline int64_t normeq_blocks(int64_t m) { return (m + MHX_NORMEQ_BLOCK - 1) / MHX_NORMEQ_BLOCK; }
+hipError_t normeq_configure();
+hipError_t launch_normeq(int spec, hipStream_t st, const ProblemDesc* P, const ChainState& S,
+                         const NormEqArgs& A);
+hipError_t launch_normeq_totals(hipStream_t st, const NormEqArgs& A, int d, double* jtj, double* jtr,
+                                double* chi2);
+
 }  // namespace mhx

@@ -465,6 +465,40 @@ hipError_t launch_resid_totals(hipStream_t st, int64_t n, int64_t nb_total, cons
   return hipGetLastError();
 }
 
+// mhx_get_normal_equations (k_normeq, k_normeq_totals): as k_waic, compiled in this family only.  The
+// tile of the widest function takes the dynamic LDS past the 64 KiB a kernel has unasked.
+hipError_t normeq_configure() {
+  hipError_t e = hipSuccess;
+  for (int s = 0; s < SPEC__COUNT; ++s)
+    for_spec(s, [&](auto sp) {
+      using SpecT = decltype(sp);
+      if (e == hipSuccess) e = no_static_lds(&k_normeq<SpecT>);
+      if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_normeq<SpecT>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kNormEqLdsBudget);
+    });
+  return e;
+}
+hipError_t launch_normeq(int spec, hipStream_t st, const ProblemDesc* P, const ChainState& S,
+                         const NormEqArgs& A) {
+  if (A.n <= 0 || A.m <= 0) return hipSuccess;
+  for_spec(spec, [&](auto sp) {
+    using SpecT = decltype(sp);
+    NormEqArgs a = A;
+    a.lanes = normeq_lanes(kWavesPerGroup, A.p), a.sub = normeq_sub(kWavesPerGroup, A.p);
+    k_normeq<SpecT><<<grid_for(A.n * A.n_blocks), dim3(kThreads), normeq_lds_bytes(kWavesPerGroup, A.p), st>>>(P, S, a);
+  });
+  return hipGetLastError();
+}
+hipError_t launch_normeq_totals(hipStream_t st, const NormEqArgs& A, int d, double* jtj, double* jtr,
+                                double* chi2) {
+  if (A.n <= 0) return hipSuccess;
+  const int64_t threads = A.n * A.n_tasks;
+  k_normeq_totals<<<dim3((unsigned)((threads + kThreads - 1) / kThreads)), dim3(kThreads), 0, st>>>(A, d, jtj, jtr,
+                                                                                                   chi2);
+  return hipGetLastError();
+}
+
 // mhx_get_fit_percentiles (k_fitpct_values, k_fitpct_select): as k_waic, compiled in this family only
 hipError_t fitpct_configure() {
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fitpct_select),

@@ -345,6 +345,9 @@ static std::string generate(const std::vector<UserExpr>& models,
        "extern \"C\" __global__ __launch_bounds__(MHX_USER_THREADS) void mhx_user_resid(\n"
        "    const ProblemDesc* P, ChainState S, ResidArgs A) {\n"
        "  k_resid_body<UserSpec>(P, S, A);\n}\n"
+       "extern \"C\" __global__ __launch_bounds__(MHX_USER_THREADS) void mhx_user_normeq(\n"
+       "    const ProblemDesc* P, ChainState S, NormEqArgs A) {\n"
+       "  k_normeq_body<UserSpec>(P, S, A);\n}\n"
        "extern \"C\" __global__ __launch_bounds__(MHX_USER_THREADS) void mhx_user_fitpct(\n"
        "    const ProblemDesc* P, ChainState S, FitPctArgs A) {\n"
        "  k_fitpct_values_body<UserSpec>(P, S, A);\n}\n"
@@ -611,6 +614,16 @@ static int build_once(const std::vector<UserExpr>& models, const std::vector<Use
                             : std::string("module function mhx_user_resid has static LDS");
     return -1;
   }
+  // (its tile can take the dynamic LDS past the 64 KiB a kernel has unasked)
+  he = hipModuleGetFunction(&prog->f_normeq, prog->module, "mhx_user_normeq");
+  if (he == hipSuccess)
+    he = hipFuncSetAttribute(reinterpret_cast<const void*>(prog->f_normeq),
+                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)kNormEqLdsBudget);
+  if (he != hipSuccess || static_lds(prog->f_normeq) != 0) {
+    *err = he != hipSuccess ? std::string("module function mhx_user_normeq: ") + hipGetErrorString(he)
+                            : std::string("module function mhx_user_normeq has static LDS");
+    return -1;
+  }
   he = hipModuleGetFunction(&prog->f_fitpct, prog->module, "mhx_user_fitpct");
   if (he != hipSuccess || static_lds(prog->f_fitpct) != 0) {
     *err = he != hipSuccess ? std::string("module function mhx_user_fitpct: ") + hipGetErrorString(he)
@@ -749,6 +762,16 @@ hipError_t rtc_launch_resid(const UserProgram& p, hipStream_t st, const ProblemD
   void* args[] = {(void*)&P, (void*)&s, (void*)&a};
   return hipModuleLaunchKernel(p.f_resid, grid_for(p, A.n * A.n_blocks), 1, 1, (unsigned)p.fam->threads,
                                1, 1, fit_lds_bytes(p.fam->waves_per_group), st, args, nullptr);
+}
+hipError_t rtc_launch_normeq(const UserProgram& p, hipStream_t st, const ProblemDesc* P,
+                             const ChainState& S, const NormEqArgs& A) {
+  if (A.n <= 0 || A.m <= 0) return hipSuccess;
+  ChainState s = S;
+  NormEqArgs a = A;
+  a.lanes = normeq_lanes(p.fam->waves_per_group, A.p), a.sub = normeq_sub(p.fam->waves_per_group, A.p);
+  void* args[] = {(void*)&P, (void*)&s, (void*)&a};
+  return hipModuleLaunchKernel(p.f_normeq, grid_for(p, A.n * A.n_blocks), 1, 1, (unsigned)p.fam->threads,
+                               1, 1, normeq_lds_bytes(p.fam->waves_per_group, A.p), st, args, nullptr);
 }
 hipError_t rtc_launch_fitpct(const UserProgram& p, hipStream_t st, const ProblemDesc* P,
                              const ChainState& S, const FitPctArgs& A) {

@@ -239,6 +239,30 @@ inline ResidPieces carve_resid(Carver& c, int64_t nb_total, int d, int with_thet
   s.z = c.take((want & RESID_WANT_Z) ? n * m * sizeof(double) : 0);
   return s;
 }
+// Normal equations of n chains at m points of a function of nb_total blocks and n_tasks tasks in a
+// problem of d parameters: the shared steps [d] come first (per_chain_steps: empty here), then
+// what depends on the chains alone and keeps its place from one chunk of points to the next -
+// status, chi2 [n], jtr [n][d], jtj [n][d][d], the per-chain steps [n][d] (else empty), the
+// caller's parameter vectors theta [n][d] (with_theta 0: empty), the blocks' partials
+// [n][nb_total][n_tasks] - then the Jacobian g [n][d][m] where the caller asked for it.
+struct NormEqPieces {
+  size_t steps, status, chi2, jtr, jtj, chain_steps, theta, part, g;
+};
+inline NormEqPieces carve_normeq(Carver& c, int64_t nb_total, int n_tasks, int d_, int per_chain_steps,
+                                 int with_theta, int want_g, int64_t n_, int64_t m_) {
+  const size_t n = (size_t)n_, m = (size_t)m_, nb = (size_t)nb_total, d = (size_t)d_;
+  NormEqPieces s;
+  s.steps = c.take(per_chain_steps ? 0 : d * sizeof(double));
+  s.status = c.take(n * sizeof(int32_t));
+  s.chi2 = c.take(n * sizeof(double));
+  s.jtr = c.take(n * d * sizeof(double));
+  s.jtj = c.take(n * d * d * sizeof(double));
+  s.chain_steps = c.take(per_chain_steps ? n * d * sizeof(double) : 0);
+  s.theta = c.take(with_theta ? n * d * sizeof(double) : 0);
+  s.part = c.take(n * nb * (size_t)n_tasks * sizeof(double));
+  s.g = c.take(want_g ? n * d * m * sizeof(double) : 0);
+  return s;
+}
 // batched traces: the caller's column list [n_cols] - it does not grow with n and comes first -
 // the rows values [n][max_out][n_cols], their envelopes lo and hi of the same shape (envelope 0:
 // both empty, the kernel does not write them), n_out, n_kept, n_used [n], and the kept-index

@@ -343,6 +343,60 @@ struct ResidArgs {
   int32_t* status;      // [n] MHX_RESID_NONFINITE is stored where a value or a residual is not finite
 };
 
+// k_normeq (mhx_get_normal_equations): the scaled Jacobian g by central differences, the weighted
+// residual u and the block sums of their products, for function `fn` at ONE parameter vector per
+// chain over the chain's own data (read through pitches as ResidArgs has them).  A wave serves one
+// chain and one block of MHX_NORMEQ_BLOCK points, in sub-steps of `sub` = kNormEqPts * `lanes` <= 256
+// points (a lane evaluates kNormEqPts = 4 of them, as k_waic: k_normeq_body says why) whose rows
+// {g_i0 .. g_i,p-1, u_i} lie point-major in the wave's LDS tile, `pitch` doubles apart.  The p
+// columns are the distinct places of theta the function reads, col[] ascending; a TASK is a pair
+// (a <= b) of the p + 1 columns of a row - a, b < p an entry of jtj, b == p one of jtr, a == b == p
+// chi2 - in the order k = b (b + 1) / 2 + a.  Lane l keeps tasks l, l + 64, ... in registers.
+// part [n][nb_total][n_tasks] receives the blocks' sums; k_normeq_totals adds them in block order.
+//   pitch  odd, >= p + 1: the 16 lanes of a ds_write_b64 group, `pitch` doubles apart, fall on 16
+//          different pairs of the 32 write banks; a phase-2 ds_read_b64 has all lanes in ONE row of
+//          at most 33 doubles (66 dwords of the 64 read banks): equal addresses broadcast, and only
+//          columns 0 and 32 of the widest tile share a bank
+//   sub    what keeps the workgroup's LDS inside kNormEqLdsBudget, a CU's 160 KiB: all 64 lanes
+//          have points up to p = 8 in the family of 8 waves, one workgroup a CU
+constexpr int kNormEqCols = MHX_MAX_FN_PARAMS + 1;
+constexpr int kNormEqMaxTasks = kNormEqCols * (kNormEqCols + 1) / 2;  // 561
+constexpr int kNormEqLaneTasks = (kNormEqMaxTasks + kWave - 1) / kWave;  // 9
+constexpr unsigned kNormEqLdsBudget = 160u * 1024u;
+constexpr int kNormEqPts = 4;  // points a lane evaluates in one Spec::values
+static_assert(kNormEqLaneTasks == 9, "nine tasks a lane at MHX_MAX_FN_PARAMS columns");
+constexpr int normeq_tasks(int p) { return (p + 1) * (p + 2) / 2; }
+constexpr int normeq_pitch(int p) { return (p + 1) | 1; }
+constexpr int normeq_lanes(int wpg, int p) {  // lanes of a wave that have points in a sub-step
+  const unsigned per_point = (unsigned)wpg * (unsigned)normeq_pitch(p) * 8u;
+  const unsigned fit = (kNormEqLdsBudget - fit_lds_bytes(wpg)) / per_point / (unsigned)kNormEqPts;
+  return fit >= (unsigned)kWave ? kWave : (int)fit;
+}
+constexpr int normeq_sub(int wpg, int p) { return kNormEqPts * normeq_lanes(wpg, p); }
+constexpr unsigned normeq_lds_bytes(int wpg, int p) {
+  return fit_lds_bytes(wpg) + (unsigned)wpg * (unsigned)normeq_sub(wpg, p) * (unsigned)normeq_pitch(p) * 8u;
+}
+static_assert(normeq_lanes(16, MHX_MAX_FN_PARAMS) >= 8 && normeq_lanes(8, 8) == kWave, "normeq_lanes");
+static_assert(MHX_NORMEQ_BLOCK % (kNormEqPts * kWave) == 0, "whole sub-steps at the widest");
+struct NormEqArgs {
+  int64_t c0, n;
+  int32_t fn, n_blocks, w_step, p;
+  int32_t n_tasks, pitch, sub, steps_pitch;  // steps_pitch 0: one [d] for all chains; d: [n][d]
+  int32_t lanes, pad_;
+  int64_t blk0, nb_total, m;
+  int64_t y_pitch, w_pitch;
+  int32_t col[MHX_MAX_FN_PARAMS];  // [p] the places of theta the function reads, ascending
+  const double* theta;  // [n][d] or nullptr
+  const double* steps;  // [d] or [n][d]
+  const double* x0;
+  const double* x1;     // the second column of x, or nullptr
+  const double* y;
+  const double* w;
+  double* g;            // [n][d][m] or nullptr (zeroed by the host: the kernel writes active columns)
+  double* part;         // [n][nb_total][n_tasks]
+  int32_t* status;      // [n] MHX_NORMEQ_NONFINITE is stored where a value is not finite
+};
+
 // mhx_user_derived (mhx_get_derived, mhx_derived.hpp): the expressions of one run-time compiled
 // module over the windows of the n chains from c0 on.  idx[j] = the place in theta of the j-th
 // name; values [n][n_expr][pitch] newest first, at_best [n][n_expr] (the most-likely step).

@@ -14,6 +14,14 @@ def percentile_ratio(p):
     return f.numerator, f.denominator
 
 
+def normeq_steps(theta):
+    """the default half-widths of normal_equations' central differences: cbrt(2^-52) |theta_t|, the
+    step that balances a central difference's truncation against its rounding, with 1.0 in place
+    of |theta_t| where theta_t is 0"""
+    th = np.abs(np.asarray(theta, dtype=np.float64))
+    return np.cbrt(2.0 ** -52) * np.where(th == 0.0, 1.0, th)
+
+
 class _Summaries:
     """walker-set-get's batched read-backs (include/mhx.h): every chain in one launch.  Shared by
     Engine (mhx_get_*) and Group (mhx_group_get_*)."""
@@ -291,6 +299,41 @@ class _Summaries:
             *(out[k].ctypes.data_as(capi.f64p) for k in ("chi2", "sum_z", "dw", "max_abs_z")),
             out["max_index"].ctypes.data_as(capi.i64p),
             *(out[k].ctypes.data_as(capi.i32p) for k in ("n_pos", "n_runs", "n_out", "status"))))
+        return out
+
+    def normal_equations(self, fn, theta=None, steps=None, pointwise=False):
+        """The normal equations of every walker's least-squares problem for function `fn` at one
+        parameter vector each (mhx_get_normal_equations, which has the definition): theta
+        [n_chains, d], None: every chain's most-likely parameters; steps the half-widths of the
+        central differences, [d] for all chains or [n_chains, d], None: normeq_steps(theta); a step
+        of 0 leaves that parameter out (its row and column are +0.0).  A dict of jtj [n_chains, d,
+        d] (g^T g of the scaled Jacobian g, the Fisher matrix), jtr [n_chains, d] (g^T u with u
+        the weighted residual data minus fit: F delta = jtr is the Gauss-Newton step), chi2 (u^T u)
+        and status (NORMEQ_NONFINITE 1) [n_chains].  pointwise=True adds g [n_chains, d, N]."""
+        n, d = self.n_chains, self.d
+        pts = getattr(self, "_datasets", {}).get(int(fn), (0, 1))[0]
+        if pointwise and pts < 1:
+            raise ValueError("normal_equations: function %d has no dataset set through this object" % int(fn))
+        thp = None
+        if theta is not None:
+            th = np.ascontiguousarray(theta, dtype=np.float64)
+            if th.shape != (n, d):
+                raise ValueError("normal_equations: theta must be [n_chains, d] = [%d, %d]" % (n, d))
+            thp = th.ctypes.data_as(capi.f64p)
+        if steps is None:
+            steps = normeq_steps(th if theta is not None else self.state()["best_theta"])
+        hs = np.ascontiguousarray(steps, dtype=np.float64)
+        if hs.shape not in ((d,), (n, d)):
+            raise ValueError("normal_equations: steps must be [d] or [n_chains, d]")
+        out = {"jtj": np.zeros((n, d, d)), "jtr": np.zeros((n, d)), "chi2": np.zeros(n),
+               "status": np.zeros(n, dtype=np.int32)}
+        if pointwise:
+            out["g"] = np.zeros((n, d, pts))
+        capi.check(self._summary("normal_equations")(
+            self._h, int(fn), thp, hs.ctypes.data_as(capi.f64p), int(hs.ndim == 2),
+            *(out[k].ctypes.data_as(capi.f64p) for k in ("jtj", "jtr", "chi2")),
+            out["g"].ctypes.data_as(capi.f64p) if pointwise else None,
+            out["status"].ctypes.data_as(capi.i32p)))
         return out
 
     TRACE_FILTERS ={"steps": capi.TRACE_STEPS, "unique": capi.TRACE_UNIQUE, "forward": capi.TRACE_FORWARD}

@@ -293,6 +293,14 @@ library, or without a gfx950 device, walker-create signals MHX-ERROR."
   (g :pointer) (fn :int) (theta :pointer) (z-limit :double) (fit :pointer) (z :pointer)
   (chi2 :pointer) (sum-z :pointer) (dw :pointer) (max-abs-z :pointer) (max-index :pointer)
   (n-pos :pointer) (n-runs :pointer) (n-out :pointer) (status :pointer))
+;; normal equations: g^T g, g^T u and u^T u of every walker's least-squares problem (theta may be null)
+(defconstant +normeq-nonfinite+ 1)
+(cffi:defcfun ("mhx_get_normal_equations" %mhx-get-normal-equations) :int
+  (e :pointer) (fn :int) (theta :pointer) (steps :pointer) (per-chain-steps :int) (jtj :pointer)
+  (jtr :pointer) (chi2 :pointer) (g :pointer) (status :pointer))
+(cffi:defcfun ("mhx_group_get_normal_equations" %mhx-group-get-normal-equations) :int
+  (g :pointer) (fn :int) (theta :pointer) (steps :pointer) (per-chain-steps :int) (jtj :pointer)
+  (jtr :pointer) (chi2 :pointer) (g-out :pointer) (status :pointer))
 (cffi:defcfun ("mhx_get_traces" %mhx-get-traces) :int
   (e :pointer) (take :int) (filter :int) (stride :int) (start :int) (cols :pointer) (n-cols :int)
   (max-out :int) (values :pointer) (lo :pointer) (hi :pointer) (n-out :pointer) (n-kept :pointer)

@@ -25,6 +25,7 @@
    #:walker-set-autocorr #:walker-set-rhat #:walker-set-ensemble-get
    #:walker-set-waic #:walker-waic
    #:walker-set-get-residuals #:walker-set-goodness-of-fit #:walker-goodness-of-fit #:runs-z
+   #:walker-set-laplace #:walker-laplace #:normeq-steps
    #:walker-set-trace #:walker-set-catepillar
    #:walker-save #:walker-load #:diagonal-covariance
    #:mfit-walker-estop #:request-stop

@@ -1498,6 +1498,93 @@ than a few walkers call walker-set-goodness-of-fit once and take its elements."
              :operation 'walker-goodness-of-fit :operands (list :chain chain)))
     entry))
 
+;;; ------------------------------------------------------------------ before the walk: Laplace
+;;; The normal equations of every walker's least-squares problem from ONE device call per function
+;;; (mhx_get_normal_equations, whose comment in include/mhx.h has the definition): the sums F =
+;;; g^T g, b = g^T u and chi2 = u^T u, added over the functions of a global fit in ascending order.
+;;; The shim returns the device's sums; the inverse of F, the proposal factor and the
+;;; Levenberg-Marquardt polish are host linear algebra and stay in the Python mirror
+;;; (walker_set_laplace, least_squares), as waic_compare does.
+(defun normeq-steps (values)
+  "the default half-widths of the central differences: cbrt(2^-52) |v|, with 1 in place of |v|
+where v is 0"
+  (mapcar (lambda (v)
+            (let ((a (abs (coerce v 'double-float))))
+              (* 6.0554544523933395d-6 (if (zerop a) 1d0 a))))
+          values))
+
+(defun walker-set-laplace (walker &key (which-solution :most-likely) (take 1000) steps fixed)
+  "For every walker of the set the plist (:params :chi2 :dof :reduced-chi2 :gradient :fisher-matrix
+:status) of its least-squares problem at its most-likely parameters (WHICH-SOLUTION :median: at
+the medians over TAKE): the sum of the squared weighted residuals, the points minus the varied
+keys, their quotient, the plist key -> b = g^T u, F = g^T g as a list of rows in the order of the
+walker's keys, and 0 or +normeq-nonfinite+ (the sums of such a walker mean nothing).  STEPS: a plist
+key -> half-width of the central difference (default: normeq-steps of the parameters); the keys in
+FIXED are held: their rows and columns are zero.  The covariance is the inverse of F over the
+varied keys."
+  (let* ((n (walker-n-chains walker))
+         (keys (walker-param-keys walker))
+         (d (length keys))
+         (k-fns (length (force-list (walker-function walker))))
+         (points (loop for fn below k-fns
+                       sum (length (first (elt (walker-data walker) fn)))))
+         (dof (- points (- d (length fixed))))
+         (plists (if (eq which-solution :most-likely)
+                     (loop for c below n
+                           collect (walker-step-params (walker-most-likely-step walker c)))
+                     (walker-set-get walker :get :median-params :take take)))
+         (f-sum (make-array (* n d d) :element-type 'double-float :initial-element 0d0))
+         (b-sum (make-array (* n d) :element-type 'double-float :initial-element 0d0))
+         (chi-sum (make-array n :element-type 'double-float :initial-element 0d0))
+         (flags (make-array n :element-type 'fixnum :initial-element 0))
+         (none (cffi:null-pointer)))
+    (cffi:with-foreign-objects ((th :double (* n d)) (hs :double (* n d)) (jtj :double (* n d d))
+                                (jtr :double (* n d)) (chi2 :double n) (status :int32 n))
+      (fill-doubles th (loop for plist in plists append (%parameter-vector walker plist)))
+      (fill-doubles hs (loop for plist in plists
+                             append (loop for k in keys
+                                          for h in (normeq-steps (%parameter-vector walker plist))
+                                          collect (cond ((member k fixed) 0d0)
+                                                        ((getf steps k)
+                                                         (coerce (getf steps k) 'double-float))
+                                                        (t h)))))
+      (dotimes (fn k-fns)
+        (%set-call walker #'%mhx-get-normal-equations #'%mhx-group-get-normal-equations
+                   fn th hs 1 jtj jtr chi2 none status)
+        (dotimes (i (* n d d))
+          (incf (aref f-sum i) (cffi:mem-aref jtj :double i)))
+        (dotimes (i (* n d))
+          (incf (aref b-sum i) (cffi:mem-aref jtr :double i)))
+        (dotimes (c n)
+          (incf (aref chi-sum c) (cffi:mem-aref chi2 :double c))
+          (unless (zerop (cffi:mem-aref status :int32 c))
+            (setf (aref flags c) +normeq-nonfinite+)))))
+    (loop for c below n
+          for plist in plists
+          collect (let ((chi (aref chi-sum c))
+                        (flag (aref flags c)))
+                    (list :params plist :chi2 chi :dof dof
+                          :reduced-chi2 (if (and (zerop flag) (plusp dof)) (/ chi dof) nil)
+                          :gradient (loop for k in keys
+                                          for j from 0
+                                          append (list k (aref b-sum (+ (* c d) j))))
+                          :fisher-matrix (loop for i below d
+                                               collect (loop for j below d
+                                                             collect (aref f-sum (+ (* c d d) (* i d) j))))
+                          :status flag)))))
+
+(defun walker-laplace (walker &key (chain 0) (which-solution :most-likely) (take 1000) steps fixed)
+  "One walker's entry of walker-set-laplace.  FLOATING-POINT-INVALID-OPERATION where a value of
+that walker is not finite.  The device call is the whole set's: for more than a few walkers call
+walker-set-laplace once and take its elements."
+  (let ((entry (elt (walker-set-laplace walker :which-solution which-solution :take take
+                                               :steps steps :fixed fixed)
+                    chain)))
+    (unless (zerop (getf entry :status))
+      (error 'floating-point-invalid-operation
+             :operation 'walker-laplace :operands (list :chain chain)))
+    entry))
+
 ;;; ------------------------------------------------------------------ save / load M:971-1001
 ;;; The plist the reference's (commented) walker-construct-print-list builds, written and read
 ;;; under with-standard-io-syntax; functions are only NAMED in the file, so walker-load wants

@@ -1028,6 +1028,199 @@ def walker_goodness_of_fit(walker, chain=0, take=1000, fn_number=0, which_soluti
                             "walker-goodness-of-fit")[0]
 
 
+# ---------------------------------------------------------------------- before the walk: Laplace
+# The classical answer beside the sampled one, and a proposal to start the walk from: the normal
+# equations of every walker come from ONE device call per function (mhx_get_normal_equations,
+# whose comment in include/mhx.h has the definition, bit for bit); what is done with them here -
+# the inverse, the Cholesky factor, the polish - is numpy's linear algebra and is NOT bit-defined.
+LAPLACE_NONFINITE, LAPLACE_NOT_POSITIVE = 1, 2
+
+
+def laplace_summary(F, b, chi2, n_points, varied, status=0):
+    """The Laplace (Gauss-Newton) summary of ONE walker from its normal equations F [d, d], b [d],
+    chi2 over n_points points, host arithmetic: `varied` are the places of theta that were varied
+    (p of them; the others are fixed: their rows and columns of F are zero).  A dict of
+    "chi2", "dof" = n_points - p, "reduced-chi2", "gradient" = b [d], "covariance-matrix" = F^-1
+    over the varied places [p, p], "stddev-params" [d] (0 for a fixed place), "correlation" [p, p],
+    "newton-decrement" = b^T F^-1 b, "l-matrix" = chol(F^-1) 2.38 / sqrt(p) laid into [d, d] with
+    a zero row and column for a fixed place, and "status": 0, LAPLACE_NONFINITE (a value of the
+    device's or of F is not finite) or LAPLACE_NOT_POSITIVE (F has no Cholesky factor); what cannot
+    be formed then is None."""
+    F = np.asarray(F, dtype=np.float64)
+    b = np.asarray(b, dtype=np.float64)
+    d = b.size
+    varied = [int(t) for t in varied]
+    p = len(varied)
+    dof = int(n_points) - p
+    out = {"chi2": float(chi2), "dof": dof,
+           "reduced-chi2": float(np.float64(chi2) / np.float64(dof)) if dof > 0 else float("nan"),
+           "gradient": b.copy(), "covariance-matrix": None, "stddev-params": None, "correlation": None,
+           "newton-decrement": None, "l-matrix": None, "status": 0}
+    Fv, bv = F[np.ix_(varied, varied)], b[varied]
+    if status or not (np.isfinite(Fv).all() and np.isfinite(bv).all() and np.isfinite(chi2)):
+        out["status"] = LAPLACE_NONFINITE
+        return out
+    try:
+        np.linalg.cholesky(Fv)
+        cov = np.linalg.inv(Fv)
+        cov = 0.5 * (cov + cov.T)
+        lc = np.linalg.cholesky(cov)
+    except np.linalg.LinAlgError:
+        out["status"] = LAPLACE_NOT_POSITIVE
+        return out
+    sd = np.sqrt(np.diag(cov))
+    stddev, L = np.zeros(d), np.zeros((d, d))
+    stddev[varied] = sd
+    L[np.ix_(varied, varied)] = lc * (2.38 / np.sqrt(p))
+    out.update({"covariance-matrix": cov, "stddev-params": stddev, "correlation": cov / np.outer(sd, sd),
+                "newton-decrement": float(bv @ np.linalg.solve(Fv, bv)), "l-matrix": L})
+    return out
+
+
+def _normal_equations_all(engine, theta, steps):
+    """(F, b, chi2, status) of every walker, summed over the functions of a global fit in
+    ascending k: one mhx_get_normal_equations call per function"""
+    F = b = chi2 = status = None
+    for k in range(engine.K):
+        r = engine.normal_equations(k, theta, steps)
+        if F is None:
+            F, b, chi2, status = r["jtj"], r["jtr"], r["chi2"], r["status"].copy()
+        else:
+            with np.errstate(all="ignore"):
+                F, b, chi2 = F + r["jtj"], b + r["jtr"], chi2 + r["chi2"]
+            status |= r["status"]
+    return F, b, chi2, status
+
+
+def _laplace_steps(walker, theta, steps, fixed):
+    """the steps [n_chains, d] of a Laplace call: `steps` None (normeq_steps of theta), an array [d]
+    or [n_chains, d], or a plist / dict key -> h for some keys; 0 for the keys named in `fixed`"""
+    from .engine import normeq_steps
+    e = walker.engine
+    keys = list(walker.param_keys)
+    hs = normeq_steps(theta)
+    if isinstance(steps, dict) or (isinstance(steps, (list, tuple)) and steps and isinstance(steps[0], str)):
+        for k, h in zip(*_plist(steps)):
+            hs[:, keys.index(k)] = float(h)
+    elif steps is not None:
+        hs = np.broadcast_to(np.asarray(steps, dtype=np.float64), (e.n_chains, e.d)).copy()
+    fixed_at = sorted(keys.index(_key(k)) for k in fixed)
+    hs[:, fixed_at] = 0.0
+    return hs, [t for t in range(e.d) if t not in fixed_at]
+
+
+def _laplace(walker, theta, steps, fixed, chains):
+    e = walker.engine
+    if theta is None:
+        theta = e.state()["best_theta"]
+    theta = np.ascontiguousarray(theta, dtype=np.float64)
+    hs, varied = _laplace_steps(walker, theta, steps, fixed)
+    F, b, chi2, status = _normal_equations_all(e, theta, hs)
+    n_points = sum(len(np.asarray(walker.data_of(k, 0)[-1]).reshape(-1)) for k in range(e.K))
+    out = []
+    for c in (range(e.n_chains) if chains is None else [chains]):
+        s = laplace_summary(F[c], b[c], chi2[c], n_points, varied, int(status[c]))
+        s["params"] = dict(zip(walker.param_keys, (float(v) for v in theta[c])))
+        s["varied-keys"] = [walker.param_keys[t] for t in varied]
+        out.append(s)
+    return out
+
+
+def _laplace_theta(walker, which_solution, take, who):
+    if _residual_solution(which_solution, who) == "median":
+        return _fit_solution(walker, ":median", take)[1]
+    return None
+
+
+def walker_set_laplace(walker, which_solution=":most-likely", take=1000, steps=None, fixed=()):
+    """The classical least-squares answer of every walker of the set, at its most-likely parameters
+    (which_solution ':median': at the medians over `take`): a list with, walker by walker,
+    laplace_summary's dict - chi2, dof, reduced-chi2, gradient, covariance-matrix (J^T W J)^-1 over
+    the varied keys, stddev-params, correlation, newton-decrement, l-matrix, status - and "params"
+    and "varied-keys".  `steps`: the half-widths of the central differences (_laplace_steps);
+    keys named in `fixed` are held.  F and b are summed over the functions of a global fit in
+    ascending k.  The "l-matrix" is a proposal factor walker_adaptive_steps_full takes as
+    l_matrix=: np.array([s["l-matrix"] for s in ...]) gives every walker its own.  One device call
+    per function for the whole set, a dataset per walker included; the linear algebra is numpy's
+    and not bit-defined."""
+    return _laplace(walker, _laplace_theta(walker, which_solution, take, "walker-set-laplace"), steps, fixed, None)
+
+
+def walker_laplace(walker, chain=0, which_solution=":most-likely", take=1000, steps=None, fixed=()):
+    """One walker's entry of walker_set_laplace.  The device call is the whole set's: for more than
+    a few walkers call walker_set_laplace once."""
+    return _laplace(walker, _laplace_theta(walker, which_solution, take, "walker-laplace"), steps, fixed,
+                    int(chain))[0]
+
+
+def least_squares(normal_equations, objective, theta0, iterations=25, damping=1e-3):
+    """Levenberg-Marquardt for many walkers at once, over two callables (host arithmetic, not
+    bit-defined): normal_equations(theta [n, d]) -> (F [n, d, d], b [n, d]) with F delta = b the
+    Gauss-Newton step that raises the fit, and objective(theta [n, d]) -> [n], what must not fall
+    (the log-posterior, so that the soft bounds hold).  Per walker and iteration
+    (F + lambda diag F) delta = b is solved and theta + delta is taken only where the objective
+    RISES; lambda, `damping` at first, is divided by 10 on success and multiplied by 10 on
+    failure.  A place whose row of F is zero (a fixed key) does not move.  Returns {"theta",
+    "objective", "iterations": the last iteration (1-based) that moved the walker, 0 if none,
+    "damping": lambda at the end, "history": the objective after every iteration [iterations + 1,
+    n]}."""
+    theta = np.array(theta0, dtype=np.float64, ndmin=2)
+    n, d = theta.shape
+    obj = np.asarray(objective(theta), dtype=np.float64).copy()
+    lam = np.full(n, float(damping))
+    used = np.zeros(n, dtype=np.int64)
+    history = [obj.copy()]
+    for it in range(1, int(iterations) + 1):
+        F, b = normal_equations(theta)[:2]
+        F, b = np.asarray(F, dtype=np.float64), np.asarray(b, dtype=np.float64)
+        trial = theta.copy()
+        ok = np.zeros(n, dtype=bool)
+        for c in range(n):
+            dg = np.diag(F[c]).copy()
+            live = dg > 0.0
+            if not live.any() or not (np.isfinite(F[c]).all() and np.isfinite(b[c]).all()):
+                continue
+            A = F[c][np.ix_(live, live)] + lam[c] * np.diag(dg[live])
+            try:
+                delta = np.linalg.solve(A, b[c][live])
+            except np.linalg.LinAlgError:
+                continue
+            if np.isfinite(delta).all():
+                trial[c, live] = theta[c, live] + delta
+                ok[c] = True
+        with np.errstate(all="ignore"):
+            new = np.asarray(objective(trial), dtype=np.float64)
+            took = ok & (new > obj)
+        theta[took], obj[took], used[took] = trial[took], new[took], it
+        lam = np.where(took, lam / 10.0, lam * 10.0)
+        history.append(obj.copy())
+    return {"theta": theta, "objective": obj, "iterations": used, "damping": lam, "history": np.array(history)}
+
+
+def walker_set_least_squares(walker, iterations=25, apply=False):
+    """Polish every walker of the set to its least-squares point before the walk: least_squares
+    from the walkers' most-likely parameters, driven by Engine.normal_equations (summed over the
+    functions of a global fit) and Engine.logpost - (2 p + 1) model sweeps and one log-posterior
+    per iteration for the WHOLE set.  Returns {"theta" [n_chains, d], "params": the plists,
+    "laplace": walker_set_laplace's entries at the polished parameters, "iterations",
+    "objective"}.  apply=True calls init_chains on the result: the walkers stand there and their
+    histories are reset, as that call documents."""
+    from .engine import normeq_steps
+    e = walker.engine
+
+    def equations(theta):
+        F, b, _, _ = _normal_equations_all(e, theta, normeq_steps(theta))
+        return F, b
+    r = least_squares(equations, lambda theta: e.logpost(np.ascontiguousarray(theta)),
+                      e.state()["best_theta"], iterations=iterations)
+    theta = np.ascontiguousarray(r["theta"])
+    lap = _laplace(walker, theta, None, (), None)
+    if apply:
+        e.init_chains(theta)
+    return {"theta": theta, "params": [s["params"] for s in lap], "laplace": lap,
+            "iterations": r["iterations"], "objective": r["objective"]}
+
+
 _EXP_PERCENTILES = {"median": (50,), "95cr": (2.5, 97.5), "iqr": (25, 75),
                     "stddev-normal": (50, 84.1)}
 _EXP_SELECTORS = ("most-likely", "median", "95cr", "iqr", "mean", "stddev", "stddev-normal",
