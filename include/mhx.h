@@ -481,8 +481,8 @@ int mhx_get_window_best(mhx_engine* e, int take, double* prob, double* theta);
 int mhx_get_history_capacity(mhx_engine* e, int32_t* capacity);
 /* HIP-event milliseconds the kernels of the engine's last mhx_get_percentiles / _covariances /
  * _proposal_factors / _window_best / _fit_bands / _derived / _histograms / _pair_grids / _waic /
- * _traces / _fit_percentiles / _residuals / _normal_equations or mhx_eval_function call ran (all
- * portions; copies excluded). */
+ * _traces / _fit_percentiles / _residuals / _normal_equations / _candidate_scores or
+ * mhx_eval_function call ran (all portions; copies excluded). */
 int mhx_get_summary_timing(mhx_engine* e, double* kernel_ms);
 /* The same for a group, gathered in global chain order like mhx_group_get_state; every
  * device's launch is enqueued before any is waited for. */
@@ -1026,6 +1026,58 @@ int mhx_get_normal_equations(mhx_engine* e, int fn, const double* theta, const d
 int mhx_group_get_normal_equations(mhx_group* g, int fn, const double* theta, const double* steps,
                                    int per_chain_steps, double* jtj, double* jtr, double* chi2,
                                    double* g_out, int32_t* status);
+
+/* ---- candidate search: the chi-square of MANY parameter vectors per walker, ranked on the device.
+ * The brute-force stage of a least-squares toolkit (lmfit's brute, MINUIT's scan) for a walker set:
+ * every chain tries m candidate vectors against its own data in one call, the points are read once,
+ * and the `keep` best come back.  Levenberg-Marquardt and the walk's proposal are local; where a
+ * line moves from spectrum to spectrum this finds the basin they start in.  It also gives the
+ * chi-square maps drawn around a solution (per_chain candidates: each walker's own vector with one
+ * or two places replaced).  The definition fixes the results operation by operation.
+ *   cand      per_chain == 0: [m][d], tried by every chain; else [n_chains][m][d], chain c's own.
+ *             Full parameter vectors.
+ *   fn        >= 0: that function alone; -1: all K functions of the problem
+ *   term      chi2_k(c, j), for function k, chain c and candidate j, is exactly the chi2 that
+ *             mhx_get_residuals defines for theta = cand_j over chain c's data: the shared dataset
+ *             or the chain's plane (all four sigma_kinds); v_i the bits of mhx_eval_function; z_i per
+ *             likelihood as stated there; t_i = z_i * z_i summed by the MHX_RESID_BLOCK rule (lane
+ *             j = i mod 64 of a block serially from 0.0, the lanes pairwise 32, 16, 8, 4, 2, 1 apart,
+ *             the blocks serially in ascending order from 0.0).  Nothing is fused.
+ *   score     score[c][j] = 0.0 + chi2_k0 + chi2_k1 + ..., added serially in ascending k over the
+ *             selected functions
+ *   not finite  where some v_i or z_i of a selected function is not finite, or the total is not
+ *             finite, score[c][j] is exactly +infinity and the candidate counts in n_bad[c].  No
+ *             other candidate or chain is touched by it.
+ *   ranking   best_index[c][r], best_score[c][r], r = 0 .. keep-1: chain c's candidates in ascending
+ *             (score, index) order - equal scores (those at +infinity too) go to the smaller index.
+ *             Where m < keep the remaining entries are index -1, score +infinity.
+ * The results are the same bits from call to call, whatever portions the call is worked through in
+ * and however a group's chains are split over its engines.
+ * score [n_chains][m]; best_index, best_score [n_chains][keep]; n_bad [n_chains].  Any output may be
+ * NULL.  m in [1, 2^31 - 2], keep in [1, MHX_CAND_KEEP_MAX], fn -1 or a function of the problem and
+ * cand not NULL, else MHX_EINVAL; MHX_EINVAL too where ONE chain's pieces - m scores and m block sums
+ * for each of the selected functions' blocks, 8 bytes each, and the shared candidates - outgrow the
+ * stage: try fewer candidates a call.  MHX_ESTATE before mhx_init_chains.  MHX_EUNSUPPORTED, by name,
+ * where a selected function has an expression likelihood (MHX_LIK_EXPR), as mhx_get_residuals
+ * refuses it.  The outputs stay untouched on error.  Serves every model the engine can walk.  Worked
+ * through in portions of chains whose device scratch stays below 64 MiB; mhx_get_summary_timing
+ * covers the call.
+ * Measured (tools/cand_timing.py, 4096 chains, one MI355X, build csrc:2a3e91c16c6b7519 - the
+ * kernels of this commit, before this comment was completed - medians of 9 warm calls): 4096
+ * spectra of 334 points, a dataset per walker, 7 parameters, a shared 17 x 17 grid: 1.43 ms wall,
+ * 1.03 ms of kernel, against 57.8 ms by 289 mhx_get_residuals calls; 64 shared candidates of 8
+ * parameters on 1e5 shared points: 55.8 ms wall, 54.6 ms of kernel (4.8e11 model values/s), against
+ * 288 ms by 64 mhx_get_residuals calls.  (One mhx_logpost of all 262144 rows - the walk's own sum,
+ * other bits, shared data only - takes 9.7 ms there.) */
+#define MHX_CAND_KEEP_MAX 16 /* the most candidates mhx_get_candidate_scores ranks per chain */
+int mhx_get_candidate_scores(mhx_engine* e, int fn, const double* cand, int64_t m, int per_chain,
+                             int keep, double* score, int32_t* best_index, double* best_score,
+                             int32_t* n_bad);
+/* The same for a group, in global chain order (per-chain candidates too); every device's work is
+ * enqueued before any is waited for. */
+int mhx_group_get_candidate_scores(mhx_group* g, int fn, const double* cand, int64_t m, int per_chain,
+                                   int keep, double* score, int32_t* best_index, double* best_score,
+                                   int32_t* n_bad);
 
 /* ---- batched traces: the steps of EVERY chain, filtered and thinned on the device -------------
  * What (mapcar (lambda (w) (walker-get w :get :steps / :unique-steps / :forward-steps / :params /

@@ -32,6 +32,7 @@ from .walker import (  # noqa: F401
     walker_set_trace, walker_set_catepillar,
     walker_set_get_residuals, walker_set_goodness_of_fit, walker_goodness_of_fit, runs_z,
     walker_set_laplace, walker_laplace, laplace_summary, least_squares, walker_set_least_squares,
+    candidate_grid, walker_set_search, walker_search, walker_set_chi2_map,
 )
 
 __all__ = ["capi", "MhxError", "Engine", "Group", "comm_unique_id", "partition", "models", "Walker", "WalkerStep", "walker_create",
@@ -51,4 +52,5 @@ __all__ = ["capi", "MhxError", "Engine", "Group", "comm_unique_id", "partition",
            "trace_rows", "walker_set_trace", "walker_set_catepillar",
            "walker_set_get_residuals", "walker_set_goodness_of_fit", "walker_goodness_of_fit", "runs_z",
            "normeq_steps", "walker_set_laplace", "walker_laplace", "laplace_summary", "least_squares",
-           "walker_set_least_squares"]
+           "walker_set_least_squares",
+           "candidate_grid", "walker_set_search", "walker_search", "walker_set_chi2_map"]

@@ -29,6 +29,7 @@ AUTOCORR_NONFINITE, AUTOCORR_CONSTANT, AUTOCORR_OPEN, MAX_AUTOCORR_LAG = 1, 2, 4
 WAIC_NONFINITE, WAIC_ONE_STEP, WAIC_BLOCK = 1, 2, 256
 RESID_NONFINITE, RESID_BLOCK = 1, 256
 NORMEQ_NONFINITE, NORMEQ_BLOCK = 1, 1024
+CAND_KEEP_MAX = 16
 FITPCT_NONFINITE, FITPCT_ONE_STEP, FITPCT_EMPTY, FITPCT_BLOCK = 1, 2, 4, 128
 TRACE_STEPS, TRACE_UNIQUE, TRACE_FORWARD, TRACE_PROB = 0, 1, 2, -1
 
@@ -179,6 +180,10 @@ SIGNATURES = {
                                            i32p]),
     "mhx_group_get_normal_equations": (C.c_int, [C.c_void_p, C.c_int, f64p, f64p, C.c_int, f64p, f64p, f64p,
                                                  f64p, i32p]),
+    "mhx_get_candidate_scores": (C.c_int, [C.c_void_p, C.c_int, f64p, C.c_int64, C.c_int, C.c_int, f64p, i32p,
+                                           f64p, i32p]),
+    "mhx_group_get_candidate_scores": (C.c_int, [C.c_void_p, C.c_int, f64p, C.c_int64, C.c_int, C.c_int, f64p,
+                                                 i32p, f64p, i32p]),
     "mhx_get_fit_percentiles": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f64p, C.c_int, C.c_int64, i32p, i32p,
                                           C.c_int, f64p, f64p, f64p, i32p, i32p]),
     "mhx_group_get_fit_percentiles": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f64p, C.c_int, C.c_int64, i32p,

@@ -1414,7 +1414,8 @@ int mhx_create(const mhx_config* cfg, mhx_engine** out) {
     if (family_w8().configure() != hipSuccess || family_w16().configure() != hipSuccess ||
         summary_configure() != hipSuccess || fit_configure() != hipSuccess ||
         waic_configure() != hipSuccess || fitpct_configure() != hipSuccess ||
-        resid_configure() != hipSuccess || normeq_configure() != hipSuccess) {
+        resid_configure() != hipSuccess || normeq_configure() != hipSuccess ||
+        cand_configure() != hipSuccess) {
       rc = fail(MHX_EDEVICE, "hipFuncSetAttribute(max dynamic LDS = %zu / %zu) failed",
                 family_w8().lds_bytes, family_w16().lds_bytes);
       break;
@@ -3144,6 +3145,126 @@ int mhx_get_normal_equations(mhx_engine* e, int fn, const double* theta, const d
                                     g, status));
 }
 
+// ---- candidate scores (include/mhx.h has the definition): the chi-square of m_cand parameter
+// vectors per chain over the chain's own data, function by function (k_cand: one launch a selected
+// function, over all of its points - nothing pointwise comes back, so the points need no chunks and
+// a block is the same points whatever the portions), then every candidate's total and the chain's
+// `keep` best (k_cand_totals).  An item is a chain; its pieces are the m_cand scores and the
+// m_cand x nb_pitch block sums, nb_pitch the blocks of all selected functions.  The data are read
+// where the engine holds them, as ResidCall reads them.
+struct CandCall {
+  int fn = 0, per_chain = 0, keep = 0;
+  int64_t m_cand = 0, nb_pitch = 0;
+  enum { SCORE, BEST_INDEX, BEST_SCORE, N_BAD, CAND, N_DST };
+  HostDst dst[N_DST];  // (CAND is read, not written: it lies here to move with a group's chains)
+
+  CandCall(int fn_, const double* cand, int64_t m, int per_chain_, int keep_, double* score,
+           int32_t* best_index, double* best_score, int32_t* n_bad)
+      : fn(fn_), per_chain(per_chain_ != 0), keep(keep_), m_cand(m) {
+    dst[SCORE].p = score, dst[BEST_INDEX].p = best_index, dst[BEST_SCORE].p = best_score;
+    dst[N_BAD] = {n_bad, sizeof(int32_t)};
+    dst[CAND].p = const_cast<double*>(cand);
+  }
+  int first_fn() const { return fn >= 0 ? fn : 0; }
+  int end_fn(const mhx_engine* e) const { return fn >= 0 ? fn + 1 : e->P.K; }
+  int check(mhx_engine* e) {
+    if (!e) return fail(MHX_EINVAL, "engine is NULL");
+    if (!dst[CAND].p) return fail(MHX_EINVAL, "cand is NULL");
+    if (m_cand < 1 || m_cand > (int64_t)INT32_MAX - 1)
+      return fail(MHX_EINVAL, "m must be in [1, 2^31 - 2]");
+    if (keep < 1 || keep > MHX_CAND_KEEP_MAX)
+      return fail(MHX_EINVAL, "keep must be in [1,%d]", MHX_CAND_KEEP_MAX);
+    if (!e->chains_ready) return fail(MHX_ESTATE, "mhx_init_chains has not been called");
+    int rc = use_device(e);
+    if (rc != MHX_OK || (rc = finalize_problem(e)) != MHX_OK) return rc;
+    if (fn < -1 || fn >= e->P.K) return fail(MHX_EINVAL, "function %d out of range (-1: all)", fn);
+    nb_pitch = 0;
+    for (int k = first_fn(); k < end_fn(e); ++k) {
+      if (e->P.fn[k].lik == MHX_LIK_EXPR)
+        return fail(MHX_EUNSUPPORTED, "mhx_get_candidate_scores with MHX_LIK_EXPR (function %d): an expression "
+                                      "likelihood's `error` need not be a sigma to divide a residual by", k);
+      if (e->P.fn[k].n < 1) return fail(MHX_EINVAL, "function %d has no data points", k);
+      nb_pitch += resid_blocks(e->P.fn[k].n);
+    }
+    const int d = e->P.d;
+    if (!one_item_fits([&](Carver& c, int64_t n) { carve_cand(c, nb_pitch, d, per_chain, keep, m_cand, n); }))
+      return fail(MHX_EINVAL, "%lld candidates over %lld blocks of points outgrow the stage: try fewer a call",
+                  (long long)m_cand, (long long)nb_pitch);
+    dst[SCORE].item_bytes = (size_t)m_cand * sizeof(double);
+    dst[BEST_INDEX].item_bytes = (size_t)keep * sizeof(int32_t);
+    dst[BEST_SCORE].item_bytes = (size_t)keep * sizeof(double);
+    dst[CAND].item_bytes = per_chain ? (size_t)m_cand * (size_t)d * sizeof(double) : 0;
+    return MHX_OK;
+  }
+  int64_t items(const mhx_engine* e) const { return e->cfg.n_chains; }
+  int64_t points() const { return 1; }
+  CandPieces carve(const mhx_engine* e, Carver& c, int64_t n_items, int64_t) const {
+    return carve_cand(c, nb_pitch, e->P.d, per_chain, keep, m_cand, n_items);
+  }
+  int upload(mhx_engine* e, const Portion& p) const {
+    Carver c;
+    const CandPieces s = carve(e, c, p.n, p.m);
+    const size_t row = (size_t)m_cand * (size_t)e->P.d * sizeof(double);
+    HIP_TRY(hipMemcpyAsync(stage_at<double>(e, s.cand), per_chain ? dst[CAND].at(p.i0) : dst[CAND].p,
+                           per_chain ? (size_t)p.n * row : row, hipMemcpyHostToDevice, e->stream));
+    return MHX_OK;
+  }
+  int launch(mhx_engine* e, const Portion& p) const {
+    Carver c;
+    const CandPieces s = carve(e, c, p.n, p.m);
+    int64_t blk0 = 0;
+    for (int k = first_fn(); k < end_fn(e); ++k) {
+      const FnDesc& f = e->P.fn[k];
+      const Dataset& D = e->data[k];
+      CandArgs A{};
+      A.c0 = p.i0, A.n = p.n;
+      A.fn = k;
+      A.n_blocks = (int32_t)resid_blocks(f.n);
+      A.m_cand = m_cand, A.cand_pitch = per_chain ? m_cand : 0;
+      A.blk0 = blk0, A.nb_pitch = nb_pitch, A.m = f.n;
+      A.cand = stage_at<double>(e, s.cand);
+      A.x0 = f.x;
+      A.x1 = f.n_xcols > 1 ? f.c : nullptr;
+      if (D.planes) {  // row c of the planes is the engine's chain c
+        A.y = D.pd.y, A.y_pitch = D.pd.pitch;
+        switch (D.pd.w_kind) {
+          case kPlaneWShared: A.w = f.w, A.w_pitch = 0, A.w_step = 1; break;
+          case kPlaneWScalar: A.w = D.pd.w, A.w_pitch = 1, A.w_step = 0; break;
+          default: A.w = D.pd.w, A.w_pitch = D.pd.pitch, A.w_step = 1; break;
+        }
+      } else {
+        A.y = f.y, A.y_pitch = 0;
+        A.w = f.w, A.w_pitch = 0, A.w_step = 1;
+      }
+      A.part = stage_at<double>(e, s.part);
+      HIP_TRY(e->spec == SPEC_USER ? rtc_launch_cand(*e->user_prog, e->stream, e->dP.p, A)
+                                   : launch_cand(e->spec, e->stream, e->dP.p, A));
+      blk0 += A.n_blocks;
+    }
+    HIP_TRY(launch_cand_totals(e->stream, e->dP.p, fn, p.n, m_cand, nb_pitch, keep, stage_at<double>(e, s.part),
+                               stage_at<double>(e, s.score), stage_at<int32_t>(e, s.best_index),
+                               stage_at<double>(e, s.best_score), stage_at<int32_t>(e, s.n_bad)));
+    e->launches++;
+    return MHX_OK;
+  }
+  int collect(mhx_engine* e, const Portion& p) const {
+    Carver c;
+    const CandPieces s = carve(e, c, p.n, p.m);
+    const size_t off[4] = {s.score, s.best_index, s.best_score, s.n_bad};
+    for (int k = 0; k < 4; ++k) {
+      const int rc = copy_back(dst[k], p.i0, p.n, e->stage.p + off[k]);
+      if (rc != MHX_OK) return rc;
+    }
+    return MHX_OK;
+  }
+};
+
+int mhx_get_candidate_scores(mhx_engine* e, int fn, const double* cand, int64_t m, int per_chain,
+                             int keep, double* score, int32_t* best_index, double* best_score,
+                             int32_t* n_bad) {
+  return run_portions(e, CandCall(fn, cand, m, per_chain, keep, score, best_index, best_score, n_bad));
+}
+
 // ---- credible bands (include/mhx.h has the definition): every chain's pointwise percentiles and
 // moments of function fn over its window (k_fitpct_values, then the model-free k_fitpct_select).
 // An item is a chain.  The window's values of a portion are staged, `take` doubles per chain and
@@ -4528,6 +4649,12 @@ int mhx_group_get_normal_equations(mhx_group* g, int fn, const double* theta, co
   if (g)
     for (int64_t c : g->count) n_all += c;
   return run_portions(g, NormEqCall(n_all, fn, theta, steps, per_chain_steps, jtj, jtr, chi2, g_out, status));
+}
+
+int mhx_group_get_candidate_scores(mhx_group* g, int fn, const double* cand, int64_t m, int per_chain,
+                                   int keep, double* score, int32_t* best_index, double* best_score,
+                                   int32_t* n_bad) {
+  return run_portions(g, CandCall(fn, cand, m, per_chain, keep, score, best_index, best_score, n_bad));
 }
 
 int mhx_group_get_traces(mhx_group* g, int take, int filter, int stride, int start, const int32_t* cols,

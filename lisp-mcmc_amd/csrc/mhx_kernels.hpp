@@ -4607,6 +4607,154 @@ __global__ __launch_bounds__(kThreads) void k_normeq_totals(NormEqArgs A, int d,
 }
 #endif
 
+// mhx_get_candidate_scores (include/mhx.h has the definition): k_resid's chi2 for MANY parameter
+// vectors per chain, the points read once.  Wave g serves chain g / n_blocks of the launch and block
+// g % n_blocks of its points: x, y/sigma and 1/sigma of kResidPts points per lane stay in registers
+// while the wave walks the chain's candidates (CandArgs has the layout), each through the wave's LDS
+// row with the next one's load in flight as k_fit does: ONE Spec::values (the bits of
+// mhx_eval_function), z per likelihood, the lane's serial sum of z * z and wave_sum - the
+// operations, in the order, of k_resid's chi2.  Points beyond m take the last point's inputs and add
+// 0.0.  A block in which some value or residual is not finite stores a NaN, which no sum of
+// k_cand_totals leaves behind.  Every product and sum is rounded on its own (the unit is compiled
+// without contraction; no fma is written here).
+template <class Spec>
+__device__ __forceinline__ void k_cand_body(const ProblemDesc* __restrict__ Pp, CandArgs A) {
+  FitLds& lds = *reinterpret_cast<FitLds*>(mhx_lds_raw);
+  lds_tables_begin();
+  __syncthreads();  // (the only barrier: waves without work leave behind it)
+  const int w = wave_in_group(), l = lane_id();
+  const int64_t g = (int64_t)blockIdx.x * kWavesPerGroup + w;
+  if (g >= A.n * A.n_blocks) return;
+  const int64_t i = g / A.n_blocks;
+  const int64_t blk = g - i * A.n_blocks;
+  const int64_t p0 = blk * (int64_t)(kWave * kResidPts) + l;
+  const FnDesc& f = Pp->fn[A.fn];
+  const int d = Pp->d;
+  const int lik = __builtin_amdgcn_readfirstlane(f.lik);
+  const int64_t row = A.c0 + i;
+  const double* yr = A.y + row * A.y_pitch;
+  const double* wr = A.w + row * A.w_pitch;
+  double x0[kResidPts], x1[kResidPts], ys[kResidPts], wi[kResidPts];
+#pragma unroll
+  for (int j = 0; j < kResidPts; ++j) {
+    const int64_t p = p0 + (int64_t)j * kWave;
+    const int64_t q = p < A.m ? p : A.m - 1;  // (beyond m: the last point once more)
+    x0[j] = A.x0[q];
+    x1[j] = A.x1 ? A.x1[q] : 0.0;
+    ys[j] = yr[q];
+    wi[j] = wr[q * A.w_step];
+  }
+  const double* cd = A.cand + i * A.cand_pitch * d;
+  double* out = A.part + i * A.m_cand * A.nb_pitch + A.blk0 + blk;
+  double* th = lds.th[w];
+  double thn = l < d ? cd[l] : 0.0;
+  for (int64_t k = 0; k < A.m_cand; ++k) {
+    if (l < d) th[l] = thn;
+    __builtin_amdgcn_wave_barrier();
+    if (k + 1 < A.m_cand && l < d) thn = cd[(k + 1) * d + l];
+    auto pf = [&](int j) -> double { return th[f.idx[j]]; };
+    double v[kResidPts], z[kResidPts];
+    Spec::template values<kResidPts>(f, pf, lds.scr[w], x0, x1, v);
+    if (lik == MHX_LIK_POISSON) {
+#pragma unroll
+      for (int j = 0; j < kResidPts; ++j) {
+        const double dl = v[j] - ys[j];
+        const double rt = __builtin_sqrt(v[j]);
+        z[j] = dl / rt;
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < kResidPts; ++j) {
+        const double a = v[j] * wi[j];
+        z[j] = a - ys[j];
+      }
+    }
+    double sc = 0.0;
+    bool bad = false;
+#pragma unroll
+    for (int j = 0; j < kResidPts; ++j) {
+      const bool in = p0 + (int64_t)j * kWave < A.m;
+      sc = sc + (in ? z[j] * z[j] : 0.0);
+      bad = bad || (in && (!finite_f64(v[j]) || !finite_f64(z[j])));
+    }
+    sc = wave_sum(sc);
+    const bool any_bad = __ballot(bad) != 0ULL;
+    if (l == 0) out[k * A.nb_pitch] = any_bad ? __builtin_nan("") : sc;
+  }
+}
+#ifndef __HIPCC_RTC__
+template <class Spec>
+__global__ __launch_bounds__(kThreads) void k_cand(const ProblemDesc* __restrict__ Pp, CandArgs A) {
+  k_cand_body<Spec>(Pp, A);
+}
+#endif
+#if defined(MHX_FAMILY_PRIMARY) && !defined(__HIPCC_RTC__)
+// mhx_get_candidate_scores, totals and ranking: one wave per chain.  Lane l takes candidates l,
+// l + 64, ...: a function's blocks are added in block order to a sum that starts at 0.0 (chi2_k,
+// the bits of mhx_get_residuals), the functions' sums in ascending k to a total that starts at 0.0;
+// a total that is not finite - a NaN block is one of its terms where a value or residual was not -
+// becomes +infinity and counts in n_bad.  Then `keep` passes, each the wave's lexicographic minimum
+// of (score, index) over the candidates above the one taken last: no flags are kept.  No score is a
+// NaN, so every comparison is decided; index INT32_MAX stands for "none left" and is stored as -1.
+__global__ __launch_bounds__(kWave) void k_cand_totals(const ProblemDesc* __restrict__ Pp, int fn,
+                                                       int64_t n, int64_t m_cand, int64_t nb_pitch,
+                                                       int keep, const double* __restrict__ part,
+                                                       double* __restrict__ score,
+                                                       int32_t* __restrict__ best_index,
+                                                       double* __restrict__ best_score,
+                                                       int32_t* __restrict__ n_bad) {
+  const int64_t i = blockIdx.x;
+  if (i >= n) return;
+  const int l = threadIdx.x;
+  const int k0 = fn >= 0 ? fn : 0, k1 = fn >= 0 ? fn + 1 : Pp->K;
+  const double inf = __builtin_inf();
+  double* sr = score + i * m_cand;
+  int bad = 0;
+  for (int64_t j = l; j < m_cand; j += kWave) {
+    const double* pj = part + (i * m_cand + j) * nb_pitch;
+    double total = 0.0;
+    for (int k = k0; k < k1; ++k) {
+      const int64_t nb = (Pp->fn[k].n + MHX_RESID_BLOCK - 1) / MHX_RESID_BLOCK;
+      double c = 0.0;
+      for (int64_t b = 0; b < nb; ++b) c = c + pj[b];
+      pj += nb;
+      total = total + c;
+    }
+    const bool fin = finite_f64(total);
+    bad += fin ? 0 : 1;
+    sr[j] = fin ? total : inf;
+  }
+  bad = wave_sum_i(bad);
+  if (l == 0) n_bad[i] = bad;
+  // (a lane reads back below only the scores it stored above: candidates l, l + 64, ...)
+  double ls = -inf;  // the candidate taken last: every (score, index) lies above (-inf, -1)
+  int32_t lj = -1;
+  for (int r = 0; r < keep; ++r) {
+    double bs = inf;
+    int32_t bj = INT32_MAX;
+    for (int64_t j = l; j < m_cand; j += kWave) {
+      const double s = sr[j];
+      const bool above = s > ls || (s == ls && (int32_t)j > lj);
+      const bool less = s < bs || (s == bs && (int32_t)j < bj);
+      if (above && less) bs = s, bj = (int32_t)j;
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+      const double os = __shfl_xor(bs, m, kWave);
+      const int32_t oj = __shfl_xor(bj, m, kWave);
+      const bool take = os < bs || (os == bs && oj < bj);
+      bs = take ? os : bs;
+      bj = take ? oj : bj;
+    }
+    if (l == 0) {
+      best_index[i * keep + r] = bj == INT32_MAX ? -1 : bj;
+      best_score[i * keep + r] = bs;
+    }
+    ls = bs, lj = bj;  // (none left: (inf, INT32_MAX), above which nothing lies)
+  }
+}
+#endif
+
 // mhx_get_fit_percentiles, first half (include/mhx.h has the definition): k_waic's walk over the
 // window with nothing behind the model.  Wave g serves chain g / n_blocks of the launch and block
 // g % n_blocks of its points: kFitPctPts points per lane, whose x and Welford pair {mean, M2} stay

@@ -226,4 +226,15 @@ hipError_t launch_normeq(int spec, hipStream_t st, const ProblemDesc* P, const C
 hipError_t launch_normeq_totals(hipStream_t st, const NormEqArgs& A, int d, double* jtj, double* jtr,
                                 double* chi2);
 
+// mhx_get_candidate_scores: the blocks' chi-square of every candidate of every chain for one
+// function (CandArgs, mhx_types.hpp) for the ahead-of-time specs - run-time compiled problems go
+// through rtc_launch_cand - and, once all selected functions (fn, or all of them at -1) have written
+// their blocks, the scores [n][m_cand], the `keep` best of each chain and its count of candidates
+// that are not finite.
+hipError_t cand_configure();
+hipError_t launch_cand(int spec, hipStream_t st, const ProblemDesc* P, const CandArgs& A);
+hipError_t launch_cand_totals(hipStream_t st, const ProblemDesc* P, int fn, int64_t n, int64_t m_cand,
+                              int64_t nb_pitch, int keep, const double* part, double* score,
+                              int32_t* best_index, double* best_score, int32_t* n_bad);
+
 }  // namespace mhx

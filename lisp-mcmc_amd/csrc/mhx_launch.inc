@@ -499,6 +499,33 @@ hipError_t launch_normeq_totals(hipStream_t st, const NormEqArgs& A, int d, doub
   return hipGetLastError();
 }
 
+// mhx_get_candidate_scores (k_cand, k_cand_totals): as k_waic, compiled in this family only
+hipError_t cand_configure() {
+  hipError_t e = hipSuccess;
+  for (int s = 0; s < SPEC__COUNT; ++s)
+    for_spec(s, [&](auto sp) {
+      using SpecT = decltype(sp);
+      if (e == hipSuccess) e = no_static_lds(&k_cand<SpecT>);
+    });
+  return e;
+}
+hipError_t launch_cand(int spec, hipStream_t st, const ProblemDesc* P, const CandArgs& A) {
+  if (A.n <= 0 || A.m <= 0 || A.m_cand <= 0) return hipSuccess;
+  for_spec(spec, [&](auto sp) {
+    using SpecT = decltype(sp);
+    k_cand<SpecT><<<grid_for(A.n * A.n_blocks), dim3(kThreads), fit_lds_bytes(kWavesPerGroup), st>>>(P, A);
+  });
+  return hipGetLastError();
+}
+hipError_t launch_cand_totals(hipStream_t st, const ProblemDesc* P, int fn, int64_t n, int64_t m_cand,
+                              int64_t nb_pitch, int keep, const double* part, double* score,
+                              int32_t* best_index, double* best_score, int32_t* n_bad) {
+  if (n <= 0) return hipSuccess;
+  k_cand_totals<<<dim3((unsigned)n), dim3(kWave), 0, st>>>(P, fn, n, m_cand, nb_pitch, keep, part, score,
+                                                           best_index, best_score, n_bad);
+  return hipGetLastError();
+}
+
 // mhx_get_fit_percentiles (k_fitpct_values, k_fitpct_select): as k_waic, compiled in this family only
 hipError_t fitpct_configure() {
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fitpct_select),

@@ -348,6 +348,9 @@ static std::string generate(const std::vector<UserExpr>& models,
        "extern \"C\" __global__ __launch_bounds__(MHX_USER_THREADS) void mhx_user_normeq(\n"
        "    const ProblemDesc* P, ChainState S, NormEqArgs A) {\n"
        "  k_normeq_body<UserSpec>(P, S, A);\n}\n"
+       "extern \"C\" __global__ __launch_bounds__(MHX_USER_THREADS) void mhx_user_cand(\n"
+       "    const ProblemDesc* P, CandArgs A) {\n"
+       "  k_cand_body<UserSpec>(P, A);\n}\n"
        "extern \"C\" __global__ __launch_bounds__(MHX_USER_THREADS) void mhx_user_fitpct(\n"
        "    const ProblemDesc* P, ChainState S, FitPctArgs A) {\n"
        "  k_fitpct_values_body<UserSpec>(P, S, A);\n}\n"
@@ -624,6 +627,12 @@ static int build_once(const std::vector<UserExpr>& models, const std::vector<Use
                             : std::string("module function mhx_user_normeq has static LDS");
     return -1;
   }
+  he = hipModuleGetFunction(&prog->f_cand, prog->module, "mhx_user_cand");
+  if (he != hipSuccess || static_lds(prog->f_cand) != 0) {
+    *err = he != hipSuccess ? std::string("module function mhx_user_cand: ") + hipGetErrorString(he)
+                            : std::string("module function mhx_user_cand has static LDS");
+    return -1;
+  }
   he = hipModuleGetFunction(&prog->f_fitpct, prog->module, "mhx_user_fitpct");
   if (he != hipSuccess || static_lds(prog->f_fitpct) != 0) {
     *err = he != hipSuccess ? std::string("module function mhx_user_fitpct: ") + hipGetErrorString(he)
@@ -772,6 +781,14 @@ hipError_t rtc_launch_normeq(const UserProgram& p, hipStream_t st, const Problem
   void* args[] = {(void*)&P, (void*)&s, (void*)&a};
   return hipModuleLaunchKernel(p.f_normeq, grid_for(p, A.n * A.n_blocks), 1, 1, (unsigned)p.fam->threads,
                                1, 1, normeq_lds_bytes(p.fam->waves_per_group, A.p), st, args, nullptr);
+}
+hipError_t rtc_launch_cand(const UserProgram& p, hipStream_t st, const ProblemDesc* P,
+                           const CandArgs& A) {
+  if (A.n <= 0 || A.m <= 0 || A.m_cand <= 0) return hipSuccess;
+  CandArgs a = A;
+  void* args[] = {(void*)&P, (void*)&a};
+  return hipModuleLaunchKernel(p.f_cand, grid_for(p, A.n * A.n_blocks), 1, 1, (unsigned)p.fam->threads,
+                               1, 1, fit_lds_bytes(p.fam->waves_per_group), st, args, nullptr);
 }
 hipError_t rtc_launch_fitpct(const UserProgram& p, hipStream_t st, const ProblemDesc* P,
                              const ChainState& S, const FitPctArgs& A) {

@@ -45,6 +45,7 @@ struct UserProgram {
   hipFunction_t f_waic = nullptr;  // mhx_user_waic: mhx_get_waic's accumulation (k_waic_body)
   hipFunction_t f_resid = nullptr;  // mhx_user_resid: mhx_get_residuals' block partials (k_resid_body)
   hipFunction_t f_normeq = nullptr;  // mhx_user_normeq: mhx_get_normal_equations' block partials (k_normeq_body)
+  hipFunction_t f_cand = nullptr;  // mhx_user_cand: mhx_get_candidate_scores' block partials (k_cand_body)
   hipFunction_t f_fitpct = nullptr;  // mhx_user_fitpct: mhx_get_fit_percentiles' values (k_fitpct_values_body)
   hipFunction_t f_split_sweep = nullptr, f_split_step = nullptr;  // only with has_split
   hipFunction_t f_split_tsweep = nullptr;                         // (the tile-sliced sweep)
@@ -96,6 +97,8 @@ hipError_t rtc_launch_resid(const UserProgram& p, hipStream_t st, const ProblemD
                             const ChainState& S, const ResidArgs& A);
 hipError_t rtc_launch_normeq(const UserProgram& p, hipStream_t st, const ProblemDesc* P,
                              const ChainState& S, const NormEqArgs& A);
+hipError_t rtc_launch_cand(const UserProgram& p, hipStream_t st, const ProblemDesc* P,
+                           const CandArgs& A);
 hipError_t rtc_launch_fitpct(const UserProgram& p, hipStream_t st, const ProblemDesc* P,
                              const ChainState& S, const FitPctArgs& A);
 hipError_t rtc_launch_init(const UserProgram& p, hipStream_t st, const ProblemDesc* P,

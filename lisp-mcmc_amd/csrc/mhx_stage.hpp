@@ -263,6 +263,26 @@ inline NormEqPieces carve_normeq(Carver& c, int64_t nb_total, int n_tasks, int d
   s.g = c.take(want_g ? n * d * m * sizeof(double) : 0);
   return s;
 }
+// Candidate scores of n chains, m_cand candidates each, over functions of nb_pitch blocks in all:
+// the candidates [m_cand][d] - one set for every chain (per_chain 0: the piece does not grow with n
+// and comes first either way) or [n][m_cand][d] - then n_bad [n], best_index, best_score [n][keep],
+// the scores [n][m_cand] (always carved: the ranking reads them) and the blocks' sums
+// [n][m_cand][nb_pitch].
+struct CandPieces {
+  size_t cand, n_bad, best_index, best_score, score, part;
+};
+inline CandPieces carve_cand(Carver& c, int64_t nb_pitch, int d_, int per_chain, int keep_, int64_t m_cand,
+                             int64_t n_) {
+  const size_t n = (size_t)n_, m = (size_t)m_cand, nb = (size_t)nb_pitch, d = (size_t)d_, keep = (size_t)keep_;
+  CandPieces s;
+  s.cand = c.take((per_chain ? n : 1) * m * d * sizeof(double));
+  s.n_bad = c.take(n * sizeof(int32_t));
+  s.best_index = c.take(n * keep * sizeof(int32_t));
+  s.best_score = c.take(n * keep * sizeof(double));
+  s.score = c.take(n * m * sizeof(double));
+  s.part = c.take(n * m * nb * sizeof(double));
+  return s;
+}
 // batched traces: the caller's column list [n_cols] - it does not grow with n and comes first -
 // the rows values [n][max_out][n_cols], their envelopes lo and hi of the same shape (envelope 0:
 // both empty, the kernel does not write them), n_out, n_kept, n_used [n], and the kept-index

@@ -397,6 +397,30 @@ struct NormEqArgs {
   int32_t* status;      // [n] MHX_NORMEQ_NONFINITE is stored where a value is not finite
 };
 
+// k_cand (mhx_get_candidate_scores): function `fn` at m_cand parameter vectors per chain over the
+// chain's own data (read through pitches as ResidArgs has them), for each of n chains from c0 on.
+// A wave serves one chain and one block of MHX_RESID_BLOCK points: it loads the block's points
+// once, kResidPts per lane, and walks the candidates - cand[j] (cand_pitch 0: one [m_cand][d] for
+// every chain) or cand[i * cand_pitch + j] of the launch's chain i - each through the wave's LDS row,
+// the next one's load in flight.  The block's sum of z^2 goes to
+//   part[(i * m_cand + j) * nb_pitch + blk0 + block]
+// where nb_pitch is the blocks of ALL the call's functions and blk0 this function's first; a block
+// with a value or residual that is not finite stores a NaN.  k_cand_totals adds a candidate's
+// blocks function by function and ranks the chain's candidates.
+struct CandArgs {
+  int64_t c0, n;
+  int32_t fn, n_blocks, w_step, pad_;
+  int64_t m_cand, cand_pitch;  // cand_pitch in candidates: 0 or m_cand
+  int64_t blk0, nb_pitch, m;
+  int64_t y_pitch, w_pitch;
+  const double* cand;  // [m_cand][d] or [n][m_cand][d]
+  const double* x0;
+  const double* x1;    // the second column of x, or nullptr
+  const double* y;
+  const double* w;
+  double* part;        // [n][m_cand][nb_pitch]
+};
+
 // mhx_user_derived (mhx_get_derived, mhx_derived.hpp): the expressions of one run-time compiled
 // module over the windows of the n chains from c0 on.  idx[j] = the place in theta of the j-th
 // name; values [n][n_expr][pitch] newest first, at_best [n][n_expr] (the most-likely step).

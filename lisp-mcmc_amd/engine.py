@@ -336,6 +336,35 @@ class _Summaries:
             out["status"].ctypes.data_as(capi.i32p)))
         return out
 
+    def candidate_scores(self, cand, fn=-1, keep=1, scores=False):
+        """The chi-square of many parameter vectors per walker, ranked on the device
+        (mhx_get_candidate_scores, which has the definition): cand [m, d], tried by every chain,
+        or [n_chains, m, d], each chain's own; fn a function, -1: the sum over all of them; keep in
+        1 .. CAND_KEEP_MAX.  A dict of best_index, best_score [n_chains, keep] (ascending (score,
+        index); index -1 and +inf where m < keep), n_bad [n_chains] (candidates whose score is not
+        finite: they score +inf) and, with scores=True, score [n_chains, m]."""
+        n, d = self.n_chains, self.d
+        cd = np.ascontiguousarray(cand, dtype=np.float64)
+        if not ((cd.ndim == 2 and cd.shape[1] == d) or (cd.ndim == 3 and cd.shape[0] == n and cd.shape[2] == d)):
+            raise ValueError("candidate_scores: cand must be [m, d] or [n_chains, m, d] with n_chains = %d, d = %d"
+                             % (n, d))
+        m = cd.shape[-2]
+        if m < 1:
+            raise ValueError("candidate_scores: no candidates")
+        keep = int(keep)
+        if not 1 <= keep <= capi.CAND_KEEP_MAX:
+            raise ValueError("candidate_scores: keep must be in 1 .. %d" % capi.CAND_KEEP_MAX)
+        out = {"best_index": np.zeros((n, keep), dtype=np.int32), "best_score": np.zeros((n, keep)),
+               "n_bad": np.zeros(n, dtype=np.int32)}
+        if scores:
+            out["score"] = np.zeros((n, m))
+        capi.check(self._summary("candidate_scores")(
+            self._h, int(fn), cd.ctypes.data_as(capi.f64p), m, int(cd.ndim == 3), keep,
+            out["score"].ctypes.data_as(capi.f64p) if scores else None,
+            out["best_index"].ctypes.data_as(capi.i32p), out["best_score"].ctypes.data_as(capi.f64p),
+            out["n_bad"].ctypes.data_as(capi.i32p)))
+        return out
+
     TRACE_FILTERS ={"steps": capi.TRACE_STEPS, "unique": capi.TRACE_UNIQUE, "forward": capi.TRACE_FORWARD}
 
     def traces(self, take, cols=None, filter="steps", stride=1, start=0, max_out=None, envelope=False):

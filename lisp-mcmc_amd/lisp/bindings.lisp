@@ -301,6 +301,14 @@ library, or without a gfx950 device, walker-create signals MHX-ERROR."
 (cffi:defcfun ("mhx_group_get_normal_equations" %mhx-group-get-normal-equations) :int
   (g :pointer) (fn :int) (theta :pointer) (steps :pointer) (per-chain-steps :int) (jtj :pointer)
   (jtr :pointer) (chi2 :pointer) (g-out :pointer) (status :pointer))
+;; candidate search: the chi-square of m vectors per walker, ranked (any output may be null)
+(defconstant +cand-keep-max+ 16)
+(cffi:defcfun ("mhx_get_candidate_scores" %mhx-get-candidate-scores) :int
+  (e :pointer) (fn :int) (cand :pointer) (m :int64) (per-chain :int) (keep :int) (score :pointer)
+  (best-index :pointer) (best-score :pointer) (n-bad :pointer))
+(cffi:defcfun ("mhx_group_get_candidate_scores" %mhx-group-get-candidate-scores) :int
+  (g :pointer) (fn :int) (cand :pointer) (m :int64) (per-chain :int) (keep :int) (score :pointer)
+  (best-index :pointer) (best-score :pointer) (n-bad :pointer))
 (cffi:defcfun ("mhx_get_traces" %mhx-get-traces) :int
   (e :pointer) (take :int) (filter :int) (stride :int) (start :int) (cols :pointer) (n-cols :int)
   (max-out :int) (values :pointer) (lo :pointer) (hi :pointer) (n-out :pointer) (n-kept :pointer)

@@ -26,6 +26,7 @@
    #:walker-set-waic #:walker-waic
    #:walker-set-get-residuals #:walker-set-goodness-of-fit #:walker-goodness-of-fit #:runs-z
    #:walker-set-laplace #:walker-laplace #:normeq-steps
+   #:walker-set-search #:candidate-grid
    #:walker-set-trace #:walker-set-catepillar
    #:walker-save #:walker-load #:diagonal-covariance
    #:mfit-walker-estop #:request-stop

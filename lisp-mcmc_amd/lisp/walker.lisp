@@ -1585,6 +1585,61 @@ walker-set-laplace once and take its elements."
              :operation 'walker-laplace :operands (list :chain chain)))
     entry))
 
+;;; ------------------------------------------------------------------ before the polish: search
+;;; The brute-force stage of a least-squares toolkit for a walker set: every walker tries the same
+;;; candidate vectors against its own data in ONE device call (mhx_get_candidate_scores, whose
+;;; comment in include/mhx.h has the definition) and the device ranks them.  Ranking the kept ones
+;;; again under the prior, candidates per walker and the chi-square maps stay in the Python mirror
+;;; (walker_set_search, walker_set_chi2_map).
+(defun candidate-grid (params axes)
+  "The starts of a search: the plist PARAMS with the keys of the plist AXES (key -> list of values)
+replaced by the Cartesian product of the axes' values.  Two values: the list of plists in row-major
+order, the first axis slowest, and the list of the axes' lengths."
+  (let ((rows (list (copy-list params))))
+    (loop for (key vals) on axes by #'cddr
+          do (setf rows (loop for row in rows
+                              append (loop for v in vals
+                                           collect (let ((new (copy-list row)))
+                                                     (setf (getf new key) v)
+                                                     new)))))
+    (values rows (loop for (key vals) on axes by #'cddr
+                       collect (progn key (length vals))))))
+
+(defun walker-set-search (walker candidates &key (keep 4))
+  "For every walker of the set the plist (:params :index :chi2 :kept :n-bad) of a search over
+CANDIDATES, a list of parameter plists every walker tries against its own data, summed over the
+functions of a global fit: the candidate of least chi-square (among equals the first), its place in
+CANDIDATES and its chi-square; :kept the KEEP best as (index chi2) lists in ascending (chi2, index)
+order, at most +cand-keep-max+; :n-bad the candidates with a value or residual that is not finite
+(they rank last).  A walker without a finite candidate gets :index -1 and :params nil.  One device
+call."
+  (let* ((n (walker-n-chains walker))
+         (d (length (walker-param-keys walker)))
+         (m (length candidates))
+         (none (cffi:null-pointer))
+         (cand (cffi:foreign-alloc :double :count (max 1 (* m d)))))
+    (unwind-protect
+         (cffi:with-foreign-objects ((best-index :int32 (* n keep)) (best-score :double (* n keep))
+                                     (n-bad :int32 n))
+           (fill-doubles cand (loop for plist in candidates
+                                    append (%parameter-vector walker plist)))
+           (%set-call walker #'%mhx-get-candidate-scores #'%mhx-group-get-candidate-scores
+                      -1 cand m 0 keep none best-index best-score n-bad)
+           (loop for c below n
+                 collect (let* ((kept (loop for r below keep
+                                            for j = (cffi:mem-aref best-index :int32 (+ (* c keep) r))
+                                            when (>= j 0)
+                                              collect (list j (cffi:mem-aref best-score :double
+                                                                             (+ (* c keep) r)))))
+                                (best (first kept))
+                                (found (and best (<= (second best) most-positive-double-float))))
+                           (list :params (if found (copy-list (elt candidates (first best))) nil)
+                                 :index (if found (first best) -1)
+                                 :chi2 (if best (second best) nil)
+                                 :kept kept
+                                 :n-bad (cffi:mem-aref n-bad :int32 c)))))
+      (cffi:foreign-free cand))))
+
 ;;; ------------------------------------------------------------------ save / load M:971-1001
 ;;; The plist the reference's (commented) walker-construct-print-list builds, written and read
 ;;; under with-standard-io-syntax; functions are only NAMED in the file, so walker-load wants

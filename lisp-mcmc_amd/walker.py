@@ -1197,9 +1197,136 @@ def least_squares(normal_equations, objective, theta0, iterations=25, damping=1e
     return {"theta": theta, "objective": obj, "iterations": used, "damping": lam, "history": np.array(history)}
 
 
-def walker_set_least_squares(walker, iterations=25, apply=False):
+def _axes_items(axes):
+    """a key -> values map (a dict, or a plist key values key values ...) as [(key, values [n_k])]"""
+    if isinstance(axes, dict):
+        items = list(axes.items())
+    else:
+        a = list(axes)
+        if len(a) % 2:
+            raise ValueError("axes plist must have an even number of elements")
+        items = [(a[i], a[i + 1]) for i in range(0, len(a), 2)]
+    out = []
+    for k, v in items:
+        v = np.asarray(v, dtype=np.float64).reshape(-1)
+        if v.size < 1:
+            raise ValueError("axis %s has no values" % _key(k))
+        if _key(k) in [q for q, _ in out]:
+            raise ValueError("axis %s is named twice" % _key(k))
+        out.append((_key(k), v))
+    if not out:
+        raise ValueError("no axes")
+    return out
+
+
+def _grid_rows(keys, base, items):
+    """base [..., d] with the places of the axes' keys replaced by their Cartesian product in
+    row-major order, the first axis slowest: ([..., m, d], shape)"""
+    keys = list(keys)
+    for k, _ in items:
+        if k not in keys:
+            raise ValueError("axis %s is not a parameter (%s)" % (k, " ".join(keys)))
+    shape = tuple(len(v) for _, v in items)
+    m = int(np.prod(shape))
+    base = np.asarray(base, dtype=np.float64)
+    cand = np.repeat(base[..., None, :], m, axis=-2)
+    mesh = np.meshgrid(*(v for _, v in items), indexing="ij")
+    for (k, _), g in zip(items, mesh):
+        cand[..., keys.index(k)] = g.reshape(-1)
+    return np.ascontiguousarray(cand), shape
+
+
+def candidate_grid(params, axes):
+    """The starts of a brute-force search: `params` (a plist or dict, the base vector) with the keys
+    of `axes` (key -> values) replaced by the Cartesian product of the axes' values.  Returns (cand
+    [m, d], shape): row-major, the first axis slowest, shape = the axes' lengths, so that
+    scores.reshape(shape) is the map over the axes."""
+    keys, vals = _plist(params)
+    return _grid_rows(keys, vals, _axes_items(axes))
+
+
+def walker_set_search(walker, candidates=None, axes=None, keep=4, with_prior=True, apply=False):
+    """The brute-force stage before a polish, for every walker of the set: each walker tries the
+    candidates against its own data in ONE device call (Engine.candidate_scores over all functions)
+    and the `keep` least chi-squares are kept.  candidates: [m, d] for all walkers or [n_chains, m,
+    d]; or axes (key -> values): every walker's own most-likely parameters with those keys replaced
+    by the axes' Cartesian product (candidate_grid's order).  with_prior ranks the kept ones again
+    by Engine.logpost - `keep` calls of [n_chains, d] rows, row = walker - so that the soft bounds
+    count: the winner has the greatest log-posterior among the kept, among equals the lesser
+    chi-square; without it the winner is the least chi-square.  A candidate whose chi-square is not
+    finite never wins.  Returns, walker by walker, {"params", "index" (into the candidates),
+    "chi2", "logpost" (None without the prior), "n-bad": candidates that were not finite}; a walker
+    none of whose candidates is finite gets index -1 and its most-likely parameters.  apply=True
+    calls init_chains at the winners: the walkers stand there and their histories are reset."""
+    e = walker.engine
+    n, d = e.n_chains, e.d
+    if (candidates is None) == (axes is None):
+        raise ValueError("walker-set-search: give candidates or axes, one of them")
+    start = None
+    if candidates is None:
+        start = e.state()["best_theta"]
+        cand, _ = _grid_rows(walker.param_keys, start, _axes_items(axes))
+    else:
+        cand = np.ascontiguousarray(candidates, dtype=np.float64)
+    r = e.candidate_scores(cand, fn=-1, keep=keep)
+    idx, chi = r["best_index"], r["best_score"]
+    if start is None:
+        start = e.state()["best_theta"]
+    rows_of = (lambda j: cand[np.arange(n), j]) if cand.ndim == 3 else (lambda j: cand[j])
+    usable = (idx >= 0) & np.isfinite(chi)
+    pick = np.zeros(n, dtype=np.int64)
+    lp = None
+    if with_prior:
+        lp = np.full(idx.shape, -np.inf)
+        for k in range(idx.shape[1]):
+            rows = np.where(usable[:, k, None], rows_of(np.maximum(idx[:, k], 0)), start)
+            with np.errstate(all="ignore"):
+                v = np.asarray(e.logpost(np.ascontiguousarray(rows)), dtype=np.float64)
+            lp[:, k] = np.where(usable[:, k] & ~np.isnan(v), v, -np.inf)
+        pick = np.argmax(lp, axis=1)  # (the first of equals: the lesser chi-square)
+    found = usable[np.arange(n), pick]
+    win = np.where(found, idx[np.arange(n), pick], -1)
+    theta = np.ascontiguousarray(np.where(found[:, None], rows_of(np.maximum(win, 0)), start))
+    if apply:
+        e.init_chains(theta)
+    return [{"params": dict(zip(walker.param_keys, (float(v) for v in theta[c]))),
+             "index": int(win[c]), "chi2": float(chi[c, pick[c]]),
+             "logpost": float(lp[c, pick[c]]) if with_prior else None,
+             "n-bad": int(r["n_bad"][c])} for c in range(n)]
+
+
+def walker_search(walker, chain=0, candidates=None, axes=None, keep=4, with_prior=True):
+    """One walker's entry of walker_set_search.  The device call is the whole set's: for more than a
+    few walkers call walker_set_search once."""
+    return walker_set_search(walker, candidates=candidates, axes=axes, keep=keep,
+                             with_prior=with_prior)[int(chain)]
+
+
+def walker_set_chi2_map(walker, axes, which_solution=":most-likely", take=1000):
+    """The chi-square map around every walker's own solution - what one draws to see whether a
+    second minimum exists: the walker's most-likely parameters (which_solution ':median': the
+    medians over `take`) with the one or two keys of `axes` (key -> values) replaced by the axes'
+    values, scored over all functions in one device call.  Returns {"axes": {key: values}, "chi2"
+    [n_chains, *shape] (+inf where not finite), "delta-chi2": chi2 minus the walker's least}."""
+    e = walker.engine
+    items = _axes_items(axes)
+    if len(items) > 2:
+        raise ValueError("walker-set-chi2-map: one or two axes, not %d" % len(items))
+    theta = _laplace_theta(walker, which_solution, take, "walker-set-chi2-map")
+    if theta is None:
+        theta = e.state()["best_theta"]
+    cand, shape = _grid_rows(walker.param_keys, theta, items)
+    chi = e.candidate_scores(cand, fn=-1, keep=1, scores=True)["score"].reshape((e.n_chains,) + shape)
+    low = chi.reshape(e.n_chains, -1).min(axis=1).reshape((e.n_chains,) + (1,) * len(shape))
+    with np.errstate(invalid="ignore"):
+        delta = np.where(np.isfinite(chi), chi - low, np.inf)
+    return {"axes": {k: v for k, v in items}, "chi2": chi, "delta-chi2": delta}
+
+
+def walker_set_least_squares(walker, iterations=25, apply=False, theta0=None):
     """Polish every walker of the set to its least-squares point before the walk: least_squares
-    from the walkers' most-likely parameters, driven by Engine.normal_equations (summed over the
+    from the walkers' most-likely parameters (theta0 [n_chains, d]: from there instead, the
+    winners of walker_set_search, say), driven by Engine.normal_equations (summed over the
     functions of a global fit) and Engine.logpost - (2 p + 1) model sweeps and one log-posterior
     per iteration for the WHOLE set.  Returns {"theta" [n_chains, d], "params": the plists,
     "laplace": walker_set_laplace's entries at the polished parameters, "iterations",
@@ -1207,12 +1334,19 @@ def walker_set_least_squares(walker, iterations=25, apply=False):
     histories are reset, as that call documents."""
     from .engine import normeq_steps
     e = walker.engine
+    if theta0 is None:
+        theta0 = e.state()["best_theta"]
+    else:
+        theta0 = np.ascontiguousarray(theta0, dtype=np.float64)
+        if theta0.shape != (e.n_chains, e.d):
+            raise ValueError("walker-set-least-squares: theta0 must be [n_chains, d] = [%d, %d]"
+                             % (e.n_chains, e.d))
 
     def equations(theta):
         F, b, _, _ = _normal_equations_all(e, theta, normeq_steps(theta))
         return F, b
     r = least_squares(equations, lambda theta: e.logpost(np.ascontiguousarray(theta)),
-                      e.state()["best_theta"], iterations=iterations)
+                      theta0, iterations=iterations)
     theta = np.ascontiguousarray(r["theta"])
     lap = _laplace(walker, theta, None, (), None)
     if apply:
