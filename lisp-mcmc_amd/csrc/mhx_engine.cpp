@@ -1412,10 +1412,7 @@ int mhx_create(const mhx_config* cfg, mhx_engine** out) {
       break;
     }
     if (family_w8().configure() != hipSuccess || family_w16().configure() != hipSuccess ||
-        summary_configure() != hipSuccess || fit_configure() != hipSuccess ||
-        waic_configure() != hipSuccess || fitpct_configure() != hipSuccess ||
-        resid_configure() != hipSuccess || normeq_configure() != hipSuccess ||
-        cand_configure() != hipSuccess) {
+        summary_configure() != hipSuccess || model_readouts_configure() != hipSuccess) {
       rc = fail(MHX_EDEVICE, "hipFuncSetAttribute(max dynamic LDS = %zu / %zu) failed",
                 family_w8().lds_bytes, family_w16().lds_bytes);
       break;
@@ -2302,6 +2299,23 @@ static int copy_back(const HostDst& h, int64_t i0, int64_t n, const void* dev) {
     HIP_TRY(hipMemcpy(h.at(i0), dev, (size_t)n * h.item_bytes, hipMemcpyDeviceToHost));
   return MHX_OK;
 }
+// ... the pieces at off[k] of the stage to dst[k], k < N: portion p's results of one value per item
+template <size_t N>
+static int copy_back_each(const mhx_engine* e, const HostDst* dst, const Portion& p, const size_t (&off)[N]) {
+  for (size_t k = 0; k < N; ++k) {
+    const int rc = copy_back(dst[k], p.i0, p.n, e->stage.p + off[k]);
+    if (rc != MHX_OK) return rc;
+  }
+  return MHX_OK;
+}
+// ... and a pointwise result that arrives a chunk of points at a time: `rows` rows per item of p.m
+// points each, `per` bytes a point, to their places p.m0 .. in the caller's rows of m points
+static int copy_back_points(const HostDst& h, const Portion& p, int64_t m, size_t per, size_t rows, const void* dev) {
+  if (h.p && rows > 0)
+    HIP_TRY(hipMemcpy2D(static_cast<unsigned char*>(h.at(p.i0)) + (size_t)p.m0 * per, (size_t)m * per, dev,
+                        (size_t)p.m * per, (size_t)p.m * per, (size_t)p.n * rows, hipMemcpyDeviceToHost));
+  return MHX_OK;
+}
 // the window of a read-out of the chains' histories
 static int window_check(const mhx_engine* e, int take) {
   if (!e) return fail(MHX_EINVAL, "engine is NULL");
@@ -2309,6 +2323,26 @@ static int window_check(const mhx_engine* e, int take) {
   if (take < 1 || take > e->S.R)
     return fail(MHX_EINVAL, "take must be in [1, history_capacity = %d]", e->S.R);
   return MHX_OK;
+}
+// function fn of a ready engine, for a read-out of its model over its data: the problem is made
+// final.  sigma_of: the public call that divides a residual by sigma, which MHX_LIK_EXPR has none of.
+static int fn_check(mhx_engine* e, int fn, const char* sigma_of = nullptr) {
+  if (!e) return fail(MHX_EINVAL, "engine is NULL");
+  if (!e->chains_ready) return fail(MHX_ESTATE, "mhx_init_chains has not been called");
+  int rc = use_device(e);
+  if (rc != MHX_OK || (rc = finalize_problem(e)) != MHX_OK) return rc;
+  if (fn < 0 || fn >= e->P.K) return fail(MHX_EINVAL, "function %d out of range", fn);
+  if (sigma_of && e->P.fn[fn].lik == MHX_LIK_EXPR)
+    return fail(MHX_EUNSUPPORTED, "%s with MHX_LIK_EXPR (function %d): an expression likelihood's `error` "
+                                  "need not be a sigma to divide a residual by", sigma_of, fn);
+  if (e->P.fn[fn].n < 1) return fail(MHX_EINVAL, "function %d has no data points", fn);
+  return MHX_OK;
+}
+// the model read-out kernel of A's type: the ahead-of-time spec's, or the run-time compiled program's
+template <class Args>
+static hipError_t launch_model(mhx_engine* e, const Args& A) {
+  return e->spec == SPEC_USER ? rtc_launch_model(*e->user_prog, e->stream, e->dP.p, e->S, A)
+                              : launch_model(e->spec, e->stream, e->dP.p, e->S, A);
 }
 static int fill_pcts(PctList* pc, const int32_t* num, const int32_t* den, int n_pct) {
   if (n_pct < 0 || n_pct > MHX_MAX_PERCENTILES)
@@ -2471,12 +2505,7 @@ struct SummaryCall {
   int collect(mhx_engine* e, const Portion& p) const {
     Carver c;
     const SummaryPieces s = carve(e, c, p.n, p.m);
-    const size_t off[4] = {s.dv[0], s.dv[1], s.iv[0], s.iv[1]};
-    for (int k = 0; k < 4; ++k) {
-      const int rc = copy_back(dst[k], p.i0, p.n, e->stage.p + off[k]);
-      if (rc != MHX_OK) return rc;
-    }
-    return MHX_OK;
+    return copy_back_each(e, dst, p, {s.dv[0], s.dv[1], s.iv[0], s.iv[1]});
   }
 };
 
@@ -2710,8 +2739,7 @@ struct FitCall {
       A.theta = stage_at<double>(e, s.theta);
       A.rows_per_item = 1;
     }
-    HIP_TRY(e->spec == SPEC_USER ? rtc_launch_fit(*e->user_prog, e->stream, e->dP.p, A)
-                                 : launch_fit(e->spec, e->stream, e->dP.p, A));
+    HIP_TRY(launch_model(e, A));
     e->launches++;
     return MHX_OK;
   }
@@ -2719,17 +2747,12 @@ struct FitCall {
     Carver c;
     const FitPieces s = carve(e, c, p.n, p.m);
     const size_t dv[2] = {s.ymax, s.ymin};
-    for (int k = 0; k < (take > 0 ? 2 : 1); ++k)
-      if (dst[k].p)
-        HIP_TRY(hipMemcpy2D(static_cast<double*>(dst[k].at(p.i0)) + p.m0, (size_t)m * sizeof(double),
-                            stage_at<double>(e, dv[k]), (size_t)p.m * sizeof(double),
-                            (size_t)p.m * sizeof(double), (size_t)p.n, hipMemcpyDeviceToHost));
-    if (take > 0 && p.m0 + p.m >= m) {  // (the status gathers over the chunks of points)
-      int rc = copy_back(dst[N_SEL], p.i0, p.n, stage_at<int32_t>(e, s.n_sel));
-      if (rc != MHX_OK || (rc = copy_back(dst[STATUS], p.i0, p.n, stage_at<int32_t>(e, s.status))) != MHX_OK)
-        return rc;
+    for (int k = 0; k < (take > 0 ? 2 : 1); ++k) {
+      const int rc = copy_back_points(dst[k], p, m, sizeof(double), 1, e->stage.p + dv[k]);
+      if (rc != MHX_OK) return rc;
     }
-    return MHX_OK;
+    if (take == 0 || p.m0 + p.m < m) return MHX_OK;  // (the status gathers over the chunks of points)
+    return copy_back_each(e, dst + N_SEL, p, {s.n_sel, s.status});
   }
 };
 
@@ -2771,15 +2794,13 @@ struct WaicCall {
   }
   int check(mhx_engine* e) {
     int rc = window_check(e, take);
-    if (rc != MHX_OK || (rc = use_device(e)) != MHX_OK || (rc = finalize_problem(e)) != MHX_OK) return rc;
-    if (fn < 0 || fn >= e->P.K) return fail(MHX_EINVAL, "function %d out of range", fn);
+    if (rc != MHX_OK || (rc = fn_check(e, fn)) != MHX_OK) return rc;
     for (int k = 0; k < e->P.K; ++k)
       if (e->data[k].planes)
         return fail(MHX_EUNSUPPORTED, "mhx_get_waic on an engine with a dataset per walker "
                                       "(mhx_set_dataset_planes): the planes' per-point constants "
                                       "live per walker and are not on the device");
     m = e->P.fn[fn].n;
-    if (m < 1) return fail(MHX_EINVAL, "function %d has no data points", fn);
     nb_total = waic_blocks(m);
     dst[PW_LPPD].item_bytes = dst[PW_P].item_bytes = (size_t)m * sizeof(double);
     dst[PW_ACC].item_bytes = (size_t)m * 4 * sizeof(double);
@@ -2825,8 +2846,7 @@ struct WaicCall {
     A.part_p = stage_at<double>(e, s.part_p);
     A.part_high = stage_at<int32_t>(e, s.part_high);
     A.status = stage_at<int32_t>(e, s.status);
-    HIP_TRY(e->spec == SPEC_USER ? rtc_launch_waic(*e->user_prog, e->stream, e->dP.p, e->S, A)
-                                 : launch_waic(e->spec, e->stream, e->dP.p, e->S, A));
+    HIP_TRY(launch_model(e, A));
     if (p.m0 + p.m >= m)
       HIP_TRY(launch_waic_totals(e->stream, e->S, p.i0, p.n, take, nb_total, A.part_lppd, A.part_p, A.part_high,
                                  stage_at<double>(e, s.elpd), stage_at<double>(e, s.lppd),
@@ -2839,21 +2859,13 @@ struct WaicCall {
     Carver c;
     const WaicPieces s = carve(e, c, p.n, p.m);
     const size_t pw[3] = {s.pw_lppd, s.pw_p, s.pw_acc};
-    for (int k = 0; k < 3; ++k) {
-      const HostDst& h = dst[PW_LPPD + k];
-      const size_t per = (k == 2 ? 4 : 1) * sizeof(double);  // bytes of a point
-      if (h.p)
-        HIP_TRY(hipMemcpy2D(static_cast<unsigned char*>(h.at(p.i0)) + (size_t)p.m0 * per, (size_t)m * per,
-                            e->stage.p + pw[k], (size_t)p.m * per, (size_t)p.m * per, (size_t)p.n,
-                            hipMemcpyDeviceToHost));
-    }
-    if (p.m0 + p.m < m) return MHX_OK;  // (the totals come with the last chunk of points)
-    const size_t off[6] = {s.elpd, s.lppd, s.p_waic, s.n_high, s.n_used, s.status};
-    for (int k = 0; k < 6; ++k) {
-      const int rc = copy_back(dst[k], p.i0, p.n, e->stage.p + off[k]);
+    for (int k = 0; k < 3; ++k) {  // (pw_acc: four doubles a point)
+      const size_t per = (k == 2 ? 4 : 1) * sizeof(double);
+      const int rc = copy_back_points(dst[PW_LPPD + k], p, m, per, 1, e->stage.p + pw[k]);
       if (rc != MHX_OK) return rc;
     }
-    return MHX_OK;
+    if (p.m0 + p.m < m) return MHX_OK;  // (the totals come with the last chunk of points)
+    return copy_back_each(e, dst, p, {s.elpd, s.lppd, s.p_waic, s.n_high, s.n_used, s.status});
   }
 };
 
@@ -2869,7 +2881,7 @@ int mhx_get_waic(mhx_engine* e, int fn, int take, double* elpd, double* lppd, do
 // kFitChunkPoints, a whole number of MHX_RESID_BLOCK blocks, so a block is the same points whatever
 // the split.  The partials of all chunks stay in the stage; the totals are taken on the last chunk.
 // The data are read where the engine holds them: the shared arrays, or the planes of a dataset per
-// walker (PlaneDesc) by the pitches ResidArgs describes.
+// walker (PlaneDesc), through a DataView (data_view, mhx_stage.hpp).
 struct ResidCall {
   int fn = 0, want = 0;
   double z_limit = 0.0;
@@ -2891,17 +2903,10 @@ struct ResidCall {
     want = (fit ? RESID_WANT_FIT : 0) | (z ? RESID_WANT_Z : 0);
   }
   int check(mhx_engine* e) {
-    if (!e) return fail(MHX_EINVAL, "engine is NULL");
-    if (!e->chains_ready) return fail(MHX_ESTATE, "mhx_init_chains has not been called");
-    int rc = use_device(e);
-    if (rc != MHX_OK || (rc = finalize_problem(e)) != MHX_OK) return rc;
-    if (fn < 0 || fn >= e->P.K) return fail(MHX_EINVAL, "function %d out of range", fn);
+    const int rc = fn_check(e, fn, "mhx_get_residuals");
+    if (rc != MHX_OK) return rc;
     if (z_limit != z_limit) return fail(MHX_EINVAL, "z_limit is not a number");
-    if (e->P.fn[fn].lik == MHX_LIK_EXPR)
-      return fail(MHX_EUNSUPPORTED, "mhx_get_residuals with MHX_LIK_EXPR: an expression likelihood's "
-                                    "`error` need not be a sigma to divide a residual by");
     m = e->P.fn[fn].n;
-    if (m < 1) return fail(MHX_EINVAL, "function %d has no data points", fn);
     nb_total = resid_blocks(m);
     dst[FIT].item_bytes = dst[Z].item_bytes = (size_t)m * sizeof(double);
     dst[THETA].item_bytes = (size_t)e->P.d * sizeof(double);
@@ -2926,7 +2931,6 @@ struct ResidCall {
   int launch(mhx_engine* e, const Portion& p) const {
     Carver c;
     const ResidPieces s = carve(e, c, p.n, p.m);
-    const FnDesc& f = e->P.fn[fn];
     const Dataset& D = e->data[fn];
     ResidArgs A{};
     A.c0 = p.i0, A.n = p.n;
@@ -2935,19 +2939,7 @@ struct ResidCall {
     A.blk0 = p.m0 / MHX_RESID_BLOCK, A.nb_total = nb_total, A.m = p.m, A.p_first = p.m0;
     A.z_limit = z_limit;
     A.theta = dst[THETA].p ? stage_at<double>(e, s.theta) : nullptr;
-    A.x0 = f.x + p.m0;
-    A.x1 = f.n_xcols > 1 ? f.c + p.m0 : nullptr;
-    if (D.planes) {  // row c of the planes is the engine's chain c
-      A.y = D.pd.y + p.m0, A.y_pitch = D.pd.pitch;
-      switch (D.pd.w_kind) {
-        case kPlaneWShared: A.w = f.w + p.m0, A.w_pitch = 0, A.w_step = 1; break;
-        case kPlaneWScalar: A.w = D.pd.w, A.w_pitch = 1, A.w_step = 0; break;
-        default: A.w = D.pd.w + p.m0, A.w_pitch = D.pd.pitch, A.w_step = 1; break;
-      }
-    } else {
-      A.y = f.y + p.m0, A.y_pitch = 0;
-      A.w = f.w + p.m0, A.w_pitch = 0, A.w_step = 1;
-    }
+    A.data = data_view(e->P.fn[fn], D.planes ? &D.pd : nullptr, p.m0);
     A.fit = (want & RESID_WANT_FIT) ? stage_at<double>(e, s.fit) : nullptr;
     A.z = (want & RESID_WANT_Z) ? stage_at<double>(e, s.z) : nullptr;
     A.part_chi2 = stage_at<double>(e, s.part_chi2);
@@ -2957,8 +2949,7 @@ struct ResidCall {
     A.part_idx = stage_at<int64_t>(e, s.part_idx);
     A.part_cnt = stage_at<int32_t>(e, s.part_cnt);
     A.status = stage_at<int32_t>(e, s.status);
-    HIP_TRY(e->spec == SPEC_USER ? rtc_launch_resid(*e->user_prog, e->stream, e->dP.p, e->S, A)
-                                 : launch_resid(e->spec, e->stream, e->dP.p, e->S, A));
+    HIP_TRY(launch_model(e, A));
     if (p.m0 + p.m >= m)
       HIP_TRY(launch_resid_totals(e->stream, p.n, nb_total, A, stage_at<double>(e, s.chi2),
                                   stage_at<double>(e, s.sum_z), stage_at<double>(e, s.dw),
@@ -2973,19 +2964,12 @@ struct ResidCall {
     const ResidPieces s = carve(e, c, p.n, p.m);
     const size_t pw[2] = {s.fit, s.z};
     for (int k = 0; k < 2; ++k) {
-      const HostDst& h = dst[FIT + k];
-      if (h.p)
-        HIP_TRY(hipMemcpy2D(static_cast<double*>(h.at(p.i0)) + p.m0, (size_t)m * sizeof(double),
-                            e->stage.p + pw[k], (size_t)p.m * sizeof(double), (size_t)p.m * sizeof(double),
-                            (size_t)p.n, hipMemcpyDeviceToHost));
-    }
-    if (p.m0 + p.m < m) return MHX_OK;  // (the totals come with the last chunk of points)
-    const size_t off[9] = {s.chi2, s.sum_z, s.dw, s.max_abs_z, s.max_index, s.n_pos, s.n_runs, s.n_out, s.status};
-    for (int k = 0; k < 9; ++k) {
-      const int rc = copy_back(dst[k], p.i0, p.n, e->stage.p + off[k]);
+      const int rc = copy_back_points(dst[FIT + k], p, m, sizeof(double), 1, e->stage.p + pw[k]);
       if (rc != MHX_OK) return rc;
     }
-    return MHX_OK;
+    if (p.m0 + p.m < m) return MHX_OK;  // (the totals come with the last chunk of points)
+    return copy_back_each(e, dst, p,
+                          {s.chi2, s.sum_z, s.dw, s.max_abs_z, s.max_index, s.n_pos, s.n_runs, s.n_out, s.status});
   }
 };
 
@@ -3002,7 +2986,7 @@ int mhx_get_residuals(mhx_engine* e, int fn, const double* theta, double z_limit
 // (k_normeq), then their totals, scattered through the function's gather map (k_normeq_totals).
 // An item is a chain; the function's points go in chunks of kFitChunkPoints, a whole number of
 // MHX_NORMEQ_BLOCK blocks, so a block is the same points whatever the split.  The partials of all
-// chunks stay in the stage; the totals are taken on the last chunk.  g moves as ResidCall's fit.
+// chunks stay in the stage; the totals are taken on the last chunk.  g moves by copy_back_points.
 struct NormEqCall {
   int fn = 0, per_chain = 0, p = 0, n_tasks = 0;
   int32_t col[MHX_MAX_FN_PARAMS] = {};
@@ -3020,15 +3004,9 @@ struct NormEqCall {
     dst[THETA].p = const_cast<double*>(theta), dst[STEPS].p = const_cast<double*>(steps);
   }
   int check(mhx_engine* e) {
-    if (!e) return fail(MHX_EINVAL, "engine is NULL");
-    if (!e->chains_ready) return fail(MHX_ESTATE, "mhx_init_chains has not been called");
-    int rc = use_device(e);
-    if (rc != MHX_OK || (rc = finalize_problem(e)) != MHX_OK) return rc;
-    if (fn < 0 || fn >= e->P.K) return fail(MHX_EINVAL, "function %d out of range", fn);
+    const int rc = fn_check(e, fn, "mhx_get_normal_equations");
+    if (rc != MHX_OK) return rc;
     const FnDesc& f = e->P.fn[fn];
-    if (f.lik == MHX_LIK_EXPR)
-      return fail(MHX_EUNSUPPORTED, "mhx_get_normal_equations with MHX_LIK_EXPR: an expression likelihood's "
-                                    "`error` need not be a sigma to weigh a residual by");
     if (!dst[STEPS].p) return fail(MHX_EINVAL, "steps is NULL");
     const int d = e->P.d;
     // (checked before a group's calls move to their engines' chains: all of the caller's steps)
@@ -3038,7 +3016,6 @@ struct NormEqCall {
       if (!(hs[k] >= 0.0) || !std::isfinite(hs[k]))
         return fail(MHX_EINVAL, "step %lld is negative or not finite", (long long)k);
     m = f.n;
-    if (m < 1) return fail(MHX_EINVAL, "function %d has no data points", fn);
     // the columns: the distinct places of theta the function reads, ascending
     bool reads[MHX_MAX_PARAMS + 1] = {};
     for (int j = 0; j < f.n_idx; ++j) reads[f.idx[j]] = true;
@@ -3084,7 +3061,6 @@ struct NormEqCall {
   int launch(mhx_engine* e, const Portion& pn) const {
     Carver c;
     const NormEqPieces s = carve(e, c, pn.n, pn.m);
-    const FnDesc& f = e->P.fn[fn];
     const Dataset& D = e->data[fn];
     NormEqArgs A{};
     A.c0 = pn.i0, A.n = pn.n;
@@ -3096,25 +3072,11 @@ struct NormEqCall {
     for (int a = 0; a < p; ++a) A.col[a] = col[a];
     A.theta = dst[THETA].p ? stage_at<double>(e, s.theta) : nullptr;
     A.steps = stage_at<double>(e, per_chain ? s.chain_steps : s.steps);
-    A.x0 = f.x + pn.m0;
-    A.x1 = f.n_xcols > 1 ? f.c + pn.m0 : nullptr;
-    if (D.planes) {  // row c of the planes is the engine's chain c
-      A.y = D.pd.y + pn.m0, A.y_pitch = D.pd.pitch;
-      switch (D.pd.w_kind) {
-        case kPlaneWShared: A.w = f.w + pn.m0, A.w_pitch = 0, A.w_step = 1; break;
-        case kPlaneWScalar: A.w = D.pd.w, A.w_pitch = 1, A.w_step = 0; break;
-        default: A.w = D.pd.w + pn.m0, A.w_pitch = D.pd.pitch, A.w_step = 1; break;
-      }
-    } else {
-      A.y = f.y + pn.m0, A.y_pitch = 0;
-      A.w = f.w + pn.m0, A.w_pitch = 0, A.w_step = 1;
-    }
+    A.data = data_view(e->P.fn[fn], D.planes ? &D.pd : nullptr, pn.m0);
     A.g = dst[G].p ? stage_at<double>(e, s.g) : nullptr;
     A.part = stage_at<double>(e, s.part);
     A.status = stage_at<int32_t>(e, s.status);
-    // (A.sub, the points of a sub-step, is the launcher's: it depends on the kernel's family)
-    HIP_TRY(e->spec == SPEC_USER ? rtc_launch_normeq(*e->user_prog, e->stream, e->dP.p, e->S, A)
-                                 : launch_normeq(e->spec, e->stream, e->dP.p, e->S, A));
+    HIP_TRY(launch_model(e, A));  // (A.sub, A.lanes are the launcher's: they depend on the kernel's family)
     if (pn.m0 + pn.m >= m)
       HIP_TRY(launch_normeq_totals(e->stream, A, e->P.d, stage_at<double>(e, s.jtj), stage_at<double>(e, s.jtr),
                                    stage_at<double>(e, s.chi2)));
@@ -3124,17 +3086,10 @@ struct NormEqCall {
   int collect(mhx_engine* e, const Portion& pn) const {
     Carver c;
     const NormEqPieces s = carve(e, c, pn.n, pn.m);
-    if (dst[G].p)  // rows (chain, place) of pn.m points each, m apart at the caller's
-      HIP_TRY(hipMemcpy2D(static_cast<double*>(dst[G].at(pn.i0)) + pn.m0, (size_t)m * sizeof(double),
-                          e->stage.p + s.g, (size_t)pn.m * sizeof(double), (size_t)pn.m * sizeof(double),
-                          (size_t)pn.n * (size_t)e->P.d, hipMemcpyDeviceToHost));
-    if (pn.m0 + pn.m < m) return MHX_OK;  // (the totals come with the last chunk of points)
-    const size_t off[4] = {s.jtj, s.jtr, s.chi2, s.status};
-    for (int k = 0; k < 4; ++k) {
-      const int rc = copy_back(dst[k], pn.i0, pn.n, e->stage.p + off[k]);
-      if (rc != MHX_OK) return rc;
-    }
-    return MHX_OK;
+    // (g: rows (chain, place) of pn.m points each, m apart at the caller's)
+    const int rc = copy_back_points(dst[G], pn, m, sizeof(double), (size_t)e->P.d, e->stage.p + s.g);
+    if (rc != MHX_OK || pn.m0 + pn.m < m) return rc;  // (the totals come with the last chunk of points)
+    return copy_back_each(e, dst, pn, {s.jtj, s.jtr, s.chi2, s.status});
   }
 };
 
@@ -3151,7 +3106,7 @@ int mhx_get_normal_equations(mhx_engine* e, int fn, const double* theta, const d
 // a block is the same points whatever the portions), then every candidate's total and the chain's
 // `keep` best (k_cand_totals).  An item is a chain; its pieces are the m_cand scores and the
 // m_cand x nb_pitch block sums, nb_pitch the blocks of all selected functions.  The data are read
-// where the engine holds them, as ResidCall reads them.
+// where the engine holds them, through a DataView.
 struct CandCall {
   int fn = 0, per_chain = 0, keep = 0;
   int64_t m_cand = 0, nb_pitch = 0;
@@ -3175,15 +3130,11 @@ struct CandCall {
     if (keep < 1 || keep > MHX_CAND_KEEP_MAX)
       return fail(MHX_EINVAL, "keep must be in [1,%d]", MHX_CAND_KEEP_MAX);
     if (!e->chains_ready) return fail(MHX_ESTATE, "mhx_init_chains has not been called");
-    int rc = use_device(e);
-    if (rc != MHX_OK || (rc = finalize_problem(e)) != MHX_OK) return rc;
     if (fn < -1 || fn >= e->P.K) return fail(MHX_EINVAL, "function %d out of range (-1: all)", fn);
     nb_pitch = 0;
     for (int k = first_fn(); k < end_fn(e); ++k) {
-      if (e->P.fn[k].lik == MHX_LIK_EXPR)
-        return fail(MHX_EUNSUPPORTED, "mhx_get_candidate_scores with MHX_LIK_EXPR (function %d): an expression "
-                                      "likelihood's `error` need not be a sigma to divide a residual by", k);
-      if (e->P.fn[k].n < 1) return fail(MHX_EINVAL, "function %d has no data points", k);
+      const int rc = fn_check(e, k, "mhx_get_candidate_scores");
+      if (rc != MHX_OK) return rc;
       nb_pitch += resid_blocks(e->P.fn[k].n);
     }
     const int d = e->P.d;
@@ -3223,22 +3174,9 @@ struct CandCall {
       A.m_cand = m_cand, A.cand_pitch = per_chain ? m_cand : 0;
       A.blk0 = blk0, A.nb_pitch = nb_pitch, A.m = f.n;
       A.cand = stage_at<double>(e, s.cand);
-      A.x0 = f.x;
-      A.x1 = f.n_xcols > 1 ? f.c : nullptr;
-      if (D.planes) {  // row c of the planes is the engine's chain c
-        A.y = D.pd.y, A.y_pitch = D.pd.pitch;
-        switch (D.pd.w_kind) {
-          case kPlaneWShared: A.w = f.w, A.w_pitch = 0, A.w_step = 1; break;
-          case kPlaneWScalar: A.w = D.pd.w, A.w_pitch = 1, A.w_step = 0; break;
-          default: A.w = D.pd.w, A.w_pitch = D.pd.pitch, A.w_step = 1; break;
-        }
-      } else {
-        A.y = f.y, A.y_pitch = 0;
-        A.w = f.w, A.w_pitch = 0, A.w_step = 1;
-      }
+      A.data = data_view(f, D.planes ? &D.pd : nullptr, 0);  // (all of the function's points: no chunks)
       A.part = stage_at<double>(e, s.part);
-      HIP_TRY(e->spec == SPEC_USER ? rtc_launch_cand(*e->user_prog, e->stream, e->dP.p, A)
-                                   : launch_cand(e->spec, e->stream, e->dP.p, A));
+      HIP_TRY(launch_model(e, A));
       blk0 += A.n_blocks;
     }
     HIP_TRY(launch_cand_totals(e->stream, e->dP.p, fn, p.n, m_cand, nb_pitch, keep, stage_at<double>(e, s.part),
@@ -3250,12 +3188,7 @@ struct CandCall {
   int collect(mhx_engine* e, const Portion& p) const {
     Carver c;
     const CandPieces s = carve(e, c, p.n, p.m);
-    const size_t off[4] = {s.score, s.best_index, s.best_score, s.n_bad};
-    for (int k = 0; k < 4; ++k) {
-      const int rc = copy_back(dst[k], p.i0, p.n, e->stage.p + off[k]);
-      if (rc != MHX_OK) return rc;
-    }
-    return MHX_OK;
+    return copy_back_each(e, dst, p, {s.score, s.best_index, s.best_score, s.n_bad});
   }
 };
 
@@ -3288,8 +3221,7 @@ struct FitPctCall {
   }
   int check(mhx_engine* e) {
     int rc = window_check(e, take);
-    if (rc != MHX_OK || (rc = use_device(e)) != MHX_OK || (rc = finalize_problem(e)) != MHX_OK) return rc;
-    if (fn < 0 || fn >= e->P.K) return fail(MHX_EINVAL, "function %d out of range", fn);
+    if (rc != MHX_OK || (rc = fn_check(e, fn)) != MHX_OK) return rc;
     if (n_cols != FitCall::fn_cols(e, fn))
       return fail(MHX_EINVAL, "function %d reads %d column(s) of x, n_cols is %d", fn, FitCall::fn_cols(e, fn),
                   n_cols);
@@ -3345,8 +3277,7 @@ struct FitPctCall {
     A.mean = stage_at<double>(e, s.mean);
     A.stddev = stage_at<double>(e, s.stddev);
     A.status = stage_at<int32_t>(e, s.status);
-    HIP_TRY(e->spec == SPEC_USER ? rtc_launch_fitpct(*e->user_prog, e->stream, e->dP.p, e->S, A)
-                                 : launch_fitpct_values(e->spec, e->stream, e->dP.p, e->S, A));
+    HIP_TRY(launch_model(e, A));
     // (no percentile asked for: the selection only completes n_used and the status - no column is laid down)
     const bool lds = pc.n > 0 && !e->knobs.fitpct_no_lds && fitpct_cols(take) > 0;
     HIP_TRY(launch_fitpct_select(e->stream, e->S, p.i0, p.n, take, p.m, A.vs_step, A.vs_point, pc, lds,
@@ -3359,18 +3290,12 @@ struct FitPctCall {
     Carver c;
     const FitPctPieces s = carve(e, c, p.n, p.m);
     const size_t dv[3] = {s.pct, s.mean, s.stddev};
-    for (int k = 0; k < 3; ++k) {
-      const size_t rows = (size_t)p.n * (k == PCT ? (size_t)pc.n : 1);  // (pct: a row per chain and percentile)
-      if (dst[k].p && rows > 0)
-        HIP_TRY(hipMemcpy2D(static_cast<double*>(dst[k].at(p.i0)) + p.m0, (size_t)m * sizeof(double),
-                            stage_at<double>(e, dv[k]), (size_t)p.m * sizeof(double),
-                            (size_t)p.m * sizeof(double), rows, hipMemcpyDeviceToHost));
+    for (int k = 0; k < 3; ++k) {  // (pct: a row per chain and percentile)
+      const int rc = copy_back_points(dst[k], p, m, sizeof(double), k == PCT ? (size_t)pc.n : 1, e->stage.p + dv[k]);
+      if (rc != MHX_OK) return rc;
     }
     if (p.m0 + p.m < m) return MHX_OK;  // (the status gathers over the chunks of points)
-    int rc = copy_back(dst[N_USED], p.i0, p.n, stage_at<int32_t>(e, s.n_used));
-    if (rc != MHX_OK || (rc = copy_back(dst[STATUS], p.i0, p.n, stage_at<int32_t>(e, s.status))) != MHX_OK)
-      return rc;
-    return MHX_OK;
+    return copy_back_each(e, dst + N_USED, p, {s.n_used, s.status});
   }
 };
 

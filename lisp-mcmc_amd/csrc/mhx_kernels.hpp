@@ -4268,8 +4268,8 @@ __device__ __forceinline__ void k_resid_body(const ProblemDesc* __restrict__ Pp,
   const int d = Pp->d;
   const int lik = __builtin_amdgcn_readfirstlane(f.lik);
   const int64_t row = A.c0 + i;
-  const double* yr = A.y + row * A.y_pitch;
-  const double* wr = A.w + row * A.w_pitch;
+  const double* yr = A.data.y + row * A.data.y_pitch;
+  const double* wr = A.data.w + row * A.data.w_pitch;
   constexpr int kN = kResidPts;  // the neighbour's slot
   double x0[kResidPts + 1], x1[kResidPts + 1], ys[kResidPts + 1], wi[kResidPts + 1];
   // the point before the block's first: index -1 of a later launch is the launch before's last
@@ -4279,10 +4279,10 @@ __device__ __forceinline__ void k_resid_body(const ProblemDesc* __restrict__ Pp,
   for (int j = 0; j <= kResidPts; ++j) {
     const int64_t p = p0 + (int64_t)j * kWave;
     const int64_t q = j == kN ? qn : (p < A.m ? p : A.m - 1);  // (beyond m: the last point once more)
-    x0[j] = A.x0[q];
-    x1[j] = A.x1 ? A.x1[q] : 0.0;
+    x0[j] = A.data.x0[q];
+    x1[j] = A.data.x1 ? A.data.x1[q] : 0.0;
     ys[j] = yr[q];
-    wi[j] = wr[q * A.w_step];
+    wi[j] = wr[q * A.data.w_step];
   }
   const double* src = A.theta ? A.theta + i * d : S.best_theta + row * d;
   double* th = lds.th[w];
@@ -4439,8 +4439,8 @@ __device__ __forceinline__ void k_normeq_body(const ProblemDesc* __restrict__ Pp
   const int lik = __builtin_amdgcn_readfirstlane(f.lik);
   const int p = A.p, pitch = A.pitch, sub = A.sub, lanes = A.lanes;
   const int64_t row = A.c0 + i;
-  const double* yr = A.y + row * A.y_pitch;
-  const double* wr = A.w + row * A.w_pitch;
+  const double* yr = A.data.y + row * A.data.y_pitch;
+  const double* wr = A.data.w + row * A.data.w_pitch;
   const double* hs = A.steps + i * A.steps_pitch;
   double* tile = reinterpret_cast<double*>(mhx_lds_raw + sizeof(FitLds)) + (size_t)w * sub * pitch;
   const double* src = A.theta ? A.theta + i * d : S.best_theta + row * d;
@@ -4477,10 +4477,10 @@ __device__ __forceinline__ void k_normeq_body(const ProblemDesc* __restrict__ Pp
       const int r = j * lanes + l;  // the point's row of the tile
       in[j] = l < lanes && r < cnt;
       pt[j] = in[j] ? s0 + r : b1 - 1;  // (beyond the sub-step: the block's last point, never stored)
-      x0[j] = A.x0[pt[j]];
-      x1[j] = A.x1 ? A.x1[pt[j]] : 0.0;
+      x0[j] = A.data.x0[pt[j]];
+      x1[j] = A.data.x1 ? A.data.x1[pt[j]] : 0.0;
       ys[j] = yr[pt[j]];
-      wi[j] = wr[pt[j] * A.w_step];
+      wi[j] = wr[pt[j] * A.data.w_step];
       mine[j] = tile + (in[j] ? r : 0) * pitch;
       vp[j] = 0.0, rt[j] = 1.0;
     }
@@ -4632,17 +4632,17 @@ __device__ __forceinline__ void k_cand_body(const ProblemDesc* __restrict__ Pp, 
   const int d = Pp->d;
   const int lik = __builtin_amdgcn_readfirstlane(f.lik);
   const int64_t row = A.c0 + i;
-  const double* yr = A.y + row * A.y_pitch;
-  const double* wr = A.w + row * A.w_pitch;
+  const double* yr = A.data.y + row * A.data.y_pitch;
+  const double* wr = A.data.w + row * A.data.w_pitch;
   double x0[kResidPts], x1[kResidPts], ys[kResidPts], wi[kResidPts];
 #pragma unroll
   for (int j = 0; j < kResidPts; ++j) {
     const int64_t p = p0 + (int64_t)j * kWave;
     const int64_t q = p < A.m ? p : A.m - 1;  // (beyond m: the last point once more)
-    x0[j] = A.x0[q];
-    x1[j] = A.x1 ? A.x1[q] : 0.0;
+    x0[j] = A.data.x0[q];
+    x1[j] = A.data.x1 ? A.data.x1[q] : 0.0;
     ys[j] = yr[q];
-    wi[j] = wr[q * A.w_step];
+    wi[j] = wr[q * A.data.w_step];
   }
   const double* cd = A.cand + i * A.cand_pitch * d;
   double* out = A.part + i * A.m_cand * A.nb_pitch + A.blk0 + blk;

@@ -161,30 +161,77 @@ hipError_t launch_l_matrices(hipStream_t st, const ChainState& S, int64_t c0, in
 hipError_t launch_window_best(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
                               double* prob, double* theta);
 
+// ---- The model read-outs: the kernels that evaluate a model for a batched read-out
+// (mhx_kernels.hpp).  Each is compiled ahead of time as KERNEL<Spec> for every spec - in the
+// primary family only, whichever family steps the problem: a wave is an item and a block of
+// points in either - and at run time as the twin mhx_user_ID over the same KERNEL_body.  A wave is
+// a unit of work, a workgroup is the family's, and no kernel may have static LDS (the device math
+// reads its tables at absolute LDS addresses).  What differs from kernel to kernel is stated here,
+// once, and everything that configures, generates, looks up or launches them goes by this list:
+//   ID       names the twin, and MR_ID is its handle's place in UserProgram::f_model
+//   ARGS     the argument struct (mhx_types.hpp); launch_model(.., A) finds the kernel by its type
+//   KERNEL   the kernel template; KERNEL(P, A), or KERNEL(P, S, A) where STATE says it takes ChainState
+//   WAVES    the waves a launch needs, of its arguments A (<= 0: nothing to launch)
+//   LDS      its dynamic LDS, of the waves per workgroup wpg and A
+//   MAX_LDS  what hipFuncAttributeMaxDynamicSharedMemorySize must be raised to (0: the 64 KiB a
+//            kernel has unasked are enough)
+//   FIX_UP   what the launcher completes in its copy of A, because it depends on wpg
+#define MHX_MODEL_READOUTS(X)                                                                                  \
+  /* ID      ARGS        KERNEL           STATE  WAVES                             LDS  MAX_LDS  FIX_UP */     \
+  X(fit,    FitArgs,    k_fit,           false, A.m <= 0 ? 0 : A.n * A.n_chunks, fit_lds_bytes(wpg), 0, (void)0)    \
+  X(waic,   WaicArgs,   k_waic,          true,  A.m <= 0 ? 0 : A.n * A.n_blocks, fit_lds_bytes(wpg), 0, (void)0)    \
+  X(resid,  ResidArgs,  k_resid,         true,  A.m <= 0 ? 0 : A.n * A.n_blocks, fit_lds_bytes(wpg), 0, (void)0)    \
+  /* (the tile of the widest function takes the LDS past 64 KiB; sub, lanes: normeq_sub says why) */          \
+  X(normeq, NormEqArgs, k_normeq,        true,  A.m <= 0 ? 0 : A.n * A.n_blocks, normeq_lds_bytes(wpg, A.p),        \
+    kNormEqLdsBudget, (A.lanes = normeq_lanes(wpg, A.p), A.sub = normeq_sub(wpg, A.p)))                        \
+  X(cand,   CandArgs,   k_cand,          false, A.m <= 0 || A.m_cand <= 0 ? 0 : A.n * A.n_blocks,              \
+    fit_lds_bytes(wpg), 0, (void)0)                                                                            \
+  X(fitpct, FitPctArgs, k_fitpct_values, true,  A.m <= 0 ? 0 : A.n * A.n_blocks, fit_lds_bytes(wpg), 0, (void)0)
+
+enum ModelReadoutId {
+#define MHX_X(ID, ...) MR_##ID,
+  MHX_MODEL_READOUTS(MHX_X)
+#undef MHX_X
+  MR__COUNT
+};
+// the list's line of an argument type, for the templated launch paths
+template <class Args>
+struct ModelReadout;
+#define MHX_X(ID, ARGS, KERNEL, STATE, WAVES, LDS, MAX_LDS, FIX_UP)                   \
+  template <>                                                                         \
+  struct ModelReadout<ARGS> {                                                         \
+    static constexpr int kId = MR_##ID;                                               \
+    static constexpr bool kState = STATE;                                             \
+    static constexpr unsigned kMaxLds = MAX_LDS;                                      \
+    static int64_t waves(const ARGS& A) { return WAVES; }                             \
+    static unsigned lds(int wpg, const ARGS& A) { return (void)A, LDS; }              \
+    static void fix_up(int wpg, ARGS& A) { (void)wpg, (void)A, FIX_UP; }              \
+  };
+MHX_MODEL_READOUTS(MHX_X)
+#undef MHX_X
+// The ahead-of-time kernel of A's type for `spec` (S: what a kernel without ChainState leaves
+// unread); run-time compiled problems go through rtc_launch_model (mhx_rtc.hpp).
+hipError_t model_readouts_configure();
+template <class Args>
+hipError_t launch_model(int spec, hipStream_t st, const ProblemDesc* P, const ChainState& S, const Args& A);
+
 // mhx_eval_function / mhx_get_fit_bands: the steps every chain's band envelopes (sel [n][take]
 // ring slots, n_sel [n]), and the model values / envelopes themselves (FitArgs, mhx_types.hpp)
-// for the ahead-of-time specs; run-time compiled problems go through rtc_launch_fit.
+// through launch_model.
 inline int fit_chunks(int64_t m) { return (int)((m + kWave * kFitPts - 1) / (kWave * kFitPts)); }
-hipError_t fit_configure();
 hipError_t launch_band_select(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
                               int32_t* sel, int32_t* n_sel);
-hipError_t launch_fit(int spec, hipStream_t st, const ProblemDesc* P, const FitArgs& A);
 
 // mhx_get_waic: the pointwise accumulation and the blocks' partial sums (WaicArgs, mhx_types.hpp)
-// for the ahead-of-time specs - run-time compiled problems go through rtc_launch_waic - and the
-// totals of n chains from the partials of all nb_total blocks.
+// through launch_model, and the totals of n chains from the partials of all nb_total blocks.
 inline int64_t waic_blocks(int64_t m) { return (m + MHX_WAIC_BLOCK - 1) / MHX_WAIC_BLOCK; }
-hipError_t waic_configure();
-hipError_t launch_waic(int spec, hipStream_t st, const ProblemDesc* P, const ChainState& S,
-                       const WaicArgs& A);
 hipError_t launch_waic_totals(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
                               int64_t nb_total, const double* part_lppd, const double* part_p,
                               const int32_t* part_high, double* elpd, double* lppd, double* p_waic,
                               int32_t* n_high, int32_t* n_used, int32_t* status);
 
-// mhx_get_fit_percentiles: the values and moments (FitPctArgs, mhx_types.hpp) for the
-// ahead-of-time specs - run-time compiled problems go through rtc_launch_fitpct - and the
-// model-free selection over the staged values.  fitpct_cols: the neighbouring points one
+// mhx_get_fit_percentiles: the values and moments (FitPctArgs, mhx_types.hpp) through launch_model,
+// and the model-free selection over the staged values.  fitpct_cols: the neighbouring points one
 // selection workgroup takes - the most of 8, 4, 2, 1 whose key columns fit kPctLdsBudget (two
 // workgroups a CU), 0 where not even one column does: the selection then reads the stage.
 // together: a column's percentiles share their passes (select_percentiles_together).
@@ -195,44 +242,31 @@ inline int fitpct_cols(int take) {
   return 0;
 }
 constexpr int kFitPctMemCols = 4;  // ... a workgroup's points on the memory path: one per wave
-hipError_t fitpct_configure();
-hipError_t launch_fitpct_values(int spec, hipStream_t st, const ProblemDesc* P, const ChainState& S,
-                                const FitPctArgs& A);
 hipError_t launch_fitpct_select(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
                                 int64_t m, int64_t vs_step, int64_t vs_point, const PctList& pc,
                                 bool use_lds, bool together, const double* vals, double* pct,
                                 int32_t* n_used, int32_t* status);
 
-// mhx_get_residuals: the residuals' block sums, counts and extremes (ResidArgs, mhx_types.hpp) for
-// the ahead-of-time specs - run-time compiled problems, every engine with a dataset per walker among
-// them, go through rtc_launch_resid - and the totals of n chains from the partials of all nb_total
-// blocks.
+// mhx_get_residuals: the residuals' block sums, counts and extremes (ResidArgs, mhx_types.hpp)
+// through launch_model - every engine with a dataset per walker is run-time compiled - and the
+// totals of n chains from the partials of all nb_total blocks.
 inline int64_t resid_blocks(int64_t m) { return (m + MHX_RESID_BLOCK - 1) / MHX_RESID_BLOCK; }
-hipError_t resid_configure();
-hipError_t launch_resid(int spec, hipStream_t st, const ProblemDesc* P, const ChainState& S,
-                        const ResidArgs& A);
 hipError_t launch_resid_totals(hipStream_t st, int64_t n, int64_t nb_total, const ResidArgs& A,
                                double* chi2, double* sum_z, double* dw, double* max_abs_z,
                                int64_t* max_index, int32_t* n_pos, int32_t* n_runs, int32_t* n_out);
 
 // mhx_get_normal_equations: the block sums of the products of the scaled Jacobian and the residual
-// (NormEqArgs, mhx_types.hpp) for the ahead-of-time specs - run-time compiled problems go through
-// rtc_launch_normeq - and the totals of A.n chains from the partials of all A.nb_total blocks,
-// scattered into jtj [n][d][d], jtr [n][d] (both zeroed by the caller) and chi2 [n].
+// (NormEqArgs, mhx_types.hpp) through launch_model, and the totals of A.n chains from the partials
+// of all A.nb_total blocks, scattered into jtj [n][d][d], jtr [n][d] (both zeroed by the caller) and
+// chi2 [n].
 inline int64_t normeq_blocks(int64_t m) { return (m + MHX_NORMEQ_BLOCK - 1) / MHX_NORMEQ_BLOCK; }
-hipError_t normeq_configure();
-hipError_t launch_normeq(int spec, hipStream_t st, const ProblemDesc* P, const ChainState& S,
-                         const NormEqArgs& A);
 hipError_t launch_normeq_totals(hipStream_t st, const NormEqArgs& A, int d, double* jtj, double* jtr,
                                 double* chi2);
 
 // mhx_get_candidate_scores: the blocks' chi-square of every candidate of every chain for one
-// function (CandArgs, mhx_types.hpp) for the ahead-of-time specs - run-time compiled problems go
-// through rtc_launch_cand - and, once all selected functions (fn, or all of them at -1) have written
-// their blocks, the scores [n][m_cand], the `keep` best of each chain and its count of candidates
-// that are not finite.
-hipError_t cand_configure();
-hipError_t launch_cand(int spec, hipStream_t st, const ProblemDesc* P, const CandArgs& A);
+// function (CandArgs, mhx_types.hpp) through launch_model and, once all selected functions (fn, or
+// all of them at -1) have written their blocks, the scores [n][m_cand], the `keep` best of each
+// chain and its count of candidates that are not finite.
 hipError_t launch_cand_totals(hipStream_t st, const ProblemDesc* P, int fn, int64_t n, int64_t m_cand,
                               int64_t nb_pitch, int keep, const double* part, double* score,
                               int32_t* best_index, double* best_score, int32_t* n_bad);

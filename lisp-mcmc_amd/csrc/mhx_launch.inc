@@ -276,6 +276,9 @@ hipError_t summary_configure() {
   if (e == hipSuccess)
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ensemble_digits),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPctLdsBudget);
+  if (e == hipSuccess)
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fitpct_select),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPctLdsBudget);
   return e;
 }
 hipError_t launch_percentiles(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
@@ -381,51 +384,67 @@ hipError_t launch_window_best(hipStream_t st, const ChainState& S, int64_t c0, i
   return hipGetLastError();
 }
 
-// mhx_eval_function / mhx_get_fit_bands (k_band_select, k_fit): compiled in this family only,
-// whichever family steps the problem - a wave is an item and a chunk of x in either
-hipError_t fit_configure() {
+// ---- the model read-outs (MHX_MODEL_READOUTS, mhx_launch.hpp): one configure and one launcher
+template <class Spec, class Args>
+struct ModelKernel;
+#define MHX_X(ID, ARGS, KERNEL, ...)                    \
+  template <class Spec>                                 \
+  struct ModelKernel<Spec, ARGS> {                      \
+    static constexpr auto* fn = &KERNEL<Spec>;          \
+  };
+MHX_MODEL_READOUTS(MHX_X)
+#undef MHX_X
+template <class Spec, class Args>
+static hipError_t configure_model() {
+  constexpr auto* fn = ModelKernel<Spec, Args>::fn;
+  hipError_t e = no_static_lds(fn);
+  if (e == hipSuccess && ModelReadout<Args>::kMaxLds != 0)
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)ModelReadout<Args>::kMaxLds);
+  return e;
+}
+hipError_t model_readouts_configure() {
   hipError_t e = hipSuccess;
   for (int s = 0; s < SPEC__COUNT; ++s)
     for_spec(s, [&](auto sp) {
       using SpecT = decltype(sp);
-      if (e == hipSuccess) e = no_static_lds(&k_fit<SpecT>);
+#define MHX_X(ID, ARGS, ...) \
+  if (e == hipSuccess) e = configure_model<SpecT, ARGS>();
+      MHX_MODEL_READOUTS(MHX_X)
+#undef MHX_X
     });
   return e;
 }
+template <class Args>
+hipError_t launch_model(int spec, hipStream_t st, const ProblemDesc* P, const ChainState& S, const Args& A) {
+  using R = ModelReadout<Args>;
+  const int64_t waves = R::waves(A);
+  if (waves <= 0) return hipSuccess;
+  Args a = A;
+  R::fix_up(kWavesPerGroup, a);
+  for_spec(spec, [&](auto sp) {
+    constexpr auto* fn = ModelKernel<decltype(sp), Args>::fn;
+    if constexpr (R::kState)
+      fn<<<grid_for(waves), dim3(kThreads), R::lds(kWavesPerGroup, a), st>>>(P, S, a);
+    else
+      fn<<<grid_for(waves), dim3(kThreads), R::lds(kWavesPerGroup, a), st>>>(P, a);
+  });
+  return hipGetLastError();
+}
+#define MHX_X(ID, ARGS, ...) \
+  template hipError_t launch_model<ARGS>(int, hipStream_t, const ProblemDesc*, const ChainState&, const ARGS&);
+MHX_MODEL_READOUTS(MHX_X)
+#undef MHX_X
+
+// mhx_eval_function / mhx_get_fit_bands: the steps every chain's band envelopes (k_band_select)
 hipError_t launch_band_select(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
                               int32_t* sel, int32_t* n_sel) {
   if (n <= 0) return hipSuccess;
   k_band_select<<<grid_for(n), dim3(kThreads), 0, st>>>(S, c0, n, take, sel, n_sel);
   return hipGetLastError();
 }
-hipError_t launch_fit(int spec, hipStream_t st, const ProblemDesc* P, const FitArgs& A) {
-  if (A.n <= 0 || A.m <= 0) return hipSuccess;
-  for_spec(spec, [&](auto sp) {
-    using SpecT = decltype(sp);
-    k_fit<SpecT><<<grid_for(A.n * A.n_chunks), dim3(kThreads), fit_lds_bytes(kWavesPerGroup), st>>>(P, A);
-  });
-  return hipGetLastError();
-}
 
-// mhx_get_waic (k_waic, k_waic_totals): as k_fit, compiled in this family only
-hipError_t waic_configure() {
-  hipError_t e = hipSuccess;
-  for (int s = 0; s < SPEC__COUNT; ++s)
-    for_spec(s, [&](auto sp) {
-      using SpecT = decltype(sp);
-      if (e == hipSuccess) e = no_static_lds(&k_waic<SpecT>);
-    });
-  return e;
-}
-hipError_t launch_waic(int spec, hipStream_t st, const ProblemDesc* P, const ChainState& S,
-                       const WaicArgs& A) {
-  if (A.n <= 0 || A.m <= 0) return hipSuccess;
-  for_spec(spec, [&](auto sp) {
-    using SpecT = decltype(sp);
-    k_waic<SpecT><<<grid_for(A.n * A.n_blocks), dim3(kThreads), fit_lds_bytes(kWavesPerGroup), st>>>(P, S, A);
-  });
-  return hipGetLastError();
-}
+// mhx_get_waic: the totals (k_waic_totals)
 hipError_t launch_waic_totals(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
                               int64_t nb_total, const double* part_lppd, const double* part_p,
                               const int32_t* part_high, double* elpd, double* lppd, double* p_waic,
@@ -436,25 +455,7 @@ hipError_t launch_waic_totals(hipStream_t st, const ChainState& S, int64_t c0, i
   return hipGetLastError();
 }
 
-// mhx_get_residuals (k_resid, k_resid_totals): as k_waic, compiled in this family only
-hipError_t resid_configure() {
-  hipError_t e = hipSuccess;
-  for (int s = 0; s < SPEC__COUNT; ++s)
-    for_spec(s, [&](auto sp) {
-      using SpecT = decltype(sp);
-      if (e == hipSuccess) e = no_static_lds(&k_resid<SpecT>);
-    });
-  return e;
-}
-hipError_t launch_resid(int spec, hipStream_t st, const ProblemDesc* P, const ChainState& S,
-                        const ResidArgs& A) {
-  if (A.n <= 0 || A.m <= 0) return hipSuccess;
-  for_spec(spec, [&](auto sp) {
-    using SpecT = decltype(sp);
-    k_resid<SpecT><<<grid_for(A.n * A.n_blocks), dim3(kThreads), fit_lds_bytes(kWavesPerGroup), st>>>(P, S, A);
-  });
-  return hipGetLastError();
-}
+// mhx_get_residuals: the totals (k_resid_totals)
 hipError_t launch_resid_totals(hipStream_t st, int64_t n, int64_t nb_total, const ResidArgs& A,
                                double* chi2, double* sum_z, double* dw, double* max_abs_z,
                                int64_t* max_index, int32_t* n_pos, int32_t* n_runs, int32_t* n_out) {
@@ -465,31 +466,7 @@ hipError_t launch_resid_totals(hipStream_t st, int64_t n, int64_t nb_total, cons
   return hipGetLastError();
 }
 
-// mhx_get_normal_equations (k_normeq, k_normeq_totals): as k_waic, compiled in this family only.  The
-// tile of the widest function takes the dynamic LDS past the 64 KiB a kernel has unasked.
-hipError_t normeq_configure() {
-  hipError_t e = hipSuccess;
-  for (int s = 0; s < SPEC__COUNT; ++s)
-    for_spec(s, [&](auto sp) {
-      using SpecT = decltype(sp);
-      if (e == hipSuccess) e = no_static_lds(&k_normeq<SpecT>);
-      if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_normeq<SpecT>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kNormEqLdsBudget);
-    });
-  return e;
-}
-hipError_t launch_normeq(int spec, hipStream_t st, const ProblemDesc* P, const ChainState& S,
-                         const NormEqArgs& A) {
-  if (A.n <= 0 || A.m <= 0) return hipSuccess;
-  for_spec(spec, [&](auto sp) {
-    using SpecT = decltype(sp);
-    NormEqArgs a = A;
-    a.lanes = normeq_lanes(kWavesPerGroup, A.p), a.sub = normeq_sub(kWavesPerGroup, A.p);
-    k_normeq<SpecT><<<grid_for(A.n * A.n_blocks), dim3(kThreads), normeq_lds_bytes(kWavesPerGroup, A.p), st>>>(P, S, a);
-  });
-  return hipGetLastError();
-}
+// mhx_get_normal_equations: the totals (k_normeq_totals)
 hipError_t launch_normeq_totals(hipStream_t st, const NormEqArgs& A, int d, double* jtj, double* jtr,
                                 double* chi2) {
   if (A.n <= 0) return hipSuccess;
@@ -499,24 +476,7 @@ hipError_t launch_normeq_totals(hipStream_t st, const NormEqArgs& A, int d, doub
   return hipGetLastError();
 }
 
-// mhx_get_candidate_scores (k_cand, k_cand_totals): as k_waic, compiled in this family only
-hipError_t cand_configure() {
-  hipError_t e = hipSuccess;
-  for (int s = 0; s < SPEC__COUNT; ++s)
-    for_spec(s, [&](auto sp) {
-      using SpecT = decltype(sp);
-      if (e == hipSuccess) e = no_static_lds(&k_cand<SpecT>);
-    });
-  return e;
-}
-hipError_t launch_cand(int spec, hipStream_t st, const ProblemDesc* P, const CandArgs& A) {
-  if (A.n <= 0 || A.m <= 0 || A.m_cand <= 0) return hipSuccess;
-  for_spec(spec, [&](auto sp) {
-    using SpecT = decltype(sp);
-    k_cand<SpecT><<<grid_for(A.n * A.n_blocks), dim3(kThreads), fit_lds_bytes(kWavesPerGroup), st>>>(P, A);
-  });
-  return hipGetLastError();
-}
+// mhx_get_candidate_scores: the totals and the ranking (k_cand_totals)
 hipError_t launch_cand_totals(hipStream_t st, const ProblemDesc* P, int fn, int64_t n, int64_t m_cand,
                               int64_t nb_pitch, int keep, const double* part, double* score,
                               int32_t* best_index, double* best_score, int32_t* n_bad) {
@@ -526,26 +486,7 @@ hipError_t launch_cand_totals(hipStream_t st, const ProblemDesc* P, int fn, int6
   return hipGetLastError();
 }
 
-// mhx_get_fit_percentiles (k_fitpct_values, k_fitpct_select): as k_waic, compiled in this family only
-hipError_t fitpct_configure() {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fitpct_select),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPctLdsBudget);
-  for (int s = 0; s < SPEC__COUNT; ++s)
-    for_spec(s, [&](auto sp) {
-      using SpecT = decltype(sp);
-      if (e == hipSuccess) e = no_static_lds(&k_fitpct_values<SpecT>);
-    });
-  return e;
-}
-hipError_t launch_fitpct_values(int spec, hipStream_t st, const ProblemDesc* P, const ChainState& S,
-                                const FitPctArgs& A) {
-  if (A.n <= 0 || A.m <= 0) return hipSuccess;
-  for_spec(spec, [&](auto sp) {
-    using SpecT = decltype(sp);
-    k_fitpct_values<SpecT><<<grid_for(A.n * A.n_blocks), dim3(kThreads), fit_lds_bytes(kWavesPerGroup), st>>>(P, S, A);
-  });
-  return hipGetLastError();
-}
+// mhx_get_fit_percentiles: the model-free selection (k_fitpct_select)
 hipError_t launch_fitpct_select(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
                                 int64_t m, int64_t vs_step, int64_t vs_point, const PctList& pc,
                                 bool use_lds, bool together, const double* vals, double* pct,

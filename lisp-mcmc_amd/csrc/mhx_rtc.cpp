@@ -335,26 +335,15 @@ static std::string generate(const std::vector<UserExpr>& models,
        "using namespace mhx;\n"
        "extern \"C\" __global__ __launch_bounds__(MHX_USER_THREADS) void mhx_user_logpost(\n"
        "    const ProblemDesc* P, const double* theta, int64_t n, double* out, double* parts) {\n"
-       "  k_logpost_body<UserSpec>(P, theta, n, out, parts);\n}\n"
-       "extern \"C\" __global__ __launch_bounds__(MHX_USER_THREADS) void mhx_user_fit(\n"
-       "    const ProblemDesc* P, FitArgs A) {\n"
-       "  k_fit_body<UserSpec>(P, A);\n}\n"
-       "extern \"C\" __global__ __launch_bounds__(MHX_USER_THREADS) void mhx_user_waic(\n"
-       "    const ProblemDesc* P, ChainState S, WaicArgs A) {\n"
-       "  k_waic_body<UserSpec>(P, S, A);\n}\n"
-       "extern \"C\" __global__ __launch_bounds__(MHX_USER_THREADS) void mhx_user_resid(\n"
-       "    const ProblemDesc* P, ChainState S, ResidArgs A) {\n"
-       "  k_resid_body<UserSpec>(P, S, A);\n}\n"
-       "extern \"C\" __global__ __launch_bounds__(MHX_USER_THREADS) void mhx_user_normeq(\n"
-       "    const ProblemDesc* P, ChainState S, NormEqArgs A) {\n"
-       "  k_normeq_body<UserSpec>(P, S, A);\n}\n"
-       "extern \"C\" __global__ __launch_bounds__(MHX_USER_THREADS) void mhx_user_cand(\n"
-       "    const ProblemDesc* P, CandArgs A) {\n"
-       "  k_cand_body<UserSpec>(P, A);\n}\n"
-       "extern \"C\" __global__ __launch_bounds__(MHX_USER_THREADS) void mhx_user_fitpct(\n"
-       "    const ProblemDesc* P, ChainState S, FitPctArgs A) {\n"
-       "  k_fitpct_values_body<UserSpec>(P, S, A);\n}\n"
-       "extern \"C\" __global__ __launch_bounds__(MHX_USER_THREADS) void mhx_user_init(const ProblemDesc* P,\n"
+       "  k_logpost_body<UserSpec>(P, theta, n, out, parts);\n}\n";
+  // the model read-outs' twins
+#define MHX_X(ID, ARGS, KERNEL, STATE, ...)                                                                \
+  s << "extern \"C\" __global__ __launch_bounds__(MHX_USER_THREADS) void mhx_user_" #ID "(\n"             \
+       "    const ProblemDesc* P, " << (STATE ? "ChainState S, " : "") << #ARGS " A) {\n"                  \
+       "  " #KERNEL "_body<UserSpec>(P, " << (STATE ? "S, " : "") << "A);\n}\n";
+  MHX_MODEL_READOUTS(MHX_X)
+#undef MHX_X
+  s << "extern \"C\" __global__ __launch_bounds__(MHX_USER_THREADS) void mhx_user_init(const ProblemDesc* P,\n"
        "                                                              ChainState S) {\n"
        "  k_init_body<UserSpec>(P, S);\n}\n"
        "extern \"C\" __global__ __launch_bounds__(MHX_USER_THREADS) void mhx_user_step(\n"
@@ -547,6 +536,17 @@ static int compile_module(const std::string& source, const std::vector<EmbeddedH
   return 0;
 }
 
+// (the device math reads its tables at absolute LDS addresses: no static LDS in these kernels)
+static int static_lds(hipFunction_t f) {
+  int v = 0;
+  return hipFuncGetAttribute(&v, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, f) == hipSuccess ? v : -1;
+}
+static int no_static_lds(hipFunction_t f, const char* name, std::string* err) {
+  if (static_lds(f) == 0) return 0;
+  *err = std::string("module function ") + name + " has static LDS";
+  return -1;
+}
+
 static int build_once(const std::vector<UserExpr>& models, const std::vector<UserExpr>& priors,
                       bool builtin_fallback, bool with_split, const Family& fam, int min_waves,
                       UserProgram* prog, std::string* err) {
@@ -589,55 +589,23 @@ static int build_once(const std::vector<UserExpr>& models, const std::vector<Use
       return -1;
     }
   }
-  // (the device math reads its tables at absolute LDS addresses: no static LDS in these kernels)
-  auto static_lds = [](hipFunction_t f) {
-    int v = 0;
-    return hipFuncGetAttribute(&v, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, f) == hipSuccess ? v : -1;
-  };
   for (auto& x : fs)
-    if (static_lds(*x.f) != 0) {
-      *err = std::string("module function ") + x.n + " has static LDS";
+    if (no_static_lds(*x.f, x.n, err) != 0) return -1;
+  static const struct { const char* n; unsigned max_lds; } twins[MR__COUNT] = {
+#define MHX_X(ID, ARGS, KERNEL, STATE, WAVES, LDS, MAX_LDS, ...) {"mhx_user_" #ID, MAX_LDS},
+      MHX_MODEL_READOUTS(MHX_X)
+#undef MHX_X
+  };
+  for (int k = 0; k < MR__COUNT; ++k) {
+    he = hipModuleGetFunction(&prog->f_model[k], prog->module, twins[k].n);
+    if (he == hipSuccess && twins[k].max_lds != 0)
+      he = hipFuncSetAttribute(reinterpret_cast<const void*>(prog->f_model[k]),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)twins[k].max_lds);
+    if (he != hipSuccess) {
+      *err = std::string("module function ") + twins[k].n + ": " + hipGetErrorString(he);
       return -1;
     }
-  he = hipModuleGetFunction(&prog->f_fit, prog->module, "mhx_user_fit");
-  if (he != hipSuccess || static_lds(prog->f_fit) != 0) {
-    *err = he != hipSuccess ? std::string("module function mhx_user_fit: ") + hipGetErrorString(he)
-                            : std::string("module function mhx_user_fit has static LDS");
-    return -1;
-  }
-  he = hipModuleGetFunction(&prog->f_waic, prog->module, "mhx_user_waic");
-  if (he != hipSuccess || static_lds(prog->f_waic) != 0) {
-    *err = he != hipSuccess ? std::string("module function mhx_user_waic: ") + hipGetErrorString(he)
-                            : std::string("module function mhx_user_waic has static LDS");
-    return -1;
-  }
-  he = hipModuleGetFunction(&prog->f_resid, prog->module, "mhx_user_resid");
-  if (he != hipSuccess || static_lds(prog->f_resid) != 0) {
-    *err = he != hipSuccess ? std::string("module function mhx_user_resid: ") + hipGetErrorString(he)
-                            : std::string("module function mhx_user_resid has static LDS");
-    return -1;
-  }
-  // (its tile can take the dynamic LDS past the 64 KiB a kernel has unasked)
-  he = hipModuleGetFunction(&prog->f_normeq, prog->module, "mhx_user_normeq");
-  if (he == hipSuccess)
-    he = hipFuncSetAttribute(reinterpret_cast<const void*>(prog->f_normeq),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)kNormEqLdsBudget);
-  if (he != hipSuccess || static_lds(prog->f_normeq) != 0) {
-    *err = he != hipSuccess ? std::string("module function mhx_user_normeq: ") + hipGetErrorString(he)
-                            : std::string("module function mhx_user_normeq has static LDS");
-    return -1;
-  }
-  he = hipModuleGetFunction(&prog->f_cand, prog->module, "mhx_user_cand");
-  if (he != hipSuccess || static_lds(prog->f_cand) != 0) {
-    *err = he != hipSuccess ? std::string("module function mhx_user_cand: ") + hipGetErrorString(he)
-                            : std::string("module function mhx_user_cand has static LDS");
-    return -1;
-  }
-  he = hipModuleGetFunction(&prog->f_fitpct, prog->module, "mhx_user_fitpct");
-  if (he != hipSuccess || static_lds(prog->f_fitpct) != 0) {
-    *err = he != hipSuccess ? std::string("module function mhx_user_fitpct: ") + hipGetErrorString(he)
-                            : std::string("module function mhx_user_fitpct has static LDS");
-    return -1;
+    if (no_static_lds(prog->f_model[k], twins[k].n, err) != 0) return -1;
   }
   prog->has_split = false;
   if (with_split) {
@@ -746,59 +714,26 @@ hipError_t rtc_launch_logpost(const UserProgram& p, hipStream_t st, const Proble
   return hipModuleLaunchKernel(p.f_logpost, grid_for(p, n), 1, 1, (unsigned)p.fam->threads, 1, 1,
                                (unsigned)p.fam->lds_bytes, st, args, nullptr);
 }
-hipError_t rtc_launch_fit(const UserProgram& p, hipStream_t st, const ProblemDesc* P,
-                          const FitArgs& A) {
-  if (A.n <= 0 || A.m <= 0) return hipSuccess;
-  FitArgs a = A;
-  void* args[] = {(void*)&P, (void*)&a};
-  return hipModuleLaunchKernel(p.f_fit, grid_for(p, A.n * A.n_chunks), 1, 1, (unsigned)p.fam->threads,
-                               1, 1, fit_lds_bytes(p.fam->waves_per_group), st, args, nullptr);
-}
-hipError_t rtc_launch_waic(const UserProgram& p, hipStream_t st, const ProblemDesc* P,
-                           const ChainState& S, const WaicArgs& A) {
-  if (A.n <= 0 || A.m <= 0) return hipSuccess;
+template <class Args>
+hipError_t rtc_launch_model(const UserProgram& p, hipStream_t st, const ProblemDesc* P,
+                            const ChainState& S, const Args& A) {
+  using R = ModelReadout<Args>;
+  const int wpg = p.fam->waves_per_group;
+  const int64_t waves = R::waves(A);
+  if (waves <= 0) return hipSuccess;
   ChainState s = S;
-  WaicArgs a = A;
-  void* args[] = {(void*)&P, (void*)&s, (void*)&a};
-  return hipModuleLaunchKernel(p.f_waic, grid_for(p, A.n * A.n_blocks), 1, 1, (unsigned)p.fam->threads,
-                               1, 1, fit_lds_bytes(p.fam->waves_per_group), st, args, nullptr);
+  Args a = A;
+  R::fix_up(wpg, a);
+  void* with_state[] = {(void*)&P, (void*)&s, (void*)&a};
+  void* without[] = {(void*)&P, (void*)&a};
+  return hipModuleLaunchKernel(p.f_model[R::kId], grid_for(p, waves), 1, 1, (unsigned)p.fam->threads, 1, 1,
+                               R::lds(wpg, a), st, R::kState ? with_state : without, nullptr);
 }
-hipError_t rtc_launch_resid(const UserProgram& p, hipStream_t st, const ProblemDesc* P,
-                            const ChainState& S, const ResidArgs& A) {
-  if (A.n <= 0 || A.m <= 0) return hipSuccess;
-  ChainState s = S;
-  ResidArgs a = A;
-  void* args[] = {(void*)&P, (void*)&s, (void*)&a};
-  return hipModuleLaunchKernel(p.f_resid, grid_for(p, A.n * A.n_blocks), 1, 1, (unsigned)p.fam->threads,
-                               1, 1, fit_lds_bytes(p.fam->waves_per_group), st, args, nullptr);
-}
-hipError_t rtc_launch_normeq(const UserProgram& p, hipStream_t st, const ProblemDesc* P,
-                             const ChainState& S, const NormEqArgs& A) {
-  if (A.n <= 0 || A.m <= 0) return hipSuccess;
-  ChainState s = S;
-  NormEqArgs a = A;
-  a.lanes = normeq_lanes(p.fam->waves_per_group, A.p), a.sub = normeq_sub(p.fam->waves_per_group, A.p);
-  void* args[] = {(void*)&P, (void*)&s, (void*)&a};
-  return hipModuleLaunchKernel(p.f_normeq, grid_for(p, A.n * A.n_blocks), 1, 1, (unsigned)p.fam->threads,
-                               1, 1, normeq_lds_bytes(p.fam->waves_per_group, A.p), st, args, nullptr);
-}
-hipError_t rtc_launch_cand(const UserProgram& p, hipStream_t st, const ProblemDesc* P,
-                           const CandArgs& A) {
-  if (A.n <= 0 || A.m <= 0 || A.m_cand <= 0) return hipSuccess;
-  CandArgs a = A;
-  void* args[] = {(void*)&P, (void*)&a};
-  return hipModuleLaunchKernel(p.f_cand, grid_for(p, A.n * A.n_blocks), 1, 1, (unsigned)p.fam->threads,
-                               1, 1, fit_lds_bytes(p.fam->waves_per_group), st, args, nullptr);
-}
-hipError_t rtc_launch_fitpct(const UserProgram& p, hipStream_t st, const ProblemDesc* P,
-                             const ChainState& S, const FitPctArgs& A) {
-  if (A.n <= 0 || A.m <= 0) return hipSuccess;
-  ChainState s = S;
-  FitPctArgs a = A;
-  void* args[] = {(void*)&P, (void*)&s, (void*)&a};
-  return hipModuleLaunchKernel(p.f_fitpct, grid_for(p, A.n * A.n_blocks), 1, 1, (unsigned)p.fam->threads,
-                               1, 1, fit_lds_bytes(p.fam->waves_per_group), st, args, nullptr);
-}
+#define MHX_X(ID, ARGS, ...)                                                                          \
+  template hipError_t rtc_launch_model<ARGS>(const UserProgram&, hipStream_t, const ProblemDesc*, \
+                                             const ChainState&, const ARGS&);
+MHX_MODEL_READOUTS(MHX_X)
+#undef MHX_X
 hipError_t rtc_launch_init(const UserProgram& p, hipStream_t st, const ProblemDesc* P,
                            const ChainState& S) {
   ChainState s = S;
@@ -956,14 +891,11 @@ std::shared_ptr<DerivedProgram> rtc_get_derived(const std::vector<std::string>& 
                      err) != 0)
     return nullptr;
   hipError_t he = hipModuleGetFunction(&prog->f_derived, prog->module, "mhx_user_derived");
-  int lds = -1;
-  if (he == hipSuccess)
-    he = hipFuncGetAttribute(&lds, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, prog->f_derived);
-  if (he != hipSuccess || lds != 0) {
-    *err = he != hipSuccess ? std::string("module function mhx_user_derived: ") + hipGetErrorString(he)
-                            : std::string("module function mhx_user_derived has static LDS");
+  if (he != hipSuccess) {
+    *err = std::string("module function mhx_user_derived: ") + hipGetErrorString(he);
     return nullptr;
   }
+  if (no_static_lds(prog->f_derived, "mhx_user_derived", err) != 0) return nullptr;
   if (order.size() >= kCap) {
     cache.erase(order.front());
     order.erase(order.begin());

@@ -41,12 +41,7 @@ struct UserExpr {
 struct UserProgram {
   hipModule_t module = nullptr;
   hipFunction_t f_logpost = nullptr, f_init = nullptr, f_step = nullptr, f_adaptive = nullptr;
-  hipFunction_t f_fit = nullptr;  // mhx_user_fit: model values and bands (k_fit_body)
-  hipFunction_t f_waic = nullptr;  // mhx_user_waic: mhx_get_waic's accumulation (k_waic_body)
-  hipFunction_t f_resid = nullptr;  // mhx_user_resid: mhx_get_residuals' block partials (k_resid_body)
-  hipFunction_t f_normeq = nullptr;  // mhx_user_normeq: mhx_get_normal_equations' block partials (k_normeq_body)
-  hipFunction_t f_cand = nullptr;  // mhx_user_cand: mhx_get_candidate_scores' block partials (k_cand_body)
-  hipFunction_t f_fitpct = nullptr;  // mhx_user_fitpct: mhx_get_fit_percentiles' values (k_fitpct_values_body)
+  hipFunction_t f_model[MR__COUNT] = {};  // the model read-outs' twins (MHX_MODEL_READOUTS, mhx_launch.hpp)
   hipFunction_t f_split_sweep = nullptr, f_split_step = nullptr;  // only with has_split
   hipFunction_t f_split_tsweep = nullptr;                         // (the tile-sliced sweep)
   hipFunction_t f_persist = nullptr, f_persist_ts = nullptr;      // (the persistent split kernels)
@@ -89,18 +84,10 @@ std::shared_ptr<UserProgram> rtc_get(const std::vector<UserExpr>& models,
 
 hipError_t rtc_launch_logpost(const UserProgram& p, hipStream_t st, const ProblemDesc* P,
                               const double* theta, int64_t n, double* out, double* parts);
-hipError_t rtc_launch_fit(const UserProgram& p, hipStream_t st, const ProblemDesc* P,
-                          const FitArgs& A);
-hipError_t rtc_launch_waic(const UserProgram& p, hipStream_t st, const ProblemDesc* P,
-                           const ChainState& S, const WaicArgs& A);
-hipError_t rtc_launch_resid(const UserProgram& p, hipStream_t st, const ProblemDesc* P,
-                            const ChainState& S, const ResidArgs& A);
-hipError_t rtc_launch_normeq(const UserProgram& p, hipStream_t st, const ProblemDesc* P,
-                             const ChainState& S, const NormEqArgs& A);
-hipError_t rtc_launch_cand(const UserProgram& p, hipStream_t st, const ProblemDesc* P,
-                           const CandArgs& A);
-hipError_t rtc_launch_fitpct(const UserProgram& p, hipStream_t st, const ProblemDesc* P,
-                             const ChainState& S, const FitPctArgs& A);
+// the twin of launch_model (mhx_launch.hpp): the program's model read-out kernel of A's type
+template <class Args>
+hipError_t rtc_launch_model(const UserProgram& p, hipStream_t st, const ProblemDesc* P,
+                            const ChainState& S, const Args& A);
 hipError_t rtc_launch_init(const UserProgram& p, hipStream_t st, const ProblemDesc* P,
                            const ChainState& S);
 hipError_t rtc_launch_step_injected(const UserProgram& p, hipStream_t st, const ProblemDesc* P,

@@ -2,11 +2,14 @@
 // plain numbers (no HIP, no engine): how a portion of items is carved into 256-byte aligned
 // pieces, how many items fit the budget, and the order in which portions are worked through.
 // mhx_engine.cpp's portion runner launches what these describe; tests/test_stage_plan.py pins the
-// portion sizes and the carving on the CPU.
+// portion sizes and the carving on the CPU.  With them, and as free of HIP: data_view, where a
+// chain's own data lie for a launch (tests/test_dataview_host.py).
 #pragma once
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+
+#include "mhx_types.hpp"
 
 namespace mhx {
 
@@ -282,6 +285,26 @@ inline CandPieces carve_cand(Carver& c, int64_t nb_pitch, int d_, int per_chain,
   s.score = c.take(n * m * sizeof(double));
   s.part = c.take(n * m * nb * sizeof(double));
   return s;
+}
+// The DataView (mhx_types.hpp) of function f from point m0 of its dataset on: the shared arrays
+// (pd NULL), or the planes of a dataset per walker, whose row c is the engine's chain c.  Every
+// array a point indexes is offset by m0; the one 1/sigma per walker of kPlaneWScalar is not.
+inline DataView data_view(const FnDesc& f, const PlaneDesc* pd, int64_t m0) {
+  DataView v{};
+  v.x0 = f.x + m0;
+  v.x1 = f.n_xcols > 1 ? f.c + m0 : nullptr;
+  if (pd) {
+    v.y = pd->y + m0, v.y_pitch = pd->pitch;
+    switch (pd->w_kind) {
+      case kPlaneWShared: v.w = f.w + m0, v.w_pitch = 0, v.w_step = 1; break;
+      case kPlaneWScalar: v.w = pd->w, v.w_pitch = 1, v.w_step = 0; break;
+      default: v.w = pd->w + m0, v.w_pitch = pd->pitch, v.w_step = 1; break;
+    }
+  } else {
+    v.y = f.y + m0, v.y_pitch = 0;
+    v.w = f.w + m0, v.w_pitch = 0, v.w_step = 1;
+  }
+  return v;
 }
 // batched traces: the caller's column list [n_cols] - it does not grow with n and comes first -
 // the rows values [n][max_out][n_cols], their envelopes lo and hi of the same shape (envelope 0:

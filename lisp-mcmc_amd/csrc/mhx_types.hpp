@@ -209,6 +209,36 @@ inline int64_t band_count_of(int64_t take) {
 }
 #endif
 
+// The data of one function as each chain reads its own, from the first point of a launch on: what
+// k_resid, k_normeq and k_cand are given (data_view, mhx_stage.hpp, builds it on the host).  x0, x1,
+// y, w come offset to the launch's first point, and the data are on the device in full: index -1 is
+// the point before it.  Chain c, counted from the engine's chain 0 as the planes' rows are, reads
+//   ys_i = y[c * y_pitch + i]               y_pitch 0: the shared dataset; a plane's pitch else
+//   w_i  = w[c * w_pitch + i * w_step]      (0, 1) the shared 1/sigma - the shared dataset's and
+//                                           kPlaneWShared's; (1, 0) one per walker, kPlaneWScalar:
+//                                           w is NOT offset to the first point; (pitch, 1) a plane
+//                                           of them, kPlaneWPlane
+// so that one kernel serves shared datasets and all three PlaneDesc::w_kinds.  y_row(c), w_row(c):
+// the rows these index.  The three kernel bodies write the two products out, member by member, as
+// they did before there was a view: through the accessors three k_resid instances and one k_cand
+// came out of the compiler with other VGPR counts (poly2, poly8: 56 -> 50; generic 106 -> 108;
+// k_cand pvoigt2 107 -> 100), the same as ever without them.
+#ifdef __HIPCC__
+#define MHX_HOST_DEVICE __host__ __device__
+#else
+#define MHX_HOST_DEVICE
+#endif
+struct DataView {
+  const double* x0;
+  const double* x1;  // the second column of x, or nullptr
+  const double* y;
+  const double* w;
+  int64_t y_pitch, w_pitch;
+  int32_t w_step, pad_;
+  MHX_HOST_DEVICE const double* y_row(int64_t c) const { return y + c * y_pitch; }
+  MHX_HOST_DEVICE const double* w_row(int64_t c) const { return w + c * w_pitch; }
+};
+
 // k_fit (mhx_eval_function, mhx_get_fit_bands): the model of function `fn` at m points for n
 // items.  An item is ONE parameter vector (sel == nullptr: row row0 + i of theta; ymax receives
 // the values) or a chain's selected steps (rows row0 + i rows_per_item + sel[i sel_pitch + k],
@@ -307,31 +337,21 @@ struct FitPctArgs {
 // data, for each of n chains from c0 on, and the block sums, counts and extreme of the standardized
 // residuals.  A wave serves one chain and one block of MHX_RESID_BLOCK = kWave x kResidPts points;
 // n_blocks blocks cover the m points of this launch, which are blocks blk0 .. of the function's
-// nb_total and begin at point p_first of the dataset.  x0, x1, y, w come offset to the launch's
-// first point, and the data are on the device in full: index -1 is the point before it, which the
-// first block of a later chunk reads for its neighbour.  Chain c reads
-//   ys_i = y[c * y_pitch + i]               y_pitch 0: the shared dataset; a plane's pitch else
-//   w_i  = w[c * w_pitch + i * w_step]      (0, 1) the shared 1/sigma; (1, 0) one per walker;
-//                                           (pitch, 1) a plane of them
-// so that one kernel serves shared datasets and all three PlaneDesc::w_kinds; c counts from the
-// engine's chain 0, as the planes' rows do.  theta [n][d] is the launch's (nullptr:
-// ChainState::best_theta).  A lane keeps five points - its four and, in a fifth slot, the block's
-// neighbour (the last point of the block before, recomputed from the same inputs: the same bits) -
-// so that ONE Spec::values with one prepare serves both.
+// nb_total and begin at point p_first of the dataset.  The chain's data come as a DataView; its
+// index -1 is what the first block of a later chunk reads for its neighbour.  theta [n][d] is the
+// launch's (nullptr: ChainState::best_theta).  A lane keeps five points - its four and, in a fifth
+// slot, the block's neighbour (the last point of the block before, recomputed from the same inputs:
+// the same bits) - so that ONE Spec::values with one prepare serves both.
 constexpr int kResidPts = MHX_RESID_BLOCK / kWave;
 static_assert(kResidPts * kWave == MHX_RESID_BLOCK && kResidPts == 4, "MHX_RESID_BLOCK (include/mhx.h)");
 static_assert(MHX_RESID_BLOCK == MHX_WAIC_BLOCK, "mhx_get_residuals' sums follow mhx_get_waic's rule");
 struct ResidArgs {
   int64_t c0, n;
-  int32_t fn, n_blocks, w_step, pad_;
+  int32_t fn, n_blocks;
   int64_t blk0, nb_total, m, p_first;
-  int64_t y_pitch, w_pitch;
   double z_limit;
   const double* theta;  // [n][d] or nullptr
-  const double* x0;
-  const double* x1;     // the second column of x, or nullptr
-  const double* y;
-  const double* w;
+  DataView data;
   double* fit;          // [n][m] or nullptr
   double* z;            // [n][m] or nullptr
   double* part_chi2;    // [n][nb_total] the blocks' sums of z^2
@@ -345,8 +365,8 @@ struct ResidArgs {
 
 // k_normeq (mhx_get_normal_equations): the scaled Jacobian g by central differences, the weighted
 // residual u and the block sums of their products, for function `fn` at ONE parameter vector per
-// chain over the chain's own data (read through pitches as ResidArgs has them).  A wave serves one
-// chain and one block of MHX_NORMEQ_BLOCK points, in sub-steps of `sub` = kNormEqPts * `lanes` <= 256
+// chain over the chain's own data (read through a DataView).  A wave serves one chain
+// and one block of MHX_NORMEQ_BLOCK points, in sub-steps of `sub` = kNormEqPts * `lanes` <= 256
 // points (a lane evaluates kNormEqPts = 4 of them, as k_waic: k_normeq_body says why) whose rows
 // {g_i0 .. g_i,p-1, u_i} lie point-major in the wave's LDS tile, `pitch` doubles apart.  The p
 // columns are the distinct places of theta the function reads, col[] ascending; a TASK is a pair
@@ -380,25 +400,21 @@ static_assert(normeq_lanes(16, MHX_MAX_FN_PARAMS) >= 8 && normeq_lanes(8, 8) == 
 static_assert(MHX_NORMEQ_BLOCK % (kNormEqPts * kWave) == 0, "whole sub-steps at the widest");
 struct NormEqArgs {
   int64_t c0, n;
-  int32_t fn, n_blocks, w_step, p;
-  int32_t n_tasks, pitch, sub, steps_pitch;  // steps_pitch 0: one [d] for all chains; d: [n][d]
-  int32_t lanes, pad_;
+  int32_t fn, n_blocks, p, n_tasks;
+  int32_t pitch, steps_pitch;  // steps_pitch 0: one [d] for all chains; d: [n][d]
+  int32_t sub, lanes;          // (the launcher's: they depend on the kernel's family)
   int64_t blk0, nb_total, m;
-  int64_t y_pitch, w_pitch;
   int32_t col[MHX_MAX_FN_PARAMS];  // [p] the places of theta the function reads, ascending
   const double* theta;  // [n][d] or nullptr
   const double* steps;  // [d] or [n][d]
-  const double* x0;
-  const double* x1;     // the second column of x, or nullptr
-  const double* y;
-  const double* w;
+  DataView data;
   double* g;            // [n][d][m] or nullptr (zeroed by the host: the kernel writes active columns)
   double* part;         // [n][nb_total][n_tasks]
   int32_t* status;      // [n] MHX_NORMEQ_NONFINITE is stored where a value is not finite
 };
 
 // k_cand (mhx_get_candidate_scores): function `fn` at m_cand parameter vectors per chain over the
-// chain's own data (read through pitches as ResidArgs has them), for each of n chains from c0 on.
+// chain's own data (read through a DataView), for each of n chains from c0 on.
 // A wave serves one chain and one block of MHX_RESID_BLOCK points: it loads the block's points
 // once, kResidPts per lane, and walks the candidates - cand[j] (cand_pitch 0: one [m_cand][d] for
 // every chain) or cand[i * cand_pitch + j] of the launch's chain i - each through the wave's LDS row,
@@ -409,15 +425,11 @@ struct NormEqArgs {
 // blocks function by function and ranks the chain's candidates.
 struct CandArgs {
   int64_t c0, n;
-  int32_t fn, n_blocks, w_step, pad_;
+  int32_t fn, n_blocks;
   int64_t m_cand, cand_pitch;  // cand_pitch in candidates: 0 or m_cand
   int64_t blk0, nb_pitch, m;
-  int64_t y_pitch, w_pitch;
   const double* cand;  // [m_cand][d] or [n][m_cand][d]
-  const double* x0;
-  const double* x1;    // the second column of x, or nullptr
-  const double* y;
-  const double* w;
+  DataView data;
   double* part;        // [n][m_cand][nb_pitch]
 };
 

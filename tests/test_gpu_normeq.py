@@ -374,6 +374,23 @@ def test_planes_every_sigma_kind_in_both_forms(mhx, monkeypatch, kind):
     assert len(set(runs["0"]["chi2"].tolist())) == C
 
 
+@pytest.mark.parametrize("kind", [NONE, SHARED, PER_CHAIN, PER_POINT])
+def test_planes_beyond_one_chunk_of_points(mhx, kind):
+    """the second chunk of a dataset per walker: what a point indexes moves on to the chunk's first
+    point - x, the walker's row of y, a shared sigma or the walker's row of it - and a walker's one
+    sigma does not"""
+    C, N = 2, CHUNK + 257
+    x, y, sigma, rows, truth = plane_data(N, C, kind, seed=900 + kind)
+    e = mhx.Engine(C, 2, 1)
+    e.set_function(0, mhx.capi.MODEL_POLY, (), [0, 1])
+    e.set_dataset_planes(0, x, y, sigma, kind)
+    e.init_chains(truth)
+    sig_of = (lambda c: None) if kind == NONE else (lambda c: rows[c])
+    r, _ = check(e, 0, None, None, nc.NORMAL, lambda c: y[c], sig_of, [0, 1], where="planes, two chunks")
+    assert r["g"].shape == (C, 2, N) and r["chi2"][0] != r["chi2"][1]
+    e.close()
+
+
 # ---- 7. a group ----------------------------------------------------------------------------------------
 def test_a_group_gives_the_bits_of_one_engine(mhx):
     s = pb.two_peak(n=334, seed=4)

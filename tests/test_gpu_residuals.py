@@ -326,6 +326,23 @@ def test_planes_every_sigma_kind_in_both_forms(mhx, monkeypatch, N, kind):
     assert len(set(runs["0"]["chi2"].tolist())) == C
 
 
+@pytest.mark.parametrize("kind", [NONE, SHARED, PER_CHAIN, PER_POINT])
+def test_planes_beyond_one_chunk_of_points(mhx, kind):
+    """the second chunk of a dataset per walker: what a point indexes moves on to the chunk's first
+    point - x, the walker's row of y, a shared sigma or the walker's row of it - and a walker's one
+    sigma does not"""
+    C, N = 2, CHUNK + 257
+    x, y, sigma, rows, truth = plane_data(N, C, kind, seed=900 + kind)
+    e = mhx.Engine(C, 2, 1)
+    e.set_function(0, mhx.capi.MODEL_POLY, (), [0, 1])
+    e.set_dataset_planes(0, x, y, sigma, kind)
+    e.init_chains(truth)
+    sig_of = (lambda c: None) if kind == NONE else (lambda c: rows[c])
+    r = check(e, 0, None, rc.NORMAL, lambda c: y[c], sig_of, where="planes, two chunks")
+    assert r["z"].shape == (C, N) and r["chi2"][0] != r["chi2"][1]
+    e.close()
+
+
 def test_a_global_fit_mixing_a_plane_function_with_a_shared_one(mhx):
     C, N = 5, 130
     x, y, sigma, rows, truth = plane_data(N, C, PER_CHAIN, seed=77)
