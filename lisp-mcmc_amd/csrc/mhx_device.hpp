@@ -60,6 +60,26 @@ __device__ __forceinline__ lds_cdptr_t opaque_lds(lds_cdptr_t p) {
 #endif
   return p;
 }
+// Global loads and LDS-DMA by SCALAR BASE + LANE OFFSET: a wave-uniform 64-bit address in a pair
+// of SGPRs plus one 32-bit VGPR, no vector address arithmetic.  The base is whatever scalar
+// arithmetic gives (array + tile); the lane's byte offset is `v << SH`, formed where it is used
+// (one instruction, no register held across the sweep): instruction selection works a basic
+// block at a time and only takes the scalar-base form when it sees the offset widened from 32
+// bits in the block of the load itself - a loop-invariant offset is hoisted, widened once out of
+// sight and folded into the base, which then is a 64-bit VGPR pair with a vector add per tile.
+typedef const __attribute__((address_space(1))) char* glb_cptr_t;
+// a wave-uniform int pinned in an SGPR (the optimiser may not split or re-associate it)
+__device__ __forceinline__ int scalar_int(int v /*uniform*/) {
+  asm volatile("" : "+s"(v));
+  return v;
+}
+// the lane's byte offset v << SH of such a load (above)
+template <int SH>
+__device__ __forceinline__ unsigned lane_offset(unsigned v) {
+  unsigned r;
+  asm volatile("v_lshlrev_b32 %0, %1, %2" : "=v"(r) : "n"(SH), "v"(v));
+  return r;
+}
 __device__ __forceinline__ lds_cdptr_t lds_logtab() {
   return (lds_cdptr_t)reinterpret_cast<LdsHead*>(mhx_lds_raw)->logtab;
 }

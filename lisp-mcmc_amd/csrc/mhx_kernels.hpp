@@ -117,20 +117,39 @@ typedef const __attribute__((address_space(1))) void* glb_ptr_t;
 // no VGPR staging; each wave instruction lands 64 x 16 B = 1 KiB contiguously at a
 // wave-uniform LDS base).  Asynchronous: retired by the s_waitcnt vmcnt(0) the compiler puts in
 // front of the next __syncthreads().
-template <int NARR>
-__device__ __forceinline__ void tile_dma(const FnDesc& f, int64_t t, GroupLds& lds, int buf,
-                                         int w) {
-  const int64_t base = t * kTilePoints + 2 * (int)threadIdx.x;
+// The source of each instruction is a scalar base - this wave's KiB of the array's tile, a
+// 64-bit scalar add away from the array's start - plus the lane's 16 B: no vector address
+// arithmetic (lane_offset).  SB = false keeps a 64-bit address per thread: the generic kernel,
+// which inlines 21 sweeps, spills 16 B more per lane with the scalar form.
+template <int NARR, bool SB = true>
+__device__ __forceinline__ void tile_dma(const FnDesc& f, int64_t t /*uniform*/, GroupLds& lds,
+                                         int buf, int w) {
   const int wbase = 2 * kWave * w;  // first element this wave fills
-  __builtin_amdgcn_global_load_lds((glb_ptr_t)(f.x + base), (lds_ptr_t)&lds.tiles[buf][0][wbase],
-                                   16, 0, 0);
-  __builtin_amdgcn_global_load_lds((glb_ptr_t)(f.y + base), (lds_ptr_t)&lds.tiles[buf][1][wbase],
-                                   16, 0, 0);
+  if constexpr (!SB) {
+    const int64_t base = t * kTilePoints + 2 * (int)threadIdx.x;
+    __builtin_amdgcn_global_load_lds((glb_ptr_t)(f.x + base),
+                                     (lds_ptr_t)&lds.tiles[buf][0][wbase], 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((glb_ptr_t)(f.y + base),
+                                     (lds_ptr_t)&lds.tiles[buf][1][wbase], 16, 0, 0);
+    if constexpr (NARR > 2)
+      __builtin_amdgcn_global_load_lds((glb_ptr_t)(f.w + base),
+                                       (lds_ptr_t)&lds.tiles[buf][2][wbase], 16, 0, 0);
+    if constexpr (NARR > 3)
+      __builtin_amdgcn_global_load_lds((glb_ptr_t)(f.c + base),
+                                       (lds_ptr_t)&lds.tiles[buf][3][wbase], 16, 0, 0);
+    return;
+  }
+  const int64_t go = t * (kTilePoints * 8) + wbase * 8;  // bytes from the start of each array
+  const unsigned vo = lane_offset<4>((unsigned)lane_id());
+  __builtin_amdgcn_global_load_lds((glb_ptr_t)(((glb_cptr_t)f.x + go) + vo),
+                                   (lds_ptr_t)&lds.tiles[buf][0][wbase], 16, 0, 0);
+  __builtin_amdgcn_global_load_lds((glb_ptr_t)(((glb_cptr_t)f.y + go) + vo),
+                                   (lds_ptr_t)&lds.tiles[buf][1][wbase], 16, 0, 0);
   if constexpr (NARR > 2)
-    __builtin_amdgcn_global_load_lds((glb_ptr_t)(f.w + base),
+    __builtin_amdgcn_global_load_lds((glb_ptr_t)(((glb_cptr_t)f.w + go) + vo),
                                      (lds_ptr_t)&lds.tiles[buf][2][wbase], 16, 0, 0);
   if constexpr (NARR > 3)
-    __builtin_amdgcn_global_load_lds((glb_ptr_t)(f.c + base),
+    __builtin_amdgcn_global_load_lds((glb_ptr_t)(((glb_cptr_t)f.c + go) + vo),
                                      (lds_ptr_t)&lds.tiles[buf][3][wbase], 16, 0, 0);
 }
 
@@ -219,33 +238,58 @@ __device__ __forceinline__ double sweep_yw(const FnDesc& f, const typename Model
   constexpr unsigned kAll = (1u << Model::kPeaks) - 1u;
   const int l = lane_id();
   const int w = wave_in_group();
-  const int64_t nw = (f.n + kPadPoints - 1) / kPadPoints;  // windows of the dataset (>= 1)
-  const int64_t nt2 = (nw + WPT - 1) / WPT;
+  // THE TILE PLAN of this sweep: wave-uniform, formed once, in front of the tile loop.  The
+  // bookkeeping of a tile - which halves of it exist, where they come from, how much of a window
+  // is data - is then 32-bit scalar arithmetic; as 64-bit quantities re-read from the FnDesc
+  // behind every barrier it went through the vector pipe (64-bit compares, per-thread 64-bit
+  // addresses) and through two scalar-memory waits per tile that the 16 waves sat out together.
+  // A window index fits an int: n < 2^42 points whenever x, y and 1/sigma of a function fit the
+  // device's memory at all (three arrays of 2^42 doubles are 96 TiB); the BYTE offsets of the
+  // tiles stay 64-bit scalars.
+  const int64_t n = f.n;
+  const int nw = (int)((n + kPadPoints - 1) / kPadPoints);  // windows of the dataset (>= 1)
+  const int nt2 = (nw + WPT - 1) / WPT;
+  const int nv_last = (int)(n - (int64_t)(nw - 1) * kPadPoints);  // data points of the last window
+  const glb_cptr_t gx = (glb_cptr_t)f.x, gy = (glb_cptr_t)f.y, gw = (glb_cptr_t)f.w;
+  // (what a thread adds to a scalar base - its 16 B of an LDS-DMA instruction, its x of a
+  // window - is one shift where it is used: lane_offset)
   double* const base = &lds.tiles[0][0][0];  // buffer b: y at base + 2 b T2, 1/sigma at + T2
   // yw tile j -> buffer b: two LDS-DMA instructions per array and thread (16 B each); the arrays
   // are padded to whole windows, so the second half of the last tile may not exist
-  auto dma = [&](int64_t j, int b) {
+  auto dma = [&](int j, int b) {
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
-      const int64_t p0 = j * T2 + (int64_t)q * kTilePoints;
-      if (p0 < nw * kPadPoints) {  // uniform
-        const int64_t g = p0 + 2 * (int)threadIdx.x;
+      if (j * WPT + (q * kTilePoints) / kPadPoints < nw) {  // the window this half lies in exists
         const int dst = q * kTilePoints + 2 * kWave * w;
-        __builtin_amdgcn_global_load_lds((glb_ptr_t)(f.y + g),
+        const int64_t go = (int64_t)j * (T2 * 8) + dst * 8;  // this wave's KiB: bytes, scalar
+        const unsigned vo = lane_offset<4>((unsigned)l);
+        __builtin_amdgcn_global_load_lds((glb_ptr_t)((gy + go) + vo),
                                          (lds_ptr_t)(base + (2 * b) * T2 + dst), 16, 0, 0);
-        __builtin_amdgcn_global_load_lds((glb_ptr_t)(f.w + g),
+        __builtin_amdgcn_global_load_lds((glb_ptr_t)((gw + go) + vo),
                                          (lds_ptr_t)(base + (2 * b + 1) * T2 + dst), 16, 0, 0);
       }
     }
   };
   // the lane's x at the first point of each window of tile j (what the recurrence is seeded from)
-  auto load_xs = [&](int64_t j, double (&xs)[WPT]) {
+  auto load_xs = [&](int j, double (&xs)[WPT]) {
 #pragma unroll
     for (int q = 0; q < WPT; ++q) {
-      const int64_t wi = j * WPT + q;
-      xs[q] = f.x[(wi < nw ? wi : nw - 1) * kPadPoints + l];
+      const int wi = j * WPT + q;
+      const int64_t go = (int64_t)(wi < nw ? wi : nw - 1) * (kPadPoints * 8);
+      xs[q] = *(const __attribute__((address_space(1))) double*)((gx + go) +
+                                                                 lane_offset<3>((unsigned)l));
     }
   };
+  // The lane's element of point slot 0 ... P-1 of window 0 of buffer 0, y and 1/sigma: four LDS
+  // addresses the compiler cannot relate to one another (opaque_lds: see tile_work in sweep()),
+  // formed ONCE per sweep.  (buffer, window, section) is a scalar offset on top of them, the
+  // iteration an immediate of the read.
+  lds_cdptr_t py[P], pw[P];
+#pragma unroll
+  for (int i = 0; i < P; ++i) {
+    py[i] = opaque_lds((lds_cdptr_t)base + i * kWave + l);
+    pw[i] = opaque_lds((lds_cdptr_t)(base + T2) + i * kWave + l);
+  }
   double acc0 = 0.0, acc1 = 0.0;
   double xs[WPT], xs_next[WPT];
   unsigned tile_masks = ~0u;
@@ -254,8 +298,8 @@ __device__ __forceinline__ double sweep_yw(const FnDesc& f, const typename Model
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (threadIdx.x == 0) lds.vote[3] = 0;  // (the vote of sweep(): everybody has read it)
-  for (int64_t j = 0; j < nt2; ++j) {
-    const int b = (int)(j & 1);
+  for (int j = 0; j < nt2; ++j) {
+    const int b = j & 1;
     if (j + 1 < nt2) {
       dma(j + 1, b ^ 1);  // (that buffer was last read in tile j - 1: everybody left it through the barrier)
       load_xs(j + 1, xs_next);
@@ -263,24 +307,18 @@ __device__ __forceinline__ double sweep_yw(const FnDesc& f, const typename Model
     if (active) {
 #pragma unroll
       for (int q = 0; q < WPT; ++q) {
-        const int64_t wi = j * WPT + q;
+        const int wi = j * WPT + q;
         if (wi >= nw) break;
         if ((wi & 63) == 0) {  // the masks of 64 windows at once, lane i taking window wi + i
-          const int64_t ti = wi + l < nw ? wi + l : nw - 1;
+          const int ti = wi + l < nw ? wi + l : nw - 1;
           tile_masks = Model::tile_mask(prep, f.txlo[ti], f.txhi[ti]);
         }
         // (no guarded window can occur: the vote asked for Prep::fast, |t| < kFastT over the
         // whole x range, of which every window's range is a part)
         const unsigned tm =
             (unsigned)__builtin_amdgcn_readlane((int)tile_masks, (int)(wi & 63)) & kAll;
-        lds_cdptr_t py[P], pw[P];
-#pragma unroll
-        for (int i = 0; i < P; ++i) {  // (opaque: see tile_work in sweep())
-          py[i] = opaque_lds((lds_cdptr_t)(base + (2 * b) * T2 + q * kPadPoints) + i * kWave + l);
-          pw[i] = opaque_lds((lds_cdptr_t)(base + (2 * b + 1) * T2 + q * kPadPoints) + i * kWave + l);
-        }
-        const int64_t left = f.n - wi * (int64_t)kPadPoints;
-        const int nv = (int)(left < (int64_t)kPadPoints ? left : (int64_t)kPadPoints);
+        const int wo = (2 * b) * T2 + q * kPadPoints;  // the window in the tile buffers: scalar
+        const int nv = wi + 1 < nw ? kPadPoints : nv_last;  // (only the last window is ragged)
         const double x0 = xs[q];
         auto window = [&](auto mk) {
           const unsigned mask = mk;
@@ -289,11 +327,14 @@ __device__ __forceinline__ double sweep_yw(const FnDesc& f, const typename Model
           for (int sec = 0; sec < NSEC; ++sec) {
             const int sb = sec * NIN * P * kWave;  // first point of the section in the window
             if (sb >= nv) break;
+            // (one scalar add per section, pinned: split into a window's part and a section's,
+            // as the optimiser would, it is four more vector adds per window)
+            const int so = scalar_int(wo + sb);
             double y[P], wv[P];
 #pragma unroll
             for (int i = 0; i < P; ++i) {
-              y[i] = py[i][sb];
-              wv[i] = pw[i][sb];
+              y[i] = py[i][so];
+              wv[i] = pw[i][so];
             }
 #pragma unroll
             for (int it = 0; it < NIN; ++it) {
@@ -304,8 +345,8 @@ __device__ __forceinline__ double sweep_yw(const FnDesc& f, const typename Model
               for (int i = 0; i < P; ++i) {
                 yn[i] = wn[i] = 0.0;
                 if (it + 1 < NIN) {
-                  yn[i] = py[i][sb + (it + 1) * P * kWave];
-                  wn[i] = pw[i][sb + (it + 1) * P * kWave];
+                  yn[i] = py[i][so + (it + 1) * P * kWave];
+                  wn[i] = pw[i][so + (it + 1) * P * kWave];
                 }
               }
               __builtin_amdgcn_sched_barrier(0);  // keep the reads ahead of the arithmetic below
@@ -379,7 +420,7 @@ struct PickType<false, T, F> {
 // hot loops, as a second instance inside the same kernel from 74.8 to 104.5 ms per 20
 // iterations and config 2's by 3.5 % (same box) - and the datasets of one grid, or none, must
 // not pay for it.
-template <class Model, int LIK, bool WG = false>
+template <class Model, int LIK, bool WG = false, bool SB = true>
 __device__ __forceinline__ double sweep(const FnDesc& f, const typename Model::Prep& prep_in,
                                         bool active, GroupLds& lds, bool fast = false,
                                         unsigned rmask = 0u, bool bgrec = false) {
@@ -398,7 +439,9 @@ __device__ __forceinline__ double sweep(const FnDesc& f, const typename Model::P
   static_assert(kTilePoints == 2 * kThreads, "one double2 per thread per array per tile");
   const int l = lane_id();
   const int w = wave_in_group();
-  const int64_t nt = f.n_tiles;
+  // The tile plan (see sweep_yw): tile and window counts as 32-bit scalars, so that the loop's
+  // own tests are scalar compares; tile byte offsets stay 64-bit (tile_dma).
+  const int nt = (int)f.n_tiles;
   double acc0 = 0.0, acc1 = 0.0;
 #ifdef MHX_EARLY_REJECT
   // EXACT EARLY REJECTION (programs compiled at run time with -DMHX_EARLY_REJECT: the engine asks
@@ -422,7 +465,7 @@ __device__ __forceinline__ double sweep(const FnDesc& f, const typename Model::P
   // formed per window and the recurrence seeded at its start, so both families evaluate the same
   // expressions in the same order and give the same bits.
   constexpr int kTPW = kPadPoints / kTilePoints;
-  const int64_t nw = (nt + kTPW - 1) / kTPW;
+  const int nw = (nt + kTPW - 1) / kTPW;
   unsigned tile_masks = ~0u;  // lane i: which peaks window (wi & ~63) + i needs (PeaksModel::tile_mask)
   // (REC) the peaks' running g, r live from one seed to the next: across the sections of a
   // window, or within a section
@@ -469,7 +512,7 @@ __device__ __forceinline__ double sweep(const FnDesc& f, const typename Model::P
   if (solo && !have) __syncthreads();
   MHX_TIM(lds, 2);
   if (!have) {
-    tile_dma<NARR>(f, 0, lds, 0, w);
+    tile_dma<NARR, SB>(f, 0, lds, 0, w);
     // An LDS-DMA is ordered for the readers only by the ISSUING wave's vmcnt wait followed by a
     // barrier: written out here, never left to the compiler's handling of __syncthreads().
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -482,25 +525,25 @@ __device__ __forceinline__ double sweep(const FnDesc& f, const typename Model::P
   MHX_TIM(lds, 3);
   // Between the two tiles of a window (8-wave family): everybody is through with tile `tcur`
   // and the next one has landed; the buffer just read takes the tile after that.
-  auto mid_hook = [&](int64_t tcur, int bufc) {
+  auto mid_hook = [&](int tcur, int bufc) {
 #ifndef MHX_NO_TILE_PRIO
     __builtin_amdgcn_s_setprio(0);
 #endif
     if (have) return;  // (a resident window: both its tiles are where an earlier sweep put them)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (tcur + 2 < nt) tile_dma<NARR>(f, tcur + 2, lds, bufc, w);
+    if (tcur + 2 < nt) tile_dma<NARR, SB>(f, tcur + 2, lds, bufc, w);
   };
   // One pass of this loop is one WINDOW: a tile of the 16-wave family, two tiles of the 8-wave
   // family (which then always finds the window's first tile in buffer 0, its second in buffer 1).
-  for (int64_t t = 0; t < nt; t += kTPW) {
-    const int buf = (int)(t & 1);
-    const int64_t wi = t / kTPW;  // the window
+  for (int t = 0; t < nt; t += kTPW) {
+    const int buf = t & 1;
+    const int wi = t / kTPW;  // the window
     constexpr bool wstart = true;
     (void)wi;
     // buffer buf^1 was last read in tile t-1, which every wave left through the barrier; (two
     // tiles per window: tile t itself was sent for by the previous window's mid_hook)
-    if (t + 1 < nt && !have) tile_dma<NARR>(f, t + 1, lds, buf ^ 1, w);
+    if (t + 1 < nt && !have) tile_dma<NARR, SB>(f, t + 1, lds, buf ^ 1, w);
     // Which Gaussian peaks this window needs (those that cannot change any of its sums by even
     // one bit are left out: PeaksModel::tile_mask; exact, so the results do not depend on it),
     // and whether the window can take the table exp: decided per WINDOW for such models, so one
@@ -510,7 +553,7 @@ __device__ __forceinline__ double sweep(const FnDesc& f, const typename Model::P
     if constexpr (model_has_skip<Model>::value && model_has_fast<Model>::value) {
       // the words of 64 consecutive windows are worked out at once, lane i taking window wi + i
       if (wstart && (wi & 63) == 0) {
-        const int64_t ti = wi + l < nw ? wi + l : nw - 1;
+        const int ti = wi + l < nw ? wi + l : nw - 1;
         tile_masks = Model::tile_mask(prep, f.txlo[ti], f.txhi[ti]);
       }
       const unsigned tw = (unsigned)__builtin_amdgcn_readlane((int)tile_masks, (int)(wi & 63));
@@ -521,7 +564,7 @@ __device__ __forceinline__ double sweep(const FnDesc& f, const typename Model::P
     if constexpr (kWinGrid) {
       if (wgrid) {
         if ((wi & 63) == 0) {
-          const int64_t ti = wi + l < nw ? wi + l : nw - 1;
+          const int ti = wi + l < nw ? wi + l : nw - 1;
           win_h = f.tgh[ti];
         }
         const double hw = readlane_f64(win_h, (int)(wi & 63));
@@ -562,7 +605,7 @@ __device__ __forceinline__ double sweep(const FnDesc& f, const typename Model::P
       const double* ty = lds.tiles[buf][1];
       const double* tw = lds.tiles[buf][2];
       const double* tc = lds.tiles[buf][3];
-      const int64_t gbase = t * kTilePoints;
+      const int64_t gbase = (int64_t)t * kTilePoints;
       // One tile.  `mk` is the set of Gaussian peaks to evaluate: a run-time value, or a CMask<M>
       // whose value is a compile-time constant once the lambda is inlined - the per-peak tests
       // in PeaksModel::eval then fold away and each variant is straight-line code.
@@ -600,7 +643,10 @@ __device__ __forceinline__ double sweep(const FnDesc& f, const typename Model::P
         // points of this tile that are data (the rest are neutral pads): short datasets such as
         // test.lisp's 334 points leave most of their only tile unused
         constexpr int kWinPoints = kTPW * kTilePoints;
-        const int nv = (int)((f.n - gbase) < (int64_t)kWinPoints ? (f.n - gbase) : (int64_t)kWinPoints);
+        static_assert(kWinPoints == kPadPoints, "a pass of the tile loop is a window");
+        // only the last window can be ragged (n_tiles = ceil(n / tile points)); its count is
+        // formed where it is used: a scalar less to carry through the loops of the many-peak models
+        const int nv = wi + 1 < nw ? kWinPoints : (int)(f.n - (int64_t)(nw - 1) * kWinPoints);
         RecState rs_tile;
         (void)rs_tile;
         // the sections of the window: NSEC per tile; the second tile of a window sits one buffer on
@@ -1073,12 +1119,12 @@ struct GenericSpec {
     typename Model::Prep prep = model_prepare<Model>(pf, f, lds.prm[wave_in_group()]);
     switch (f.lik) {
       case MHX_LIK_NORMAL:
-        return finish_lik<MHX_LIK_NORMAL>(f, sweep<Model, MHX_LIK_NORMAL>(f, prep, active, lds));
+        return finish_lik<MHX_LIK_NORMAL>(f, sweep<Model, MHX_LIK_NORMAL, false, false>(f, prep, active, lds));
       case MHX_LIK_NORMAL_CUTOFF:
         return finish_lik<MHX_LIK_NORMAL_CUTOFF>(
-            f, sweep<Model, MHX_LIK_NORMAL_CUTOFF>(f, prep, active, lds));
+            f, sweep<Model, MHX_LIK_NORMAL_CUTOFF, false, false>(f, prep, active, lds));
       default:
-        return finish_lik<MHX_LIK_POISSON>(f, sweep<Model, MHX_LIK_POISSON>(f, prep, active, lds));
+        return finish_lik<MHX_LIK_POISSON>(f, sweep<Model, MHX_LIK_POISSON, false, false>(f, prep, active, lds));
     }
   }
   // one model with ONE likelihood: what run-time compiled problems use (mhx_rtc.cpp knows both)
@@ -1095,12 +1141,12 @@ struct GenericSpec {
     __builtin_amdgcn_wave_barrier();
     switch (f.lik) {
       case MHX_LIK_NORMAL:
-        return finish_lik<MHX_LIK_NORMAL>(f, sweep<Model, MHX_LIK_NORMAL>(f, prep, active, lds));
+        return finish_lik<MHX_LIK_NORMAL>(f, sweep<Model, MHX_LIK_NORMAL, false, false>(f, prep, active, lds));
       case MHX_LIK_NORMAL_CUTOFF:
         return finish_lik<MHX_LIK_NORMAL_CUTOFF>(
-            f, sweep<Model, MHX_LIK_NORMAL_CUTOFF>(f, prep, active, lds));
+            f, sweep<Model, MHX_LIK_NORMAL_CUTOFF, false, false>(f, prep, active, lds));
       default:
-        return finish_lik<MHX_LIK_POISSON>(f, sweep<Model, MHX_LIK_POISSON>(f, prep, active, lds));
+        return finish_lik<MHX_LIK_POISSON>(f, sweep<Model, MHX_LIK_POISSON, false, false>(f, prep, active, lds));
     }
   }
   template <class PF>
