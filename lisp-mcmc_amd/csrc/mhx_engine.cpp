@@ -20,6 +20,7 @@
 #include <memory>
 
 #include "mhx_ensemble.hpp"
+#include "mhx_finalize.hpp"
 #include "mhx_launch.hpp"
 #include "mhx_plan.hpp"
 #include "mhx_rtc.hpp"
@@ -329,28 +330,6 @@ void drain(mhx_engine* e) {
   if (hipSetDevice(e->device) == hipSuccess && e->stream) (void)hipStreamSynchronize(e->stream);
 }
 
-// The C++ type (csrc/mhx_device.hpp) that evaluates function f with everything about its shape
-// known at compile time, or "" when the shape is too big for scalar registers.
-std::string builtin_model_type(const FnDesc& f) {
-  switch (f.model) {
-    case MHX_MODEL_POLY:
-      if (f.n_idx >= 1 && f.n_idx <= 16) return "PolyModel<" + std::to_string(f.n_idx) + ">";
-      return "";
-    case MHX_MODEL_GAUSS_PEAKS:
-    case MHX_MODEL_LORENTZ_PEAKS: {
-      const int nbg = f.shape[0], npk = f.shape[1];
-      if (npk < 1 || npk > 6 || nbg < 0 || nbg > 4) return "";
-      return "PeaksModel<" + std::to_string(nbg) + ", " + std::to_string(npk) + ", " +
-             (f.model == MHX_MODEL_LORENTZ_PEAKS ? "true" : "false") + ">";
-    }
-    case MHX_MODEL_LORDER_MIXED: return "LorderModel";
-    case MHX_MODEL_EXP_DECAY: return "ExpDecayModel";
-    case MHX_MODEL_SINUSOID: return "SinusoidModel";
-    case MHX_MODEL_PVOIGT2: return "PVoigt2Model";
-    default: return "";
-  }
-}
-
 // The slice table of the tile-sliced split mode: function k, slice s = windows [s per_k,
 // (s + 1) per_k) of its dataset, as a FnDesc of its own (what k_split_tsweep hands to sweep()).
 int build_ts_table(mhx_engine* e, int ts) {
@@ -394,304 +373,180 @@ int build_ts_table(mhx_engine* e, int ts) {
   return MHX_OK;
 }
 
+// one of a dataset's per-window tables (mhx_finalize.hpp), on the device
+int upload_table(DevBuf<double>& buf, const std::vector<double>& tab, int k, const char* what) {
+  if (buf.alloc(tab.size(), false) != hipSuccess)
+    return fail(MHX_ENOMEM, "hipMalloc of dataset %d's %s failed", k, what);
+  HIP_TRY(hipMemcpy(buf.p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
+  return MHX_OK;
+}
+
+// The split modes' partial sums and the persistent kernels' handshake blocks, for the launch form
+// that was planned.
+int alloc_split_buffers(mhx_engine* e) {
+  e->S.split_slots = e->tsplit ? e->split_slices : e->split_slices * e->fam->waves_per_group;
+  e->S.split_part = nullptr;
+  if (e->tsplit) {
+    const int rc = build_ts_table(e, e->split_slices);
+    if (rc != MHX_OK) return rc;
+  }
+  HIP_TRY(hipMemset(e->split_pending.p, 0, (size_t)e->cfg.n_chains * sizeof(int32_t)));
+  if (e->split_slices == 0) return MHX_OK;
+  // (tile-sliced: room for the most slices a later re-slicing may take - compact_tsplit)
+  const size_t slots_max = e->tsplit ? (size_t)std::max<int64_t>(e->S.split_slots, std::min<int64_t>(e->shape.nwin, 512))
+                                     : (size_t)e->S.split_slots;
+  const size_t np = (size_t)e->cfg.n_chains * e->P.K * slots_max;
+  if (e->split_part.alloc(np) != hipSuccess)
+    return fail(MHX_ENOMEM, "hipMalloc of the split-mode partial sums failed");
+  e->S.split_part = e->split_part.p;
+  if (e->persist) {  // (the handshake blocks of the persistent kernels: mhx_types.hpp)
+    const size_t nm = 64 * (size_t)e->cfg.n_chains;
+    const size_t npb = 16 * np;
+    if ((e->persist_msg.n < nm && e->persist_msg.alloc(nm) != hipSuccess) ||
+        (e->persist_part.n < npb && e->persist_part.alloc(npb) != hipSuccess))
+      return fail(MHX_ENOMEM, "hipMalloc of the persistent kernel's handshake buffers failed");
+    if (!e->persist_error.p && e->persist_error.alloc(1) != hipSuccess)
+      return fail(MHX_ENOMEM, "hipMalloc of the persistent kernel's error word failed");
+    e->S.persist_msg = e->persist_msg.p;
+    e->S.persist_part = e->persist_part.p;
+    e->S.persist_error = e->persist_error.p;
+  }
+  return MHX_OK;
+}
+
+// Every rule below is a function of mhx_finalize.hpp or mhx_plan.hpp; what is done here is the
+// allocating, uploading and compiling between them.
 int finalize_problem(mhx_engine* e) {
   if (!e->problem_dirty) return MHX_OK;
   e->knobs = read_knobs();
   const EngineKnobs& kn = e->knobs;
+  ProblemDesc& P = e->P;
   drop_split_graph(e);
   // a new problem may run in another mode and family: slot s is chain s until the next deal
   e->S.slot_chain = nullptr;
   e->S.n_slots = e->cfg.n_chains;
   e->slots_mapped = 0;
-  for (int k = 0; k < e->P.K; ++k) {
-    if (!e->fn_set[k]) return fail(MHX_ESTATE, "function %d was never set (mhx_set_function)", k);
-    if (!e->data[k].set) return fail(MHX_ESTATE, "dataset %d was never set (mhx_set_dataset)", k);
+  // 1. is everything there
+  const bool pooled = e->cfg.adapt_mode == MHX_ADAPT_POOLED;
+  FnInput in[MHX_MAX_FUNCTIONS];
+  for (int k = 0; k < P.K; ++k) {
+    in[k].fn_set = e->fn_set[k];
+    in[k].data_set = e->data[k].set;
+    in[k].planes = e->data[k].planes;
+    in[k].expr = &e->fn_expr[k];
+    in[k].recog = &e->fn_recog[k];
+    in[k].prior_expr = !e->prior_expr[k].expr.empty();
+    in[k].lik_expr = !e->lik_expr[k].empty();
   }
-  // the kernel family fixes the tile size and with it the tiles per dataset; the x ranges that
-  // tile-level peak skipping tests against (PeaksModel::tile_mask) are those of WINDOWS of
-  // kPadPoints points, pads included, whatever the family (sweep: one mask and one seeding of the
-  // Gaussian recurrence per window)
+  if (Refusal r = validate_problem(P, in, pooled)) return fail(r.code, "%s", r.msg.c_str());
+  // 2. the shape the mode rules read, and the kernel family: it fixes the tile size and with it
+  // the tiles per dataset
   ProblemShape& sh = e->shape;
   sh = ProblemShape{};
-  for (int k = 0; k < e->P.K; ++k) sh.longest = std::max<int64_t>(sh.longest, e->P.fn[k].n);
+  for (int k = 0; k < P.K; ++k) {
+    sh.longest = std::max<int64_t>(sh.longest, P.fn[k].n);
+    sh.planes = sh.planes || in[k].planes;
+  }
   sh.nwin = ceil_div(sh.longest, kPadPoints);
-  sh.K = e->P.K;
-  sh.d = e->P.d;
+  sh.K = P.K;
+  sh.d = P.d;
   sh.chains = e->cfg.n_chains;
-  sh.pooled = e->cfg.adapt_mode == MHX_ADAPT_POOLED;
+  sh.pooled = pooled;
   sh.persist_off = e->persist_off;
   sh.cus = e->cus;
-  // a dataset per walker: what it cannot be combined with, by name
-  int n_planes = 0;
-  for (int k = 0; k < e->P.K; ++k) n_planes += e->data[k].planes ? 1 : 0;
-  sh.planes = n_planes > 0;
-  if (sh.planes) {
-    if (sh.pooled)
-      return fail(MHX_EUNSUPPORTED, "a dataset per walker (mhx_set_dataset_planes) with "
-                                    "MHX_ADAPT_POOLED: one pooled covariance assumes one posterior");
-    for (int k = 0; k < e->P.K; ++k)
-      if (e->P.fn[k].n_xcols > 1)
-        return fail(MHX_EUNSUPPORTED, "a dataset per walker (mhx_set_dataset_planes) in a problem "
-                                      "whose dataset %d has two columns of x (mhx_set_dataset_cols)", k);
-  }
   e->fam = choose_family(sh, kn) == 16 ? &family_w16() : &family_w8();
   sh.waves_per_group = e->fam->waves_per_group;
   sh.tile_points = e->fam->tile_points;
-  const size_t tp = (size_t)e->fam->tile_points;
-  const size_t wp = (size_t)kPadPoints;
-  for (int k = 0; k < e->P.K; ++k) {
-    FnDesc& f = e->P.fn[k];
+  // 3. the windows' x ranges and grids
+  for (int k = 0; k < P.K; ++k) {
+    FnDesc& f = P.fn[k];
     Dataset& D = e->data[k];
-    const size_t nt = ((size_t)f.n + tp - 1) / tp;
-    const size_t ntp = std::max<size_t>(((size_t)f.n + wp - 1) / wp, 1);
-    std::vector<double> tlo(ntp), thi(ntp);
-    for (size_t t = 0; t < ntp; ++t) {
-      double lo = INFINITY, hi = -INFINITY;
-      bool ok = true;
-      for (size_t i = t * wp; i < (t + 1) * wp; ++i) {
-        ok = ok && std::isfinite(D.hx[i]);
-        lo = std::min(lo, D.hx[i]);
-        hi = std::max(hi, D.hx[i]);
-      }
-      tlo[t] = ok ? lo : -INFINITY;
-      thi[t] = ok ? hi : INFINITY;
-    }
-    if (D.txlo.alloc(ntp, false) != hipSuccess || D.txhi.alloc(ntp, false) != hipSuccess)
-      return fail(MHX_ENOMEM, "hipMalloc of dataset %d's tile ranges failed", k);
-    HIP_TRY(hipMemcpy(D.txlo.p, tlo.data(), ntp * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(D.txhi.p, thi.data(), ntp * sizeof(double), hipMemcpyHostToDevice));
+    std::vector<double> lo, hi, gh;
+    window_ranges(D.hx.data(), D.n, &lo, &hi);
+    int rc = upload_table(D.txlo, lo, k, "tile ranges");
+    if (rc == MHX_OK) rc = upload_table(D.txhi, hi, k, "tile ranges");
+    if (rc != MHX_OK) return rc;
     f.txlo = D.txlo.p;
     f.txhi = D.txhi.p;
-    f.n_tiles = (int64_t)nt;
-    // Per-window grids.  A dataset that is not ONE grid (grid_H == 0) may still be a grid window
-    // by window - concatenated scans, a re-gridded stretch, one jittered region: window w gets
-    // H_w = 64 h when its data points are x_first + i h to 8 ulp of the window's max |x| - first
-    // tried with the previous grid window's h, so that runs of windows on one grid carry the SAME
-    // bits (the kernel re-derives its constants only where H changes: PeaksModel::regrid), then
-    // with its own h = (x_last - x_first) / (points - 1) - and 0 otherwise (direct form there).
-    // MHX_NO_WINDOW_GRIDS=1: off (round 3's rule: one grid or none).
+    f.n_tiles = ceil_div(f.n, e->fam->tile_points);
+    // (a dataset that is ONE grid needs no table; MHX_NO_WINDOW_GRIDS=1: round 3's rule, one
+    // grid or none)
     f.tgh = nullptr;
-    if (f.grid_H == 0.0 && !D.no_rec && !kn.no_window_grids && D.n >= 2) {
-      std::vector<double> gh(ntp, 0.0);
-      double h_prev = 0.0;
-      bool any = false;
-      for (size_t t = 0; t < ntp; ++t) {
-        const size_t i0 = t * wp, cnt = std::min(wp, D.n > i0 ? D.n - i0 : 0);
-        if (cnt < 2) continue;
-        const double* xw = &D.hx[i0];
-        if (!std::isfinite(xw[0]) || !std::isfinite(xw[cnt - 1])) continue;
-        const double tol = 8.0 * 0x1p-52 * std::max(std::fabs(xw[0]), std::fabs(xw[cnt - 1]));
-        auto fits = [&](double h) {
-          if (h == 0.0 || !std::isfinite(h)) return false;
-          for (size_t i = 0; i < cnt; ++i)
-            if (!(std::fabs(xw[i] - (xw[0] + (double)i * h)) <= tol)) return false;
-          return true;
-        };
-        double h = h_prev;
-        if (!fits(h)) h = (xw[cnt - 1] - xw[0]) / (double)(cnt - 1);
-        if (!fits(h)) continue;
-        gh[t] = 64.0 * h;
-        h_prev = h;
-        any = true;
-      }
-      if (any) {
-        if (D.tgh.alloc(ntp, false) != hipSuccess)
-          return fail(MHX_ENOMEM, "hipMalloc of dataset %d's window grids failed", k);
-        HIP_TRY(hipMemcpy(D.tgh.p, gh.data(), ntp * sizeof(double), hipMemcpyHostToDevice));
-        f.tgh = D.tgh.p;
-      }
+    if (f.grid_H == 0.0 && !D.no_rec && !kn.no_window_grids && window_grids(D.hx.data(), D.n, &gh)) {
+      rc = upload_table(D.tgh, gh, k, "window grids");
+      if (rc != MHX_OK) return rc;
+      f.tgh = D.tgh.p;
     }
     // the one tile stays in LDS (sweep).  Measured (tools/ab_tree.sh, test.lisp's shape): +9 %
     // with one chain, -5 % with 512 and -15 % with 2048 chains: only the single-walker case, the
-    // reference's own way of working, gets it
-    f.solo = (e->P.K == 1 && nt == 1 && e->cfg.n_chains <= e->fam->waves_per_group) ? 1 : 0;
-    if (D.planes) {  // (no per-window grids, no resident tile: a sweep of its own, planes_loglik)
-      f.tgh = nullptr;
-      f.solo = 2;
-    }
+    // reference's own way of working, gets it.  (A dataset per walker: no resident tile, a sweep
+    // of its own, planes_loglik.)
+    f.solo = D.planes ? 2 : (P.K == 1 && f.n_tiles == 1 && e->cfg.n_chains <= e->fam->waves_per_group) ? 1 : 0;
   }
-  // ... resident in the tile buffers or streamed (mhx_plan.hpp: planes_resident), one decision for
-  // the problem; the layout of GroupLds::tiles follows the functions' order
+  // 4. a dataset per walker: resident in the tile buffers or streamed, and where
   bool planes_res = false;
   if (sh.planes) {
-    int64_t pn[MHX_MAX_FUNCTIONS];
-    int pk[MHX_MAX_FUNCTIONS];
-    int np_ = 0;
-    for (int k = 0; k < e->P.K; ++k)
-      if (e->data[k].planes) {
-        pn[np_] = e->P.fn[k].n;
-        pk[np_++] = e->data[k].sigma_kind;
-      }
-    planes_res = planes_resident(pn, pk, np_, e->P.K, e->fam->waves_per_group, kn);
-    int64_t off = 0;
-    for (int k = 0; k < e->P.K; ++k) {
+    PlanesFn pf[MHX_MAX_FUNCTIONS];
+    PlanesLayout pl[MHX_MAX_FUNCTIONS];
+    for (int k = 0; k < P.K; ++k) pf[k] = PlanesFn{in[k].planes, P.fn[k].n, e->data[k].sigma_kind};
+    planes_res = planes_layout(pf, P.K, e->fam->waves_per_group, kn, pl);
+    for (int k = 0; k < P.K; ++k) {
       Dataset& D = e->data[k];
       if (!D.planes) continue;
-      PlaneDesc& pd = D.pd;
-      pd.resident = planes_res ? 1 : 0;
-      pd.bit = 1 << k;
-      pd.off_x = pd.off_w = pd.off_rows = pd.row_stride = 0;
-      if (planes_res) {
-        pd.off_x = (int32_t)off;
-        pd.off_w = (int32_t)(off + pd.pitch);
-        off += planes_shared_doubles(e->P.fn[k].n, D.sigma_kind);
-        pd.off_rows = (int32_t)off;
-        pd.row_stride = (int32_t)planes_wave_doubles(e->P.fn[k].n, D.sigma_kind);
-        off += (int64_t)e->fam->waves_per_group * pd.row_stride;
-      }
-      HIP_TRY(hipMemcpy(D.pdesc.p, &pd, sizeof(PlaneDesc), hipMemcpyHostToDevice));
-      e->P.fn[k].c = reinterpret_cast<const double*>(D.pdesc.p);
+      D.pd.resident = pl[k].resident;
+      D.pd.bit = pl[k].bit;
+      D.pd.off_x = pl[k].off_x;
+      D.pd.off_w = pl[k].off_w;
+      D.pd.off_rows = pl[k].off_rows;
+      D.pd.row_stride = pl[k].row_stride;
+      HIP_TRY(hipMemcpy(D.pdesc.p, &D.pd, sizeof(PlaneDesc), hipMemcpyHostToDevice));
+      P.fn[k].c = reinterpret_cast<const double*>(D.pdesc.p);
     }
   }
-  // MHX_NO_TILE_SKIP=1: evaluate every Gaussian peak at every point (the skipping is exact, so
-  // this only exists to show that the results do not change)
-  const int tile_skip = kn.no_tile_skip ? 0 : 1;
-  bool any_expr = false;
-  // MHX_NO_RECOGNISE=1: every expression compiled as written (A/B runs; bench.py --workload c2expr)
-  const bool recognise = e->recognise && !kn.no_recognise;
-  for (int k = 0; k < e->P.K; ++k) {
-    FnDesc& f = e->P.fn[k];
-    f.user_slot = f.prior_slot = -1;
-    f.tile_skip = tile_skip;
-    if (!e->fn_expr[k].expr.empty()) {
-      // A function given as an expression: a body that IS polynomial background + Gaussian /
-      // Lorentzian peaks runs as that enumerated model (same gather map, permuted into the
-      // model's order), unless its likelihood is an expression too (which reads `model` from
-      // an expression model) or recognition is off.  Decided here, not in
-      // mhx_set_function_expr: the dataset's likelihood may be set before or after.
-      const UserExpr& u = e->fn_expr[k];
-      const RecognisedModel& r = e->fn_recog[k];
-      if (recognise && r.model >= 0 && f.lik != MHX_LIK_EXPR) {
-        f.model = r.model;
-        f.n_idx = (int)r.order.size();
-        for (int j = 0; j < f.n_idx; ++j) f.idx[j] = u.index[(size_t)r.order[(size_t)j]];
-        f.shape[0] = r.shape[0];
-        f.shape[1] = r.shape[1];
-      } else {
-        f.model = MHX_MODEL_EXPR;
-        f.n_idx = (int)u.index.size();
-        for (int j = 0; j < f.n_idx; ++j) f.idx[j] = u.index[(size_t)j];
-        f.shape[0] = f.shape[1] = 0;
-      }
-    }
-    // MHX_NO_YW=1: the shared-tile layout with x for every step (A/B runs; same bits either way)
-    f.no_yw = kn.no_yw ? 1 : 0;
-    if (f.lik == MHX_LIK_EXPR) {
-      if (e->lik_expr[k].empty())
-        return fail(MHX_ESTATE, "dataset %d uses MHX_LIK_EXPR but mhx_set_likelihood_expr was "
-                                "never called for it", k);
-      if (f.model != MHX_MODEL_EXPR)
-        return fail(MHX_EUNSUPPORTED, "function %d: an expression likelihood needs an expression "
-                                      "model (mhx_set_function_expr)", k);
-    }
-    if (f.model == MHX_MODEL_EXPR && e->fn_expr[k].xcols > f.n_xcols)
-      return fail(MHX_ESTATE, "function %d reads xcol1 but dataset %d has one column of x "
-                              "(mhx_set_dataset_cols)", k, k);
-    any_expr = any_expr || f.model == MHX_MODEL_EXPR || !e->prior_expr[k].expr.empty();
-    sh.heavy = sh.heavy || f.lik == MHX_LIK_POISSON || f.lik == MHX_LIK_EXPR ||
-               f.model == MHX_MODEL_PVOIGT2 || f.model == MHX_MODEL_EXPR;
-  }
-  // Which kernels: an ahead-of-time specialisation if the problem matches one; otherwise kernels
-  // compiled at run time (hiprtc) in which EVERY function - expression or enumerated model - gets
-  // its own compile-time specialisation (parameters in SGPRs, fast exp path, tile-level peak
-  // skipping): 2.4-2.8x the run-time-dispatched generic kernels on configs 2 and 3.  The generic
-  // kernels remain for MHX_FORCE_GENERIC=1 / MHX_NO_RTC_SPECIALISE=1 and for machines without
-  // hiprtc.
+  // 5. what the expressions run as; the switches the kernels read.  MHX_NO_TILE_SKIP=1: every
+  // Gaussian peak at every point (the skipping is exact, so this only exists to show that the
+  // results do not change); MHX_NO_YW=1: the shared-tile layout with x for every step;
   // MHX_NO_DEAL=1: every wave judges its own chain's proposal (A/B runs; same bits either way)
-  e->P.no_deal = kn.no_deal ? 1 : 0;
-  e->P.test_lose_sweepers = 0;
+  for (int k = 0; k < P.K; ++k) {
+    P.fn[k].tile_skip = kn.no_tile_skip ? 0 : 1;
+    P.fn[k].no_yw = kn.no_yw ? 1 : 0;
+  }
+  P.no_deal = kn.no_deal ? 1 : 0;
+  P.test_lose_sweepers = 0;
 #ifdef MHX_DEBUG_HOOKS  // (tests/hooks/libmhx_hooks.so: a persistent launch whose sweepers never come)
-  e->P.test_lose_sweepers = kn.test_lose_sweepers ? 1 : 0;
+  P.test_lose_sweepers = kn.test_lose_sweepers ? 1 : 0;
 #endif
-  const bool force_generic = kn.force_generic;
-  const bool specialise = !kn.no_rtc_specialise && !force_generic;
-  // a function with a per-window grid table needs the kernel instance that follows it
-  // (FixedSpec<Model, LIK, true>, mhx_kernels.hpp): compiled at run time, like every problem
-  // without an ahead-of-time kernel - the ahead-of-time ones stay what they were
-  bool any_wgrid = false;
-  for (int k = 0; k < e->P.K; ++k) {
-    FnDesc& f = e->P.fn[k];
-    const bool can = specialise && !e->data[k].planes && f.tgh != nullptr && f.model == MHX_MODEL_GAUSS_PEAKS &&
-                     f.shape[0] >= 1 && f.shape[0] <= 2 && f.shape[1] >= 1 && f.shape[1] <= 6 &&
-                     f.lik != MHX_LIK_EXPR;
-    if (!can) f.tgh = nullptr;  // (nobody would read it: the direct form everywhere, as before)
-    any_wgrid = any_wgrid || can;
-  }
-  // MHX_EARLY_REJECT=1: sweep()'s exact early rejection (mhx_kernels.hpp) for a problem of ONE
-  // function of a bounded enumerated model (peaks, polynomial: no term of theirs overflows at
-  // finite parameters) with the weighted normal likelihood and no prior body - compiled at run
-  // time too, so that the ahead-of-time kernels do not carry the test (4-5 % in a walk's first
-  // iterations even when it never fires)
-  const FnDesc& f0 = e->P.fn[0];
-  const bool any_er = kn.early_reject && specialise && e->P.K == 1 && f0.lik == MHX_LIK_NORMAL &&
-                      (f0.model == MHX_MODEL_GAUSS_PEAKS || f0.model == MHX_MODEL_LORENTZ_PEAKS ||
-                       f0.model == MHX_MODEL_POLY) &&
-                      e->prior_expr[0].expr.empty() && !builtin_model_type(f0).empty() &&
-                      e->cfg.adapt_mode != MHX_ADAPT_POOLED && !sh.planes;
-  // a dataset per walker has its sweep in programs compiled at run time only (MHX_PLANES)
-  const bool any_planes = sh.planes;
-  const int aot = (any_expr || any_wgrid || any_er || any_planes) ? SPEC_GENERIC : select_spec(e->P);
+  if (Refusal r = resolve_functions(P, in, e->recognise && !kn.no_recognise)) return fail(r.code, "%s", r.msg.c_str());
+  sh.heavy = heavy_problem(P);
+  // 6. which kernels
+  bool has_tgh[MHX_MAX_FUNCTIONS];
+  for (int k = 0; k < P.K; ++k) has_tgh[k] = P.fn[k].tgh != nullptr;
+  KernelChoice choice = choose_kernels(P, in, has_tgh, pooled, kn);
+  // 7. the program compiled at run time, or - enumerated models only - the generic kernels
+  // instead (no hiprtc on this machine?)
   e->rtc_note.clear();
-  HIP_TRY(hipMemcpy(e->dP.p, &e->P, sizeof(ProblemDesc), hipMemcpyHostToDevice));
-  if (!any_expr && !any_wgrid && !any_er && !any_planes && (aot != SPEC_GENERIC || !specialise)) {
-    e->spec = force_generic ? SPEC_GENERIC : aot;
-    e->user_prog.reset();
-  } else {
-    std::vector<UserExpr> models, priors;
-    bool builtin = false;
-    for (int k = 0; k < e->P.K; ++k) {
-      FnDesc& f = e->P.fn[k];
-      if (f.model == MHX_MODEL_EXPR) {
-        f.user_slot = (int)models.size();
-        models.push_back(e->fn_expr[k]);
-        models.back().lik = f.lik;
-        models.back().planes = e->data[k].planes;
-        if (f.lik == MHX_LIK_EXPR) models.back().lik_expr = e->lik_expr[k];
-      } else {
-        const std::string type = specialise ? builtin_model_type(f) : std::string();
-        if (type.empty() && e->data[k].planes) {  // (the run-time dispatch, on planes)
-          f.user_slot = (int)models.size();
-          UserExpr u;
-          u.lik = f.lik;
-          u.planes = u.dispatch = true;
-          models.push_back(u);
-        } else if (!type.empty()) {
-          f.user_slot = (int)models.size();
-          UserExpr u;
-          u.builtin = type;
-          u.lik = f.lik;
-          u.wgrid = f.tgh != nullptr;
-          u.planes = e->data[k].planes;
-          u.early_reject = any_er;
-          models.push_back(u);
-        } else {
-          builtin = true;  // stays with the generic dispatcher inside the compiled kernels
-        }
-      }
-      if (!e->prior_expr[k].expr.empty()) {
-        f.prior_slot = (int)priors.size();
-        priors.push_back(e->prior_expr[k]);
-      }
-    }
-    HIP_TRY(hipMemcpy(e->dP.p, &e->P, sizeof(ProblemDesc), hipMemcpyHostToDevice));
+  std::shared_ptr<UserProgram> prog;
+  if (choice.rtc) {
+    std::vector<UserExpr> priors;
+    for (int k = 0; k < P.K; ++k)
+      if (choice.fn[k].prior_slot >= 0) priors.push_back(e->prior_expr[k]);
     std::string err;
-    std::shared_ptr<UserProgram> prog =
-        rtc_get(models, priors, builtin, want_split(sh, kn, !builtin), *e->fam, &err);
-    if (prog) {
-      e->user_prog = prog;
-      e->spec = SPEC_USER;
-    } else if (any_expr || any_planes) {
-      return fail(MHX_EUNSUPPORTED, "%s%s", any_planes ? "a dataset per walker needs kernels compiled at run time: " : "",
+    prog = rtc_get(program_models(choice, e->fn_expr, e->lik_expr), priors, choice.builtin_fallback,
+                   want_split(sh, kn, !choice.builtin_fallback), *e->fam, &err);
+    if (!prog && choice.compile_required)
+      return fail(MHX_EUNSUPPORTED, "%s%s", sh.planes ? "a dataset per walker needs kernels compiled at run time: " : "",
                   err.c_str());
-    } else {  // enumerated models only: the generic kernels serve (no hiprtc on this machine?)
+    if (!prog) {
       e->rtc_note = err.substr(0, err.find('\n'));
-      for (int k = 0; k < e->P.K; ++k) e->P.fn[k].user_slot = -1;
-      HIP_TRY(hipMemcpy(e->dP.p, &e->P, sizeof(ProblemDesc), hipMemcpyHostToDevice));
-      e->user_prog.reset();
-      e->spec = SPEC_GENERIC;
+      fall_back_to_generic(&choice);
     }
   }
-  // the launch form (mhx_plan.hpp), then its tables and buffers
+  e->user_prog = prog;
+  e->spec = choice.rtc ? SPEC_USER : choice.spec;
+  // 8. the problem as the kernels read it
+  apply_choice(choice, &P);
+  HIP_TRY(hipMemcpy(e->dP.p, &P, sizeof(ProblemDesc), hipMemcpyHostToDevice));
+  // 9. the launch form (mhx_plan.hpp) ...
   sh.capable = e->spec == SPEC_USER ? e->user_prog->has_split : e->fam->split_capable(e->spec);
   if (sh.capable) {
     for (int ts = 0; ts < 2; ++ts)
@@ -703,57 +558,11 @@ int finalize_problem(mhx_engine* e) {
   e->split_slices = plan.split_slices;
   e->persist = plan.persist;
   e->ts_initial = plan.ts_initial;
-  e->S.split_slots = e->tsplit ? e->split_slices : e->split_slices * e->fam->waves_per_group;
-  e->S.split_part = nullptr;
-  if (e->tsplit) {
-    const int rc = build_ts_table(e, e->split_slices);
-    if (rc != MHX_OK) return rc;
-  }
-  HIP_TRY(hipMemset(e->split_pending.p, 0, (size_t)e->cfg.n_chains * sizeof(int32_t)));
-  if (e->split_slices > 0) {
-    // (tile-sliced: room for the most slices a later re-slicing may take - compact_tsplit)
-    const size_t slots_max = e->tsplit ? (size_t)std::max<int64_t>(e->S.split_slots, std::min<int64_t>(sh.nwin, 512))
-                                       : (size_t)e->S.split_slots;
-    const size_t np = (size_t)e->cfg.n_chains * e->P.K * slots_max;
-    if (e->split_part.alloc(np) != hipSuccess)
-      return fail(MHX_ENOMEM, "hipMalloc of the split-mode partial sums failed");
-    e->S.split_part = e->split_part.p;
-    if (e->persist) {  // (the handshake blocks of the persistent kernels: mhx_types.hpp)
-      const size_t nm = 64 * (size_t)e->cfg.n_chains;
-      const size_t npb = 16 * np;
-      if ((e->persist_msg.n < nm && e->persist_msg.alloc(nm) != hipSuccess) ||
-          (e->persist_part.n < npb && e->persist_part.alloc(npb) != hipSuccess))
-        return fail(MHX_ENOMEM, "hipMalloc of the persistent kernel's handshake buffers failed");
-      if (!e->persist_error.p && e->persist_error.alloc(1) != hipSuccess)
-        return fail(MHX_ENOMEM, "hipMalloc of the persistent kernel's error word failed");
-      e->S.persist_msg = e->persist_msg.p;
-      e->S.persist_part = e->persist_part.p;
-      e->S.persist_error = e->persist_error.p;
-    }
-  }
-  // a name for what was chosen (mhx_kernel_name)
-  static const char* kLik[] = {"normal", "normal_cutoff", "poisson", "expr"};
-  e->kernel_name = "w" + std::to_string(e->fam->waves_per_group) + "/";
-  if (e->spec == SPEC_USER) {
-    e->kernel_name += "rtc[";
-    for (int k = 0; k < e->P.K; ++k) {
-      const FnDesc& f = e->P.fn[k];
-      const std::string t = f.model == MHX_MODEL_EXPR ? std::string("expr")
-                            : (f.user_slot >= 0 && !builtin_model_type(f).empty() && !(e->data[k].planes && !specialise)
-                                   ? builtin_model_type(f) + (f.tgh ? "+wgrid" : "") + (any_er ? "+early-reject" : "")
-                                   : std::string("generic"));
-      e->kernel_name += (k ? ", " : "") + t + ":" + kLik[f.lik & 3] +
-                        (e->data[k].planes ? (planes_res ? "+planes(resident)" : "+planes(streamed)") : "");
-    }
-    e->kernel_name += "]";
-  } else {
-    e->kernel_name += spec_name(e->spec);
-    if (!e->rtc_note.empty()) e->kernel_name += " [not specialised: " + e->rtc_note + "]";
-  }
-  if (e->split_slices > 0)
-    e->kernel_name += (e->tsplit ? (e->persist ? " persistent tsplit x" : " tsplit x")
-                                 : (e->persist ? " persistent split x" : " split x")) +
-                      std::to_string(e->split_slices);
+  // 10. ... its tables and buffers
+  const int rc = alloc_split_buffers(e);
+  if (rc != MHX_OK) return rc;
+  // 11. a name for what was chosen (mhx_kernel_name)
+  e->kernel_name = kernel_name(choice, e->fam->waves_per_group, planes_res, plan, e->rtc_note);
   e->problem_dirty = false;
   return MHX_OK;
 }
@@ -1554,24 +1363,15 @@ static int set_dataset_impl(mhx_engine* e, int k, const double* x, const double*
   }
   // A uniformly spaced x grid (spectra, histograms, time series: x_i = x_0 + i h) lets the
   // Gaussian peaks advance by a two-multiply recurrence instead of an exp per point
-  // (PeaksModel, csrc/mhx_device.hpp).  Accepted when every x_i is within 8 ulp of max |x| of
-  // x_0 + i h with h = (x_(n-1) - x_0) / (n - 1); MHX_NO_RECURRENCE=1 keeps the direct form.
-  f.grid_H = 0.0;
+  // (PeaksModel, csrc/mhx_device.hpp).  Accepted when the n points are a grid of step
+  // h = (x_(n-1) - x_0) / (n - 1) (mhx_finalize.hpp: grid_step); MHX_NO_RECURRENCE=1 keeps the
+  // direct form.
+  const char* nr = getenv("MHX_NO_RECURRENCE");
+  D.no_rec = nr && atoi(nr) != 0;
+  f.grid_H = D.no_rec ? 0.0 : 64.0 * grid_step(x, n);
   f.tgh = nullptr;  // (per-window grids: finalize_problem)
   f.n_xcols = x1 ? 2 : 1;
   D.n = n;
-  {
-    const char* nr = getenv("MHX_NO_RECURRENCE");
-    D.no_rec = nr && atoi(nr) != 0;
-    if (!(nr && atoi(nr) != 0) && n >= 2 && std::isfinite(x[0]) && std::isfinite(x[n - 1])) {
-      const double h = (x[n - 1] - x[0]) / (double)(n - 1);
-      const double tol = 8.0 * 0x1p-52 * std::max(std::fabs(x[0]), std::fabs(x[n - 1]));
-      bool grid = h != 0.0 && std::isfinite(h);
-      for (size_t i = 0; i < n && grid; ++i)
-        grid = std::fabs(x[i] - (x[0] + (double)i * h)) <= tol;
-      if (grid) f.grid_H = 64.0 * h;
-    }
-  }
   D.set = true;
   if (D.planes) {  // (a shared dataset replaces a dataset per walker)
     D.planes = false;

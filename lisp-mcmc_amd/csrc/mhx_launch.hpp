@@ -3,31 +3,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "mhx_finalize.hpp"
 #include "mhx_types.hpp"
 
 namespace mhx {
 
-// Compiled problem specialisations.  SPEC_GENERIC dispatches on (model, shape, likelihood) at
-// run time; the others fix one model + likelihood for all K functions so that their
-// parameters live in scalar registers and the kernel's register budget is its own.
-enum SpecId {
-  SPEC_GENERIC = 0,
-  SPEC_GAUSS22_NORMAL = 1,   // 2 background terms + 2 Gaussian peaks, weighted normal (8 params)
-  SPEC_GAUSS15_POISSON = 2,  // constant background + 5 Gaussian peaks, Poisson (16 params)
-  SPEC_PVOIGT2_NORMAL = 3,   // 11-parameter two-peak pseudo-Voigt (global fits)
-  SPEC_POLY2_NORMAL = 4,     // b + m x
-  SPEC_POLY8_NORMAL = 5,     // degree-7 polynomial
-  SPEC_LORDER_NORMAL = 6,    // test.lisp's 6-parameter lineshape
-  SPEC_GAUSS22_CUTOFF = 7,
-#ifdef MHX_AOT_G23
-  SPEC__COUNT = 9
-#else
-  SPEC__COUNT = 8
-#endif
-};
-
-int select_spec(const ProblemDesc& P);
-const char* spec_name(int spec);
+// (the compiled problem specialisations, SpecId, and their choice: mhx_finalize.hpp)
 
 // One family of kernels: everything that depends on the workgroup shape goes through this table.
 struct Family {

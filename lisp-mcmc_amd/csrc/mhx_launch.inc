@@ -503,37 +503,6 @@ hipError_t launch_fitpct_select(hipStream_t st, const ChainState& S, int64_t c0,
   return hipGetLastError();
 }
 
-const char* spec_name(int spec) {
-  static const char* names[] = {"generic",      "gauss22_normal", "gauss15_poisson",
-                                           "pvoigt2_normal", "poly2_normal",   "poly8_normal",
-                                           "lorder_normal", "gauss22_cutoff"};
-  if (spec == 8) return "gauss23_normal_aot_experiment";
-  return spec >= 0 && spec < 8 ? names[spec] : "?";
-}
-
-static bool all_fns(const ProblemDesc& P, int model, int lik, int n_idx, int s0, int s1) {
-  for (int k = 0; k < P.K; ++k) {
-    const FnDesc& f = P.fn[k];
-    if (f.model != model || f.lik != lik || f.n_idx != n_idx) return false;
-    if (s0 >= 0 && (f.shape[0] != s0 || f.shape[1] != s1)) return false;
-  }
-  return true;
-}
-
-int select_spec(const ProblemDesc& P) {
-  if (all_fns(P, MHX_MODEL_GAUSS_PEAKS, MHX_LIK_NORMAL, 8, 2, 2)) return SPEC_GAUSS22_NORMAL;
-  if (all_fns(P, MHX_MODEL_GAUSS_PEAKS, MHX_LIK_POISSON, 16, 1, 5)) return SPEC_GAUSS15_POISSON;
-  if (all_fns(P, MHX_MODEL_PVOIGT2, MHX_LIK_NORMAL, 11, -1, -1)) return SPEC_PVOIGT2_NORMAL;
-  if (all_fns(P, MHX_MODEL_POLY, MHX_LIK_NORMAL, 2, -1, -1)) return SPEC_POLY2_NORMAL;
-  if (all_fns(P, MHX_MODEL_POLY, MHX_LIK_NORMAL, 8, -1, -1)) return SPEC_POLY8_NORMAL;
-  if (all_fns(P, MHX_MODEL_LORDER_MIXED, MHX_LIK_NORMAL, 6, -1, -1)) return SPEC_LORDER_NORMAL;
-  if (all_fns(P, MHX_MODEL_GAUSS_PEAKS, MHX_LIK_NORMAL_CUTOFF, 8, 2, 2)) return SPEC_GAUSS22_CUTOFF;
-#ifdef MHX_AOT_G23
-  if (all_fns(P, MHX_MODEL_GAUSS_PEAKS, MHX_LIK_NORMAL, 11, 2, 3)) return 8;
-#endif
-  return SPEC_GENERIC;
-}
-
 #endif
 
 }  // namespace mhx

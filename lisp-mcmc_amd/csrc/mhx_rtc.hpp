@@ -10,33 +10,13 @@
 #include <string>
 #include <vector>
 
+#include "mhx_finalize.hpp"
 #include "mhx_launch.hpp"
 #include "mhx_types.hpp"
 
 namespace mhx {
 
-constexpr int SPEC_USER = 100;
-
-struct UserExpr {
-  std::string expr;                // validated, identifiers already rewritten
-  std::vector<std::string> names;  // as given by the caller
-  std::vector<int> index;
-  std::string builtin;   // models: non-empty = the C++ type of an ahead-of-time model struct
-                         // ("PeaksModel<1, 3, false>"): no expression, the function is only
-                         // given its own compile-time specialisation
-  int xcols = 1;         // expression models: 2 when the text names xcol1 (a second column of x)
-  bool wgrid = false;    // builtin peaks models: the function has a per-window grid table
-                         // (FnDesc::tgh) - its kernel is FixedSpec<Model, LIK, true>
-  bool early_reject = false;  // builtin models: compile the program with sweep()'s exact early
-                              // rejection (-DMHX_EARLY_REJECT; mhx_kernels.hpp)
-  bool planes = false;   // models: the function has a dataset per walker (mhx_set_dataset_planes):
-                         // its likelihood is planes_loglik, and the program is compiled with
-                         // MHX_PLANES (mhx_kernels.hpp)
-  bool dispatch = false; // planes models: an enumerated model without a compile-time type - the
-                         // slot goes through the run-time dispatch on FnDesc::model
-  int lik = -1;          // models: the function's likelihood kind (-1: dispatch at run time)
-  std::string lik_expr;  // models with MHX_LIK_EXPR: the per-point term over y, model, error
-};
+// (UserExpr, RecognisedModel and SPEC_USER: mhx_finalize.hpp, the HIP-free side)
 
 struct UserProgram {
   hipModule_t module = nullptr;
@@ -58,15 +38,8 @@ struct UserProgram {
 int rtc_prepare_expr(const std::string& expr, const std::vector<std::string>& names,
                      const char* extra, std::string* out, std::string* err);
 
-// What an expression IS (mhx_expr.cpp): a polynomial background plus Gaussian or Lorentzian peaks
-// over distinct parameters is served by the enumerated model's kernels.  `expr` is the text as
-// the caller gave it, `names` its parameter names.  order[j] = which of `names` is local
-// parameter j of the enumerated model (bg_0 .., then A, mu, w per peak).
-struct RecognisedModel {
-  int model = -1;  // MHX_MODEL_POLY / _GAUSS_PEAKS / _LORENTZ_PEAKS, -1: not of the shape
-  int shape[2] = {0, 0};
-  std::vector<int> order;
-};
+// What an expression IS (mhx_expr.cpp; RecognisedModel: mhx_finalize.hpp).  `expr` is the text as
+// the caller gave it, `names` its parameter names.
 bool rtc_recognise(const std::string& expr, const std::vector<std::string>& names,
                    RecognisedModel* out);
 
