@@ -481,7 +481,7 @@ int mhx_get_window_best(mhx_engine* e, int take, double* prob, double* theta);
 int mhx_get_history_capacity(mhx_engine* e, int32_t* capacity);
 /* HIP-event milliseconds the kernels of the engine's last mhx_get_percentiles / _covariances /
  * _proposal_factors / _window_best / _fit_bands / _derived / _histograms / _pair_grids / _waic /
- * _traces / _fit_percentiles / _residuals / _normal_equations / _candidate_scores or
+ * _loo / _traces / _fit_percentiles / _residuals / _normal_equations / _candidate_scores or
  * mhx_eval_function call ran (all portions; copies excluded). */
 int mhx_get_summary_timing(mhx_engine* e, double* kernel_ms);
 /* The same for a group, gathered in global chain order like mhx_group_get_state; every
@@ -832,6 +832,103 @@ int mhx_get_waic(mhx_engine* e, int fn, int take, double* elpd, double* lppd, do
 int mhx_group_get_waic(mhx_group* g, int fn, int take, double* elpd, double* lppd, double* p_waic,
                        int32_t* n_high, double* pw_lppd, double* pw_p, double* pw_acc,
                        int32_t* n_used, int32_t* status);
+
+/* ---- PSIS-LOO: Pareto-smoothed importance-sampling leave-one-out (Vehtari, Gelman and Gabry 2017;
+ * Vehtari, Simpson, Gelman, Yao and Gabry), the remedy for the points mhx_get_waic counts in n_high:
+ * per data point the leave-one-out predictive accuracy elpd_loo_i and the Pareto shape khat_i that
+ * says whether it can be trusted (khat above about 0.7: it cannot; the point is influential or an
+ * outlier), from the same window of the same ring.  The reference has no such function: the
+ * definition is this library's own and fixes the results operation by operation.  All arithmetic is
+ * IEEE binary64 multiply, add, subtract, divide and square root, never fused; gexp and tlog are the
+ * engine's exp and log (< 1 ulp each).  (double) of an integer is exact.  For chain c, function fn of
+ * N points, point i:
+ *   window, value, term   exactly mhx_get_waic's: n = min(take, walker-length, steps held) steps,
+ *            newest first, with the terms l_0 ... l_{n-1} of point i, the same bits.  n_used[c] = n
+ *   lppd     pw_lppd[c][i] by mhx_get_waic's running log-sum-exp, then M + tlog(S / n): the bits of
+ *            mhx_get_waic's pw_lppd
+ *   tail length   M = mhx_loo_tail_length(n, tail_len) (below)
+ *   order    the steps are ordered by (key(l_s) ascending, s ascending), key the order of
+ *            mhx_get_percentiles (-0 before +0).  The tail T_1 <= ... <= T_M is the first M of that
+ *            order - the smallest terms, which are the largest importance ratios -, the body is the
+ *            rest and l_cut is the body's first term.  With M = 0, T_1 = l_cut = the smallest term
+ *            and every step is body.  Of steps with equal terms across the cut the newer ones
+ *            (smaller s) are tail
+ *   body sum S_b = the sum of gexp(T_1 - l_s) over the body's steps in ascending s, serially from 0.0
+ *   ratios   for k = 1 .. M:  u_k = T_{M+1-k};  r_k = gexp(T_1 - u_k);  x_k = r_k - r_cut,
+ *            r_cut = gexp(T_1 - l_cut)
+ *   fit      (Zhang and Stephens 2009, with the prior of Vehtari et al.)  Md = (double)M,
+ *            Mg = 30 + floor(sqrt M) as an integer (G = (double)Mg), x* = x_q, q = (M + 2) / 4 in
+ *            integer division.  Unless x* > 0 and x_M > 0 the point is FLAT (below).  For j = 1 .. Mg:
+ *              theta_j = 1.0 / x_M + ((1.0 - sqrt(G / (j - 0.5))) / 3.0) / x*
+ *              k_j = (sum over k = 1 .. M, serially from 0.0, of tlog(1.0 - theta_j * x_k)) / Md
+ *              L_j = Md * ((tlog((-theta_j) / k_j) - k_j) - 1.0)
+ *            then w_j = 1.0 / (sum over i = 1 .. Mg, serially from 0.0, of gexp(L_i - L_j)),
+ *            theta^ = the sum over j, serially from 0.0, of theta_j * w_j,
+ *            k_raw = (sum over k, serially from 0.0, of tlog(1.0 - theta^ * x_k)) / Md,
+ *            sigma = (-k_raw) / theta^,  khat = (Md * k_raw + 5.0) / (double)(M + 10).
+ *            Any of theta^, k_raw, sigma, khat not finite, or sigma <= 0: the point is FLAT
+ *   smoothing   for k = 1 .. M:  p_k = (k - 0.5) / Md;  t_k = tlog(1.0 - p_k);  y_k = (-khat) * t_k;
+ *            q_k = (sigma * E(y_k)) / khat, where E(y) = gexp(y) - 1.0 unless |y| < 2^-5, where it is
+ *            y * (1 + y * (c_2 + y * (c_3 + ... + y * c_8))) with c_m = 1.0 / m! (the quotients of
+ *            1.0 by 2, 6, 24, 120, 720, 5040, 40320), every product and sum rounded;  khat = 0
+ *            exactly: q_k = (-sigma) * t_k.  lw_k = min(tlog(q_k + r_cut), 0.0).
+ *            A FLAT point, and every point where M = 0, takes the raw lw_k = T_1 - u_k and
+ *            khat = +infinity (sigma is given as 0.0)
+ *   estimate   W = the sum over k = 1 .. M, serially from 0.0, of gexp(lw_k + (u_k - T_1)),
+ *            V = the same of gexp(lw_k);  A = (double)(n - M) + W;  D = S_b + V;
+ *            pw_elpd[c][i] = T_1 + tlog(A / D);  pw_khat[c][i] = khat;
+ *            pw_acc[c][i] = {T_1, l_cut, S_b, sigma};  tail[c][i][0 .. M-1] = T_1 .. T_M, NaN beyond
+ *   chain    elpd_loo[c] and lppd[c] are the sums of pw_elpd and pw_lppd over blocks of MHX_LOO_BLOCK
+ *            points by mhx_get_waic's rule (lane-serial, pairwise over the 64 lanes, serial over the
+ *            blocks);  p_loo[c] = lppd[c] - elpd_loo[c], one subtraction (looic = -2 elpd_loo is the
+ *            caller's);  n_high[c] = the exact count of points with khat > k_limit (+infinity, the
+ *            khat of a point that was not fitted, exceeds every finite k_limit)
+ *   status   a sum of
+ *              MHX_LOO_NONFINITE  a value or a term of the chain is not finite (the reference would
+ *                                 have trapped): the chain's numbers are unspecified; no other chain
+ *                                 is touched by it
+ *              MHX_LOO_SHORT      n < 25: M = 0, no point has a tail to fit
+ *              MHX_LOO_FLAT       M > 0 and at least one point was FLAT (a chain that never moved is
+ *                                 FLAT at every point: pw_elpd is the term itself)
+ *              MHX_LOO_EMPTY      n = 0 (with MHX_LOO_SHORT): n_used[c] = 0, the pointwise results
+ *                                 are NaN (pw_khat +infinity), the totals their sums
+ * The results are the same bits from call to call, whatever portions the call is worked through in,
+ * whether the fit reads its columns from LDS or from the staged terms (MHX_LOO_NO_LDS=1), and however
+ * a group's chains are split over its engines.
+ * elpd_loo, p_loo, lppd [n_chains]; n_high, n_used, status [n_chains]; pw_elpd, pw_khat, pw_lppd
+ * [n_chains][N]; pw_acc [n_chains][N][4]; tail [n_chains][N][P] with P = mhx_loo_tail_length(take,
+ * tail_len).  Any output may be NULL.  take in [1, history_capacity], tail_len in
+ * [0, MHX_LOO_MAX_TAIL], fn a function of the problem, k_limit not a NaN, else MHX_EINVAL;
+ * MHX_ESTATE before mhx_init_chains; MHX_EUNSUPPORTED for an engine with a dataset per walker
+ * (mhx_set_dataset_planes: its per-point constants are per walker and not on the device), and where
+ * the `take` staged terms of each of a chain's first MHX_LOO_BLOCK points do not fit the 64 MiB of a
+ * portion (mhx_last_error names the greatest take that fits).  The outputs stay untouched on
+ * error.  Serves every model the engine can walk.  Worked through in portions whose device scratch
+ * stays below 64 MiB; mhx_get_summary_timing covers the call. */
+#define MHX_LOO_BLOCK 256     /* points of one block of mhx_get_loo's sums */
+#define MHX_LOO_MAX_TAIL 1024 /* the longest tail fitted */
+enum {
+  MHX_LOO_NONFINITE = 1,
+  MHX_LOO_SHORT = 2,
+  MHX_LOO_FLAT = 4,
+  MHX_LOO_EMPTY = 8
+};
+/* The tail length of a window of n steps.  tail_len = 0: *M = min(floor(n / 5), R) with R the least
+ * integer whose square is at least 9 n (ceil(3 sqrt n), in integer arithmetic).  tail_len > 0:
+ * *M = min(tail_len, floor(n / 5)) - the caller's way to shorten the tail for an autocorrelated
+ * chain.  Never above MHX_LOO_MAX_TAIL; a length below 5 (n < 25) is given as 0.  1000 -> 95,
+ * 8192 -> 272, a full ring of 65536 -> 768.  Host only: needs no engine and no device.  MHX_EINVAL
+ * unless n >= 0 and tail_len is in [0, MHX_LOO_MAX_TAIL].  M may be NULL. */
+int mhx_loo_tail_length(int64_t n, int32_t tail_len, int32_t* M);
+int mhx_get_loo(mhx_engine* e, int fn, int take, int tail_len, double k_limit, double* elpd_loo,
+                double* p_loo, double* lppd, int32_t* n_high, int32_t* n_used, int32_t* status,
+                double* pw_elpd, double* pw_khat, double* pw_lppd, double* pw_acc, double* tail);
+/* The same for a group, in global chain order; every device's work is enqueued before any is
+ * waited for. */
+int mhx_group_get_loo(mhx_group* g, int fn, int take, int tail_len, double k_limit, double* elpd_loo,
+                      double* p_loo, double* lppd, int32_t* n_high, int32_t* n_used,
+                      int32_t* status, double* pw_elpd, double* pw_khat, double* pw_lppd,
+                      double* pw_acc, double* tail);
 
 /* ---- credible bands: the pointwise posterior of the fit curve, of every chain, on the device ring.
  * mhx_get_fit_bands is the reference's envelope - the extremes of the model over the most probable

@@ -11,7 +11,7 @@ importlib.import_module("lisp-mcmc_amd").
 """
 from . import _capi as capi  # noqa: F401
 from ._capi import MhxError  # noqa: F401
-from .engine import Engine, Group, band_count, comm_unique_id, partition, split_rhat, ensemble_pick, trace_rows, normeq_steps  # noqa: F401
+from .engine import Engine, Group, band_count, loo_tail_length, comm_unique_id, partition, split_rhat, ensemble_pick, trace_rows, normeq_steps  # noqa: F401
 from . import models  # noqa: F401
 from . import sexpr  # noqa: F401
 from . import distributed  # noqa: F401
@@ -29,6 +29,7 @@ from .walker import (  # noqa: F401
     walker_set_corner_grid,
     autocorr, walker_autocorr, walker_set_autocorr, walker_set_rhat, walker_set_ensemble_get,
     walker_set_waic, walker_waic, waic_compare, waic_merge,
+    walker_set_loo, walker_loo, loo_compare,
     walker_set_trace, walker_set_catepillar,
     walker_set_get_residuals, walker_set_goodness_of_fit, walker_goodness_of_fit, runs_z,
     walker_set_laplace, walker_laplace, laplace_summary, least_squares, walker_set_least_squares,
@@ -49,6 +50,7 @@ __all__ = ["capi", "MhxError", "Engine", "Group", "comm_unique_id", "partition",
            "autocorr", "walker_autocorr", "walker_set_autocorr", "walker_set_rhat", "split_rhat",
            "walker_set_ensemble_get", "ensemble_pick",
            "walker_set_waic", "walker_waic", "waic_compare", "waic_merge",
+           "walker_set_loo", "walker_loo", "loo_compare", "loo_tail_length",
            "trace_rows", "walker_set_trace", "walker_set_catepillar",
            "walker_set_get_residuals", "walker_set_goodness_of_fit", "walker_goodness_of_fit", "runs_z",
            "normeq_steps", "walker_set_laplace", "walker_laplace", "laplace_summary", "least_squares",

@@ -2675,6 +2675,142 @@ int mhx_get_waic(mhx_engine* e, int fn, int take, double* elpd, double* lppd, do
   return run_portions(e, WaicCall(fn, take, elpd, lppd, p_waic, n_high, pw_lppd, pw_p, pw_acc, n_used, status));
 }
 
+// ---- PSIS-LOO (include/mhx.h has the definition): every chain's likelihood terms of function fn
+// over its window, staged, and pw_lppd (k_loo_values), the Pareto-smoothed estimate of every (chain,
+// point) column (the model-free k_loo_fit), the block sums of the chunk (k_loo_block_sums) and the
+// totals (k_loo_totals).  An item is a chain.  The terms of a portion are staged, `take` doubles per
+// chain and point, so the chunk of points is the call's own (loo_cursor, mhx_stage.hpp): whole
+// MHX_LOO_BLOCK blocks, as many as let one chain fit the budget - a block is the same points
+// whatever the split.  The blocks' partial sums of all chunks stay in the stage; the totals are
+// taken on the last chunk.
+struct LooCall {
+  int fn = 0, take = 0, tail_len = 0, P = 0, want = 0;
+  double k_limit = 0.7;
+  int64_t m = 0, nb_total = 0;
+  enum { ELPD, P_LOO, LPPD, N_HIGH, N_USED, STATUS, PW_ELPD, PW_KHAT, PW_LPPD, PW_ACC, TAIL, N_DST };
+  HostDst dst[N_DST];
+  static_assert(kLooBlock == MHX_LOO_BLOCK, "MHX_LOO_BLOCK (include/mhx.h)");
+
+  LooCall(int fn_, int take_, int tail_len_, double k_limit_, double* elpd, double* p_loo, double* lppd,
+          int32_t* n_high, int32_t* n_used, int32_t* status, double* pw_elpd, double* pw_khat, double* pw_lppd,
+          double* pw_acc, double* tail)
+      : fn(fn_), take(take_), tail_len(tail_len_), k_limit(k_limit_) {
+    dst[ELPD] = {elpd, sizeof(double)}, dst[P_LOO] = {p_loo, sizeof(double)}, dst[LPPD] = {lppd, sizeof(double)};
+    dst[N_HIGH] = {n_high, sizeof(int32_t)}, dst[N_USED] = {n_used, sizeof(int32_t)};
+    dst[STATUS] = {status, sizeof(int32_t)};
+    dst[PW_ELPD].p = pw_elpd, dst[PW_KHAT].p = pw_khat, dst[PW_LPPD].p = pw_lppd;
+    dst[PW_ACC].p = pw_acc, dst[TAIL].p = tail;
+    want = (pw_acc ? LOO_WANT_ACC : 0) | (tail ? LOO_WANT_TAIL : 0);
+  }
+  int check(mhx_engine* e) {
+    int rc = window_check(e, take);
+    if (rc != MHX_OK || (rc = fn_check(e, fn)) != MHX_OK) return rc;
+    if (tail_len < 0 || tail_len > MHX_LOO_MAX_TAIL)
+      return fail(MHX_EINVAL, "tail_len must be in [0, MHX_LOO_MAX_TAIL = %d]", MHX_LOO_MAX_TAIL);
+    if (k_limit != k_limit) return fail(MHX_EINVAL, "k_limit is a NaN");
+    for (int k = 0; k < e->P.K; ++k)
+      if (e->data[k].planes)
+        return fail(MHX_EUNSUPPORTED, "mhx_get_loo on an engine with a dataset per walker "
+                                      "(mhx_set_dataset_planes): the planes' per-point constants "
+                                      "live per walker and are not on the device");
+    m = e->P.fn[fn].n;
+    nb_total = loo_blocks(m);
+    P = loo_tail_length_of(take, tail_len);
+    if (cursor(e).chunk < 1)
+      return fail(MHX_EUNSUPPORTED, "mhx_get_loo: the %d staged terms of each of a chain's first %lld "
+                                    "points do not fit the 64 MiB of a portion: the greatest take that fits is %d",
+                  take, (long long)std::min<int64_t>(m, kLooBlock), loo_max_take(m, P, want));
+    const size_t row = (size_t)m * sizeof(double);
+    dst[PW_ELPD].item_bytes = dst[PW_KHAT].item_bytes = dst[PW_LPPD].item_bytes = row;
+    dst[PW_ACC].item_bytes = 4 * row;
+    dst[TAIL].item_bytes = (size_t)P * row;
+    return MHX_OK;
+  }
+  int64_t items(const mhx_engine* e) const { return e->cfg.n_chains; }
+  int64_t points() const { return m; }
+  PortionCursor cursor(const mhx_engine* e) const { return loo_cursor(items(e), m, take, P, want); }
+  LooPieces carve(const mhx_engine*, Carver& c, int64_t n_items, int64_t m_points) const {
+    return carve_loo(c, nb_total, take, P, want, n_items, m_points);
+  }
+  // the per-point constants of the chunk, as mhx_get_waic takes them; the status gathers over the chunks
+  int upload(mhx_engine* e, const Portion& p) const {
+    Carver c;
+    const LooPieces s = carve(e, c, p.n, p.m);
+    const Dataset& D = e->data[fn];
+    if (!D.hconst.empty())
+      HIP_TRY(hipMemcpyAsync(stage_at<double>(e, s.cst), D.hconst.data() + p.m0, (size_t)p.m * sizeof(double),
+                             hipMemcpyHostToDevice, e->stream));
+    if (p.m0 == 0)
+      HIP_TRY(hipMemsetAsync(stage_at<int32_t>(e, s.status), 0, (size_t)p.n * sizeof(int32_t), e->stream));
+    return MHX_OK;
+  }
+  int launch(mhx_engine* e, const Portion& p) const {
+    Carver c;
+    const LooPieces s = carve(e, c, p.n, p.m);
+    const FnDesc& f = e->P.fn[fn];
+    const bool on_host = !e->data[fn].hconst.empty();
+    LooArgs A{};
+    A.c0 = p.i0, A.n = p.n;
+    A.take = take, A.fn = fn;
+    A.n_blocks = (int32_t)loo_value_blocks(p.m);
+    A.m = p.m;
+    A.x0 = f.x + p.m0;
+    A.x1 = f.n_xcols > 1 ? f.c + p.m0 : nullptr;
+    A.y = f.y + p.m0;
+    A.w = f.w + p.m0;
+    A.c = on_host ? stage_at<double>(e, s.cst) : f.lik == MHX_LIK_EXPR ? nullptr : f.c + p.m0;
+    A.terms = stage_at<double>(e, s.terms);
+    A.pw_lppd = stage_at<double>(e, s.pw_lppd);
+    A.status = stage_at<int32_t>(e, s.status);
+    HIP_TRY(launch_model(e, A));
+    double* const pw_elpd = stage_at<double>(e, s.pw_elpd);
+    double* const pw_khat = stage_at<double>(e, s.pw_khat);
+    double* const part_elpd = stage_at<double>(e, s.part_elpd);
+    double* const part_lppd = stage_at<double>(e, s.part_lppd);
+    int32_t* const part_high = stage_at<int32_t>(e, s.part_high);
+    HIP_TRY(launch_loo_fit(e->stream, e->S, p.i0, p.n, take, tail_len, p.m,
+                           !e->knobs.loo_no_lds && loo_use_lds(take, P), A.terms, pw_elpd, pw_khat,
+                           (want & LOO_WANT_ACC) ? stage_at<double>(e, s.pw_acc) : nullptr,
+                           (want & LOO_WANT_TAIL) ? stage_at<double>(e, s.tail) : nullptr, A.status));
+    HIP_TRY(launch_loo_block_sums(e->stream, p.n, p.m, p.m0 / MHX_LOO_BLOCK, nb_total, k_limit, pw_elpd,
+                                  A.pw_lppd, pw_khat, part_elpd, part_lppd, part_high));
+    if (p.m0 + p.m >= m)
+      HIP_TRY(launch_loo_totals(e->stream, e->S, p.i0, p.n, take, nb_total, part_elpd, part_lppd, part_high,
+                                stage_at<double>(e, s.elpd), stage_at<double>(e, s.p_loo),
+                                stage_at<double>(e, s.lppd), stage_at<int32_t>(e, s.n_high),
+                                stage_at<int32_t>(e, s.n_used), A.status));
+    e->launches++;
+    return MHX_OK;
+  }
+  int collect(mhx_engine* e, const Portion& p) const {
+    Carver c;
+    const LooPieces s = carve(e, c, p.n, p.m);
+    const size_t pw[5] = {s.pw_elpd, s.pw_khat, s.pw_lppd, s.pw_acc, s.tail};
+    const size_t per[5] = {1, 1, 1, 4, (size_t)P};  // (doubles a point)
+    for (int k = 0; k < 5; ++k) {
+      if (per[k] == 0) continue;
+      const int rc = copy_back_points(dst[PW_ELPD + k], p, m, per[k] * sizeof(double), 1, e->stage.p + pw[k]);
+      if (rc != MHX_OK) return rc;
+    }
+    if (p.m0 + p.m < m) return MHX_OK;  // (the totals come with the last chunk of points)
+    return copy_back_each(e, dst, p, {s.elpd, s.p_loo, s.lppd, s.n_high, s.n_used, s.status});
+  }
+};
+
+int mhx_loo_tail_length(int64_t n, int32_t tail_len, int32_t* M) {
+  if (n < 0) return fail(MHX_EINVAL, "n < 0");
+  if (tail_len < 0 || tail_len > MHX_LOO_MAX_TAIL)
+    return fail(MHX_EINVAL, "tail_len must be in [0, MHX_LOO_MAX_TAIL = %d]", MHX_LOO_MAX_TAIL);
+  if (M) *M = loo_tail_length_of(n, tail_len);
+  return MHX_OK;
+}
+int mhx_get_loo(mhx_engine* e, int fn, int take, int tail_len, double k_limit, double* elpd_loo, double* p_loo,
+                double* lppd, int32_t* n_high, int32_t* n_used, int32_t* status, double* pw_elpd,
+                double* pw_khat, double* pw_lppd, double* pw_acc, double* tail) {
+  return run_portions(e, LooCall(fn, take, tail_len, k_limit, elpd_loo, p_loo, lppd, n_high, n_used, status,
+                                 pw_elpd, pw_khat, pw_lppd, pw_acc, tail));
+}
+
 // ---- residuals (include/mhx.h has the definition): function fn at one parameter vector per chain
 // over the chain's own data, and the block partials of the standardized residuals (k_resid), then
 // their totals (k_resid_totals).  An item is a chain; the function's points go in chunks of
@@ -4357,6 +4493,12 @@ int mhx_group_get_waic(mhx_group* g, int fn, int take, double* elpd, double* lpp
                        int32_t* n_high, double* pw_lppd, double* pw_p, double* pw_acc,
                        int32_t* n_used, int32_t* status) {
   return run_portions(g, WaicCall(fn, take, elpd, lppd, p_waic, n_high, pw_lppd, pw_p, pw_acc, n_used, status));
+}
+int mhx_group_get_loo(mhx_group* g, int fn, int take, int tail_len, double k_limit, double* elpd_loo,
+                      double* p_loo, double* lppd, int32_t* n_high, int32_t* n_used, int32_t* status,
+                      double* pw_elpd, double* pw_khat, double* pw_lppd, double* pw_acc, double* tail) {
+  return run_portions(g, LooCall(fn, take, tail_len, k_limit, elpd_loo, p_loo, lppd, n_high, n_used, status,
+                                 pw_elpd, pw_khat, pw_lppd, pw_acc, tail));
 }
 
 int mhx_group_get_residuals(mhx_group* g, int fn, const double* theta, double z_limit, double* fit,

@@ -5011,6 +5011,405 @@ __global__ __launch_bounds__(kPctThreads) void k_fitpct_select(
 }
 #endif
 
+// mhx_get_loo, first half (include/mhx.h has the definition): k_waic's walk over the window with
+// the log-sum-exp pair alone behind the likelihood.  Wave g serves chain g / n_blocks of the launch
+// and block g % n_blocks of its points: kLooValPts points per lane, whose x, ys, w, c and the pair
+// {M, S} stay in registers.  Each step's term goes to the portion's stage piece as
+// k_fitpct_values stores its values (LooArgs has the layout): the stores of a wave are whole lines.
+// The value, the term and the recurrence are k_waic_body's, operation for operation, so pw_lppd is
+// mhx_get_waic's to the bit.  Every product and sum is rounded on its own (the unit is compiled
+// without contraction; no fma is written here).
+template <class Spec>
+__device__ __forceinline__ void k_loo_values_body(const ProblemDesc* __restrict__ Pp, ChainState S,
+                                                  LooArgs A) {
+  FitLds& lds = *reinterpret_cast<FitLds*>(mhx_lds_raw);
+  lds_tables_begin();
+  __syncthreads();  // (the only barrier: waves without work leave behind it)
+  const int w = wave_in_group(), l = lane_id();
+  const int64_t g = (int64_t)blockIdx.x * kWavesPerGroup + w;
+  if (g >= A.n * A.n_blocks) return;
+  const int64_t i = g / A.n_blocks;
+  const int64_t p0 = (g - i * A.n_blocks) * (int64_t)(kWave * kLooValPts) + l;
+  const FnDesc& f = Pp->fn[A.fn];
+  const int d = Pp->d;
+  const int lik = __builtin_amdgcn_readfirstlane(f.lik);
+  double x0[kLooValPts], x1[kLooValPts], ys[kLooValPts], wi[kLooValPts], ci[kLooValPts], aM[kLooValPts], aS[kLooValPts];
+#pragma unroll
+  for (int j = 0; j < kLooValPts; ++j) {
+    const int64_t p = p0 + (int64_t)j * kWave;
+    const int64_t q = p < A.m ? p : A.m - 1;  // (beyond m: the last point once more, never stored)
+    x0[j] = A.x0[q];
+    x1[j] = A.x1 ? A.x1[q] : 0.0;
+    ys[j] = A.y[q];
+    wi[j] = A.w[q];
+    ci[j] = A.c ? A.c[q] : 0.0;
+    aM[j] = aS[j] = 0.0;
+  }
+  const Ring r = ring_of(S, A.c0 + i);
+  const int n = ring_held(r, A.take);
+  double* th = lds.th[w];
+  double* const out = A.terms + i * ((int64_t)A.take * A.m) + p0;
+  double thn = 0.0;
+  if (n > 0 && l < d) thn = r.theta[(int64_t)r.slot(0) * d + l];
+  bool bad = false;
+  for (int s = 0; s < n; ++s) {
+    if (l < d) th[l] = thn;
+    __builtin_amdgcn_wave_barrier();
+    if (s + 1 < n && l < d) thn = r.theta[(int64_t)r.slot(s + 1) * d + l];
+    auto pf = [&](int j) -> double { return th[f.idx[j]]; };
+    double v[kLooValPts], t[kLooValPts];
+    Spec::template values<kLooValPts>(f, pf, lds.scr[w], x0, x1, v);
+    if (lik == MHX_LIK_POISSON) {
+#pragma unroll
+      for (int j = 0; j < kLooValPts; ++j) {
+        const double a = ys[j] * tlog_rate(v[j]);
+        const double b = a - v[j];
+        t[j] = b + ci[j];
+      }
+    } else if (lik == MHX_LIK_EXPR) {
+#pragma unroll
+      for (int j = 0; j < kLooValPts; ++j) t[j] = Spec::lik_term(f, ys[j], v[j], wi[j]);
+    } else {
+      const bool cut = lik == MHX_LIK_NORMAL_CUTOFF;
+#pragma unroll
+      for (int j = 0; j < kLooValPts; ++j) {
+        const double a = v[j] * wi[j];
+        const double rr = ys[j] - a;
+        const double h = 0.5 * rr;
+        const double q = h * rr;
+        const double e = ci[j] - q;
+        t[j] = cut ? (e > -5000.0 ? e : -5000.0) : e;
+      }
+    }
+    double* const row = out + (int64_t)s * A.m;
+#pragma unroll
+    for (int j = 0; j < kLooValPts; ++j) {
+      const double e = t[j];
+      bad = bad || !finite_f64(v[j]) || !finite_f64(e);
+      const bool up = e > aM[j];
+      const double ge = gexp(up ? aM[j] - e : e - aM[j]);
+      const double sn = up ? aS[j] * ge + 1.0 : aS[j] + ge;
+      aS[j] = s == 0 ? 1.0 : sn;
+      aM[j] = (s == 0 || up) ? e : aM[j];
+      if (p0 + (int64_t)j * kWave < A.m) row[j * kWave] = e;
+    }
+  }
+  const double nd = (double)n;
+#pragma unroll
+  for (int j = 0; j < kLooValPts; ++j) {
+    const int64_t p = p0 + (int64_t)j * kWave;
+    if (p < A.m) A.pw_lppd[i * A.m + p] = aM[j] + tlog(aS[j] / nd);
+  }
+  if (__ballot(bad) != 0ULL && l == 0) atomicOr(&A.status[i], (int32_t)MHX_LOO_NONFINITE);
+}
+#ifndef __HIPCC_RTC__
+template <class Spec>
+__global__ __launch_bounds__(kThreads) void k_loo_values(const ProblemDesc* __restrict__ Pp, ChainState S,
+                                                         LooArgs A) {
+  k_loo_values_body<Spec>(Pp, S, A);
+}
+#endif
+#if defined(MHX_FAMILY_PRIMARY) && !defined(__HIPCC_RTC__)
+// The key of rank `pos` (from 0) of the n keys key_at(0 .. n-1) in ascending order, by
+// select_percentile's radix selection bit by bit, and *within = its place in its run of equal keys
+// (pos minus the number of keys below it).  All lanes return the same values.
+template <class KeyAt>
+__device__ __forceinline__ unsigned long long select_key(KeyAt key_at, int n, int pos, int* within) {
+  const int l = lane_id();
+  unsigned long long prefix = 0, mask = 0;
+  int k = pos;
+  for (int b = 63; b >= 0; --b) {
+    const unsigned long long bit = 1ULL << b, upto = mask | bit;
+    int c0 = 0;
+    for (int s0 = 0; s0 < n; s0 += kWave) {
+      const bool in = s0 + l < n;
+      const unsigned long long key = in ? key_at(s0 + l) & upto : 0ULL;
+      c0 += (int)__popcll(__ballot(in && key == prefix));  // (still a candidate, and its bit is 0)
+    }
+    if (k >= c0) {
+      k -= c0;
+      prefix |= bit;
+    }
+    mask |= bit;
+  }
+  *within = k;
+  return prefix;
+}
+// exp(y) - 1 of mhx_get_loo's smoothing: the Taylor polynomial of degree 8 below 2^-5, every product
+// and sum rounded on its own (this unit is compiled without contraction), else gexp(y) - 1
+__device__ __forceinline__ double loo_expm1(double y) {
+  if (fabs(y) < 0x1p-5) {
+    double p = 1.0 / 40320.0;
+    p = 1.0 / 5040.0 + y * p;
+    p = 1.0 / 720.0 + y * p;
+    p = 1.0 / 120.0 + y * p;
+    p = 1.0 / 24.0 + y * p;
+    p = 1.0 / 6.0 + y * p;
+    p = 1.0 / 2.0 + y * p;
+    p = 1.0 + y * p;
+    return y * p;
+  }
+  return gexp(y) - 1.0;
+}
+// the sum of the first `cnt` lanes' v, serially from acc in lane order: every lane ends with the
+// same bits.  cnt is wave-uniform.
+__device__ __forceinline__ double lanes_serial_sum(double acc, double v, int cnt) {
+  for (int j = 0; j < cnt; ++j) acc = acc + readlane_f64(v, j);
+  return acc;
+}
+
+// mhx_get_loo, second half (include/mhx.h has the definition): the Pareto-smoothed estimate of the
+// staged terms, model-free.  One workgroup of kPctWaves wavefronts serves chain i and kLooCols
+// neighbouring points, ONE WAVE A COLUMN: everything between the column and its three numbers is
+// serial in the definition's order, or as wide as a tail (M of about 3 sqrt n) or as the fit's grid
+// (Mg <= 62 values of theta: one lane each), so a wave is the widest unit that has work throughout,
+// and no barrier separates the phases.  For its column a wave
+//   1 finds the key of rank M by radix selection (select_key), and T_1 by one min-reduction
+//   2 walks the steps in ascending s: a step below the cut key, or among the first `within` of the
+//     cut key's run, goes to the wave's tail buffer in LDS; every other adds gexp(T_1 - l_s) to
+//     S_b, the exponentials 64 at a time and the sum in lane order (lanes_serial_sum)
+//   3 sorts the tail's keys in LDS (bitonic over the next power of two, padded with the greatest key)
+//   4 lays down x_k, runs the fit with theta_j in lane j - 1, each lane summing its tlog serially
+//     over the tail (x_k is one LDS broadcast for all lanes), then the weights and theta^ from
+//     readlane loops; k_raw's terms 64 at a time, summed in lane order
+//   5 smooths (a lane per k) and takes the two final sums in lane order.
+// LDS: the math tables (LdsHead, at address 0: gexp and tlog read them there), per wave its tail
+// keys [p2] and x [p2], then - use_lds - the four columns' keys at `tpad` slots each, transposed on
+// the way in as k_fitpct_select does.  use_lds = 0 (the columns do not fit, or MHX_LOO_NO_LDS=1):
+// passes 1 and 2 read the stage.  p2: the power of two that holds the call's P.
+constexpr int kLooCols = kPctWaves;
+__global__ __launch_bounds__(kPctThreads) void k_loo_fit(
+    ChainState S, int64_t c0, int take, int tail_len, int64_t m, int n_groups, int P, int p2, int use_lds,
+    int tpad, const double* __restrict__ terms, double* __restrict__ pw_elpd, double* __restrict__ pw_khat,
+    double* __restrict__ pw_acc, double* __restrict__ tail, int32_t* __restrict__ status) {
+  lds_tables_begin();
+  unsigned long long* const work = reinterpret_cast<unsigned long long*>(mhx_lds_raw + sizeof(LdsHead));
+  unsigned long long* const col = work + (size_t)kPctWaves * 2 * p2;
+  const int w = wave_in_group(), l = lane_id();
+  const int64_t i = blockIdx.x / n_groups;
+  const int64_t pg = (int64_t)(blockIdx.x - i * n_groups) * kLooCols;
+  const int nc = (int)(m - pg < kLooCols ? m - pg : kLooCols);
+  const Ring ring = ring_of(S, c0 + i);
+  const int n = ring_held(ring, take);
+  const double* v = terms + i * ((int64_t)take * m) + pg;
+  if (use_lds) {
+    for (int f = threadIdx.x; f < n * kLooCols; f += kPctThreads) {
+      const int s = f / kLooCols, q = f - s * kLooCols;
+      if (q < nc) col[(size_t)q * tpad + s] = order_key(v[(int64_t)s * m + q]);
+    }
+  }
+  __syncthreads();  // (the tables and the columns; the only barrier)
+  if (w >= nc) return;
+  const unsigned long long* cp = col + (size_t)w * tpad;
+  const double* vp = v + w;
+  auto key_at = [&](int s) -> unsigned long long {
+    return use_lds ? cp[s] : order_key(vp[(int64_t)s * m]);
+  };
+  unsigned long long* const tk = work + (size_t)w * 2 * p2;  // the tail's keys, then T ascending
+  double* const xs = reinterpret_cast<double*>(tk + p2);     // x_k, then lw_k
+  const int64_t o = i * m + pg + w;
+  const int M = n > 0 ? loo_tail_length_of(n, tail_len) : 0;
+  const double nan = __builtin_nan(""), inf = __builtin_inf();
+  double T1 = nan, lcut = nan, Sb = 0.0, sigma = 0.0, khat = inf, elpd = nan;
+  bool flat = false;
+  if (n > 0) {
+    // 1: the cut key and the smallest key
+    int within = 0;
+    const unsigned long long kcut = select_key(key_at, n, M, &within);
+    unsigned long long mn = ~0ULL;
+    for (int s = l; s < n; s += kWave) {
+      const unsigned long long k = key_at(s);
+      mn = k < mn ? k : mn;
+    }
+    mn = wave_min_u64(mn);
+    T1 = key_value(mn), lcut = key_value(kcut);
+    // 2: the tail to LDS, the body into S_b in step order
+    int n_eq = 0, n_tail = 0;
+    for (int s0 = 0; s0 < n; s0 += kWave) {
+      const bool in = s0 + l < n;
+      const unsigned long long k = in ? key_at(s0 + l) : ~0ULL;
+      const bool eq = in && k == kcut;
+      const unsigned long long beq = __ballot(eq), below = (1ULL << l) - 1ULL;
+      const bool tl = in && (k < kcut || (eq && n_eq + (int)__popcll(beq & below) < within));
+      const unsigned long long btl = __ballot(tl);
+      const int at = n_tail + (int)__popcll(btl & below);
+      if (tl && at < M) tk[at] = k;  // (at < M always: M steps are tail by the selection's count)
+      const double ge = (in && !tl) ? gexp(T1 - key_value(k)) : 0.0;
+      Sb = lanes_serial_sum(Sb, ge, n - s0 < kWave ? n - s0 : kWave);
+      n_eq += (int)__popcll(beq);
+      n_tail += (int)__popcll(btl);
+    }
+    // 3: T_1 .. T_M ascending
+    for (int f = M + l; f < p2; f += kWave) tk[f] = ~0ULL;
+    __builtin_amdgcn_wave_barrier();
+    if (M > 1) {
+      for (int kk = 2; kk <= p2; kk <<= 1)
+        for (int jj = kk >> 1; jj > 0; jj >>= 1) {
+          for (int t = l; t < p2 / 2; t += kWave) {
+            const int a = ((t & ~(jj - 1)) << 1) | (t & (jj - 1)), b = a | jj;
+            const unsigned long long ka = tk[a], kb = tk[b];
+            const bool asc = (a & kk) == 0;
+            if ((ka > kb) == asc) tk[a] = kb, tk[b] = ka;
+          }
+          __builtin_amdgcn_wave_barrier();
+        }
+    }
+    // 4: x_k = r_k - r_cut for k = 1 .. M, u_k = T_{M+1-k}; xs[k - 1]
+    const double rcut = gexp(T1 - lcut);
+    for (int k = l; k < M; k += kWave) {
+      const double u = key_value(tk[M - 1 - k]);
+      xs[k] = gexp(T1 - u) - rcut;
+    }
+    __builtin_amdgcn_wave_barrier();
+    bool fitted = false;
+    if (M > 0) {
+      const double Md = (double)M;
+      const int Mg = 30 + (int)__builtin_sqrt(Md);  // (sqrt is correctly rounded: the floor is exact for M <= 1024)
+      const double xq = xs[(M + 2) / 4 - 1], xM = xs[M - 1];
+      if (xq > 0.0 && xM > 0.0) {
+        const double G = (double)Mg;
+        const int j = l < Mg ? l + 1 : Mg;  // (lanes beyond the grid repeat its last value, unread)
+        const double a0 = G / ((double)j - 0.5);
+        const double a1 = 1.0 - __builtin_sqrt(a0);
+        const double a2 = a1 / 3.0;
+        const double th = 1.0 / xM + a2 / xq;
+        double sum = 0.0;
+        for (int k = 0; k < M; ++k) sum = sum + tlog(1.0 - th * xs[k]);
+        const double kj = sum / Md;
+        const double Lj = Md * ((tlog((-th) / kj) - kj) - 1.0);
+        double den = 0.0;
+        for (int q = 0; q < Mg; ++q) den = den + gexp(readlane_f64(Lj, q) - Lj);
+        const double wj = 1.0 / den;
+        const double that = uniform_f64(lanes_serial_sum(0.0, th * wj, Mg));
+        double ks = 0.0;
+        for (int k0 = 0; k0 < M; k0 += kWave) {
+          const double t = k0 + l < M ? tlog(1.0 - that * xs[k0 + l]) : 0.0;
+          ks = lanes_serial_sum(ks, t, M - k0 < kWave ? M - k0 : kWave);
+        }
+        const double kraw = uniform_f64(ks) / Md;
+        const double sg = (-kraw) / that;
+        const double kh = (Md * kraw + 5.0) / (double)(M + 10);
+        if (finite_f64(that) && finite_f64(kraw) && finite_f64(sg) && finite_f64(kh) && sg > 0.0) {
+          fitted = true;
+          sigma = sg, khat = kh;
+        }
+      }
+      flat = !fitted;
+    }
+    // 5: lw_k over xs, then the two sums in ascending k
+    __builtin_amdgcn_wave_barrier();
+    double W = 0.0, V = 0.0;
+    for (int k0 = 0; k0 < M; k0 += kWave) {
+      const int k = k0 + l;
+      double e1 = 0.0, e2 = 0.0;
+      if (k < M) {
+        const double u = key_value(tk[M - 1 - k]);
+        double lw = T1 - u;
+        if (fitted) {
+          const double p = ((double)(k + 1) - 0.5) / (double)M;
+          const double t = tlog(1.0 - p);
+          const double q = khat == 0.0 ? (-sigma) * t : (sigma * loo_expm1((-khat) * t)) / khat;
+          const double lq = tlog(q + rcut);
+          lw = lq < 0.0 ? lq : 0.0;
+        }
+        e1 = gexp(lw + (u - T1));
+        e2 = gexp(lw);
+      }
+      const int cnt = M - k0 < kWave ? M - k0 : kWave;
+      W = lanes_serial_sum(W, e1, cnt);
+      V = lanes_serial_sum(V, e2, cnt);
+    }
+    const double A = (double)(n - M) + W, D = Sb + V;
+    elpd = T1 + tlog(A / D);
+  }
+  if (l == 0) {
+    pw_elpd[o] = elpd;
+    pw_khat[o] = khat;
+    if (pw_acc) {
+      pw_acc[o * 4 + 0] = T1;
+      pw_acc[o * 4 + 1] = lcut;
+      pw_acc[o * 4 + 2] = Sb;
+      pw_acc[o * 4 + 3] = sigma;
+    }
+    if (flat) atomicOr(&status[i], (int32_t)MHX_LOO_FLAT);
+  }
+  if (tail)
+    for (int k = l; k < P; k += kWave) tail[o * P + k] = k < M ? key_value(tk[k]) : nan;
+}
+
+// mhx_get_loo: the block sums of a chunk of points, by mhx_get_waic's rule.  Wave g serves chain
+// g / n_blocks of the launch and block g % n_blocks of the chunk, which is block blk0 + that of the
+// function's nb_total: lane j adds its kLooPts points serially from 0.0 (a point beyond m adds 0.0),
+// then the butterfly.  part_* [n][nb_total].
+__global__ __launch_bounds__(kPctThreads) void k_loo_block_sums(
+    int64_t n, int64_t m, int n_blocks, int64_t blk0, int64_t nb_total, double k_limit,
+    const double* __restrict__ pw_elpd, const double* __restrict__ pw_lppd, const double* __restrict__ pw_khat,
+    double* __restrict__ part_elpd, double* __restrict__ part_lppd, int32_t* __restrict__ part_high) {
+  const int w = wave_in_group(), l = lane_id();
+  const int64_t g = (int64_t)blockIdx.x * kPctWaves + w;
+  if (g >= n * n_blocks) return;
+  const int64_t i = g / n_blocks, blk = g - i * n_blocks;
+  const int64_t p0 = blk * (int64_t)MHX_LOO_BLOCK + l;
+  double se = 0.0, sl = 0.0;
+  int nh = 0;
+#pragma unroll
+  for (int j = 0; j < kLooPts; ++j) {
+    const int64_t p = p0 + (int64_t)j * kWave;
+    const bool in = p < m;
+    const int64_t q = i * m + (in ? p : 0);
+    const double e = pw_elpd[q], lp = pw_lppd[q], kh = pw_khat[q];
+    se = se + (in ? e : 0.0);
+    sl = sl + (in ? lp : 0.0);
+    nh += (in && kh > k_limit) ? 1 : 0;
+  }
+  se = wave_sum(se);
+  sl = wave_sum(sl);
+  nh = wave_sum_i(nh);
+  if (l == 0) {
+    const int64_t o = i * nb_total + blk0 + blk;
+    part_elpd[o] = se;
+    part_lppd[o] = sl;
+    part_high[o] = nh;
+  }
+}
+
+// mhx_get_loo, the totals: one thread per chain adds the blocks' partial sums in block order
+// (whatever launches wrote them), takes the one subtraction and completes n_used and the status
+// (a window without a tail; an empty one).
+__global__ __launch_bounds__(kThreads) void k_loo_totals(ChainState S, int64_t c0, int64_t n, int take,
+                                                         int64_t nb_total,
+                                                         const double* __restrict__ part_elpd,
+                                                         const double* __restrict__ part_lppd,
+                                                         const int32_t* __restrict__ part_high,
+                                                         double* __restrict__ elpd,
+                                                         double* __restrict__ p_loo,
+                                                         double* __restrict__ lppd,
+                                                         int32_t* __restrict__ n_high,
+                                                         int32_t* __restrict__ n_used,
+                                                         int32_t* __restrict__ status) {
+  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  const int64_t c = c0 + i;
+  int64_t t = S.length[c] < S.n_hist[c] ? S.length[c] : S.n_hist[c];
+  if (t > (int64_t)take) t = take;
+  if (t < 0) t = 0;
+  double se = 0.0, sl = 0.0;
+  int nh = 0;
+  for (int64_t b = 0; b < nb_total; ++b) {
+    se = se + part_elpd[i * nb_total + b];
+    sl = sl + part_lppd[i * nb_total + b];
+    nh += part_high[i * nb_total + b];
+  }
+  elpd[i] = se;
+  lppd[i] = sl;
+  p_loo[i] = sl - se;
+  n_high[i] = nh;
+  n_used[i] = (int32_t)t;
+  if (t < 25) status[i] = status[i] | MHX_LOO_SHORT;
+  if (t == 0) status[i] = status[i] | MHX_LOO_EMPTY;
+}
+#endif
+
 }  // inline namespace MHX_FAMILY
 }  // namespace mhx
 

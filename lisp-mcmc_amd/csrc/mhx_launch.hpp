@@ -167,7 +167,8 @@ hipError_t launch_window_best(hipStream_t st, const ChainState& S, int64_t c0, i
     kNormEqLdsBudget, (A.lanes = normeq_lanes(wpg, A.p), A.sub = normeq_sub(wpg, A.p)))                        \
   X(cand,   CandArgs,   k_cand,          false, A.m <= 0 || A.m_cand <= 0 ? 0 : A.n * A.n_blocks,              \
     fit_lds_bytes(wpg), 0, (void)0)                                                                            \
-  X(fitpct, FitPctArgs, k_fitpct_values, true,  A.m <= 0 ? 0 : A.n * A.n_blocks, fit_lds_bytes(wpg), 0, (void)0)
+  X(fitpct, FitPctArgs, k_fitpct_values, true,  A.m <= 0 ? 0 : A.n * A.n_blocks, fit_lds_bytes(wpg), 0, (void)0)    \
+  X(loo,    LooArgs,    k_loo_values,    true,  A.m <= 0 ? 0 : A.n * A.n_blocks, fit_lds_bytes(wpg), 0, (void)0)
 
 enum ModelReadoutId {
 #define MHX_X(ID, ...) MR_##ID,
@@ -227,6 +228,36 @@ hipError_t launch_fitpct_select(hipStream_t st, const ChainState& S, int64_t c0,
                                 int64_t m, int64_t vs_step, int64_t vs_point, const PctList& pc,
                                 bool use_lds, bool together, const double* vals, double* pct,
                                 int32_t* n_used, int32_t* status);
+
+// mhx_get_loo: the staged terms and pw_lppd (LooArgs, mhx_types.hpp) through launch_model, the
+// model-free fit of every (chain, point) column, the block sums of a chunk of points and the totals.
+// A fit workgroup takes kLooCols = 4 neighbouring points, a wave each.  Its LDS: the math tables,
+// per wave the tail's keys and x (two arrays of loo_p2(P) slots), and - where that still fits
+// kPctLdsBudget - the four columns' keys (loo_use_lds); else the selection reads the stage.
+constexpr int kLooColsPerGroup = 4;
+inline int64_t loo_blocks(int64_t m) { return (m + MHX_LOO_BLOCK - 1) / MHX_LOO_BLOCK; }
+inline int64_t loo_value_blocks(int64_t m) { return (m + kLooValBlock - 1) / kLooValBlock; }
+inline int loo_p2(int P) {
+  int p2 = 64;
+  while (p2 < P) p2 <<= 1;
+  return p2;
+}
+inline size_t loo_lds_bytes(int take, int P, bool use_lds) {
+  return 6144 + (size_t)kLooColsPerGroup * 2 * loo_p2(P) * sizeof(double) +
+         (use_lds ? pct_lds_bytes(take, kLooColsPerGroup) : 0);
+}
+inline bool loo_use_lds(int take, int P) { return loo_lds_bytes(take, P, true) <= kPctLdsBudget; }
+hipError_t launch_loo_fit(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take, int tail_len,
+                          int64_t m, bool use_lds, const double* terms, double* pw_elpd, double* pw_khat,
+                          double* pw_acc, double* tail, int32_t* status);
+hipError_t launch_loo_block_sums(hipStream_t st, int64_t n, int64_t m, int64_t blk0, int64_t nb_total,
+                                 double k_limit, const double* pw_elpd, const double* pw_lppd,
+                                 const double* pw_khat, double* part_elpd, double* part_lppd,
+                                 int32_t* part_high);
+hipError_t launch_loo_totals(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
+                             int64_t nb_total, const double* part_elpd, const double* part_lppd,
+                             const int32_t* part_high, double* elpd, double* p_loo, double* lppd,
+                             int32_t* n_high, int32_t* n_used, int32_t* status);
 
 // mhx_get_residuals: the residuals' block sums, counts and extremes (ResidArgs, mhx_types.hpp)
 // through launch_model - every engine with a dataset per walker is run-time compiled - and the

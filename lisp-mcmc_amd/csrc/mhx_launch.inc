@@ -279,6 +279,10 @@ hipError_t summary_configure() {
   if (e == hipSuccess)
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fitpct_select),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPctLdsBudget);
+  if (e == hipSuccess) e = no_static_lds(&k_loo_fit);  // (gexp and tlog read their tables at LDS address 0)
+  if (e == hipSuccess)
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_loo_fit),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPctLdsBudget);
   return e;
 }
 hipError_t launch_percentiles(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
@@ -500,6 +504,43 @@ hipError_t launch_fitpct_select(hipStream_t st, const ChainState& S, int64_t c0,
   k_fitpct_select<<<dim3((unsigned)(n * n_groups)), dim3(kPctThreads), lds, st>>>(
       S, c0, take, m, cols, (int)n_groups, vs_step, vs_point, pc, use_lds ? 1 : 0, together ? 1 : 0,
       pct_column_pitch(take, cols), vals, pct, n_used, status);
+  return hipGetLastError();
+}
+
+
+// mhx_get_loo: the model-free fit (k_loo_fit), the block sums and the totals
+hipError_t launch_loo_fit(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take, int tail_len,
+                          int64_t m, bool use_lds, const double* terms, double* pw_elpd, double* pw_khat,
+                          double* pw_acc, double* tail, int32_t* status) {
+  static_assert(kLooCols == kLooColsPerGroup && sizeof(LdsHead) == 6144, "loo_lds_bytes (mhx_launch.hpp)");
+  if (n <= 0 || m <= 0) return hipSuccess;
+  const int P = loo_tail_length_of(take, tail_len);
+  const size_t lds = loo_lds_bytes(take, P, use_lds);
+  const int64_t n_groups = (m + kLooCols - 1) / kLooCols;
+  if (lds > kPctLdsBudget || n * n_groups > (int64_t)0x7fffffff) return hipErrorInvalidValue;
+  k_loo_fit<<<dim3((unsigned)(n * n_groups)), dim3(kPctThreads), lds, st>>>(
+      S, c0, take, tail_len, m, (int)n_groups, P, loo_p2(P), use_lds ? 1 : 0, pct_column_pitch(take, kLooCols),
+      terms, pw_elpd, pw_khat, pw_acc, tail, status);
+  return hipGetLastError();
+}
+hipError_t launch_loo_block_sums(hipStream_t st, int64_t n, int64_t m, int64_t blk0, int64_t nb_total,
+                                 double k_limit, const double* pw_elpd, const double* pw_lppd,
+                                 const double* pw_khat, double* part_elpd, double* part_lppd,
+                                 int32_t* part_high) {
+  if (n <= 0 || m <= 0) return hipSuccess;
+  const int64_t nb = loo_blocks(m), groups = (n * nb + kPctWaves - 1) / kPctWaves;
+  if (groups > (int64_t)0x7fffffff) return hipErrorInvalidValue;
+  k_loo_block_sums<<<dim3((unsigned)groups), dim3(kPctThreads), 0, st>>>(
+      n, m, (int)nb, blk0, nb_total, k_limit, pw_elpd, pw_lppd, pw_khat, part_elpd, part_lppd, part_high);
+  return hipGetLastError();
+}
+hipError_t launch_loo_totals(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
+                             int64_t nb_total, const double* part_elpd, const double* part_lppd,
+                             const int32_t* part_high, double* elpd, double* p_loo, double* lppd,
+                             int32_t* n_high, int32_t* n_used, int32_t* status) {
+  if (n <= 0) return hipSuccess;
+  k_loo_totals<<<dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, st>>>(
+      S, c0, n, take, nb_total, part_elpd, part_lppd, part_high, elpd, p_loo, lppd, n_high, n_used, status);
   return hipGetLastError();
 }
 

@@ -41,6 +41,7 @@ struct EngineKnobs {
   bool fitpct_no_lds = false;       // MHX_FITPCT_NO_LDS: k_fitpct_select reads its columns from the stage in every pass even where they fit LDS
   bool fitpct_select_singly = false;  // MHX_FITPCT_SELECT_SINGLY: k_fitpct_select runs select_percentile once per percentile (the form it was measured against)
   bool fitpct_step_fastest = false; // MHX_FITPCT_STEP_FASTEST: the staged values lie a point's steps side by side (measurement: DESIGN 4.9)
+  bool loo_no_lds = false;          // MHX_LOO_NO_LDS: k_loo_fit reads its columns from the staged terms in every pass even where they fit LDS
   bool planes_no_lds = false;       // MHX_PLANES_NO_LDS: a dataset per walker is streamed from memory even where it fits LDS
 #ifdef MHX_DEBUG_HOOKS
   bool test_lose_sweepers = false;  // MHX_TEST_LOSE_SWEEPERS: k_persist's sweep workgroups never come (test library)
@@ -59,7 +60,7 @@ inline EngineKnobs read_knobs() {
       {"MHX_NO_GRAPH", &EngineKnobs::no_graph}, {"MHX_SUMMARY_NO_LDS", &EngineKnobs::summary_no_lds},
       {"MHX_HISTO_NO_LDS", &EngineKnobs::histo_no_lds}, {"MHX_AUTOCORR_NO_LDS", &EngineKnobs::autocorr_no_lds},
       {"MHX_FITPCT_NO_LDS", &EngineKnobs::fitpct_no_lds}, {"MHX_FITPCT_STEP_FASTEST", &EngineKnobs::fitpct_step_fastest},
-      {"MHX_FITPCT_SELECT_SINGLY", &EngineKnobs::fitpct_select_singly},
+      {"MHX_FITPCT_SELECT_SINGLY", &EngineKnobs::fitpct_select_singly}, {"MHX_LOO_NO_LDS", &EngineKnobs::loo_no_lds},
       {"MHX_PLANES_NO_LDS", &EngineKnobs::planes_no_lds}, {"MHX_ENSEMBLE_NO_LDS", &EngineKnobs::ensemble_no_lds},
 #ifdef MHX_DEBUG_HOOKS
       {"MHX_TEST_LOSE_SWEEPERS", &EngineKnobs::test_lose_sweepers},

@@ -431,4 +431,78 @@ inline int fitpct_max_take(int64_t points, int n_pct) {
   return lo;
 }
 
+// ---- PSIS-LOO (mhx_get_loo): n chains at m points of a function of nb_total blocks.  What depends
+// on the chains alone comes first and keeps its place from one chunk of points to the next - status,
+// n_used, n_high [n], the totals elpd, p_loo, lppd [n], the blocks' partial sums [n][nb_total] (two
+// double arrays, one int) - then the chunk's per-point constants [m], the staged terms [n][take][m]
+// (a chain's window step by step, the points of a step side by side), the pointwise results pw_elpd,
+// pw_khat, pw_lppd [n][m] (always carved: the block sums read them) and, where the caller asked for
+// them (want bits 1, 2), pw_acc [n][m][4] and tail [n][m][P].
+constexpr int64_t kLooBlock = 256;  // points of a block of the sums (MHX_LOO_BLOCK)
+static_assert(kFitChunkPoints % kLooBlock == 0, "a chunk of points is whole blocks");
+enum { LOO_WANT_ACC = 1, LOO_WANT_TAIL = 2 };
+struct LooPieces {
+  size_t status, n_used, n_high, elpd, p_loo, lppd, part_elpd, part_lppd, part_high, cst, terms, pw_elpd, pw_khat,
+      pw_lppd, pw_acc, tail;
+};
+inline LooPieces carve_loo(Carver& c, int64_t nb_total, int take, int P, int want, int64_t n_, int64_t m_) {
+  const size_t n = (size_t)n_, m = (size_t)m_, nb = (size_t)nb_total;
+  LooPieces s;
+  s.status = c.take(n * sizeof(int32_t));
+  s.n_used = c.take(n * sizeof(int32_t));
+  s.n_high = c.take(n * sizeof(int32_t));
+  s.elpd = c.take(n * sizeof(double));
+  s.p_loo = c.take(n * sizeof(double));
+  s.lppd = c.take(n * sizeof(double));
+  s.part_elpd = c.take(n * nb * sizeof(double));
+  s.part_lppd = c.take(n * nb * sizeof(double));
+  s.part_high = c.take(n * nb * sizeof(int32_t));
+  s.cst = c.take(m * sizeof(double));
+  s.terms = c.take(n * m * (size_t)take * sizeof(double));
+  s.pw_elpd = c.take(n * m * sizeof(double));
+  s.pw_khat = c.take(n * m * sizeof(double));
+  s.pw_lppd = c.take(n * m * sizeof(double));
+  s.pw_acc = c.take((want & LOO_WANT_ACC) ? n * m * 4 * sizeof(double) : 0);
+  s.tail = c.take((want & LOO_WANT_TAIL) ? n * m * (size_t)P * sizeof(double) : 0);
+  return s;
+}
+// whether ONE chain's pieces at m points fit the budget
+inline bool loo_fits(int64_t nb_total, int take, int P, int want, int64_t m) {
+  return one_item_fits([&](Carver& c, int64_t n) { carve_loo(c, nb_total, take, P, want, n, m); });
+}
+// The cursor of the call, as fitpct_cursor: all of `points` where one chain fits the budget with
+// them (and they are at most kFitChunkPoints), else the largest whole number of blocks, at most
+// kFitChunkPoints, with which one chain fits.  chunk == 0: not even one block fits - the caller
+// refuses the call.
+inline PortionCursor loo_cursor(int64_t items, int64_t points, int take, int P, int want) {
+  const int64_t nb_total = (points + kLooBlock - 1) / kLooBlock;
+  PortionCursor at;
+  at.items = items;
+  at.points = points;
+  if (points <= kFitChunkPoints && loo_fits(nb_total, take, P, want, points)) {
+    at.chunk = points;
+  } else {
+    int64_t lo = 0, hi = std::min(points, kFitChunkPoints) / kLooBlock;  // blocks: lo fits, hi + 1 does not
+    while (lo < hi) {
+      const int64_t mid = (lo + hi + 1) / 2;
+      if (loo_fits(nb_total, take, P, want, mid * kLooBlock)) lo = mid; else hi = mid - 1;
+    }
+    at.chunk = lo * kLooBlock;
+  }
+  at.per_portion =
+      at.chunk > 0 ? portion_of([&](Carver& c, int64_t n) { carve_loo(c, nb_total, take, P, want, n, at.chunk); }) : 1;
+  return at;
+}
+// the greatest take at which one chain's smallest chunk of `points` fits, with the tail of P slots
+// the call asked for (0: none does)
+inline int loo_max_take(int64_t points, int P, int want) {
+  const int64_t nb_total = (points + kLooBlock - 1) / kLooBlock, m = std::min(points, kLooBlock);
+  int lo = 0, hi = 1 << 30;
+  while (lo < hi) {
+    const int mid = lo + (hi - lo + 1) / 2;
+    if (loo_fits(nb_total, mid, P, want, m)) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
 }  // namespace mhx

@@ -333,6 +333,61 @@ struct FitPctArgs {
   int32_t* status;   // [n] MHX_FITPCT_NONFINITE is or-ed in where a value is not finite
 };
 
+// mhx_get_loo's tail length M for a window of n steps (include/mhx.h: mhx_loo_tail_length), in
+// integer arithmetic: min(n / 5, R) with R the least integer whose square reaches 9 n, or
+// min(tail_len, n / 5) where the caller shortens the tail; below 5 there is no tail.
+#ifndef __HIPCC_RTC__
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+inline int32_t loo_tail_length_of(int64_t n, int32_t tail_len) {
+  if (n < 0) n = 0;
+  if (n > ((int64_t)1 << 40)) n = (int64_t)1 << 40;  // (far beyond where MHX_LOO_MAX_TAIL decides)
+  int64_t m = n / 5;
+  if (tail_len > 0) {
+    m = m < (int64_t)tail_len ? m : (int64_t)tail_len;
+  } else {
+    int64_t r = 0;
+    while (r < MHX_LOO_MAX_TAIL && r * r < 9 * n) ++r;
+    m = m < r ? m : r;
+  }
+  if (m > MHX_LOO_MAX_TAIL) m = MHX_LOO_MAX_TAIL;
+  return m < 5 ? 0 : (int32_t)m;
+}
+#endif
+
+// k_loo_values (mhx_get_loo): k_waic's walk with the log-sum-exp pair alone in registers; every
+// step's likelihood term of every point goes to the portion's stage piece for k_loo_fit, laid out
+// as k_fitpct_values lays its values: the term of point p at the step s-th from newest at
+// terms[i * take * m + s * m + p], a step's points side by side.  A wave serves one chain and one
+// block of kLooValBlock = kWave x kLooValPts points; n_blocks such blocks cover m.
+// kLooValPts = 2, k_fitpct_values' choice and for its reason: the terms are staged, `take` doubles
+// per chain and point, so the 64 MiB of a portion bound the points in flight (8 chains of 1000
+// points at take 1000), a wave's time is its window's steps one after the other whatever it holds,
+// and fewer points per lane spread the portion over more waves.  Measured at that shape with 4
+// points per lane (k_waic's): 888 ms of k_loo_values against k_fitpct_values' 505 ms.  The sums'
+// block, MHX_LOO_BLOCK = kWave x kLooPts, is k_loo_block_sums' alone; a chunk of points is whole
+// blocks of either.
+constexpr int kLooPts = MHX_LOO_BLOCK / kWave;
+static_assert(kLooPts * kWave == MHX_LOO_BLOCK && kLooPts == 4, "MHX_LOO_BLOCK (include/mhx.h)");
+static_assert(MHX_LOO_BLOCK == MHX_WAIC_BLOCK, "mhx_get_loo's sums follow mhx_get_waic's rule");
+constexpr int kLooValPts = 2;
+constexpr int kLooValBlock = kWave * kLooValPts;
+static_assert(MHX_LOO_BLOCK % kLooValBlock == 0, "a chunk of points is whole blocks of the value kernel too");
+struct LooArgs {
+  int64_t c0, n;
+  int32_t take, fn, n_blocks, pad_;
+  int64_t m;
+  const double* x0;
+  const double* x1;  // the second column of x, or nullptr
+  const double* y;
+  const double* w;
+  const double* c;
+  double* terms;     // [n][take * m]
+  double* pw_lppd;   // [n][m]
+  int32_t* status;   // [n] MHX_LOO_NONFINITE is or-ed in where a value or a term is not finite
+};
+
 // k_resid (mhx_get_residuals): function `fn` at ONE parameter vector per chain over the chain's own
 // data, for each of n chains from c0 on, and the block sums, counts and extreme of the standardized
 // residuals.  A wave serves one chain and one block of MHX_RESID_BLOCK = kWave x kResidPts points;

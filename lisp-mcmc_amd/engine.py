@@ -268,6 +268,36 @@ class _Summaries:
             out["n_used"].ctypes.data_as(capi.i32p), out["status"].ctypes.data_as(capi.i32p)))
         return out
 
+    def loo(self, fn, take, tail=0, k_limit=0.7, pointwise=False, accumulators=False):
+        """PSIS-LOO of every chain for function `fn` over the newest `take` steps (mhx_get_loo, which
+        has the definition): a dict of elpd_loo, p_loo, lppd [n_chains] (looic = -2 elpd_loo), n_high
+        [n_chains] (points whose Pareto khat exceeds k_limit), n_used and status [n_chains] (LOO_NONFINITE
+        1, LOO_SHORT 2, LOO_FLAT 4, LOO_EMPTY 8).  tail: the tail length, 0 for the rule
+        (loo_tail_length).  pointwise=True adds pw_elpd, pw_khat and pw_lppd [n_chains, N];
+        accumulators=True adds pw_acc [n_chains, N, 4] = (T_1, l_cut, S_b, sigma) and tail
+        [n_chains, N, P], T_1 .. T_M ascending and NaN beyond, P = loo_tail_length(take, tail)."""
+        n = self.n_chains
+        pts = getattr(self, "_datasets", {}).get(int(fn), (0, 1))[0]
+        if (pointwise or accumulators) and pts < 1:
+            raise ValueError("loo: function %d has no dataset set through this object" % int(fn))
+        out = {"elpd_loo": np.zeros(n), "p_loo": np.zeros(n), "lppd": np.zeros(n),
+               "n_high": np.zeros(n, dtype=np.int32), "n_used": np.zeros(n, dtype=np.int32),
+               "status": np.zeros(n, dtype=np.int32)}
+        if pointwise:
+            for k in ("pw_elpd", "pw_khat", "pw_lppd"):
+                out[k] = np.zeros((n, pts))
+        if accumulators:
+            out["pw_acc"] = np.zeros((n, pts, 4))
+            ok = int(take) >= 0 and 0 <= int(tail) <= capi.LOO_MAX_TAIL     # (else the call itself refuses)
+            out["tail"] = np.zeros((n, pts, loo_tail_length(int(take), int(tail)) if ok else 0))
+        capi.check(self._summary("loo")(
+            self._h, int(fn), int(take), int(tail), float(k_limit),
+            *(out[k].ctypes.data_as(capi.f64p) for k in ("elpd_loo", "p_loo", "lppd")),
+            *(out[k].ctypes.data_as(capi.i32p) for k in ("n_high", "n_used", "status")),
+            *(out[k].ctypes.data_as(capi.f64p) if k in out else None
+              for k in ("pw_elpd", "pw_khat", "pw_lppd", "pw_acc", "tail"))))
+        return out
+
     def residuals(self, fn, theta=None, z_limit=3.0, pointwise=False):
         """Goodness of fit of every walker for function `fn` at one parameter vector each
         (mhx_get_residuals, which has the definition): theta [n_chains, d], None: every chain's
@@ -447,6 +477,14 @@ def band_count(take):
     k = C.c_int64(0)
     capi.check(capi.lib().mhx_band_count(int(take), C.byref(k)))
     return k.value
+
+
+def loo_tail_length(n, tail=0):
+    """the tail PSIS-LOO fits in a window of n steps: min(n // 5, ceil(3 sqrt n)), or min(tail, n // 5)
+    where tail > 0 shortens it; 0 below 25 steps (mhx_loo_tail_length)"""
+    m = C.c_int32(0)
+    capi.check(capi.lib().mhx_loo_tail_length(int(n), int(tail), C.byref(m)))
+    return m.value
 
 
 def _x_columns(owner, fn, x, m):

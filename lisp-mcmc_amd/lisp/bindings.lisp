@@ -271,6 +271,22 @@ library, or without a gfx950 device, walker-create signals MHX-ERROR."
   (g :pointer) (fn :int) (take :int) (elpd :pointer) (lppd :pointer) (p-waic :pointer)
   (n-high :pointer) (pw-lppd :pointer) (pw-p :pointer) (pw-acc :pointer) (n-used :pointer)
   (status :pointer))
+;; PSIS-LOO: leave-one-out accuracy and Pareto k of every chain (status: a sum of the four constants)
+(defconstant +loo-nonfinite+ 1)
+(defconstant +loo-short+ 2)
+(defconstant +loo-flat+ 4)
+(defconstant +loo-empty+ 8)
+(defconstant +loo-max-tail+ 1024)
+(cffi:defcfun ("mhx_loo_tail_length" %mhx-loo-tail-length) :int
+  (n :int64) (tail-len :int32) (m :pointer))
+(cffi:defcfun ("mhx_get_loo" %mhx-get-loo) :int
+  (e :pointer) (fn :int) (take :int) (tail-len :int) (k-limit :double) (elpd-loo :pointer)
+  (p-loo :pointer) (lppd :pointer) (n-high :pointer) (n-used :pointer) (status :pointer)
+  (pw-elpd :pointer) (pw-khat :pointer) (pw-lppd :pointer) (pw-acc :pointer) (tail :pointer))
+(cffi:defcfun ("mhx_group_get_loo" %mhx-group-get-loo) :int
+  (g :pointer) (fn :int) (take :int) (tail-len :int) (k-limit :double) (elpd-loo :pointer)
+  (p-loo :pointer) (lppd :pointer) (n-high :pointer) (n-used :pointer) (status :pointer)
+  (pw-elpd :pointer) (pw-khat :pointer) (pw-lppd :pointer) (pw-acc :pointer) (tail :pointer))
 ;; credible bands: pointwise percentiles and moments of the fit (status: a sum of the three constants)
 (defconstant +fitpct-nonfinite+ 1)
 (defconstant +fitpct-one-step+ 2)

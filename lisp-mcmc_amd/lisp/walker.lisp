@@ -1204,6 +1204,57 @@ value or a likelihood term of a window is not finite: the reference would have t
 chains call walker-set-waic once and take its elements."
   (elt (walker-set-waic walker :take take) chain))
 
+;;; PSIS-LOO (Vehtari, Gelman and Gabry 2017) where walker-set-waic's :n-high says WAIC cannot tell:
+;;; the leave-one-out accuracy and the count of points whose Pareto khat exceeds K-LIMIT, every
+;;; chain in one call per function of a global fit (mhx_get_loo, whose comment in include/mhx.h has
+;;; the definition).  The totals only: the pointwise elpd and khat are the Python mirror's.
+(defun walker-set-loo (walker &key (take 1000) (tail 0) (k-limit 0.7d0))
+  "For every chain of the set the plist (:elpd-loo :p-loo :looic :lppd :n-high :n-used :status) over
+its newest TAKE steps, summed over the functions of a global fit: the leave-one-out expected log
+pointwise predictive density, lppd - elpd-loo, -2 elpd-loo, the log pointwise predictive density,
+the points whose Pareto khat exceeds K-LIMIT, the window, and a sum of +loo-short+, +loo-flat+ and
++loo-empty+.  TAIL: the tail length, 0 for the rule.  FLOATING-POINT-INVALID-OPERATION where a
+model value or a likelihood term of a window is not finite: the reference would have trapped there."
+  (let* ((n (walker-n-chains walker))
+         (k-fns (length (walker-function walker)))
+         (window (%bin-window walker take "walker-set-loo"))
+         (none (cffi:null-pointer))
+         (elpd-sum (make-array n :element-type 'double-float :initial-element 0d0))
+         (lppd-sum (make-array n :element-type 'double-float :initial-element 0d0))
+         (high (make-array n :element-type 'fixnum :initial-element 0))
+         (used (make-array n :element-type 'fixnum :initial-element 0))
+         (flags (make-array n :element-type 'fixnum :initial-element 0)))
+    (cffi:with-foreign-objects ((elpd :double n) (lppd :double n) (nh :int32 n) (nu :int32 n)
+                                (st :int32 n))
+      (dotimes (fn k-fns)
+        (%set-call walker #'%mhx-get-loo #'%mhx-group-get-loo
+                   fn window tail (coerce k-limit 'double-float)
+                   elpd none lppd nh nu st none none none none none)
+        (dotimes (c n)
+          (incf (aref elpd-sum c) (cffi:mem-aref elpd :double c))
+          (incf (aref lppd-sum c) (cffi:mem-aref lppd :double c))
+          (incf (aref high c) (cffi:mem-aref nh :int32 c))
+          (setf (aref used c) (cffi:mem-aref nu :int32 c))
+          ;; (the four status bits, function after function: a bit set once stays set)
+          (let ((now (cffi:mem-aref st :int32 c))
+                (before (aref flags c)))
+            (setf (aref flags c)
+                  (loop for b in (list +loo-nonfinite+ +loo-short+ +loo-flat+ +loo-empty+)
+                        sum (if (or (oddp (floor now b)) (oddp (floor before b))) b 0)))))))
+    (loop for c below n
+          do (when (oddp (aref flags c))
+               (error 'floating-point-invalid-operation
+                      :operation 'walker-set-loo :operands (list :chain c)))
+          collect (let ((elpd-loo (aref elpd-sum c)))
+                    (list :elpd-loo elpd-loo :p-loo (- (aref lppd-sum c) elpd-loo)
+                          :looic (* -2d0 elpd-loo) :lppd (aref lppd-sum c) :n-high (aref high c)
+                          :n-used (aref used c) :status (aref flags c))))))
+
+(defun walker-loo (walker &key (chain 0) (take 1000) (tail 0) (k-limit 0.7d0))
+  "One chain's entry of walker-set-loo.  The device call is the whole set's: for more than a few
+chains call walker-set-loo once and take its elements."
+  (elt (walker-set-loo walker :take take :tail tail :k-limit k-limit) chain))
+
 ;;; ------------------------------------------------------------------ data and fit M:1208-1283
 ;;; The numbers behind the reference's plots.  The :function lives on the device, so the fit
 ;;; curve is mhx_eval_function and the envelope of the model over the most probable two thirds of

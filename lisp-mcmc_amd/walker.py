@@ -1797,6 +1797,61 @@ def waic_compare(a, b):
     return {"elpd-diff": float(np.sum(diff)), "se": se}
 
 
+loo_compare = waic_compare      # (the same difference and standard error, of two walker_loo results)
+
+
+def _loo(walker, take, tail, k_limit, pointwise, chains, who):
+    e = walker.engine
+    window = _bin_window(walker, take, who)
+    parts = [e.loo(k, window, tail=0 if tail is None else int(tail), k_limit=k_limit, pointwise=pointwise)
+             for k in range(e.K)]
+    status = np.bitwise_or.reduce([r["status"] for r in parts])
+    which = range(e.n_chains) if chains is None else [chains]
+    bad = [c for c in which if status[c] & capi.LOO_NONFINITE]
+    if bad:
+        raise FloatingPointError(
+            "%s: a model value or a likelihood term is not finite at a step of walker(s) %s: the "
+            "reference would have signalled a floating-point trap here" % (who, bad[:8]))
+    out = []
+    for c in which:
+        elpd = _serial_sum([r["elpd_loo"][c] for r in parts])
+        lppd = _serial_sum([r["lppd"][c] for r in parts])
+        p = lppd - elpd if len(parts) > 1 else parts[0]["p_loo"][c]
+        entry = {"elpd-loo": float(elpd), "p-loo": float(p), "looic": float(-2.0 * elpd), "lppd": float(lppd),
+                 "n-high": int(sum(int(r["n_high"][c]) for r in parts)),
+                 "n-used": int(parts[0]["n_used"][c]), "status": int(status[c])}
+        if pointwise:
+            pw = np.concatenate([r["pw_elpd"][c] for r in parts])
+            entry["pointwise"] = pw
+            entry["khat"] = np.concatenate([r["pw_khat"][c] for r in parts])
+            with np.errstate(all="ignore"):
+                entry["se"] = float(np.sqrt(pw.size * np.var(pw, ddof=1))) if pw.size > 1 else float("nan")
+        out.append(entry)
+    return out
+
+
+def walker_set_loo(walker, take=1000, tail=None, k_limit=0.7, pointwise=False):
+    """Which model should have been fitted, where walker_set_waic's n-high says WAIC cannot tell:
+    PSIS-LOO (Vehtari, Gelman and Gabry 2017) of every chain of the set over its newest `take` steps
+    - one device call per function of a global fit (mhx_get_loo, which has the definition), no
+    history moved.  A list with, chain by chain, {"elpd-loo": the leave-one-out expected log
+    pointwise predictive density, "p-loo": lppd - elpd-loo, the effective number of parameters,
+    "looic": -2 elpd-loo, "lppd", "n-high": the points whose Pareto khat exceeds k_limit (their
+    estimate is unreliable: influential points and outliers), "n-used": the window, "status": a sum
+    of LOO_SHORT, LOO_FLAT, LOO_EMPTY}, the totals summed over the functions.  tail: the tail
+    length, None for the rule min(n // 5, ceil(3 sqrt n)) - shorten it for an autocorrelated chain.
+    pointwise=True adds "pointwise", the elpd_i of all functions' points one after another, "khat"
+    beside them and "se" = sqrt(N var(elpd_i)) (the variance with N - 1): what loo_compare takes.
+    Raises FloatingPointError where a model value or a likelihood term of a window is not finite."""
+    return _loo(walker, take, tail, k_limit, pointwise, None, "walker-set-loo")
+
+
+def walker_loo(walker, chain=0, take=1000, tail=None, k_limit=0.7, pointwise=False):
+    """One chain's entry of walker_set_loo (and only that chain's trap).  The device call is the
+    whole set's: for more than a few chains call walker_set_loo once and index its result."""
+    return _loo(walker, take, tail, k_limit, pointwise, int(chain), "walker-loo")[0]
+
+
 def waic_merge(acc, n_used):
     """ONE WAIC from the chains of a set that share their data: pools the accumulators pw_acc
     [n_chains, N, 4] = (M, S, mean, M2) of Engine.waic(..., accumulators=True) over the chains,
