@@ -158,12 +158,13 @@ def _dataset_hp(s, k):
 def hp_logpost(s, theta):
     """(log-posterior, sum |term|) of a Spec whose bounds are off, summed over the points and the
     functions.  Normal: per point orc_log_normal's (a + b) + c with a = -1/2 log 2 pi,
-    b = -log sigma, c = -1/2 ((y - f) / sigma)^2; Poisson: orc_log_poisson's
-    (k log lambda - lambda) - log-factorial(k).  The first in high precision, the second a float"""
+    b = -log sigma, c = -1/2 ((y - f) / sigma)^2; with the cutoff that term clamped from below,
+    (max -5000d0 term) M:426; Poisson: orc_log_poisson's (k log lambda - lambda) - log-factorial(k).
+    The first in high precision, the second a float"""
     E = hp()
     total, scale = E.num(0), 0.0
     for k, ((model, shape, idx), (x, y, sig, lik), b) in enumerate(zip(s.fns, s.data, s.bounds)):
-        assert lik in (pb.NORMAL, pb.POISSON) and b is None
+        assert lik in (pb.NORMAL, pb.CUTOFF, pb.POISSON) and b is None
         xs, ys, sg, cst = _dataset_hp(s, k)
         f = hp_values(model, shape, np.asarray(theta)[idx], xs)
         for i in range(len(xs)):
@@ -172,6 +173,8 @@ def hp_logpost(s, theta):
             else:
                 q = (ys[i] - f[i]) / sg[i]
                 term = cst[i] - q * q / 2
+                if lik == pb.CUTOFF and term < -5000:
+                    term = E.num(-5000)
             total += term
             scale += abs(float(term))
     return total, scale
