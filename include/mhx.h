@@ -79,6 +79,8 @@ extern "C" {
 #define MHX_MAX_GRID_BINS 64 /* bins a side of one mhx_get_pair_grids grid               */
 #define MHX_MAX_GRID_PAIRS 4096 /* pairs one mhx_get_pair_grids call may count            */
 #define MHX_MAX_AUTOCORR_LAG 1023 /* greatest lag of one mhx_get_autocorr call              */
+#define MHX_MAX_HDI_MASSES 8 /* masses one mhx_get_hdi call may ask for                   */
+#define MHX_MAX_HDI_LADDER 4096 /* ranks of one column's quantile ladder (mhx_get_hdi)    */
 
 /* ---- status codes ------------------------------------------------------ */
 enum {
@@ -1232,6 +1234,70 @@ int mhx_group_get_traces(mhx_group* g, int take, int filter, int stride, int sta
  * start + stride, ...  Host only: needs no engine and no device.  MHX_EINVAL unless n_kept >= 0,
  * stride >= 1, 0 <= start < stride. */
 int mhx_trace_rows(int64_t n_kept, int32_t stride, int32_t start, int64_t* rows);
+
+/* Highest-density intervals and quantile ladders of every chain, on the device: the narrowest
+ * interval that holds a given mass of a column's window, and the window's quantile function at
+ * evenly spaced ranks.  This library's own definition (the reference's intervals are equal-tailed:
+ * mhx_get_percentiles); the one read-out that orders a window.  For chain c and column cols[j]:
+ *   window    that of mhx_get_percentiles: the newest n = min(take, walker-length, steps held)
+ *             steps; n_used[c] = n.
+ *   order     s_0 .. s_{n-1}: the column's window values in ascending order of the key of
+ *             mhx_get_percentiles - -0 before +0, every NaN last.
+ *   span      of the mass mass_num[q] / mass_den[q] per cent: g = min(floor(n num / (100 den)),
+ *             n - 1) in exact integers = mhx_hdi_span(n, num, den).
+ *   interval  w_i = s_{i+g} - s_i for i = 0 .. n-1-g, each ONE IEEE subtraction of the two doubles;
+ *             pos[c][q][j] = the least i whose w_i is not greater than any other (of equal least
+ *             widths the lowest interval); lo[c][q][j] = s_pos and hi[c][q][j] = s_{pos+g}, numbers
+ *             of the ring bit for bit (the subtraction itself is never returned).  A mass of 100
+ *             gives the window's least and greatest value.
+ *   ladder    n_ladder = L is 0 or in [2, MHX_MAX_HDI_LADDER]: ladder[c][j][i] = s_{r_i} with
+ *             r_i = floor(i (n - 1) / (L - 1)) in exact integers, i = 0 .. L-1 (ranks repeat where
+ *             n < L).  A NaN comes back as the NaN mhx_get_percentiles returns for it.
+ *   status    status[c][j] = MHX_HDI_NONFINITE where the column's window holds a value that is not
+ *             finite; lo, hi and pos of that column are then unspecified (hi and lo are still
+ *             values of the window, pos a rank in range), its ladder stays defined, and the other
+ *             columns of the chain are unaffected.
+ * cols: distinct indices in [0, d), 1 <= n_cols <= d, as mhx_get_histograms; 0 <= n_mass <=
+ * MHX_MAX_HDI_MASSES, each mass with 1 <= den <= 1000000 and 1 <= num <= 100 den.  lo, hi, pos
+ * [n_chains][n_mass][n_cols] (the layout of mhx_get_percentiles' out), ladder
+ * [n_chains][n_cols][n_ladder], status [n_chains][n_cols], n_used [n_chains]; any output may be
+ * NULL.  MHX_EINVAL on any other argument and when the pieces of ONE chain exceed the 64 MiB of a
+ * portion - which happens only where the keys of the padded windows (n_cols columns of the least
+ * power of two >= take, 8 bytes each) lie in memory, not in a workgroup's LDS: 63 columns of a
+ * window of 2^17 steps with ladders of 4096 ranks.
+ * MHX_ESTATE before mhx_init_chains.  Worked through in portions whose device scratch stays below
+ * 64 MiB; mhx_get_summary_timing covers the call. */
+enum {
+  MHX_HDI_NONFINITE = 1
+};
+int mhx_get_hdi(mhx_engine* e, int take, const int32_t* cols, int n_cols, const int32_t* mass_num,
+                const int32_t* mass_den, int n_mass, int n_ladder, double* lo, double* hi,
+                int32_t* pos, double* ladder, int32_t* n_used, int32_t* status);
+/* The same of derived quantities: mhx_get_derived's expressions (its grammar, compile cache and
+ * value kernel, `prob` included) evaluated at every step of the window take the ring columns'
+ * place, expression k as column k (n_cols = n_expr).  status[c][k] = MHX_HDI_NONFINITE where a
+ * value of expression k is not finite, as mhx_get_derived's status.  Refuses what mhx_get_derived
+ * refuses of exprs, names, index and take. */
+int mhx_get_derived_hdi(mhx_engine* e, const char* const* exprs, int n_expr,
+                        const char* const* names, const int32_t* index, int n_names, int take,
+                        const int32_t* mass_num, const int32_t* mass_den, int n_mass, int n_ladder,
+                        double* lo, double* hi, int32_t* pos, double* ladder, int32_t* n_used,
+                        int32_t* status);
+/* The same for a group, in global chain order; every device's work is enqueued before any is
+ * waited for. */
+int mhx_group_get_hdi(mhx_group* g, int take, const int32_t* cols, int n_cols,
+                      const int32_t* mass_num, const int32_t* mass_den, int n_mass, int n_ladder,
+                      double* lo, double* hi, int32_t* pos, double* ladder, int32_t* n_used,
+                      int32_t* status);
+int mhx_group_get_derived_hdi(mhx_group* g, const char* const* exprs, int n_expr,
+                              const char* const* names, const int32_t* index, int n_names, int take,
+                              const int32_t* mass_num, const int32_t* mass_den, int n_mass,
+                              int n_ladder, double* lo, double* hi, int32_t* pos, double* ladder,
+                              int32_t* n_used, int32_t* status);
+/* *g = the span of a mass of num/den per cent among n sorted values: min(floor(n num / (100 den)),
+ * n - 1), in exact integers whatever n.  Host only: needs no engine and no device.  MHX_EINVAL
+ * unless n >= 1, 1 <= den <= 1000000 and 1 <= num <= 100 den. */
+int mhx_hdi_span(int64_t n, int32_t num, int32_t den, int64_t* g);
 
 /* Restore a saved walk (walker-load, sketched in the comments M:987-1001): prob[n], theta[n][d]
  * NEWEST FIRST, as walker-save would have written them.  Sets the ring (newest

@@ -11,7 +11,7 @@ importlib.import_module("lisp-mcmc_amd").
 """
 from . import _capi as capi  # noqa: F401
 from ._capi import MhxError  # noqa: F401
-from .engine import Engine, Group, band_count, loo_tail_length, comm_unique_id, partition, split_rhat, ensemble_pick, trace_rows, normeq_steps  # noqa: F401
+from .engine import Engine, Group, band_count, loo_tail_length, comm_unique_id, partition, split_rhat, ensemble_pick, trace_rows, normeq_steps, hdi_span  # noqa: F401
 from . import models  # noqa: F401
 from . import sexpr  # noqa: F401
 from . import distributed  # noqa: F401
@@ -28,6 +28,7 @@ from .walker import (  # noqa: F401
     make_histo, make_histo_x, histo_edges, walker_param_histo, walker_set_param_histo,
     walker_set_corner_grid,
     autocorr, walker_autocorr, walker_set_autocorr, walker_set_rhat, walker_set_ensemble_get,
+    hdi, walker_set_hdi, walker_hdi, walker_set_quantiles,
     walker_set_waic, walker_waic, waic_compare, waic_merge,
     walker_set_loo, walker_loo, loo_compare,
     walker_set_trace, walker_set_catepillar,
@@ -49,6 +50,7 @@ __all__ = ["capi", "MhxError", "Engine", "Group", "comm_unique_id", "partition",
            "walker_set_corner_grid",
            "autocorr", "walker_autocorr", "walker_set_autocorr", "walker_set_rhat", "split_rhat",
            "walker_set_ensemble_get", "ensemble_pick",
+           "hdi", "hdi_span", "walker_set_hdi", "walker_hdi", "walker_set_quantiles",
            "walker_set_waic", "walker_waic", "waic_compare", "waic_merge",
            "walker_set_loo", "walker_loo", "loo_compare", "loo_tail_length",
            "trace_rows", "walker_set_trace", "walker_set_catepillar",

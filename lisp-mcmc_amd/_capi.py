@@ -32,6 +32,7 @@ RESID_NONFINITE, RESID_BLOCK = 1, 256
 NORMEQ_NONFINITE, NORMEQ_BLOCK = 1, 1024
 CAND_KEEP_MAX = 16
 FITPCT_NONFINITE, FITPCT_ONE_STEP, FITPCT_EMPTY, FITPCT_BLOCK = 1, 2, 4, 128
+HDI_NONFINITE, MAX_HDI_MASSES, MAX_HDI_LADDER = 1, 8, 4096
 TRACE_STEPS, TRACE_UNIQUE, TRACE_FORWARD, TRACE_PROB = 0, 1, 2, -1
 
 
@@ -199,6 +200,17 @@ SIGNATURES = {
     "mhx_group_get_traces": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, i32p, C.c_int,
                                        C.c_int, f64p, f64p, f64p, i32p, i32p, i32p]),
     "mhx_trace_rows": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, i64p]),
+    "mhx_hdi_span": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, i64p]),
+    "mhx_get_hdi": (C.c_int, [C.c_void_p, C.c_int, i32p, C.c_int, i32p, i32p, C.c_int, C.c_int, f64p, f64p, i32p,
+                              f64p, i32p, i32p]),
+    "mhx_group_get_hdi": (C.c_int, [C.c_void_p, C.c_int, i32p, C.c_int, i32p, i32p, C.c_int, C.c_int, f64p, f64p,
+                                    i32p, f64p, i32p, i32p]),
+    "mhx_get_derived_hdi": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_char_p), i32p,
+                                      C.c_int, C.c_int, i32p, i32p, C.c_int, C.c_int, f64p, f64p, i32p, f64p, i32p,
+                                      i32p]),
+    "mhx_group_get_derived_hdi": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_char_p),
+                                            i32p, C.c_int, C.c_int, i32p, i32p, C.c_int, C.c_int, f64p, f64p, i32p,
+                                            f64p, i32p, i32p]),
 }
 
 _lib = None

@@ -3732,6 +3732,164 @@ int mhx_get_autocorr(mhx_engine* e, int take, const int32_t* cols, int n_cols, i
   return rc != MHX_OK ? rc : run_portions(e, q);
 }
 
+// ---- highest-density intervals and quantile ladders of every chain on the device (k_hdi;
+// include/mhx.h has the definition): the window's columns - the ring's, or the values of derived
+// expressions staged by mhx_user_derived - sorted as keys.  A portion's pieces: the staged values
+// (derived form), lo, hi, pos, the ladder, n_used, status and, on the memory path, the keys.
+extern "C++" {
+static int hdi_mass_check(int32_t num, int32_t den) {
+  return den >= 1 && den <= 1000000 && num >= 1 && (int64_t)num <= (int64_t)100 * den;
+}
+struct HdiCall {
+  int take = 0, n_cols = 0, n_mass = 0, n_ladder = 0;
+  bool derived = false, lds = false;  // lds: the path on this call's engine (check)
+  ColList cl{};
+  int32_t num[MHX_MAX_HDI_MASSES] = {0}, den[MHX_MAX_HDI_MASSES] = {0};
+  DerivedCall dq;  // the derived form's texts, names and compiled module
+  enum { LO, HI, POS, LADDER, N_USED, STATUS };
+  HostDst dst[6];
+
+  // cols NULL: the derived form, n_cols_ expressions that dq has already taken
+  int prepare(const std::vector<mhx_engine*>& engs, int take_, const int32_t* cols, int n_cols_,
+              const int32_t* mass_num, const int32_t* mass_den, int n_mass_, int n_ladder_, double* lo, double* hi,
+              int32_t* pos, double* ladder, int32_t* n_used, int32_t* status) {
+    int rc = MHX_OK;
+    for (const mhx_engine* e : engs)
+      if ((rc = window_check(e, take_)) != MHX_OK) return rc;
+    const int d = engs[0]->P.d;
+    if (!derived) {
+      if (n_cols_ < 1 || n_cols_ > d || !cols) return fail(MHX_EINVAL, "n_cols must be in [1, d = %d]", d);
+      if ((rc = fill_cols(&cl, cols, n_cols_, d)) != MHX_OK) return rc;
+    } else {
+      cl = ColList{};
+      cl.n = n_cols_;
+    }
+    if (n_mass_ < 0 || n_mass_ > MHX_MAX_HDI_MASSES || (n_mass_ > 0 && (!mass_num || !mass_den)))
+      return fail(MHX_EINVAL, "n_mass must be in [0,%d]", MHX_MAX_HDI_MASSES);
+    for (int q = 0; q < n_mass_; ++q) {
+      if (!hdi_mass_check(mass_num[q], mass_den[q]))
+        return fail(MHX_EINVAL, "mass %d: %d/%d is outside (0, 100] or its denominator outside [1, 1000000]", q,
+                    mass_num[q], mass_den[q]);
+      num[q] = mass_num[q], den[q] = mass_den[q];
+    }
+    if (n_ladder_ != 0 && (n_ladder_ < 2 || n_ladder_ > MHX_MAX_HDI_LADDER))
+      return fail(MHX_EINVAL, "n_ladder must be 0 or in [2,%d]", MHX_MAX_HDI_LADDER);
+    take = take_, n_cols = n_cols_, n_mass = n_mass_, n_ladder = n_ladder_;
+    const size_t cell = (size_t)n_mass * (size_t)n_cols;
+    dst[LO] = {lo, cell * sizeof(double)}, dst[HI] = {hi, cell * sizeof(double)};
+    dst[POS] = {pos, cell * sizeof(int32_t)};
+    dst[LADDER] = {ladder, (size_t)n_cols * (size_t)n_ladder * sizeof(double)};
+    dst[N_USED] = {n_used, sizeof(int32_t)}, dst[STATUS] = {status, (size_t)n_cols * sizeof(int32_t)};
+    return MHX_OK;
+  }
+  int check(mhx_engine* e) {
+    int rc = window_check(e, take);
+    if (rc != MHX_OK) return rc;
+    if (derived) {
+      if ((rc = dq.check(e)) != MHX_OK) return rc;
+    } else {
+      for (int c = 0; c < cl.n; ++c)
+        if (cl.idx[c] >= e->P.d) return fail(MHX_EINVAL, "cols[%d] = %d outside [0,%d)", c, cl.idx[c], e->P.d);
+    }
+    lds = hdi_use_lds(take, n_cols, e->knobs);
+    if (!one_item_fits([&](Carver& c, int64_t n) { carve(e, c, n, 1); }))
+      return fail(MHX_EINVAL, "the pieces of ONE chain (the keys of %d columns of %lld slots among them) exceed the "
+                              "stage budget of %zu bytes", n_cols, (long long)hdi_pad(take), kStageBudget);
+    return MHX_OK;
+  }
+  int64_t items(const mhx_engine* e) const { return e->cfg.n_chains; }
+  int64_t points() const { return 1; }
+  HdiPieces carve(const mhx_engine*, Carver& c, int64_t n, int64_t) const {
+    return carve_hdi(c, n_cols, n_mass, n_ladder, take, derived ? 1 : 0, lds ? 0 : hdi_pad(take), n);
+  }
+  // (the kernel writes every entry that collect() copies: nothing to clear)
+  int upload(mhx_engine*, const Portion&) const { return MHX_OK; }
+  int launch(mhx_engine* e, const Portion& p) const {
+    Carver c;
+    const HdiPieces s = carve(e, c, p.n, p.m);
+    HdiArgs A{};
+    A.c0 = p.i0;
+    A.take = take, A.n_mass = n_mass, A.n_ladder = n_ladder;
+    A.use_lds = lds ? 1 : 0;
+    A.tpad = (int32_t)hdi_pad(take);
+    for (int q = 0; q < n_mass; ++q) A.mass_num[q] = num[q], A.mass_den[q] = den[q];
+    A.cl = cl;
+    if (derived) {
+      DerivedArgs D{};
+      D.c0 = p.i0;
+      D.n = p.n;
+      D.take = take;
+      D.pitch = take;
+      for (int j = 0; j < dq.n_names; ++j) D.idx[j] = dq.idx[j];
+      D.values = stage_at<double>(e, s.values);
+      D.at_best = nullptr;
+      HIP_TRY(rtc_launch_derived(*dq.prog, e->stream, e->S, D));
+      A.vals = D.values;
+      A.vals_chain = (int64_t)n_cols * take, A.vals_col = take, A.vals_step = 1;
+      ++e->launches;
+    }
+    A.keys = lds ? nullptr : stage_at<unsigned long long>(e, s.keys);
+    A.lo = stage_at<double>(e, s.lo), A.hi = stage_at<double>(e, s.hi);
+    A.pos = stage_at<int32_t>(e, s.pos);
+    A.ladder = stage_at<double>(e, s.ladder);
+    A.n_used = stage_at<int32_t>(e, s.n_used), A.status = stage_at<int32_t>(e, s.status);
+    HIP_TRY(launch_hdi(e->stream, e->S, p.n, A));
+    ++e->launches;
+    return MHX_OK;
+  }
+  int collect(mhx_engine* e, const Portion& p) const {
+    Carver c;
+    const HdiPieces s = carve(e, c, p.n, p.m);
+    return copy_back_each(e, dst, p, {s.lo, s.hi, s.pos, s.ladder, s.n_used, s.status});
+  }
+};
+// the two forms over the engines of one call (first NULL: one engine)
+static int hdi_run(const std::vector<mhx_engine*>& engs, const int64_t* first, int take, const int32_t* cols,
+                   int n_cols, const int32_t* mass_num, const int32_t* mass_den, int n_mass, int n_ladder,
+                   double* lo, double* hi, int32_t* pos, double* ladder, int32_t* n_used, int32_t* status) {
+  HdiCall q;
+  const int rc = q.prepare(engs, take, cols, n_cols, mass_num, mass_den, n_mass, n_ladder, lo, hi, pos, ladder,
+                           n_used, status);
+  return rc != MHX_OK ? rc : run_portions(engs, first, q);
+}
+static int derived_hdi_run(const std::vector<mhx_engine*>& engs, const int64_t* first, const char* const* exprs,
+                           int n_expr, const char* const* names, const int32_t* index, int n_names, int take,
+                           const int32_t* mass_num, const int32_t* mass_den, int n_mass, int n_ladder, double* lo,
+                           double* hi, int32_t* pos, double* ladder, int32_t* n_used, int32_t* status) {
+  HdiCall q;
+  q.derived = true;
+  int rc = q.dq.prepare(exprs, n_expr, names, index, n_names, take, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
+                        nullptr, nullptr, nullptr, nullptr);
+  if (rc == MHX_OK)
+    rc = q.prepare(engs, take, nullptr, n_expr, mass_num, mass_den, n_mass, n_ladder, lo, hi, pos, ladder, n_used,
+                   status);
+  return rc != MHX_OK ? rc : run_portions(engs, first, q);
+}
+}  // extern "C++"
+
+int mhx_hdi_span(int64_t n, int32_t num, int32_t den, int64_t* g) {
+  if (n < 1) return fail(MHX_EINVAL, "n must be >= 1");
+  if (!hdi_mass_check(num, den))
+    return fail(MHX_EINVAL, "the mass %d/%d is outside (0, 100] or its denominator outside [1, 1000000]", num, den);
+  if (g) *g = hdi_span_of(n, num, den);
+  return MHX_OK;
+}
+int mhx_get_hdi(mhx_engine* e, int take, const int32_t* cols, int n_cols, const int32_t* mass_num,
+                const int32_t* mass_den, int n_mass, int n_ladder, double* lo, double* hi, int32_t* pos,
+                double* ladder, int32_t* n_used, int32_t* status) {
+  if (!e) return fail(MHX_EINVAL, "engine is NULL");
+  return hdi_run({e}, nullptr, take, cols, n_cols, mass_num, mass_den, n_mass, n_ladder, lo, hi, pos, ladder, n_used,
+                 status);
+}
+int mhx_get_derived_hdi(mhx_engine* e, const char* const* exprs, int n_expr, const char* const* names,
+                        const int32_t* index, int n_names, int take, const int32_t* mass_num,
+                        const int32_t* mass_den, int n_mass, int n_ladder, double* lo, double* hi, int32_t* pos,
+                        double* ladder, int32_t* n_used, int32_t* status) {
+  if (!e) return fail(MHX_EINVAL, "engine is NULL");
+  return derived_hdi_run({e}, nullptr, exprs, n_expr, names, index, n_names, take, mass_num, mass_den, n_mass,
+                         n_ladder, lo, hi, pos, ladder, n_used, status);
+}
+
 // ---- ensemble percentiles: ONE posterior from all chains of a walker set (k_ensemble_digits;
 // include/mhx.h has the definitions, mhx_ensemble.hpp the bookkeeping).  Eight count passes and,
 // where a `between` rank is the last of its run, one successor pass.  Per pass and engine: the
@@ -4569,6 +4727,22 @@ int mhx_group_get_autocorr(mhx_group* g, int take, const int32_t* cols, int n_co
   AutocorrCall q;
   const int rc = q.prepare(g->eng, take, cols, n_cols, max_lag, tau, ess, acf, half_mean, half_var, n_lags, n_used, status);
   return rc != MHX_OK ? rc : run_portions(g, q);
+}
+
+int mhx_group_get_hdi(mhx_group* g, int take, const int32_t* cols, int n_cols, const int32_t* mass_num,
+                      const int32_t* mass_den, int n_mass, int n_ladder, double* lo, double* hi, int32_t* pos,
+                      double* ladder, int32_t* n_used, int32_t* status) {
+  if (!g) return fail(MHX_EINVAL, "group is NULL");
+  return hdi_run(g->eng, g->first.data(), take, cols, n_cols, mass_num, mass_den, n_mass, n_ladder, lo, hi, pos,
+                 ladder, n_used, status);
+}
+int mhx_group_get_derived_hdi(mhx_group* g, const char* const* exprs, int n_expr, const char* const* names,
+                              const int32_t* index, int n_names, int take, const int32_t* mass_num,
+                              const int32_t* mass_den, int n_mass, int n_ladder, double* lo, double* hi,
+                              int32_t* pos, double* ladder, int32_t* n_used, int32_t* status) {
+  if (!g) return fail(MHX_EINVAL, "group is NULL");
+  return derived_hdi_run(g->eng, g->first.data(), exprs, n_expr, names, index, n_names, take, mass_num, mass_den,
+                         n_mass, n_ladder, lo, hi, pos, ladder, n_used, status);
 }
 
 int mhx_group_get_ensemble_percentiles(mhx_group* g, int take, const int32_t* cols, int n_cols,

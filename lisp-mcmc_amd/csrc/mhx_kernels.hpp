@@ -3772,6 +3772,186 @@ __global__ __launch_bounds__(kPctThreads) void k_derived_summary(
     }
 }
 
+// mhx_get_hdi / mhx_get_derived_hdi (include/mhx.h has the definition): the only read-out that
+// ORDERS a window.  A column's values are laid down as order keys in n = the least power of two
+// >= max(t, 2) slots, the slots past t holding the greatest key (a NaN's: both sort last), and
+// sorted by a bitonic network: the merges of size k = 2, 4, .. n, each the passes of stride k/2
+// .. 1, a pass n/2 independent compare-exchanges.  The trip counts depend on n alone; the sorted
+// order of keys is unique, so any schedule of the network gives the same bits.
+//
+// hdi_network runs, on the n keys a[0 .. n) that stand at places base .. base + n of their
+// sequence, the passes of the merges k0 .. k1 whose stride is below n.  kWaveOnly: one wavefront
+// owns the keys and a pass ends at a wave barrier; else the workgroup, at __syncthreads.
+template <bool kWaveOnly>
+__device__ __forceinline__ void hdi_pass_end() {
+  if (kWaveOnly) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  } else {
+    __syncthreads();
+  }
+}
+template <bool kWaveOnly>
+__device__ __forceinline__ void hdi_network(unsigned long long* a, int n, int base, int k0, int k1) {
+  const int me = kWaveOnly ? lane_id() : (int)threadIdx.x, nt = kWaveOnly ? kWave : kPctThreads;
+  const int half = n >> 1;
+  for (int k = k0; k <= k1; k <<= 1)
+    for (int j = k >> 1 < half ? k >> 1 : half; j >= 1; j >>= 1) {
+      for (int p = me; p < half; p += nt) {
+        const int i = ((p & ~(j - 1)) << 1) | (p & (j - 1));
+        const bool up = ((base + i) & k) == 0;
+        const unsigned long long x = a[i], y = a[i + j];
+        if ((x > y) == up) {
+          a[i] = y;
+          a[i + j] = x;
+        }
+      }
+      hdi_pass_end<kWaveOnly>();
+    }
+}
+// The narrowest interval of span g among the sorted keys key_at(0 .. t), by one wavefront: lanes
+// stride over j, each keeps its least width w_j = s_{j+g} - s_j (one IEEE subtraction; finite
+// widths are non-negative, so their bits order as integers) at its lowest j; the wave's least
+// width, then the least j among the lanes that hold it.  All lanes return the same j; where a
+// width is a NaN (a column that is not finite) any j in range.
+template <class KeyAt>
+__device__ __forceinline__ int hdi_narrowest(KeyAt key_at, int t, int g) {
+  unsigned long long best = ~0ULL, at = ~0ULL;
+  for (int j = lane_id(); j + g < t; j += kWave) {
+    const unsigned long long b = bits_of(key_value(key_at(j + g)) - key_value(key_at(j)));
+    if (b < best || at == ~0ULL) best = b, at = (unsigned long long)j;
+  }
+  const unsigned long long least = wave_min_u64(best);
+  const unsigned long long j = wave_min_u64(best == least ? at : ~0ULL);
+  return j > (unsigned long long)(t - 1 - g) ? 0 : (int)j;
+}
+// What one sorted column gives, written by `parts` wavefronts of which this is wave `part`: the
+// intervals (a mass to a wave), the ladder (its ranks over all lanes) and the status.
+template <class KeyAt>
+__device__ __forceinline__ void hdi_outputs(KeyAt key_at, int t, const HdiArgs& A, int64_t i, int c, int part,
+                                            int parts) {
+  const int l = lane_id(), nc = A.cl.n;
+  for (int q = part; q < A.n_mass; q += parts) {
+    const int g = (int)hdi_span_of(t, A.mass_num[q], A.mass_den[q]);
+    const int j = hdi_narrowest(key_at, t, g);
+    if (l == 0) {
+      const int64_t o = (i * A.n_mass + q) * nc + c;
+      A.lo[o] = key_value(key_at(j));
+      A.hi[o] = key_value(key_at(j + g));
+      A.pos[o] = j;
+    }
+  }
+  const int L = A.n_ladder;
+  for (int k = part * kWave + l; k < L; k += parts * kWave)
+    A.ladder[(i * nc + c) * L + k] = key_value(key_at((int)((int64_t)k * (t - 1) / (L - 1))));
+  if (part == 0 && l == 0) {
+    // -inf has the least key a value can have, +inf the greatest below the NaNs'
+    const bool bad = key_at(0) == 0x000fffffffffffffULL || key_at(t - 1) >= 0xfff0000000000000ULL;
+    A.status[i * nc + c] = bad ? 1 : 0;
+  }
+}
+// value s (any order of s within the window) of column c of chain i
+__device__ __forceinline__ double hdi_value(const HdiArgs& A, const Ring& ring, int64_t i, int c, int s) {
+  if (A.vals) return A.vals[i * A.vals_chain + c * A.vals_col + s * A.vals_step];
+  return ring.theta[(int64_t)ring.slot(s) * ring.d + A.cl.idx[c]];
+}
+__global__ __launch_bounds__(kPctThreads) void k_hdi(ChainState S, HdiArgs A) {
+  unsigned long long* lds = reinterpret_cast<unsigned long long*>(mhx_lds_raw);
+  const int w = wave_in_group(), tid = threadIdx.x, nc = A.cl.n, d = S.d;
+  const int64_t i = A.use_lds ? (int64_t)blockIdx.x : (int64_t)blockIdx.x / nc;
+  const Ring ring = ring_of(S, A.c0 + i);
+  const int t = ring_held(ring, A.take);
+  int n = 2;
+  while (n < t) n <<= 1;
+  if (t == 0) {  // (no step held: nothing to order)
+    if (A.use_lds || blockIdx.x % nc == 0) {
+      if (tid == 0) A.n_used[i] = 0;
+      for (int f = tid; f < A.n_mass * nc; f += kPctThreads)
+        A.lo[i * A.n_mass * nc + f] = A.hi[i * A.n_mass * nc + f] = 0.0, A.pos[i * A.n_mass * nc + f] = 0;
+      for (int f = tid; f < nc * A.n_ladder; f += kPctThreads) A.ladder[i * nc * A.n_ladder + f] = 0.0;
+      for (int f = tid; f < nc; f += kPctThreads) A.status[i * nc + f] = 0;
+    }
+    return;
+  }
+  if (A.use_lds) {
+    // one workgroup per chain: the window is read once, coalesced, by the whole workgroup; then
+    // wave w sorts and reads out the columns w, w + kPctWaves, .. on its own
+    const int cp = A.tpad + 1;
+    if (tid == 0) A.n_used[i] = t;
+    if (A.vals) {
+      for (int c = 0; c < nc; ++c)
+        for (int s = tid; s < n; s += kPctThreads)
+          lds[(size_t)c * cp + s] = s < t ? order_key(hdi_value(A, ring, i, c, s)) : ~0ULL;
+    } else {
+      const int64_t oldest = ring.nh - t;
+      const int ds = kPctThreads / d, dp = kPctThreads - ds * d;
+      int s = tid / d, p = tid - s * d;
+      for (int f = tid; f < t * d; f += kPctThreads) {
+        const int c = A.cl.of_param[p];
+        if (c >= 0) {
+          const int64_t slot = (oldest + s) & (int64_t)ring.mask;
+          lds[(size_t)c * cp + s] = order_key(ring.theta[slot * d + p]);
+        }
+        s += ds;
+        p += dp;
+        if (p >= d) {
+          p -= d;
+          ++s;
+        }
+      }
+      for (int c = 0; c < nc; ++c)
+        for (int s2 = t + tid; s2 < n; s2 += kPctThreads) lds[(size_t)c * cp + s2] = ~0ULL;
+    }
+    __syncthreads();
+    for (int c = w; c < nc; c += kPctWaves) {
+      unsigned long long* a = lds + (size_t)c * cp;
+      hdi_network<true>(a, n, 0, 2, n);
+      hdi_outputs([&](int s) { return a[s]; }, t, A, i, c, 0, 1);
+    }
+    return;
+  }
+  // one workgroup per (chain, column): the keys in the stage piece, sub-sequences of kHdiChunk
+  // keys finished in LDS, the passes of a greater stride in memory
+  const int c = (int)(blockIdx.x - i * nc);
+  unsigned long long* g = A.keys + (i * nc + c) * (int64_t)A.tpad;
+  if (c == 0 && tid == 0) A.n_used[i] = t;
+  const int ch = n < kHdiChunk ? n : kHdiChunk;
+  // the sub-sequence from `base` on through the merges k0 .. k1 in LDS; from_src: the keys are
+  // formed from the column's values, not read back
+  auto in_lds = [&](int base, int k0, int k1, bool from_src) {
+    for (int s = tid; s < ch; s += kPctThreads)
+      lds[s] = !from_src ? g[base + s] : base + s < t ? order_key(hdi_value(A, ring, i, c, base + s)) : ~0ULL;
+    __syncthreads();
+    hdi_network<false>(lds, ch, base, k0, k1);
+    if (n > ch) {
+      for (int s = tid; s < ch; s += kPctThreads) g[base + s] = lds[s];
+      __syncthreads();
+    }
+  };
+  for (int base = 0; base < n; base += ch) in_lds(base, 2, ch, true);
+  for (int k = ch << 1; k <= n; k <<= 1) {
+    for (int j = k >> 1; j >= ch; j >>= 1) {
+      for (int p = tid; p < (n >> 1); p += kPctThreads) {
+        const int e = ((p & ~(j - 1)) << 1) | (p & (j - 1));
+        const bool up = (e & k) == 0;
+        const unsigned long long x = g[e], y = g[e + j];
+        if ((x > y) == up) {
+          g[e] = y;
+          g[e + j] = x;
+        }
+      }
+      __syncthreads();
+    }
+    for (int base = 0; base < n; base += ch) in_lds(base, k, k, false);
+  }
+  // (a window of one chunk is still in LDS; a longer one is read from its piece)
+  if (n > ch)
+    hdi_outputs([&](int s) { return g[s]; }, t, A, i, c, w, kPctWaves);
+  else
+    hdi_outputs([&](int s) { return lds[s]; }, t, A, i, c, w, kPctWaves);
+}
+
 // mhx_get_covariances: :covariance-matrix M:541 = lplist-covariance (M:614-643) of :unique-steps
 // (M:492-496), one wavefront per chain.  uniq: [n][take] ring slots of the unique steps, newest
 // first (compacted in order like ring_forward_list); cov [n][d][d].

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mhx_finalize.hpp"
+#include "mhx_plan.hpp"
 #include "mhx_types.hpp"
 
 namespace mhx {
@@ -128,6 +129,10 @@ hipError_t launch_ensemble_digits(hipStream_t st, const ChainState& S, int64_t n
                                   const ColList& cl, const uint8_t* include, const EnsTask* tasks,
                                   int n_tasks, int mode, bool use_lds, uint64_t* counters,
                                   int32_t* n_used, int32_t* nan_flag);
+// mhx_get_hdi / mhx_get_derived_hdi (k_hdi) over the n chains from A.c0 on.  The caller chose the
+// path (hdi_use_lds, mhx_plan.hpp) and set A.tpad = hdi_pad(A.take); the LDS path takes
+// hdi_lds_bytes of LDS, the memory path a sub-sequence of up to kHdiChunk keys.
+hipError_t launch_hdi(hipStream_t st, const ChainState& S, int64_t n, const HdiArgs& A);
 hipError_t launch_covariances(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
                               int* uniq, double* cov, int32_t* n_unique, int32_t* status);
 // mhx_get_traces (k_traces): cols [n_cols] on the device, kept [n][take] scratch, values / lo / hi

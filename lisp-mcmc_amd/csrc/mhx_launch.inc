@@ -357,6 +357,16 @@ hipError_t launch_ensemble_digits(hipStream_t st, const ChainState& S, int64_t n
       reinterpret_cast<unsigned long long*>(counters), n_used, nan_flag);
   return hipGetLastError();
 }
+hipError_t launch_hdi(hipStream_t st, const ChainState& S, int64_t n, const HdiArgs& A) {
+  if (n <= 0 || A.cl.n <= 0) return hipSuccess;
+  if (A.tpad != hdi_pad(A.take)) return hipErrorInvalidValue;
+  const size_t lds = A.use_lds ? hdi_lds_bytes(A.take, A.cl.n) : (size_t)std::min(A.tpad, kHdiChunk) * sizeof(uint64_t);
+  const int64_t groups = A.use_lds ? n : n * A.cl.n;
+  static_assert(kHdiLdsBudget <= 64 * 1024 && kHdiChunk * sizeof(uint64_t) <= 64 * 1024, "no more LDS than a kernel has unasked");
+  if ((A.use_lds && lds > kHdiLdsBudget) || groups > 0x7fffffff || (!A.use_lds && !A.keys)) return hipErrorInvalidValue;
+  k_hdi<<<dim3((unsigned)groups), dim3(kPctThreads), lds, st>>>(S, A);
+  return hipGetLastError();
+}
 hipError_t launch_covariances(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
                               int* uniq, double* cov, int32_t* n_unique, int32_t* status) {
   if (n <= 0) return hipSuccess;

@@ -42,6 +42,7 @@ struct EngineKnobs {
   bool fitpct_select_singly = false;  // MHX_FITPCT_SELECT_SINGLY: k_fitpct_select runs select_percentile once per percentile (the form it was measured against)
   bool fitpct_step_fastest = false; // MHX_FITPCT_STEP_FASTEST: the staged values lie a point's steps side by side (measurement: DESIGN 4.9)
   bool loo_no_lds = false;          // MHX_LOO_NO_LDS: k_loo_fit reads its columns from the staged terms in every pass even where they fit LDS
+  bool hdi_no_lds = false;          // MHX_HDI_NO_LDS: k_hdi sorts every window in memory, one workgroup per (chain, column), even where a chain's keys fit LDS
   bool planes_no_lds = false;       // MHX_PLANES_NO_LDS: a dataset per walker is streamed from memory even where it fits LDS
 #ifdef MHX_DEBUG_HOOKS
   bool test_lose_sweepers = false;  // MHX_TEST_LOSE_SWEEPERS: k_persist's sweep workgroups never come (test library)
@@ -62,6 +63,7 @@ inline EngineKnobs read_knobs() {
       {"MHX_FITPCT_NO_LDS", &EngineKnobs::fitpct_no_lds}, {"MHX_FITPCT_STEP_FASTEST", &EngineKnobs::fitpct_step_fastest},
       {"MHX_FITPCT_SELECT_SINGLY", &EngineKnobs::fitpct_select_singly}, {"MHX_LOO_NO_LDS", &EngineKnobs::loo_no_lds},
       {"MHX_PLANES_NO_LDS", &EngineKnobs::planes_no_lds}, {"MHX_ENSEMBLE_NO_LDS", &EngineKnobs::ensemble_no_lds},
+      {"MHX_HDI_NO_LDS", &EngineKnobs::hdi_no_lds},
 #ifdef MHX_DEBUG_HOOKS
       {"MHX_TEST_LOSE_SWEEPERS", &EngineKnobs::test_lose_sweepers},
 #endif
@@ -336,6 +338,25 @@ inline bool planes_resident(const int64_t* n, const int* sigma_kind, int K_plane
     need += planes_shared_doubles(n[i], sigma_kind[i]) +
             (int64_t)waves_per_group * planes_wave_doubles(n[i], sigma_kind[i]);
   return need <= planes_lds_capacity(waves_per_group);
+}
+
+// Highest-density intervals (k_hdi): a column's window is sorted as keys in a power of two of
+// slots, hdi_pad(take) of them.  The LDS path lays a chain's nc columns down hdi_pad + 1 slots apart
+// (neighbouring columns then start two banks apart for the transposing store) and needs them all in
+// one workgroup's LDS; otherwise, or with MHX_HDI_NO_LDS=1, the memory path: the keys in a piece of
+// the stage buffer, one workgroup per (chain, column), which sorts a window of up to kHdiChunk keys
+// in 8 bytes of LDS a key.  kHdiLdsBudget is a CU's 160 KiB over eight: with more, fewer than eight
+// workgroups of four waves fit a CU, wave slots stay empty, and the LDS path was measured the slower
+// one (64 KiB a workgroup, 1.6 times; level at 16 KiB; 2.1 times the quicker at 8 KiB).
+constexpr size_t kHdiLdsBudget = (size_t)20 * 1024;
+inline int64_t hdi_pad(int64_t take) {
+  int64_t p = 2;
+  while (p < take) p <<= 1;
+  return p;
+}
+inline size_t hdi_lds_bytes(int take, int nc) { return (size_t)nc * (size_t)(hdi_pad(take) + 1) * sizeof(uint64_t); }
+inline bool hdi_use_lds(int take, int nc, const EngineKnobs& k) {
+  return !k.hdi_no_lds && hdi_lds_bytes(take, nc) <= kHdiLdsBudget;
 }
 
 // A repack of the chains still walking is due when a quarter of those dealt at the last deal

@@ -327,6 +327,28 @@ inline TracePieces carve_traces(Carver& c, int n_cols_, int max_out_, int take, 
   s.kept = c.take(n * (size_t)take * sizeof(int32_t));
   return s;
 }
+// highest-density intervals and quantile ladders: the staged values [n][nc][take] of the derived
+// form (with_values 0: empty, the ring's columns are read), lo, hi [n][n_mass][nc], pos of the same
+// shape, the ladder [n][nc][n_ladder], n_used [n], status [n][nc], and on the memory path the keys
+// [n][nc][key_pitch] (key_pitch 0, the LDS path: empty).  The keys of ONE chain may exceed the
+// budget (63 columns of a window of 2^17 steps): the caller asks one_item_fits first.
+struct HdiPieces {
+  size_t values, lo, hi, pos, ladder, n_used, status, keys;
+};
+inline HdiPieces carve_hdi(Carver& c, int nc_, int n_mass, int n_ladder, int take, int with_values,
+                           int64_t key_pitch, int64_t n_) {
+  const size_t n = (size_t)n_, nc = (size_t)nc_, nm = (size_t)n_mass;
+  HdiPieces s;
+  s.values = c.take(with_values ? n * nc * (size_t)take * sizeof(double) : 0);
+  s.lo = c.take(n * nm * nc * sizeof(double));
+  s.hi = c.take(n * nm * nc * sizeof(double));
+  s.pos = c.take(n * nm * nc * sizeof(int32_t));
+  s.ladder = c.take(n * nc * (size_t)n_ladder * sizeof(double));
+  s.n_used = c.take(n * sizeof(int32_t));
+  s.status = c.take(n * nc * sizeof(int32_t));
+  s.keys = c.take(n * nc * (size_t)key_pitch * sizeof(uint64_t));
+  return s;
+}
 // Whether ONE item of a piece list fits the budget at all, by portion_of's own accounting
 // (portion_of answers 1 either way: a read-out that must not outgrow the budget asks first).
 template <class Carve>

@@ -501,6 +501,43 @@ struct DerivedArgs {
 constexpr int kDerivedThreads = 256;  // one workgroup of four waves per chain, as k_percentiles
 constexpr unsigned kDerivedLdsBytes = 6144u;  // its dynamic LDS: LdsHead, the math tables
 
+// The span of a highest-density interval (include/mhx.h: mhx_hdi_span): of n sorted values, a mass
+// of num/den per cent reaches from s_j to s_{j+g}, g = min(floor(n num / (100 den)), n - 1), in
+// exact integers.  n = a D + b with D = 100 den and b < D gives a num + floor(b num / D): no
+// product leaves 64 bits.  The caller has checked n >= 1, 1 <= den <= 10^6, 1 <= num <= 100 den.
+#ifndef __HIPCC_RTC__
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+inline int64_t hdi_span_of(int64_t n, int32_t num, int32_t den) {
+  const int64_t D = (int64_t)100 * den, a = n / D, b = n % D;
+  const int64_t g = a * num + b * num / D;
+  return g < n - 1 ? g : n - 1;
+}
+#endif
+// k_hdi (mhx_get_hdi, mhx_get_derived_hdi): the windows of the chains from c0 on, nc columns each.
+// The source of the columns: the ring's parameters cl.idx[c] (vals NULL), or a staged array - the
+// value of step s (newest first) of column c of the launch's chain i is
+// vals[i * vals_chain + c * vals_col + s * vals_step] (cl then only counts the columns).
+//   use_lds = 1: one workgroup per chain, a column's keys in `tpad` slots of LDS, `tpad + 1` apart
+//   use_lds = 0: one workgroup per (chain, column), the keys in keys [n][nc][tpad]
+// tpad is a power of two >= 2 and >= take.  lo, hi, pos [n][n_mass][nc], ladder [n][nc][n_ladder],
+// n_used [n], status [n][nc].
+struct HdiArgs {
+  int64_t c0;
+  int32_t take, n_mass, n_ladder, use_lds, tpad;
+  int32_t mass_num[MHX_MAX_HDI_MASSES], mass_den[MHX_MAX_HDI_MASSES];
+  ColList cl;
+  const double* vals;
+  int64_t vals_chain, vals_col, vals_step;
+  unsigned long long* keys;
+  double *lo, *hi;
+  int32_t* pos;
+  double* ladder;
+  int32_t *n_used, *status;
+};
+constexpr int kHdiChunk = 4096;  // keys of a sub-sequence that k_hdi's memory path finishes in LDS
+
 struct RunDesc {
   int64_t n, sts, temp_steps, mwl, tail;
   int32_t auto_mode, has_mwl, adapt_mode;

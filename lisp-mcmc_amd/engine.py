@@ -214,6 +214,45 @@ class _Summaries:
             *(out[k].ctypes.data_as(capi.i32p) for k in ("n_lags", "n_used", "status"))))
         return out
 
+    def _hdi_outputs(self, masses, nc, ladder):
+        rat = [m if isinstance(m, tuple) else percentile_ratio(m) for m in masses]
+        n, nm, L = self.n_chains, len(rat), int(ladder)
+        out = {"lo": np.zeros((n, nm, nc)), "hi": np.zeros((n, nm, nc)),
+               "pos": np.zeros((n, nm, nc), dtype=np.int32), "ladder": np.zeros((n, nc, L)),
+               "n_used": np.zeros(n, dtype=np.int32), "status": np.zeros((n, nc), dtype=np.int32)}
+        num, nump = capi.as_i32([r[0] for r in rat] or [0])
+        den, denp = capi.as_i32([r[1] for r in rat] or [1])
+        args = (nump, denp, nm, L, out["lo"].ctypes.data_as(capi.f64p), out["hi"].ctypes.data_as(capi.f64p),
+                out["pos"].ctypes.data_as(capi.i32p), out["ladder"].ctypes.data_as(capi.f64p),
+                out["n_used"].ctypes.data_as(capi.i32p), out["status"].ctypes.data_as(capi.i32p))
+        return out, args, (num, den)
+
+    def hdi(self, take, masses, cols=None, ladder=0):
+        """the highest-density intervals of the parameters `cols` (None: all, in order) over every
+        chain's newest `take` steps (mhx_get_hdi, which has the definition): for each mass - a
+        number of per cent or a (num, den) pair, as for percentiles() - the narrowest interval
+        between two order statistics that holds it.  A dict of lo, hi and pos [n_chains,
+        len(masses), n_cols] (pos: the rank of lo in the sorted window), ladder [n_chains, n_cols,
+        ladder] (the sorted window at `ladder` evenly spaced ranks: 0, or 2..4096), n_used
+        [n_chains] and status [n_chains, n_cols] (1: the column holds a value that is not finite;
+        its lo, hi and pos are then unspecified)."""
+        cols = list(range(self.d)) if cols is None else [int(c) for c in cols]
+        ca, colp = capi.as_i32(cols or [0])
+        out, args, keep = self._hdi_outputs(masses, len(cols), ladder)
+        capi.check(self._summary("hdi")(self._h, int(take), colp, len(cols), *args))
+        return out
+
+    def derived_hdi(self, exprs, names, index, take, masses, ladder=0):
+        """hdi() of derived quantities (mhx_get_derived_hdi): the expressions of derived() in the
+        columns' place, expression k as column k."""
+        exprs, names = list(exprs), list(names)
+        idx, idxp = capi.as_i32(list(index) or [0])
+        ex = (C.c_char_p * max(len(exprs), 1))(*[t.encode() for t in exprs])
+        nm = (C.c_char_p * max(len(names), 1))(*[t.encode() for t in names])
+        out, args, keep = self._hdi_outputs(masses, len(exprs), ladder)
+        capi.check(self._summary("derived_hdi")(self._h, ex, len(exprs), nm, idxp, len(names), int(take), *args))
+        return out
+
     def ensemble_percentiles(self, take, pcts, cols=None, include=None):
         """ONE posterior from all chains (mhx_get_ensemble_percentiles, which has the definitions):
         nth-percentile of the pool of every included chain's newest `take` steps, for the
@@ -435,6 +474,22 @@ def trace_rows(n_kept, stride=1, start=0):
         raise ValueError(capi.lib().mhx_last_error().decode())
     capi.check(rc)
     return rows.value
+
+
+def hdi_span(n, mass):
+    """the span g of a highest-density interval of `mass` per cent - a number or a (num, den) pair -
+    among n sorted values: min(floor(n num / (100 den)), n - 1) (mhx_hdi_span: host arithmetic, no
+    device).  ValueError, with the library's message, unless n >= 1, 1 <= den <= 10^6 and
+    1 <= num <= 100 den."""
+    num, den = mass if isinstance(mass, tuple) else percentile_ratio(mass)
+    if not (-2 ** 31 <= int(num) < 2 ** 31 and -2 ** 31 <= int(den) < 2 ** 31):
+        raise ValueError("the mass %r/%r does not fit the ABI's 32-bit integers" % (num, den))
+    g = C.c_int64(0)
+    rc = capi.lib().mhx_hdi_span(int(n), int(num), int(den), C.byref(g))
+    if rc == capi.EINVAL:
+        raise ValueError(capi.lib().mhx_last_error().decode())
+    capi.check(rc)
+    return g.value
 
 
 def ensemble_pick(counts, rank):

@@ -335,6 +335,25 @@ library, or without a gfx950 device, walker-create signals MHX-ERROR."
   (n-used :pointer))
 (cffi:defcfun ("mhx_trace_rows" %mhx-trace-rows) :int
   (n-kept :int64) (stride :int32) (start :int32) (rows :pointer))
+;; highest-density intervals and quantile ladders: the one read-out that orders a window
+(cffi:defcfun ("mhx_hdi_span" %mhx-hdi-span) :int
+  (n :int64) (num :int32) (den :int32) (g :pointer))
+(cffi:defcfun ("mhx_get_hdi" %mhx-get-hdi) :int
+  (e :pointer) (take :int) (cols :pointer) (n-cols :int) (mass-num :pointer) (mass-den :pointer)
+  (n-mass :int) (n-ladder :int) (lo :pointer) (hi :pointer) (pos :pointer) (ladder :pointer)
+  (n-used :pointer) (status :pointer))
+(cffi:defcfun ("mhx_group_get_hdi" %mhx-group-get-hdi) :int
+  (g :pointer) (take :int) (cols :pointer) (n-cols :int) (mass-num :pointer) (mass-den :pointer)
+  (n-mass :int) (n-ladder :int) (lo :pointer) (hi :pointer) (pos :pointer) (ladder :pointer)
+  (n-used :pointer) (status :pointer))
+(cffi:defcfun ("mhx_get_derived_hdi" %mhx-get-derived-hdi) :int
+  (e :pointer) (exprs :pointer) (n-expr :int) (names :pointer) (index :pointer) (n-names :int)
+  (take :int) (mass-num :pointer) (mass-den :pointer) (n-mass :int) (n-ladder :int) (lo :pointer)
+  (hi :pointer) (pos :pointer) (ladder :pointer) (n-used :pointer) (status :pointer))
+(cffi:defcfun ("mhx_group_get_derived_hdi" %mhx-group-get-derived-hdi) :int
+  (g :pointer) (exprs :pointer) (n-expr :int) (names :pointer) (index :pointer) (n-names :int)
+  (take :int) (mass-num :pointer) (mass-den :pointer) (n-mass :int) (n-ladder :int) (lo :pointer)
+  (hi :pointer) (pos :pointer) (ladder :pointer) (n-used :pointer) (status :pointer))
 
 (defmacro with-c-call (&body body)
   "HIP/RCCL runtime code may raise inexact/invalid flags that SBCL turns into conditions;

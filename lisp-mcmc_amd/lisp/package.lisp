@@ -23,6 +23,7 @@
    #:make-histo #:make-histo-x #:walker-param-histo #:walker-set-param-histo
    #:walker-set-corner-grid
    #:walker-set-autocorr #:walker-set-rhat #:walker-set-ensemble-get
+   #:walker-set-hdi #:walker-hdi #:walker-set-quantiles
    #:walker-set-waic #:walker-waic #:walker-set-loo #:walker-loo
    #:walker-set-get-residuals #:walker-set-goodness-of-fit #:walker-goodness-of-fit #:runs-z
    #:walker-set-laplace #:walker-laplace #:normeq-steps

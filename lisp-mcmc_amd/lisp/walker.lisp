@@ -1113,6 +1113,74 @@ when the chains' windows differ in length or hold fewer than four steps."
             for j from 0
             append (list k (cffi:mem-aref rhat :double j))))))
 
+;;; ------------------------------------------------------------------ the narrowest interval
+;;; :95cr and its kin are equal-tailed (nth-percentile M:1495-1506): for a width pressed against its
+;;; bound or a skewed derived area they can leave out the most probable value.  The highest-density
+;;; interval needs the window in order; the device sorts it (mhx_get_hdi, whose comment in
+;;; include/mhx.h has the definition), and the sorted window at evenly spaced ranks comes with it.
+(defun %hdi-mass (mass)
+  "MASS per cent as the (num . den) mhx_get_hdi takes: a rational as it is, a float to the
+thousandth of a per cent"
+  (let ((r (if (rationalp mass) mass (/ (round (* 1000 mass)) 1000))))
+    (cons (numerator r) (denominator r))))
+
+(defun %hdi-call (walker take keys masses n-ladder who)
+  "mhx_get_hdi over KEYS: (values lo hi ladder names n-cols), lo and hi [n][n-mass][n-cols] and
+ladder [n][n-cols][n-ladder] as lisp arrays"
+  (let* ((n (walker-n-chains walker))
+         (cols (%key-columns walker keys))
+         (names (or keys (walker-param-keys walker)))
+         (nc (length cols))
+         (nm (length masses))
+         (window (%bin-window walker take who))
+         (none (cffi:null-pointer))
+         (lo (make-array (* n nm nc) :element-type 'double-float))
+         (hi (make-array (* n nm nc) :element-type 'double-float))
+         (ladder (make-array (* n nc n-ladder) :element-type 'double-float)))
+    (cffi:with-foreign-objects ((colp :int32 nc) (num :int32 (max nm 1)) (den :int32 (max nm 1))
+                                (lop :double (max 1 (* n nm nc))) (hip :double (max 1 (* n nm nc)))
+                                (ladp :double (max 1 (* n nc n-ladder))))
+      (fill-int32s colp cols)
+      (fill-int32s num (mapcar #'car masses))
+      (fill-int32s den (mapcar #'cdr masses))
+      (%set-call walker #'%mhx-get-hdi #'%mhx-group-get-hdi
+                 window colp nc num den nm n-ladder lop hip none ladp none none)
+      (dotimes (i (* n nm nc))
+        (setf (aref lo i) (cffi:mem-aref lop :double i)
+              (aref hi i) (cffi:mem-aref hip :double i)))
+      (dotimes (i (* n nc n-ladder))
+        (setf (aref ladder i) (cffi:mem-aref ladp :double i))))
+    (values lo hi ladder names nc)))
+
+(defun walker-set-hdi (walker &key (mass 95) keys (take 1000))
+  "For every chain of the set the plist (key (low high) ...) over KEYS (nil: all): the narrowest
+interval between two of the chain's newest TAKE steps that holds MASS per cent of them, from one
+device call.  Of equally narrow intervals the lowest."
+  (multiple-value-bind (lo hi ladder names nc)
+      (%hdi-call walker take keys (list (%hdi-mass mass)) 0 "walker-set-hdi")
+    (declare (ignore ladder))
+    (loop for c below (walker-n-chains walker)
+          collect (loop for k in names
+                        for j from 0
+                        append (list k (list (aref lo (+ (* c nc) j)) (aref hi (+ (* c nc) j))))))))
+
+(defun walker-hdi (walker &key (chain 0) (mass 95) keys (take 1000))
+  "One chain's entry of walker-set-hdi.  The device call is the whole set's."
+  (elt (walker-set-hdi walker :mass mass :keys keys :take take) chain))
+
+(defun walker-set-quantiles (walker &key (points 101) keys (take 1000))
+  "For every chain of the set the plist (key vector ...) over KEYS (nil: all): the chain's newest
+TAKE steps in ascending order at POINTS (2 to 4096) evenly spaced ranks - entry i has rank
+(floor (* i (1- n)) (1- points)) - for an ECDF, a violin or a Q-Q plot, from one device call."
+  (multiple-value-bind (lo hi ladder names nc)
+      (%hdi-call walker take keys nil points "walker-set-quantiles")
+    (declare (ignore lo hi))
+    (loop for c below (walker-n-chains walker)
+          collect (loop for k in names
+                        for j from 0
+                        append (list k (subseq ladder (* (+ (* c nc) j) points)
+                                               (* (+ (* c nc) j 1) points)))))))
+
 ;;; ------------------------------------------------------------------ one posterior for the set
 ;;; On a set whose chains sample the same posterior the steps of all chains make ONE sample.  The
 ;;; reference has no walker-set reduction (walker-set-get answers per chain); this is an exact

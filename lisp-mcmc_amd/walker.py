@@ -40,7 +40,7 @@ import warnings
 import numpy as np
 
 from . import _capi as capi
-from .engine import Engine, split_rhat
+from .engine import Engine, hdi_span, split_rhat
 from .models import Model
 
 _LIKS = {
@@ -1420,9 +1420,29 @@ def _exp_results(g, pcts, r, values):
     return out
 
 
+def _exp_hdi_selector(get):
+    """('hdi', mass) or ('quantiles', points) where `get` is one of walker_exp_get's two selectors
+    that order the window, else None"""
+    if isinstance(get, (tuple, list)) and len(get) == 2:
+        g = str(get[0]).lstrip(":").lower()
+        if g in ("hdi", "quantiles"):
+            return g, get[1]
+    return None
+
+
 def walker_set_exp_get(walker, exp, get=":median", take=1000):
-    """walker_exp_get for every chain of the set from ONE device call (mhx_get_derived): a list
-    with, chain by chain, exactly what walker_exp_get(..., chain=c) returns."""
+    """walker_exp_get for every chain of the set from ONE device call (mhx_get_derived; (":hdi",
+    mass) and (":quantiles", points): mhx_get_derived_hdi): a list with, chain by chain, exactly
+    what walker_exp_get(..., chain=c) returns."""
+    ordered = _exp_hdi_selector(get)
+    if ordered is not None:
+        names, index, text = _exp_call(walker, exp)
+        window = _exp_window(walker, take)
+        if ordered[0] == "hdi":
+            r = walker.engine.derived_hdi([text], names, index, window, [ordered[1]])
+            return [[float(r["lo"][c, 0, 0]), float(r["hi"][c, 0, 0])] for c in range(r["lo"].shape[0])]
+        r = walker.engine.derived_hdi([text], names, index, window, [], ladder=int(ordered[1]))
+        return [r["ladder"][c, 0].copy() for c in range(r["ladder"].shape[0])]
     g, pcts = exp_selector(get)
     names, index, text = _exp_call(walker, exp)
     r = walker.engine.derived([text], names, index, _exp_window(walker, take), pcts,
@@ -1435,7 +1455,9 @@ def walker_exp_get(walker, exp, get=":median", take=1000, chain=0):
     form is evaluated at every step of the window on the device (mhx_get_derived) and summarised
     there.  get: :most-likely (walker_with_exp), :median, :95cr (a [lo, hi] pair), :iqr, :mean,
     :stddev (NaN for a one-step window), :stddev-normal (the 84.1 point minus the median,
-    M:1529-1535), :values (newest first) or (":percentile", n)."""
+    M:1529-1535), :values (newest first), (":percentile", n), (":hdi", mass) - the narrowest [lo,
+    hi] that holds `mass` per cent of the window's values (mhx_get_derived_hdi, which has the
+    definition) - or (":quantiles", points): the sorted window at that many evenly spaced ranks."""
     return walker_set_exp_get(walker, exp, get, take)[chain]
 
 
@@ -1690,6 +1712,61 @@ def walker_set_rhat(walker, keys=None, take=1000):
     window = _bin_window(walker, take, "walker-set-rhat")
     r = walker.engine.autocorr(window, cols, 1)
     return dict(zip(names, (float(v) for v in split_rhat(r["half_mean"], r["half_var"], r["n_used"]))))
+
+
+def _order_keys(x):
+    """the 64-bit keys the device orders doubles by: -0 before +0, every NaN last"""
+    b = np.ascontiguousarray(x, dtype=np.float64).view(np.uint64)
+    k = np.where(b >> np.uint64(63) != 0, ~b, b | np.uint64(1 << 63))
+    k[np.isnan(x)] = np.uint64(2 ** 64 - 1)
+    return k
+
+
+def hdi(sequence, mass):
+    """The definition of mhx_get_hdi (include/mhx.h) on the host, for one sequence in any order:
+    (lo, hi, pos) of the narrowest interval between two order statistics that holds `mass` per
+    cent - a number or a (num, den) pair - of the values: with s the values in ascending order and
+    g = hdi_span(len, mass), the least pos whose s[pos + g] - s[pos] no other exceeds.  Also the
+    per-chain host route (one trace, this)."""
+    x = np.ascontiguousarray(sequence, dtype=np.float64)
+    if x.ndim != 1 or len(x) < 1:
+        raise ValueError("hdi needs a sequence of at least one value")
+    g = hdi_span(len(x), mass)
+    s = x[np.argsort(_order_keys(x), kind="stable")]
+    with np.errstate(all="ignore"):
+        pos = int(np.argmin(s[g:] - s[:len(x) - g]))
+    return float(s[pos]), float(s[pos + g]), pos
+
+
+def walker_set_hdi(walker, mass=95, keys=None, take=1000):
+    """The highest-density interval of every key (None: all) of every chain of the set - one
+    device call (mhx_get_hdi, which has the definition), no history moved: the narrowest interval
+    that holds `mass` per cent (a number or a (num, den) pair) of the chain's newest `take` steps.
+    Where a posterior is skewed or pressed against a bound, :95cr's equal tails can leave out its
+    most probable value; this interval cannot.  A list with, chain by chain, {key: [lo, hi]}.  The
+    reference has no counterpart: its intervals are equal-tailed."""
+    names, cols = _key_columns(walker, keys)
+    window = _bin_window(walker, take, "walker-set-hdi")
+    r = walker.engine.hdi(window, [mass], cols)
+    return [{k: [float(r["lo"][c, 0, j]), float(r["hi"][c, 0, j])] for j, k in enumerate(names)}
+            for c in range(r["lo"].shape[0])]
+
+
+def walker_hdi(walker, mass=95, keys=None, take=1000, chain=0):
+    """one chain's entry of walker_set_hdi: {key: [lo, hi]}"""
+    return walker_set_hdi(walker, mass, keys, take)[chain]
+
+
+def walker_set_quantiles(walker, points=101, keys=None, take=1000):
+    """The quantile function of every key (None: all) of every chain of the set at `points` evenly
+    spaced ranks (2..4096) of its newest `take` steps, for an ECDF, a violin or a Q-Q plot - one
+    device call (mhx_get_hdi's ladder), no history moved.  A list with, chain by chain,
+    {key: array [points]}: entry i is the sorted window's value of rank floor(i (n - 1) /
+    (points - 1)), so entry 0 is the least and the last entry the greatest."""
+    names, cols = _key_columns(walker, keys)
+    window = _bin_window(walker, take, "walker-set-quantiles")
+    lad = walker.engine.hdi(window, [], cols, ladder=int(points))["ladder"]
+    return [{k: lad[c, j].copy() for j, k in enumerate(names)} for c in range(lad.shape[0])]
 
 
 _ENSEMBLE_PERCENTILES = {"median-params": (50,), "95cr": (2.5, 97.5), "iqr": (25, 75),
