@@ -483,7 +483,7 @@ int mhx_get_window_best(mhx_engine* e, int take, double* prob, double* theta);
 int mhx_get_history_capacity(mhx_engine* e, int32_t* capacity);
 /* HIP-event milliseconds the kernels of the engine's last mhx_get_percentiles / _covariances /
  * _proposal_factors / _window_best / _fit_bands / _derived / _histograms / _pair_grids / _waic /
- * _loo / _traces / _fit_percentiles / _residuals / _normal_equations / _candidate_scores or
+ * _loo / _heldout / _traces / _fit_percentiles / _residuals / _normal_equations / _candidate_scores or
  * mhx_eval_function call ran (all portions; copies excluded). */
 int mhx_get_summary_timing(mhx_engine* e, double* kernel_ms);
 /* The same for a group, gathered in global chain order like mhx_group_get_state; every
@@ -931,6 +931,82 @@ int mhx_group_get_loo(mhx_group* g, int fn, int take, int tail_len, double k_lim
                       double* p_loo, double* lppd, int32_t* n_high, int32_t* n_used,
                       int32_t* status, double* pw_elpd, double* pw_khat, double* pw_lppd,
                       double* pw_acc, double* tail);
+
+/* ---- held-out predictive density: the log pointwise predictive density, under every chain's
+ * window, of data the CALLER hands in - a fold left out of the fit (K-fold cross-validation, the
+ * remedy the PSIS-LOO authors prescribe for points whose khat is high), a repeated measurement, or
+ * the walker's own spectrum of a set with a dataset per walker.  mhx_get_waic and mhx_get_loo score
+ * a chain on the data it walked over; this call reads the model, the ring and the caller's arrays
+ * only, so an engine with a dataset per walker (mhx_set_dataset_planes) is SERVED: its planes are
+ * not read.  The reference has no such function: the definition is this library's own and fixes the
+ * results operation by operation.  All arithmetic is plain IEEE binary64 multiply, add, subtract
+ * and divide, never fused.  For chain c, function fn and the caller's point i < m:
+ *   data     xcols [n_cols][m] as for mhx_get_fit_percentiles (never NULL here; n_cols the function's
+ *            column count), shared by all chains.  y [m], or [n_chains][m] with y_per_chain.  sigma by
+ *            sigma_kind with m in place of n: MHX_SIGMA_NONE (NULL), MHX_SIGMA_SHARED [m],
+ *            MHX_SIGMA_PER_CHAIN [n_chains], MHX_SIGMA_PER_POINT [n_chains][m].  use NULL (every
+ *            point), [m], or [n_chains][m] with use_per_chain: chain c USES point i where its byte is
+ *            nonzero
+ *   window   mhx_get_waic's: the newest n = min(take, walker-length, steps held) steps, newest
+ *            first.  n_used[c] = n
+ *   value    v_is = function fn at x_i for theta_s, the very bits mhx_eval_function returns
+ *   term     l_is = mhx_get_waic's term for the function's own likelihood (MHX_LIK_NORMAL,
+ *            _NORMAL_CUTOFF, _POISSON, _EXPR), from numbers formed of the caller's (y, sigma) exactly as
+ *            mhx_set_dataset would form them: w = 1 / sigma, ys = y * w, c = -1/2 log(2 pi) +
+ *            (-1 * log sigma) by libm's log for the normal forms (no sigma: 1); c = -log-factorial(y)
+ *            in the form mhx_config.poisson_logfact_double selects for Poisson (sigma is not read);
+ *            error = sigma (no sigma: 1) and no constant for an expression likelihood.  The caller's
+ *            arrays are checked as mhx_set_dataset checks them for that likelihood, used or not: a
+ *            sigma that is not finite and > 0, or a Poisson y that is no count, is refused by its
+ *            index in the caller's array ("sigma[3]")
+ *   over s   for s = 0 .. n-1 in that order, k = s + 1, q_k = 1.0 / k (one division):
+ *              log-sum-exp (M, S) of the TERMS l_is: mhx_get_waic's, operation for operation
+ *              Welford of the VALUES v_is:  delta = v - mean_v;  mean_v = mean_v + delta * q_k;
+ *                           M2_v = M2_v + delta * (v - mean_v)           from mean_v = 0, M2_v = 0
+ *            (mhx_get_fit_percentiles' mean is the same recurrence: the same bits at the same x)
+ *   point    pw_acc[c][i] = {M, S, mean_v, M2_v};  pw_lpd[c][i] = M + log(S / n) (the engine's log,
+ *            < 1 ulp; S / n one division).  A point chain c does not use: 0.0 in all five, and it
+ *            adds 0.0 to every sum
+ *   chain    lpd[c] = the sum of pw_lpd over blocks of MHX_HELDOUT_BLOCK points by mhx_get_waic's
+ *            rule: lane j = i mod 64 of a block adds its points serially in ascending i to a sum that
+ *            starts at 0.0 (a point beyond m or not used adds 0.0), the 64 lane sums are added
+ *            pairwise, lanes 32 apart first, then 16, 8, 4, 2, 1, and the blocks' sums serially in
+ *            ascending b to a sum that starts at 0.0.  n_scored[c] = the exact count of used points
+ *   status   a sum of
+ *              MHX_HELDOUT_NONFINITE  a v_is or l_is of a point the chain USES is not finite, or the
+ *                                     window is empty (n = 0): the chain's numbers are unspecified;
+ *                                     no other chain is touched by it.  What an unused point
+ *                                     evaluates to sets nothing
+ *              MHX_HELDOUT_NO_POINTS  the chain uses no point: lpd[c] = 0.0, n_scored[c] = 0
+ * The results are the same bits from call to call, whatever portions the call is worked through in
+ * and however a group's chains are split over its engines.  With the engine's own (x, y, sigma) and
+ * use NULL, pw_lpd, lpd and pw_acc[..][0..1] are the bits of mhx_get_waic's pw_lppd, lppd and pw_acc.
+ * lpd [n_chains]; n_scored, n_used, status [n_chains]; pw_lpd [n_chains][m]; pw_acc [n_chains][m][4].
+ * Any output may be NULL.  take in [1, history_capacity], fn a function of the problem, m >= 1,
+ * xcols and y not NULL, n_cols the function's, sigma_kind one of the four and NONE exactly where
+ * sigma is NULL, the data valid (above), else MHX_EINVAL; MHX_ESTATE before mhx_init_chains;
+ * MHX_EUNSUPPORTED where the problem cannot be made final, as for mhx_get_waic and
+ * mhx_get_fit_percentiles (a dataset per walker is not such a case).  The outputs stay untouched on
+ * error.  A chain in MHX_CHAIN_FP_TRAP is served from the history it has.  Serves every model the
+ * engine can walk.
+ * Worked through in portions whose device scratch stays below 64 MiB; mhx_get_summary_timing covers
+ * the call. */
+#define MHX_HELDOUT_BLOCK 256 /* points of one block of mhx_get_heldout's sums */
+enum {
+  MHX_HELDOUT_NONFINITE = 1,
+  MHX_HELDOUT_NO_POINTS = 2
+};
+int mhx_get_heldout(mhx_engine* e, int fn, int take, const double* xcols, int n_cols, int64_t m,
+                    const double* y, int y_per_chain, const double* sigma, int sigma_kind,
+                    const uint8_t* use, int use_per_chain, double* lpd, int32_t* n_scored,
+                    double* pw_lpd, double* pw_acc, int32_t* n_used, int32_t* status);
+/* The same for a group: y, sigma, use and the outputs that go by chain are in global chain order;
+ * every device's work is enqueued before any is waited for. */
+int mhx_group_get_heldout(mhx_group* g, int fn, int take, const double* xcols, int n_cols,
+                          int64_t m, const double* y, int y_per_chain, const double* sigma,
+                          int sigma_kind, const uint8_t* use, int use_per_chain, double* lpd,
+                          int32_t* n_scored, double* pw_lpd, double* pw_acc, int32_t* n_used,
+                          int32_t* status);
 
 /* ---- credible bands: the pointwise posterior of the fit curve, of every chain, on the device ring.
  * mhx_get_fit_bands is the reference's envelope - the extremes of the model over the most probable

@@ -31,6 +31,7 @@ from .walker import (  # noqa: F401
     hdi, walker_set_hdi, walker_hdi, walker_set_quantiles,
     walker_set_waic, walker_waic, waic_compare, waic_merge,
     walker_set_loo, walker_loo, loo_compare,
+    walker_set_score_data, walker_score_data, kfold_folds, walker_set_kfold_create, walker_set_kfold,
     walker_set_trace, walker_set_catepillar,
     walker_set_get_residuals, walker_set_goodness_of_fit, walker_goodness_of_fit, runs_z,
     walker_set_laplace, walker_laplace, laplace_summary, least_squares, walker_set_least_squares,
@@ -53,6 +54,8 @@ __all__ = ["capi", "MhxError", "Engine", "Group", "comm_unique_id", "partition",
            "hdi", "hdi_span", "walker_set_hdi", "walker_hdi", "walker_set_quantiles",
            "walker_set_waic", "walker_waic", "waic_compare", "waic_merge",
            "walker_set_loo", "walker_loo", "loo_compare", "loo_tail_length",
+           "walker_set_score_data", "walker_score_data", "kfold_folds", "walker_set_kfold_create",
+           "walker_set_kfold",
            "trace_rows", "walker_set_trace", "walker_set_catepillar",
            "walker_set_get_residuals", "walker_set_goodness_of_fit", "walker_goodness_of_fit", "runs_z",
            "normeq_steps", "walker_set_laplace", "walker_laplace", "laplace_summary", "least_squares",

@@ -28,6 +28,7 @@ L_OK, L_CAUGHT, L_INVALID, L_EMPTY = 0, 1, 2, 3
 AUTOCORR_NONFINITE, AUTOCORR_CONSTANT, AUTOCORR_OPEN, MAX_AUTOCORR_LAG = 1, 2, 4, 1023
 WAIC_NONFINITE, WAIC_ONE_STEP, WAIC_BLOCK = 1, 2, 256
 LOO_NONFINITE, LOO_SHORT, LOO_FLAT, LOO_EMPTY, LOO_BLOCK, LOO_MAX_TAIL = 1, 2, 4, 8, 256, 1024
+HELDOUT_NONFINITE, HELDOUT_NO_POINTS, HELDOUT_BLOCK = 1, 2, 256
 RESID_NONFINITE, RESID_BLOCK = 1, 256
 NORMEQ_NONFINITE, NORMEQ_BLOCK = 1, 1024
 CAND_KEEP_MAX = 16
@@ -179,6 +180,10 @@ SIGNATURES = {
                               i32p, f64p, f64p, f64p, f64p, f64p]),
     "mhx_group_get_loo": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, f64p, f64p, f64p, i32p,
                                     i32p, i32p, f64p, f64p, f64p, f64p, f64p]),
+    "mhx_get_heldout": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f64p, C.c_int, C.c_int64, f64p, C.c_int, f64p,
+                                  C.c_int, u8p, C.c_int, f64p, i32p, f64p, f64p, i32p, i32p]),
+    "mhx_group_get_heldout": (C.c_int, [C.c_void_p, C.c_int, C.c_int, f64p, C.c_int, C.c_int64, f64p, C.c_int,
+                                        f64p, C.c_int, u8p, C.c_int, f64p, i32p, f64p, f64p, i32p, i32p]),
     "mhx_get_residuals": (C.c_int, [C.c_void_p, C.c_int, f64p, C.c_double, f64p, f64p, f64p, f64p, f64p,
                                     f64p, i64p, i32p, i32p, i32p, i32p]),
     "mhx_group_get_residuals": (C.c_int, [C.c_void_p, C.c_int, f64p, C.c_double, f64p, f64p, f64p, f64p,

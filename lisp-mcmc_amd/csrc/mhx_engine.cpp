@@ -21,6 +21,7 @@
 
 #include "mhx_ensemble.hpp"
 #include "mhx_finalize.hpp"
+#include "mhx_heldout.hpp"
 #include "mhx_launch.hpp"
 #include "mhx_plan.hpp"
 #include "mhx_rtc.hpp"
@@ -639,21 +640,8 @@ int check_model(int model, const int32_t* shape, int n_shape, int n_index) {
   }
 }
 
-// M:379-380: (reduce (lambda (x y) (+ x (log y))) (up-to n)) sums SINGLE-float logs
-double log_factorial_ref(long n, bool in_double, std::vector<float>& cache) {
-  if (in_double) return std::lgamma((double)n + 1.0);
-  if (n <= 0) return 0.0;
-  if ((long)cache.size() <= n) {
-    size_t old = cache.size();
-    if (old == 0) {
-      cache.push_back(0.0f);
-      old = 1;
-    }
-    cache.resize((size_t)n + 1);
-    for (size_t m = old; m <= (size_t)n; ++m) cache[m] = cache[m - 1] + (float)std::log((double)m);
-  }
-  return (double)cache[(size_t)n];
-}
+// (log_factorial_ref, the Poisson constant of M:379-380: mhx_heldout.hpp, which forms it for
+// mhx_get_heldout too)
 
 int alloc_state(mhx_engine* e) {
   const int64_t C = e->cfg.n_chains;
@@ -2675,6 +2663,163 @@ int mhx_get_waic(mhx_engine* e, int fn, int take, double* elpd, double* lppd, do
   return run_portions(e, WaicCall(fn, take, elpd, lppd, p_waic, n_high, pw_lppd, pw_p, pw_acc, n_used, status));
 }
 
+// ---- held-out predictive density (include/mhx.h has the definition): WAIC's log-sum-exp over the
+// window, of the terms of data the CALLER hands in, with the value moments beside it (k_heldout),
+// and the totals (k_heldout_totals).  An item is a chain; the caller's points go in chunks of
+// kFitChunkPoints, whole blocks, as WAIC's do, and the blocks' partial sums of all chunks stay in
+// the stage.  The caller's arrays are turned into the kernel's ys, w, c and use bytes on the host
+// (mhx_heldout.hpp) and uploaded per portion: what all chains share once per chunk of points, the
+// rest [items][chunk].  Nothing of the engine's datasets is read, so a dataset per walker is served.
+struct HeldoutCall {
+  int fn = 0, take = 0, want = 0, n_cols = 1, lik = 0;
+  bool logfact_double = false;
+  int64_t m = 0, nb_total = 0;
+  const double* xcols = nullptr;
+  HeldoutLayout lay{};
+  int y_per_chain = 0, sigma_kind = 0, use_per_chain = 0;
+  // (Y, SIGMA, USE are read, not written: they lie here to move with a group's chains)
+  enum { LPD, N_SCORED, N_USED, STATUS, PW_LPD, PW_ACC, Y, SIGMA, USE, N_DST };
+  HostDst dst[N_DST];
+  // a portion's prepared arrays: they must outlive its copies, which collect() has waited for
+  // before the next upload() refills them
+  mutable std::vector<double> h_ys, h_w, h_c;
+  mutable std::vector<uint8_t> h_use;
+  mutable std::vector<float> lf_cache;
+  static_assert(kFitChunkPoints % MHX_HELDOUT_BLOCK == 0, "a chunk of points is whole blocks");
+
+  HeldoutCall(int fn_, int take_, const double* xcols_, int n_cols_, int64_t m_, const double* y, int y_per_chain_,
+              const double* sigma, int sigma_kind_, const uint8_t* use, int use_per_chain_, double* lpd,
+              int32_t* n_scored, double* pw_lpd, double* pw_acc, int32_t* n_used, int32_t* status)
+      : fn(fn_), take(take_), n_cols(n_cols_), m(m_), xcols(xcols_), y_per_chain(y_per_chain_ != 0),
+        sigma_kind(sigma_kind_), use_per_chain(use_per_chain_ != 0) {
+    const size_t row = (size_t)std::max<int64_t>(m, 0);
+    dst[LPD] = {lpd, sizeof(double)}, dst[N_SCORED] = {n_scored, sizeof(int32_t)};
+    dst[N_USED] = {n_used, sizeof(int32_t)}, dst[STATUS] = {status, sizeof(int32_t)};
+    dst[PW_LPD] = {pw_lpd, row * sizeof(double)}, dst[PW_ACC] = {pw_acc, row * 4 * sizeof(double)};
+    dst[Y] = {const_cast<double*>(y), y_per_chain ? row * sizeof(double) : 0};
+    dst[SIGMA] = {const_cast<double*>(sigma), sigma_kind == MHX_SIGMA_PER_CHAIN   ? sizeof(double)
+                                              : sigma_kind == MHX_SIGMA_PER_POINT ? row * sizeof(double)
+                                                                                  : 0};
+    dst[USE] = {const_cast<uint8_t*>(use), use_per_chain ? row : 0};
+    want = (pw_lpd ? HELDOUT_WANT_LPD : 0) | (pw_acc ? HELDOUT_WANT_ACC : 0);
+  }
+  // What does not depend on which engine of a group serves a chain: the arguments, and the caller's
+  // data over all n_total chains as mhx_set_dataset would check them.  e0: any engine of the call.
+  int check_data(const mhx_engine* e0, int64_t n_total) {
+    if (!e0) return fail(MHX_EINVAL, "engine is NULL");
+    if (fn < 0 || fn >= e0->P.K) return fail(MHX_EINVAL, "function %d out of range", fn);
+    if (m < 1) return fail(MHX_EINVAL, "m must be >= 1");
+    if (!xcols || !dst[Y].p) return fail(MHX_EINVAL, "mhx_get_heldout: xcols / y is NULL");
+    if (sigma_kind < MHX_SIGMA_NONE || sigma_kind > MHX_SIGMA_PER_POINT ||
+        (sigma_kind != MHX_SIGMA_NONE) != (dst[SIGMA].p != nullptr))
+      return fail(MHX_EINVAL, "mhx_get_heldout: sigma_kind %d does not go with a%s sigma", sigma_kind,
+                  dst[SIGMA].p ? "" : " NULL");
+    lik = e0->P.fn[fn].lik;
+    logfact_double = e0->cfg.poisson_logfact_double != 0;
+    char msg[160];
+    if (heldout_validate(lik, static_cast<const double*>(dst[Y].p), y_per_chain,
+                         static_cast<const double*>(dst[SIGMA].p), sigma_kind, n_total, m, msg, sizeof msg) != 0)
+      return fail(MHX_EINVAL, "%s", msg);
+    lay = heldout_layout(lik, y_per_chain, sigma_kind, dst[USE].p != nullptr, use_per_chain);
+    nb_total = waic_blocks(m);
+    return MHX_OK;
+  }
+  int check(mhx_engine* e) {
+    int rc = window_check(e, take);
+    if (rc != MHX_OK || (rc = fn_check(e, fn)) != MHX_OK) return rc;
+    if (n_cols != FitCall::fn_cols(e, fn))
+      return fail(MHX_EINVAL, "function %d reads %d column(s) of x, n_cols is %d", fn, FitCall::fn_cols(e, fn),
+                  n_cols);
+    if (e->P.fn[fn].lik != lik)
+      return fail(MHX_EINVAL, "function %d: the engines of the group differ in its likelihood", fn);
+    return MHX_OK;
+  }
+  int64_t items(const mhx_engine* e) const { return e->cfg.n_chains; }
+  int64_t points() const { return m; }
+  HeldoutPieces carve(const mhx_engine*, Carver& c, int64_t n_items, int64_t m_points) const {
+    return carve_heldout(c, nb_total, want, lay, n_items, m_points);
+  }
+  HeldoutData data() const {
+    HeldoutData D;
+    D.y = static_cast<const double*>(dst[Y].p), D.sigma = static_cast<const double*>(dst[SIGMA].p);
+    D.use = static_cast<const uint8_t*>(dst[USE].p);
+    D.y_per_chain = y_per_chain, D.sigma_kind = sigma_kind, D.use_per_chain = use_per_chain;
+    D.m = m;
+    return D;
+  }
+  // chains [i0, i0 + n) at points [m0, m0 + m): x and the prepared arrays of the chunk
+  int upload(mhx_engine* e, const Portion& p) const {
+    Carver c;
+    const HeldoutPieces s = carve(e, c, p.n, p.m);
+    const size_t mb = (size_t)p.m * sizeof(double);
+    HIP_TRY(hipMemcpyAsync(stage_at<double>(e, s.x0), xcols + p.m0, mb, hipMemcpyHostToDevice, e->stream));
+    if (n_cols > 1)
+      HIP_TRY(hipMemcpyAsync(stage_at<double>(e, s.x1), xcols + m + p.m0, mb, hipMemcpyHostToDevice, e->stream));
+    h_ys.resize(heldout_elems(lay.ys, p.n, p.m)), h_w.resize(heldout_elems(lay.w, p.n, p.m));
+    h_c.resize(heldout_elems(lay.c, p.n, p.m)), h_use.resize(heldout_elems(lay.use, p.n, p.m));
+    heldout_fill(lik, logfact_double, lay, data(), p.i0, p.n, p.m0, p.m, h_ys.data(), h_w.data(), h_c.data(),
+                 h_use.data(), lf_cache);
+    const struct { size_t at; const void* src; size_t bytes; } up[4] = {
+        {s.ys, h_ys.data(), h_ys.size() * sizeof(double)}, {s.w, h_w.data(), h_w.size() * sizeof(double)},
+        {s.c, h_c.data(), h_c.size() * sizeof(double)}, {s.use, h_use.data(), h_use.size()}};
+    for (const auto& u : up)
+      if (u.bytes > 0)
+        HIP_TRY(hipMemcpyAsync(e->stage.p + u.at, u.src, u.bytes, hipMemcpyHostToDevice, e->stream));
+    if (p.m0 == 0)
+      HIP_TRY(hipMemsetAsync(stage_at<int32_t>(e, s.status), 0, (size_t)p.n * sizeof(int32_t), e->stream));
+    return MHX_OK;
+  }
+  int launch(mhx_engine* e, const Portion& p) const {
+    Carver c;
+    const HeldoutPieces s = carve(e, c, p.n, p.m);
+    HeldoutArgs A{};
+    A.c0 = p.i0, A.n = p.n;
+    A.take = take, A.fn = fn;
+    A.n_blocks = (int32_t)waic_blocks(p.m);
+    A.blk0 = p.m0 / MHX_HELDOUT_BLOCK, A.nb_total = nb_total, A.m = p.m;
+    A.x0 = stage_at<double>(e, s.x0);
+    A.x1 = n_cols > 1 ? stage_at<double>(e, s.x1) : nullptr;
+    A.ys = stage_at<double>(e, s.ys), A.y_pitch = heldout_pitch(lay.ys, p.m);
+    A.w = stage_at<double>(e, s.w), A.w_pitch = heldout_pitch(lay.w, p.m), A.w_step = heldout_step(lay.w);
+    A.c = lay.c == kHoNone ? nullptr : stage_at<double>(e, s.c);
+    A.c_pitch = heldout_pitch(lay.c, p.m), A.c_step = heldout_step(lay.c);
+    A.use = lay.use == kHoNone ? nullptr : stage_at<unsigned char>(e, s.use);
+    A.use_pitch = heldout_pitch(lay.use, p.m);
+    A.pw_lpd = (want & HELDOUT_WANT_LPD) ? stage_at<double>(e, s.pw_lpd) : nullptr;
+    A.pw_acc = (want & HELDOUT_WANT_ACC) ? stage_at<double>(e, s.pw_acc) : nullptr;
+    A.part_lpd = stage_at<double>(e, s.part_lpd);
+    A.part_scored = stage_at<int32_t>(e, s.part_scored);
+    A.status = stage_at<int32_t>(e, s.status);
+    HIP_TRY(launch_model(e, A));
+    if (p.m0 + p.m >= m)
+      HIP_TRY(launch_heldout_totals(e->stream, e->S, p.i0, p.n, take, nb_total, A.part_lpd, A.part_scored,
+                                    stage_at<double>(e, s.lpd), stage_at<int32_t>(e, s.n_scored),
+                                    stage_at<int32_t>(e, s.n_used), A.status));
+    e->launches++;
+    return MHX_OK;
+  }
+  int collect(mhx_engine* e, const Portion& p) const {
+    Carver c;
+    const HeldoutPieces s = carve(e, c, p.n, p.m);
+    int rc = copy_back_points(dst[PW_LPD], p, m, sizeof(double), 1, e->stage.p + s.pw_lpd);
+    if (rc != MHX_OK || (rc = copy_back_points(dst[PW_ACC], p, m, 4 * sizeof(double), 1, e->stage.p + s.pw_acc)) != MHX_OK)
+      return rc;
+    if (p.m0 + p.m < m) return MHX_OK;  // (the totals come with the last chunk of points)
+    return copy_back_each(e, dst, p, {s.lpd, s.n_scored, s.n_used, s.status});
+  }
+};
+
+int mhx_get_heldout(mhx_engine* e, int fn, int take, const double* xcols, int n_cols, int64_t m,
+                    const double* y, int y_per_chain, const double* sigma, int sigma_kind,
+                    const uint8_t* use, int use_per_chain, double* lpd, int32_t* n_scored,
+                    double* pw_lpd, double* pw_acc, int32_t* n_used, int32_t* status) {
+  HeldoutCall q(fn, take, xcols, n_cols, m, y, y_per_chain, sigma, sigma_kind, use, use_per_chain, lpd, n_scored,
+                pw_lpd, pw_acc, n_used, status);
+  int rc = window_check(e, take);
+  if (rc != MHX_OK || (rc = q.check_data(e, e->cfg.n_chains)) != MHX_OK) return rc;
+  return run_portions(e, q);
+}
+
 // ---- PSIS-LOO (include/mhx.h has the definition): every chain's likelihood terms of function fn
 // over its window, staged, and pw_lppd (k_loo_values), the Pareto-smoothed estimate of every (chain,
 // point) column (the model-free k_loo_fit), the block sums of the chunk (k_loo_block_sums) and the
@@ -4651,6 +4796,19 @@ int mhx_group_get_waic(mhx_group* g, int fn, int take, double* elpd, double* lpp
                        int32_t* n_high, double* pw_lppd, double* pw_p, double* pw_acc,
                        int32_t* n_used, int32_t* status) {
   return run_portions(g, WaicCall(fn, take, elpd, lppd, p_waic, n_high, pw_lppd, pw_p, pw_acc, n_used, status));
+}
+int mhx_group_get_heldout(mhx_group* g, int fn, int take, const double* xcols, int n_cols, int64_t m,
+                          const double* y, int y_per_chain, const double* sigma, int sigma_kind,
+                          const uint8_t* use, int use_per_chain, double* lpd, int32_t* n_scored,
+                          double* pw_lpd, double* pw_acc, int32_t* n_used, int32_t* status) {
+  if (!g || g->eng.empty()) return fail(MHX_EINVAL, "group is NULL");
+  HeldoutCall q(fn, take, xcols, n_cols, m, y, y_per_chain, sigma, sigma_kind, use, use_per_chain, lpd, n_scored,
+                pw_lpd, pw_acc, n_used, status);
+  int64_t n_total = 0;
+  for (const mhx_engine* e : g->eng) n_total += e->cfg.n_chains;
+  int rc = window_check(g->eng[0], take);
+  if (rc != MHX_OK || (rc = q.check_data(g->eng[0], n_total)) != MHX_OK) return rc;
+  return run_portions(g, q);  // (the per-chain arrays move to each engine's first global chain with the outputs)
 }
 int mhx_group_get_loo(mhx_group* g, int fn, int take, int tail_len, double k_limit, double* elpd_loo,
                       double* p_loo, double* lppd, int32_t* n_high, int32_t* n_used, int32_t* status,

@@ -4465,6 +4465,176 @@ __global__ __launch_bounds__(kThreads) void k_waic_totals(ChainState S, int64_t 
 }
 #endif
 
+// mhx_get_heldout (include/mhx.h has the definition, operation by operation): k_waic_body over data
+// the caller handed in.  The same wave per (chain, block), the same four points a lane, the same
+// walk over the window with the next step's parameter row in flight, ONE Spec::values a step, the
+// same term and the same log-sum-exp - so that with the engine's own data the pair (M, S) and
+// pw_lpd are k_waic's bits.  What differs: ys, w, c and the use flag are read through the pitches of
+// HeldoutArgs (the host prepared them: one instance serves shared and per-chain data), the Welford
+// pair follows the VALUES (k_fitpct_values_body's recurrence), and a point the chain does not use
+// is computed like any other but stores 0.0, adds 0.0 and flags nothing.  Every product and sum is
+// rounded on its own (the unit is compiled without contraction; no fma is written here).  The
+// block's sum of pw_lpd and its count of used points go to part_*[chain][block]: k_heldout_totals
+// adds them in block order.
+template <class Spec>
+__device__ __forceinline__ void k_heldout_body(const ProblemDesc* __restrict__ Pp, ChainState S,
+                                               HeldoutArgs A) {
+  FitLds& lds = *reinterpret_cast<FitLds*>(mhx_lds_raw);
+  lds_tables_begin();
+  __syncthreads();  // (the only barrier: waves without work leave behind it)
+  const int w = wave_in_group(), l = lane_id();
+  const int64_t g = (int64_t)blockIdx.x * kWavesPerGroup + w;
+  if (g >= A.n * A.n_blocks) return;
+  const int64_t i = g / A.n_blocks;
+  const int64_t blk = g - i * A.n_blocks;
+  const int64_t p0 = blk * (int64_t)(kWave * kWaicPts) + l;
+  const FnDesc& f = Pp->fn[A.fn];
+  const int d = Pp->d;
+  const int lik = __builtin_amdgcn_readfirstlane(f.lik);
+  const double* const ysr = A.ys + i * A.y_pitch;
+  const double* const wr = A.w + i * A.w_pitch;
+  const double* const cr = A.c ? A.c + i * A.c_pitch : nullptr;
+  const unsigned char* const ur = A.use ? A.use + i * A.use_pitch : nullptr;
+  double x0[kWaicPts], x1[kWaicPts], ys[kWaicPts], wi[kWaicPts], ci[kWaicPts];
+  double aM[kWaicPts], aS[kWaicPts], mean[kWaicPts], m2[kWaicPts];
+  unsigned um = 0u;  // bit j: the chain uses the lane's j-th point
+#pragma unroll
+  for (int j = 0; j < kWaicPts; ++j) {
+    const int64_t p = p0 + (int64_t)j * kWave;
+    const int64_t q = p < A.m ? p : A.m - 1;  // (beyond m: the last point once more, never used)
+    x0[j] = A.x0[q];
+    x1[j] = A.x1 ? A.x1[q] : 0.0;
+    ys[j] = ysr[q];
+    wi[j] = wr[q * A.w_step];
+    ci[j] = cr ? cr[q * A.c_step] : 0.0;
+    um |= (p < A.m && (!ur || ur[q] != 0)) ? 1u << j : 0u;
+    aM[j] = aS[j] = mean[j] = m2[j] = 0.0;
+  }
+  const Ring r = ring_of(S, A.c0 + i);
+  const int n = ring_held(r, A.take);
+  double* th = lds.th[w];
+  double thn = 0.0;
+  if (n > 0 && l < d) thn = r.theta[(int64_t)r.slot(0) * d + l];
+  bool bad = false;
+  for (int s = 0; s < n; ++s) {
+    if (l < d) th[l] = thn;
+    __builtin_amdgcn_wave_barrier();
+    if (s + 1 < n && l < d) thn = r.theta[(int64_t)r.slot(s + 1) * d + l];
+    auto pf = [&](int j) -> double { return th[f.idx[j]]; };
+    double v[kWaicPts], t[kWaicPts];
+    Spec::template values<kWaicPts>(f, pf, lds.scr[w], x0, x1, v);
+    const double qk = 1.0 / (double)(s + 1);
+#pragma unroll
+    for (int j = 0; j < kWaicPts; ++j) {  // (the values' moments first: a value then lives to its term only)
+      const double u = v[j];
+      bad = bad || (((um >> j) & 1u) != 0u && !finite_f64(u));
+      const double dl = u - mean[j];
+      mean[j] = mean[j] + dl * qk;
+      m2[j] = m2[j] + dl * (u - mean[j]);
+    }
+    if (lik == MHX_LIK_POISSON) {
+#pragma unroll
+      for (int j = 0; j < kWaicPts; ++j) {
+        const double a = ys[j] * tlog_rate(v[j]);
+        const double b = a - v[j];
+        t[j] = b + ci[j];
+      }
+    } else if (lik == MHX_LIK_EXPR) {
+#pragma unroll
+      for (int j = 0; j < kWaicPts; ++j) t[j] = Spec::lik_term(f, ys[j], v[j], wi[j]);
+    } else {
+      const bool cut = lik == MHX_LIK_NORMAL_CUTOFF;
+#pragma unroll
+      for (int j = 0; j < kWaicPts; ++j) {
+        const double a = v[j] * wi[j];
+        const double rr = ys[j] - a;
+        const double h = 0.5 * rr;
+        const double q = h * rr;
+        const double e = ci[j] - q;
+        t[j] = cut ? (e > -5000.0 ? e : -5000.0) : e;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < kWaicPts; ++j) {
+      const double e = t[j];
+      bad = bad || (((um >> j) & 1u) != 0u && !finite_f64(e));
+      const bool up = e > aM[j];
+      const double ge = gexp(up ? aM[j] - e : e - aM[j]);
+      const double sn = up ? aS[j] * ge + 1.0 : aS[j] + ge;
+      aS[j] = s == 0 ? 1.0 : sn;
+      aM[j] = (s == 0 || up) ? e : aM[j];
+    }
+  }
+  const double nd = (double)n;
+  double sl = 0.0;
+  int ns = 0;
+#pragma unroll
+  for (int j = 0; j < kWaicPts; ++j) {
+    const int64_t p = p0 + (int64_t)j * kWave;
+    const bool in = ((um >> j) & 1u) != 0u;
+    const double lp = in ? aM[j] + tlog(aS[j] / nd) : 0.0;
+    sl = sl + lp;
+    ns += in ? 1 : 0;
+    if (p < A.m) {
+      const int64_t o = i * A.m + p;
+      if (A.pw_lpd) A.pw_lpd[o] = lp;
+      if (A.pw_acc) {
+        A.pw_acc[o * 4 + 0] = in ? aM[j] : 0.0;
+        A.pw_acc[o * 4 + 1] = in ? aS[j] : 0.0;
+        A.pw_acc[o * 4 + 2] = in ? mean[j] : 0.0;
+        A.pw_acc[o * 4 + 3] = in ? m2[j] : 0.0;
+      }
+    }
+  }
+  sl = wave_sum(sl);
+  ns = wave_sum_i(ns);
+  const bool any_bad = __ballot(bad) != 0ULL;
+  if (l == 0) {
+    const int64_t o = i * A.nb_total + A.blk0 + blk;
+    A.part_lpd[o] = sl;
+    A.part_scored[o] = ns;
+    if (any_bad) A.status[i] = MHX_HELDOUT_NONFINITE;
+  }
+}
+#ifndef __HIPCC_RTC__
+template <class Spec>
+__global__ __launch_bounds__(kThreads) void k_heldout(const ProblemDesc* __restrict__ Pp, ChainState S,
+                                                      HeldoutArgs A) {
+  k_heldout_body<Spec>(Pp, S, A);
+}
+#endif
+#if defined(MHX_FAMILY_PRIMARY) && !defined(__HIPCC_RTC__)
+// mhx_get_heldout, the totals: one thread per chain adds the blocks' partial sums in block order
+// (whatever launches wrote them) and completes n_used and the status (no point used; an empty
+// window, whose 0/0 quotient is flagged as not finite).
+__global__ __launch_bounds__(kThreads) void k_heldout_totals(ChainState S, int64_t c0, int64_t n, int take,
+                                                             int64_t nb_total,
+                                                             const double* __restrict__ part_lpd,
+                                                             const int32_t* __restrict__ part_scored,
+                                                             double* __restrict__ lpd,
+                                                             int32_t* __restrict__ n_scored,
+                                                             int32_t* __restrict__ n_used,
+                                                             int32_t* __restrict__ status) {
+  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  const int64_t c = c0 + i;
+  int64_t t = S.length[c] < S.n_hist[c] ? S.length[c] : S.n_hist[c];
+  if (t > (int64_t)take) t = take;
+  if (t < 0) t = 0;
+  double sl = 0.0;
+  int ns = 0;
+  for (int64_t b = 0; b < nb_total; ++b) {
+    sl = sl + part_lpd[i * nb_total + b];
+    ns += part_scored[i * nb_total + b];
+  }
+  lpd[i] = sl;
+  n_scored[i] = ns;
+  n_used[i] = (int32_t)t;
+  if (t == 0) status[i] = status[i] | MHX_HELDOUT_NONFINITE;  // (an empty walk: nothing to average)
+  if (ns == 0) status[i] = status[i] | MHX_HELDOUT_NO_POINTS;
+}
+#endif
+
 // mhx_get_residuals (include/mhx.h has the definition, operation by operation): k_waic's shape with
 // one parameter vector in place of a window - no loop over steps.  Wave g serves chain
 // g / n_blocks of the launch and block g % n_blocks of its points, kResidPts points per lane; the

@@ -173,7 +173,8 @@ hipError_t launch_window_best(hipStream_t st, const ChainState& S, int64_t c0, i
   X(cand,   CandArgs,   k_cand,          false, A.m <= 0 || A.m_cand <= 0 ? 0 : A.n * A.n_blocks,              \
     fit_lds_bytes(wpg), 0, (void)0)                                                                            \
   X(fitpct, FitPctArgs, k_fitpct_values, true,  A.m <= 0 ? 0 : A.n * A.n_blocks, fit_lds_bytes(wpg), 0, (void)0)    \
-  X(loo,    LooArgs,    k_loo_values,    true,  A.m <= 0 ? 0 : A.n * A.n_blocks, fit_lds_bytes(wpg), 0, (void)0)
+  X(loo,    LooArgs,    k_loo_values,    true,  A.m <= 0 ? 0 : A.n * A.n_blocks, fit_lds_bytes(wpg), 0, (void)0)    \
+  X(heldout, HeldoutArgs, k_heldout,     true,  A.m <= 0 ? 0 : A.n * A.n_blocks, fit_lds_bytes(wpg), 0, (void)0)
 
 enum ModelReadoutId {
 #define MHX_X(ID, ...) MR_##ID,
@@ -216,6 +217,13 @@ hipError_t launch_waic_totals(hipStream_t st, const ChainState& S, int64_t c0, i
                               int64_t nb_total, const double* part_lppd, const double* part_p,
                               const int32_t* part_high, double* elpd, double* lppd, double* p_waic,
                               int32_t* n_high, int32_t* n_used, int32_t* status);
+
+// mhx_get_heldout: the pointwise accumulation over the caller's data and the blocks' partial sums
+// (HeldoutArgs, mhx_types.hpp) through launch_model, and the totals of n chains from the partials
+// of all nb_total blocks (blocks of MHX_HELDOUT_BLOCK = MHX_WAIC_BLOCK points: waic_blocks counts them).
+hipError_t launch_heldout_totals(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
+                                 int64_t nb_total, const double* part_lpd, const int32_t* part_scored,
+                                 double* lpd, int32_t* n_scored, int32_t* n_used, int32_t* status);
 
 // mhx_get_fit_percentiles: the values and moments (FitPctArgs, mhx_types.hpp) through launch_model,
 // and the model-free selection over the staged values.  fitpct_cols: the neighbouring points one

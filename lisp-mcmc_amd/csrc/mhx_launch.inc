@@ -469,6 +469,16 @@ hipError_t launch_waic_totals(hipStream_t st, const ChainState& S, int64_t c0, i
   return hipGetLastError();
 }
 
+// mhx_get_heldout: the totals (k_heldout_totals)
+hipError_t launch_heldout_totals(hipStream_t st, const ChainState& S, int64_t c0, int64_t n, int take,
+                                 int64_t nb_total, const double* part_lpd, const int32_t* part_scored,
+                                 double* lpd, int32_t* n_scored, int32_t* n_used, int32_t* status) {
+  if (n <= 0) return hipSuccess;
+  k_heldout_totals<<<dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, st>>>(
+      S, c0, n, take, nb_total, part_lpd, part_scored, lpd, n_scored, n_used, status);
+  return hipGetLastError();
+}
+
 // mhx_get_residuals: the totals (k_resid_totals)
 hipError_t launch_resid_totals(hipStream_t st, int64_t n, int64_t nb_total, const ResidArgs& A,
                                double* chi2, double* sum_z, double* dw, double* max_abs_z,

@@ -302,6 +302,46 @@ struct WaicArgs {
   int32_t* status;     // [n] MHX_WAIC_NONFINITE is stored where a value or a term is not finite
 };
 
+// k_heldout (mhx_get_heldout): k_waic over data the caller handed in.  Per point of the launch's m,
+// the log-sum-exp of the log-likelihood terms and the Welford moments of the model VALUES over the
+// window of each of n chains from c0 on; a wave serves one chain and one block of MHX_HELDOUT_BLOCK
+// = kWave x kWaicPts points, blocks blk0 .. of the call's nb_total.  The host prepares ys, w and c
+// (mhx_heldout.hpp) and uploads them per portion, so a row is counted from the LAUNCH's first chain
+// and the arrays begin at the launch's first point.  Item i reads, in DataView's manner,
+//   ys_p  = ys[i * y_pitch + p]                y_pitch 0: one y for every chain
+//   w_p   = w[i * w_pitch + p * w_step]        (0, 1) shared; (1, 0) a scalar per chain; (pitch, 1)
+//                                              a plane; (0, 0) one number for all (no sigma)
+//   c_p   = c[i * c_pitch + p * c_step]        the same; c nullptr: none (MHX_LIK_EXPR)
+//   use_p = use[i * use_pitch + p] != 0        use nullptr: every point
+// so one instance serves shared and per-chain data.  Four accumulators a point, as k_waic (the
+// value moments take the place of the term moments, and there is no pw_p), and one byte for the use
+// flags (bits of one register): the register budget of kWaicPts above applies.  As compiled for
+// gfx950: config 2's two-peak instance 113 VGPRs and the polynomials 110 and 111 (two workgroups a
+// CU, as their k_waic), five-peak Poisson 143, pvoigt2 141, lorder 136, the generic kernel 185 (one
+// workgroup a CU, as their k_waic); no instance uses scratch.  The value moments are taken right
+// behind Spec::values, ahead of the term: with them in the log-sum-exp's loop, where k_waic has
+// its term moments, a value lived across the exponentials and every instance took 20 VGPRs more
+// (two-peak 137: one workgroup a CU).
+static_assert(MHX_HELDOUT_BLOCK == MHX_WAIC_BLOCK, "mhx_get_heldout's sums follow mhx_get_waic's rule");
+struct HeldoutArgs {
+  int64_t c0, n;
+  int32_t take, fn, n_blocks, w_step;
+  int64_t blk0, nb_total, m;
+  const double* x0;
+  const double* x1;  // the second column of x, or nullptr
+  const double* ys;
+  const double* w;
+  const double* c;       // or nullptr
+  const unsigned char* use;  // or nullptr
+  int64_t y_pitch, w_pitch, c_pitch, use_pitch;
+  int32_t c_step, pad_;
+  double* pw_lpd;        // [n][m] or nullptr
+  double* pw_acc;        // [n][m][4] or nullptr
+  double* part_lpd;      // [n][nb_total] the blocks' sums of pw_lpd
+  int32_t* part_scored;  // [n][nb_total] the blocks' counts of used points
+  int32_t* status;       // [n] MHX_HELDOUT_NONFINITE is stored where a used value or term is not finite
+};
+
 // k_fitpct_values (mhx_get_fit_percentiles): the model of function `fn` at m points for every step
 // of the window of each of n chains from c0 on, and the Welford moments of those values per point.
 // A wave serves one chain and one block of MHX_FITPCT_BLOCK = kWave x kFitPctPts points; n_blocks

@@ -337,6 +337,65 @@ class _Summaries:
               for k in ("pw_elpd", "pw_khat", "pw_lppd", "pw_acc", "tail"))))
         return out
 
+    def heldout(self, fn, take, x, y, sigma=None, sigma_kind=None, use=None, pointwise=False,
+                accumulators=False, y_per_chain=None, use_per_chain=None):
+        """The log pointwise predictive density of data the caller hands in - a fold left out of the
+        fit, a repeated measurement, a walker's own spectrum - under every chain's newest `take`
+        steps of function `fn` (mhx_get_heldout, which has the definition).  x [m] or [n_cols, m],
+        shared by the chains; y [m] or [n_chains, m]; sigma None, a number or [m] (SIGMA_SHARED),
+        [n_chains] (SIGMA_PER_CHAIN) or [n_chains, m] (SIGMA_PER_POINT); use None (every point), [m]
+        or [n_chains, m]: chain c scores point i where its entry is nonzero.  The kinds are read off
+        the shapes unless given (a sigma of one dimension whose length fits both is SIGMA_SHARED).
+        A dict of lpd [n_chains], n_scored (points used), n_used (steps) and status [n_chains]
+        (HELDOUT_NONFINITE 1, HELDOUT_NO_POINTS 2).  pointwise=True adds pw_lpd [n_chains, m];
+        accumulators=True adds pw_acc [n_chains, m, 4] = (M, S, mean_v, M2_v), the log-sum-exp pair
+        of the terms and the Welford pair of the model values.  A point a chain does not use is 0.0
+        everywhere.  An engine with a dataset per walker is served."""
+        n = self.n_chains
+        xa, xp, n_cols, m = _x_columns(self, fn, np.asarray(x, dtype=np.float64), None)
+        ya, yp = capi.as_f64(y)
+        if y_per_chain is None:
+            y_per_chain = ya.ndim == 2
+        if ya.shape != ((n, m) if y_per_chain else (m,)):
+            raise ValueError("y must be [m] or [n_chains, m] with m = %d, n_chains = %d" % (m, n))
+        sa, sp = None, None
+        if sigma is None:
+            if sigma_kind not in (None, capi.SIGMA_NONE):
+                raise ValueError("sigma is None exactly with SIGMA_NONE")
+            sigma_kind = capi.SIGMA_NONE
+        else:
+            sa = np.asarray(sigma, dtype=np.float64)
+            if sigma_kind is None:
+                if sa.ndim == 0:
+                    sa = np.full(m, float(sa))
+                sigma_kind = (capi.SIGMA_PER_POINT if sa.ndim == 2 else
+                              capi.SIGMA_SHARED if sa.shape == (m,) else capi.SIGMA_PER_CHAIN)
+            want = {capi.SIGMA_SHARED: (m,), capi.SIGMA_PER_CHAIN: (n,), capi.SIGMA_PER_POINT: (n, m)}
+            if sigma_kind not in want or sa.shape != want[sigma_kind]:
+                raise ValueError("sigma must be [m], [n_chains] or [n_chains, m] by its sigma_kind")
+            sa, sp = capi.as_f64(sa)
+        ua, up = None, None
+        if use is not None:
+            ua = np.ascontiguousarray(np.asarray(use) != 0, dtype=np.uint8)
+            if use_per_chain is None:
+                use_per_chain = ua.ndim == 2
+            if ua.shape != ((n, m) if use_per_chain else (m,)):
+                raise ValueError("use must be [m] or [n_chains, m]")
+            up = ua.ctypes.data_as(capi.u8p)
+        out = {"lpd": np.zeros(n), "n_scored": np.zeros(n, dtype=np.int32),
+               "n_used": np.zeros(n, dtype=np.int32), "status": np.zeros(n, dtype=np.int32)}
+        if pointwise:
+            out["pw_lpd"] = np.zeros((n, m))
+        if accumulators:
+            out["pw_acc"] = np.zeros((n, m, 4))
+        capi.check(self._summary("heldout")(
+            self._h, int(fn), int(take), xp, n_cols, m, yp, int(bool(y_per_chain)), sp, int(sigma_kind),
+            up, int(bool(use_per_chain)), out["lpd"].ctypes.data_as(capi.f64p),
+            out["n_scored"].ctypes.data_as(capi.i32p),
+            *(out[k].ctypes.data_as(capi.f64p) if k in out else None for k in ("pw_lpd", "pw_acc")),
+            out["n_used"].ctypes.data_as(capi.i32p), out["status"].ctypes.data_as(capi.i32p)))
+        return out
+
     def residuals(self, fn, theta=None, z_limit=3.0, pointwise=False):
         """Goodness of fit of every walker for function `fn` at one parameter vector each
         (mhx_get_residuals, which has the definition): theta [n_chains, d], None: every chain's

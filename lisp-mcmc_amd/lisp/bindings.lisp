@@ -287,6 +287,20 @@ library, or without a gfx950 device, walker-create signals MHX-ERROR."
   (g :pointer) (fn :int) (take :int) (tail-len :int) (k-limit :double) (elpd-loo :pointer)
   (p-loo :pointer) (lppd :pointer) (n-high :pointer) (n-used :pointer) (status :pointer)
   (pw-elpd :pointer) (pw-khat :pointer) (pw-lppd :pointer) (pw-acc :pointer) (tail :pointer))
+;; held-out predictive density: data the caller hands in, scored under every chain's window
+;; (status: a sum of the two constants)
+(defconstant +heldout-nonfinite+ 1)
+(defconstant +heldout-no-points+ 2)
+(cffi:defcfun ("mhx_get_heldout" %mhx-get-heldout) :int
+  (e :pointer) (fn :int) (take :int) (xcols :pointer) (n-cols :int) (m :int64) (y :pointer)
+  (y-per-chain :int) (sigma :pointer) (sigma-kind :int) (use :pointer) (use-per-chain :int)
+  (lpd :pointer) (n-scored :pointer) (pw-lpd :pointer) (pw-acc :pointer) (n-used :pointer)
+  (status :pointer))
+(cffi:defcfun ("mhx_group_get_heldout" %mhx-group-get-heldout) :int
+  (g :pointer) (fn :int) (take :int) (xcols :pointer) (n-cols :int) (m :int64) (y :pointer)
+  (y-per-chain :int) (sigma :pointer) (sigma-kind :int) (use :pointer) (use-per-chain :int)
+  (lpd :pointer) (n-scored :pointer) (pw-lpd :pointer) (pw-acc :pointer) (n-used :pointer)
+  (status :pointer))
 ;; credible bands: pointwise percentiles and moments of the fit (status: a sum of the three constants)
 (defconstant +fitpct-nonfinite+ 1)
 (defconstant +fitpct-one-step+ 2)

@@ -24,7 +24,7 @@
    #:walker-set-corner-grid
    #:walker-set-autocorr #:walker-set-rhat #:walker-set-ensemble-get
    #:walker-set-hdi #:walker-hdi #:walker-set-quantiles
-   #:walker-set-waic #:walker-waic #:walker-set-loo #:walker-loo
+   #:walker-set-waic #:walker-waic #:walker-set-loo #:walker-loo #:walker-set-score-data
    #:walker-set-get-residuals #:walker-set-goodness-of-fit #:walker-goodness-of-fit #:runs-z
    #:walker-set-laplace #:walker-laplace #:normeq-steps
    #:walker-set-search #:candidate-grid

@@ -1323,6 +1323,58 @@ model value or a likelihood term of a window is not finite: the reference would 
 chains call walker-set-loo once and take its elements."
   (elt (walker-set-loo walker :take take :tail tail :k-limit k-limit) chain))
 
+;;; Data the walk did not see - a repeated measurement, a fold left out of the fit, or each walker's
+;;; own spectrum of a set with a dataset per walker, which walker-set-waic refuses - scored under
+;;; every walker's window in one call (mhx_get_heldout, whose comment in include/mhx.h has the
+;;; definition).  The totals only: the pointwise densities, the fit moments and the K-fold layer
+;;; are the Python mirror's.
+(defun walker-set-score-data (walker data &key data-error (take 1000) (fn-number 0))
+  "For every walker of the set the plist (:lpd :n-scored :n-used :status): the log pointwise
+predictive density of DATA = (x y) under its newest TAKE steps by function FN-NUMBER's own
+likelihood, the points scored, the window, and 0 or +heldout-no-points+.  y is one sequence of
+numbers for every walker, or a sequence of one such sequence per walker.  DATA-ERROR: nil, one
+number, or one number per point.  FLOATING-POINT-INVALID-OPERATION where a model value or a
+likelihood term of a window is not finite: the reference would have trapped there."
+  (let* ((n (walker-n-chains walker))
+         (x (coerce (first data) 'list))
+         (y (second data))
+         (m (length x))
+         (per-chain (not (realp (elt y 0))))
+         (rows (if per-chain (coerce y 'list) (list y)))
+         (window (%bin-window walker take "walker-set-score-data"))
+         (none (cffi:null-pointer))
+         (sigma (cond ((null data-error) nil)
+                      ((realp data-error) (make-list m :initial-element data-error))
+                      (t (coerce data-error 'list))))
+         (yp (cffi:foreign-alloc :double :count (* (length rows) m)))
+         (sp (if sigma (cffi:foreign-alloc :double :count m) none)))
+    (unless (and (if per-chain (= (length rows) n) t)
+                 (every (lambda (row) (= (length row) m)) rows)
+                 (or (null sigma) (= (length sigma) m)))
+      (cffi:foreign-free yp)
+      (when sigma (cffi:foreign-free sp))
+      (error "walker-set-score-data: y must be ~d numbers, or ~d rows of them, and :data-error nil, ~
+              a number or ~d numbers" m n m))
+    (unwind-protect
+         (cffi:with-foreign-objects ((xp :double m) (lpd :double n) (ns :int32 n) (nu :int32 n)
+                                     (st :int32 n))
+           (fill-doubles xp x)
+           (fill-doubles yp (loop for row in rows append (coerce row 'list)))
+           (when sigma (fill-doubles sp sigma))
+           (%set-call walker #'%mhx-get-heldout #'%mhx-group-get-heldout
+                      fn-number window xp 1 m yp (if per-chain 1 0) sp (if sigma 1 0) none 0
+                      lpd ns none none nu st)
+           (loop for c below n
+                 do (when (oddp (cffi:mem-aref st :int32 c))
+                      (error 'floating-point-invalid-operation
+                             :operation 'walker-set-score-data :operands (list :chain c)))
+                 collect (list :lpd (cffi:mem-aref lpd :double c)
+                               :n-scored (cffi:mem-aref ns :int32 c)
+                               :n-used (cffi:mem-aref nu :int32 c)
+                               :status (cffi:mem-aref st :int32 c))))
+      (cffi:foreign-free yp)
+      (when sigma (cffi:foreign-free sp)))))
+
 ;;; ------------------------------------------------------------------ data and fit M:1208-1283
 ;;; The numbers behind the reference's plots.  The :function lives on the device, so the fit
 ;;; curve is mhx_eval_function and the envelope of the model over the most probable two thirds of

@@ -1929,6 +1929,176 @@ def walker_loo(walker, chain=0, take=1000, tail=None, k_limit=0.7, pointwise=Fal
     return _loo(walker, take, tail, k_limit, pointwise, int(chain), "walker-loo")[0]
 
 
+def _score_sigma(data_error, n_chains, m):
+    """(sigma, sigma_kind, rows [n_chains or 1, m]) of a :data-error for Engine.heldout: None, one
+    number, one per point, one per walker, or one list per point per walker (a list of numbers as
+    long as the points is taken per point)"""
+    if data_error is None:
+        return None, capi.SIGMA_NONE, np.ones((1, m))
+    sa = np.asarray(data_error, dtype=np.float64)
+    if sa.ndim == 0:
+        sa = np.full(m, float(sa))
+    if sa.shape == (m,):
+        return sa, capi.SIGMA_SHARED, sa[None, :]
+    if sa.shape == (n_chains,):
+        return sa, capi.SIGMA_PER_CHAIN, np.repeat(sa[:, None], m, axis=1)
+    if sa.shape == (n_chains, m):
+        return sa, capi.SIGMA_PER_POINT, sa
+    raise ValueError("data_error must be None, a number, one number per point, one per walker, or one "
+                     "list per point per walker")
+
+
+def _score_data(walker, data, data_error, take, fn_number, pointwise, chains, who, use=None):
+    e = walker.engine
+    window = _bin_window(walker, take, who)
+    x, y = data
+    ya = np.asarray(y, dtype=np.float64)
+    m = ya.shape[-1]
+    sigma, kind, rows = _score_sigma(data_error, e.n_chains, m)
+    r = e.heldout(fn_number, window, x, ya, sigma=sigma, sigma_kind=kind, use=use, pointwise=pointwise,
+                  accumulators=pointwise)
+    which = range(e.n_chains) if chains is None else [chains]
+    bad = [c for c in which if r["status"][c] & capi.HELDOUT_NONFINITE]
+    if bad:
+        raise FloatingPointError(
+            "%s: a model value or a likelihood term is not finite at a step of walker(s) %s: the "
+            "reference would have signalled a floating-point trap here" % (who, bad[:8]))
+    lk = walker.log_liklihood[fn_number]
+    lk = lk.lstrip("#':").lower() if isinstance(lk, str) else lk
+    normal = (lk is None or isinstance(lk, str)) and _LIKS.get(lk) in (capi.LIK_NORMAL, capi.LIK_NORMAL_CUTOFF)
+    out = []
+    for c in which:
+        entry = {"lpd": float(r["lpd"][c]), "n-scored": int(r["n_scored"][c]), "n-used": int(r["n_used"][c]),
+                 "status": int(r["status"][c])}
+        if pointwise:
+            n = entry["n-used"]
+            pw, acc = r["pw_lpd"][c], r["pw_acc"][c]
+            used = np.ones(m, dtype=bool) if use is None else (np.asarray(use)[c] if np.ndim(use) == 2
+                                                               else np.asarray(use)) != 0
+            entry["pointwise"] = pw
+            with np.errstate(all="ignore"):
+                ps = pw[used]
+                entry["se"] = float(np.sqrt(ps.size * np.var(ps, ddof=1))) if ps.size > 1 else float("nan")
+                var = acc[:, 3] / np.float64(n - 1)
+                entry["fit-mean"], entry["fit-stddev"] = acc[:, 2].copy(), np.sqrt(var)
+                if normal:
+                    yc = ya[c] if ya.ndim == 2 else ya
+                    sc = rows[c if rows.shape[0] > 1 else 0]
+                    entry["z-pred"] = (yc - acc[:, 2]) / np.sqrt(sc * sc + var)
+        out.append(entry)
+    return out
+
+
+def walker_set_score_data(walker, data, data_error=None, take=1000, fn_number=0, pointwise=False):
+    """Scores data the walk did NOT see under every walker's newest `take` steps - a repeated
+    measurement, a fold left out of the fit, or (for a set with a dataset per walker, which
+    walker_set_waic refuses) each walker's own spectrum: the log pointwise predictive density
+    (mhx_get_heldout, which has the definition), one device call, no history moved.  data: [x, y]
+    for every walker, or [x, [y per walker]]; data_error None, a number, one per point, one per
+    walker or one list per point per walker; the likelihood is function fn_number's own.  A list
+    with, walker by walker, {"lpd", "n-scored": the points, "n-used": the window, "status"}.
+    pointwise=True adds "pointwise" (lpd_i) and "se" = sqrt(N var(lpd_i)) (the variance with N - 1) -
+    what waic_compare takes - and, in host arithmetic that is not bit-defined, "fit-mean" and
+    "fit-stddev" (the posterior mean and sqrt(M2 / (n - 1)) of the model at each x) and, for the
+    normal likelihoods, "z-pred" = (y - fit-mean) / sqrt(sigma^2 + fit-stddev^2), the predictive
+    z-score.  Raises FloatingPointError where a model value or a term of a window is not finite."""
+    return _score_data(walker, data, data_error, take, fn_number, pointwise, None, "walker-set-score-data")
+
+
+def walker_score_data(walker, data, data_error=None, chain=0, take=1000, fn_number=0, pointwise=False):
+    """One walker's entry of walker_set_score_data (and only that walker's trap).  The device call
+    is the whole set's: for more than a few walkers call walker_set_score_data once."""
+    return _score_data(walker, data, data_error, take, fn_number, pointwise, int(chain), "walker-score-data")[0]
+
+
+def kfold_folds(n, K, scheme=":interleaved"):
+    """The fold of each of n points for K-fold cross-validation, an int32 array [n] of 0 .. K-1.
+    ":interleaved": point i is in fold i mod K (for a spectrum: every fold spans the whole x range).
+    ":blocks": K contiguous runs whose lengths differ by at most one, the longer ones first (for
+    data correlated along x).  ValueError unless 1 <= K <= n."""
+    n, K = int(n), int(K)
+    if n < 1 or K < 1 or K > n:
+        raise ValueError("kfold_folds: K = %d folds of n = %d points: 1 <= K <= n is needed" % (K, n))
+    s = str(scheme).lstrip(":").lower()
+    if s == "interleaved":
+        return (np.arange(n) % K).astype(np.int32)
+    if s == "blocks":
+        base, longer = divmod(n, K)
+        return np.repeat(np.arange(K), [base + 1 if k < longer else base for k in range(K)]).astype(np.int32)
+    raise ValueError("kfold_folds: scheme must be :interleaved or :blocks, not %r" % (scheme,))
+
+
+KFOLD_SIGMA_SCALE = 2.0 ** 400
+
+
+def walker_set_kfold_create(function=None, datasets=None, params=None, data_error=None, K=10,
+                            scheme=":interleaved", log_prior=None, **kw):
+    """K-fold cross-validation as one walker set: len(datasets) * K walkers, walker s K + k fitting
+    dataset s WITHOUT the points of fold k (kfold_folds).  A thin layer over walker_set_create: a
+    held-out point keeps its place and gets sigma_i * 2^400 (SIGMA_PER_POINT).  The factor is a
+    power of two, so 1 / sigma and y / sigma scale exactly, the point's squared residual is 2^-800
+    of its value and vanishes from the walker's sum to the last bit: the walk is the walk on the
+    training points alone.  The walker's constant carries -400 log 2 per held-out point, so the
+    :log-liklihoods of such walkers are shifted by that much - the same for every step, which no
+    walk and no percentile notices.  datasets, params (one plist, or one per dataset) and
+    data_error as walker_set_create takes them; the rest of its keywords pass through.  The walker
+    remembers w.kfold = {"K", "folds", "sigma": the unscaled stddev [len(datasets), n]}; after the
+    walk walker_set_kfold scores every fold under the walker that did not see it."""
+    dsets = [list(ds) for ds in datasets]
+    lay = planes_layout(dsets, params, data_error)
+    n = lay["x"].size
+    folds = kfold_folds(n, K, scheme)
+    K = int(K)
+    each, errors = [], []
+    for s, ds in enumerate(dsets):
+        for k in range(K):
+            each.append(ds)
+            errors.append(np.where(folds == k, lay["sigma_rows"][s] * KFOLD_SIGMA_SCALE, lay["sigma_rows"][s]))
+    one_plist = isinstance(params, dict) or (len(params) and isinstance(list(params)[0], str))
+    w = walker_set_create(function=function, datasets=each,
+                          params=params if one_plist else [q for q in params for _ in range(K)],
+                          data_error=errors, log_prior=log_prior, **kw)
+    w.kfold = {"K": K, "folds": folds, "sigma": np.array(lay["sigma_rows"], dtype=np.float64)}
+    return w
+
+
+def walker_set_kfold(walker, take=1000, pointwise=True):
+    """The K-fold estimate of a walker_set_kfold_create set: ONE device call (mhx_get_heldout with a
+    `use` mask per walker) scores fold k of dataset s under walker s K + k, which did not see it,
+    with the unscaled stddev.  A list with, dataset by dataset, {"elpd-kfold": the K walkers' lpd
+    added in fold order, "n-used": their windows, "status": their status bits or-ed}; pointwise=True
+    adds "pointwise", every point's held-out lpd exactly once and in x order, and "se" =
+    sqrt(N var(lpd_i)) (the variance with N - 1): what waic_compare takes, against another model's
+    K-fold result or a walker_waic / walker_loo result on the same points.  Raises
+    FloatingPointError where a model value or a term of a window is not finite."""
+    kf = getattr(walker, "kfold", None)
+    if kf is None or walker.planes is None:
+        raise ValueError("walker_set_kfold: the walker was not made by walker_set_kfold_create")
+    e, K, folds = walker.engine, kf["K"], kf["folds"]
+    n_sets = e.n_chains // K
+    window = _bin_window(walker, take, "walker-set-kfold")
+    use = np.array([folds == (c % K) for c in range(e.n_chains)], dtype=np.uint8)
+    r = e.heldout(0, window, walker.data[0][0], walker.planes["y"], sigma=np.repeat(kf["sigma"], K, axis=0),
+                  sigma_kind=capi.SIGMA_PER_POINT, use=use, pointwise=pointwise)
+    bad = [c for c in range(e.n_chains) if r["status"][c] & capi.HELDOUT_NONFINITE]
+    if bad:
+        raise FloatingPointError(
+            "walker-set-kfold: a model value or a likelihood term is not finite at a step of walker(s) "
+            "%s: the reference would have signalled a floating-point trap here" % (bad[:8],))
+    out = []
+    for s in range(n_sets):
+        mine = slice(s * K, (s + 1) * K)
+        entry = {"elpd-kfold": float(_serial_sum(r["lpd"][mine])), "n-used": [int(v) for v in r["n_used"][mine]],
+                 "status": int(np.bitwise_or.reduce(r["status"][mine]))}
+        if pointwise:
+            pw = r["pw_lpd"][s * K + folds, np.arange(folds.size)]
+            entry["pointwise"] = pw
+            with np.errstate(all="ignore"):
+                entry["se"] = float(np.sqrt(pw.size * np.var(pw, ddof=1))) if pw.size > 1 else float("nan")
+        out.append(entry)
+    return out
+
+
 def waic_merge(acc, n_used):
     """ONE WAIC from the chains of a set that share their data: pools the accumulators pw_acc
     [n_chains, N, 4] = (M, S, mean, M2) of Engine.waic(..., accumulators=True) over the chains,
