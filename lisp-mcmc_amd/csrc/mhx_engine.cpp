@@ -2559,6 +2559,37 @@ int mhx_get_fit_bands(mhx_engine* e, int fn, int take, const double* xcols, int 
   return run_portions(e, FitCall(fn, take, -1, nullptr, xcols, n_cols, m, ymax, ymin, n_selected, status));
 }
 
+// ---- what mhx_get_waic and mhx_get_loo share: both read the ENGINE's own data of function fn,
+// whose per-point constants are on the device (the normal forms' c array), on the host
+// (Dataset::hconst, uploaded into the portion's stage piece `cst`) or none (MHX_LIK_EXPR).
+static int refuse_planes(const mhx_engine* e, const char* who) {
+  for (int k = 0; k < e->P.K; ++k)
+    if (e->data[k].planes)
+      return fail(MHX_EUNSUPPORTED, "%s on an engine with a dataset per walker "
+                                    "(mhx_set_dataset_planes): the planes' per-point constants "
+                                    "live per walker and are not on the device", who);
+  return MHX_OK;
+}
+// the chunk's constants, where the host holds them; the status gathers over the chunks of points
+static int upload_own_data(mhx_engine* e, int fn, const Portion& p, size_t cst, size_t status) {
+  const Dataset& D = e->data[fn];
+  if (!D.hconst.empty())
+    HIP_TRY(hipMemcpyAsync(stage_at<double>(e, cst), D.hconst.data() + p.m0, (size_t)p.m * sizeof(double),
+                           hipMemcpyHostToDevice, e->stream));
+  if (p.m0 == 0)
+    HIP_TRY(hipMemsetAsync(stage_at<int32_t>(e, status), 0, (size_t)p.n * sizeof(int32_t), e->stream));
+  return MHX_OK;
+}
+extern "C++" {
+template <class Args>  // WaicArgs, LooArgs: x0, x1, y, w, c of the chunk
+static void set_own_data(const mhx_engine* e, int fn, const Portion& p, size_t cst, Args& A) {
+  const FnDesc& f = e->P.fn[fn];
+  const DataView v = data_view(f, nullptr, p.m0);
+  A.x0 = v.x0, A.x1 = v.x1, A.y = v.y, A.w = v.w;
+  A.c = !e->data[fn].hconst.empty() ? stage_at<double>(e, cst) : f.lik == MHX_LIK_EXPR ? nullptr : f.c + p.m0;
+}
+}  // extern "C++"
+
 // ---- WAIC (include/mhx.h has the definition): every chain's pointwise log-sum-exp and Welford
 // moments of the log-likelihood terms of function fn over its window (k_waic), and their totals
 // (k_waic_totals).  An item is a chain; the function's points go in chunks of kFitChunkPoints, a
@@ -2583,11 +2614,7 @@ struct WaicCall {
   int check(mhx_engine* e) {
     int rc = window_check(e, take);
     if (rc != MHX_OK || (rc = fn_check(e, fn)) != MHX_OK) return rc;
-    for (int k = 0; k < e->P.K; ++k)
-      if (e->data[k].planes)
-        return fail(MHX_EUNSUPPORTED, "mhx_get_waic on an engine with a dataset per walker "
-                                      "(mhx_set_dataset_planes): the planes' per-point constants "
-                                      "live per walker and are not on the device");
+    if ((rc = refuse_planes(e, "mhx_get_waic")) != MHX_OK) return rc;
     m = e->P.fn[fn].n;
     nb_total = waic_blocks(m);
     dst[PW_LPPD].item_bytes = dst[PW_P].item_bytes = (size_t)m * sizeof(double);
@@ -2599,34 +2626,20 @@ struct WaicCall {
   WaicPieces carve(const mhx_engine*, Carver& c, int64_t n_items, int64_t m_points) const {
     return carve_waic(c, nb_total, want, n_items, m_points);
   }
-  // the per-point constants of the chunk: on the device (the normal forms' c array), on the host
-  // (Dataset::hconst), or none (MHX_LIK_EXPR)
   int upload(mhx_engine* e, const Portion& p) const {
     Carver c;
     const WaicPieces s = carve(e, c, p.n, p.m);
-    const Dataset& D = e->data[fn];
-    if (!D.hconst.empty())
-      HIP_TRY(hipMemcpyAsync(stage_at<double>(e, s.cst), D.hconst.data() + p.m0, (size_t)p.m * sizeof(double),
-                             hipMemcpyHostToDevice, e->stream));
-    if (p.m0 == 0)
-      HIP_TRY(hipMemsetAsync(stage_at<int32_t>(e, s.status), 0, (size_t)p.n * sizeof(int32_t), e->stream));
-    return MHX_OK;
+    return upload_own_data(e, fn, p, s.cst, s.status);
   }
   int launch(mhx_engine* e, const Portion& p) const {
     Carver c;
     const WaicPieces s = carve(e, c, p.n, p.m);
-    const FnDesc& f = e->P.fn[fn];
-    const bool on_host = !e->data[fn].hconst.empty();
     WaicArgs A{};
     A.c0 = p.i0, A.n = p.n;
     A.take = take, A.fn = fn;
     A.n_blocks = (int32_t)waic_blocks(p.m);
     A.blk0 = p.m0 / MHX_WAIC_BLOCK, A.nb_total = nb_total, A.m = p.m;
-    A.x0 = f.x + p.m0;
-    A.x1 = f.n_xcols > 1 ? f.c + p.m0 : nullptr;
-    A.y = f.y + p.m0;
-    A.w = f.w + p.m0;
-    A.c = on_host ? stage_at<double>(e, s.cst) : f.lik == MHX_LIK_EXPR ? nullptr : f.c + p.m0;
+    set_own_data(e, fn, p, s.cst, A);
     A.pw_lppd = (want & WAIC_WANT_LPPD) ? stage_at<double>(e, s.pw_lppd) : nullptr;
     A.pw_p = (want & WAIC_WANT_P) ? stage_at<double>(e, s.pw_p) : nullptr;
     A.pw_acc = (want & WAIC_WANT_ACC) ? stage_at<double>(e, s.pw_acc) : nullptr;
@@ -2853,11 +2866,7 @@ struct LooCall {
     if (tail_len < 0 || tail_len > MHX_LOO_MAX_TAIL)
       return fail(MHX_EINVAL, "tail_len must be in [0, MHX_LOO_MAX_TAIL = %d]", MHX_LOO_MAX_TAIL);
     if (k_limit != k_limit) return fail(MHX_EINVAL, "k_limit is a NaN");
-    for (int k = 0; k < e->P.K; ++k)
-      if (e->data[k].planes)
-        return fail(MHX_EUNSUPPORTED, "mhx_get_loo on an engine with a dataset per walker "
-                                      "(mhx_set_dataset_planes): the planes' per-point constants "
-                                      "live per walker and are not on the device");
+    if ((rc = refuse_planes(e, "mhx_get_loo")) != MHX_OK) return rc;
     m = e->P.fn[fn].n;
     nb_total = loo_blocks(m);
     P = loo_tail_length_of(take, tail_len);
@@ -2877,33 +2886,20 @@ struct LooCall {
   LooPieces carve(const mhx_engine*, Carver& c, int64_t n_items, int64_t m_points) const {
     return carve_loo(c, nb_total, take, P, want, n_items, m_points);
   }
-  // the per-point constants of the chunk, as mhx_get_waic takes them; the status gathers over the chunks
   int upload(mhx_engine* e, const Portion& p) const {
     Carver c;
     const LooPieces s = carve(e, c, p.n, p.m);
-    const Dataset& D = e->data[fn];
-    if (!D.hconst.empty())
-      HIP_TRY(hipMemcpyAsync(stage_at<double>(e, s.cst), D.hconst.data() + p.m0, (size_t)p.m * sizeof(double),
-                             hipMemcpyHostToDevice, e->stream));
-    if (p.m0 == 0)
-      HIP_TRY(hipMemsetAsync(stage_at<int32_t>(e, s.status), 0, (size_t)p.n * sizeof(int32_t), e->stream));
-    return MHX_OK;
+    return upload_own_data(e, fn, p, s.cst, s.status);
   }
   int launch(mhx_engine* e, const Portion& p) const {
     Carver c;
     const LooPieces s = carve(e, c, p.n, p.m);
-    const FnDesc& f = e->P.fn[fn];
-    const bool on_host = !e->data[fn].hconst.empty();
     LooArgs A{};
     A.c0 = p.i0, A.n = p.n;
     A.take = take, A.fn = fn;
     A.n_blocks = (int32_t)loo_value_blocks(p.m);
     A.m = p.m;
-    A.x0 = f.x + p.m0;
-    A.x1 = f.n_xcols > 1 ? f.c + p.m0 : nullptr;
-    A.y = f.y + p.m0;
-    A.w = f.w + p.m0;
-    A.c = on_host ? stage_at<double>(e, s.cst) : f.lik == MHX_LIK_EXPR ? nullptr : f.c + p.m0;
+    set_own_data(e, fn, p, s.cst, A);
     A.terms = stage_at<double>(e, s.terms);
     A.pw_lppd = stage_at<double>(e, s.pw_lppd);
     A.status = stage_at<int32_t>(e, s.status);

@@ -4222,14 +4222,11 @@ __global__ __launch_bounds__(kThreads) void k_band_select(ChainState S, int64_t 
 }
 #endif  // MHX_FAMILY_PRIMARY
 
-// mhx_eval_function and the second half of mhx_get_fit_bands: ONE kernel, so that a band is made
-// of the very bits mhx_eval_function returns.  Wave g serves item g / n_chunks (a parameter
-// vector, or a chain and its selected steps: FitArgs, mhx_types.hpp) and chunk g % n_chunks of
-// the m points: kFitPts x per lane, kept in registers with a running max and min each.  Per step:
-// the parameter vector goes to the wave's LDS row (the next step's is on its way from memory
-// meanwhile), ONE Model::prepare with the parameters in scalar registers, then the model's
-// guarded direct form at the lane's x (Spec::values).  max / min do not depend on the order of
-// the steps.  Dynamic LDS only (the math tables lead it).
+// The model read-outs below (k_fit, k_waic, k_heldout, k_fitpct_values, k_loo_values) share ONE
+// layout of the dynamic LDS (the math tables lead it), ONE walk over parameter rows, ONE likelihood
+// term and ONE pair of recurrences: what two of them compute alike, they compute by the same
+// definition, so their bits agree by construction.  Every product and sum in them is rounded on
+// its own (the unit is compiled without contraction; no fma is written).
 struct FitLds {
   LdsHead head;
   double th[kWavesPerGroup][MHX_MAX_PARAMS + 1];
@@ -4237,9 +4234,90 @@ struct FitLds {
 };
 static_assert(sizeof(FitLds) == fit_lds_bytes(kWavesPerGroup), "fit_lds_bytes (mhx_types.hpp)");
 static_assert(__builtin_offsetof(FitLds, head) == 0, "the tables must lead the dynamic LDS");
+// The walk: the wave evaluates function f at its lanes' PTS points under each of the n parameter
+// rows r.theta[r.slot(s)], s = 0 .. n-1 (a Ring's window newest first, or SelRows).  Per row: the
+// lane's element goes to the wave's LDS row (the next row's is on its way from memory meanwhile),
+// ONE Model::prepare with the parameters in scalar registers, then the model's guarded direct form
+// at the lane's x (Spec::values: the bits of mhx_eval_function), and step(s, v) takes the values.
+template <class Spec, int PTS, class Rows, class Step>
+__device__ __forceinline__ void walk_rows(const FnDesc& f, int d, const Rows& r, int n,
+                                          const double (&x0)[PTS], const double (&x1)[PTS], Step step) {
+  FitLds& lds = *reinterpret_cast<FitLds*>(mhx_lds_raw);
+  const int w = wave_in_group(), l = lane_id();
+  double* th = lds.th[w];
+  double thn = 0.0;
+  if (n > 0 && l < d) thn = r.theta[(int64_t)r.slot(0) * d + l];
+  for (int s = 0; s < n; ++s) {
+    if (l < d) th[l] = thn;
+    __builtin_amdgcn_wave_barrier();
+    if (s + 1 < n && l < d) thn = r.theta[(int64_t)r.slot(s + 1) * d + l];
+    auto pf = [&](int j) -> double { return th[f.idx[j]]; };
+    double v[PTS];
+    Spec::template values<PTS>(f, pf, lds.scr[w], x0, x1, v);
+    step(s, v);
+  }
+}
+// The term of f's likelihood at the lane's points: t = log p(ys | v).  lik is f.lik, wave-uniform.
+template <class Spec, int PTS>
+__device__ __forceinline__ void lik_terms(const FnDesc& f, int lik, const double (&ys)[PTS],
+                                          const double (&v)[PTS], const double (&wi)[PTS],
+                                          const double (&ci)[PTS], double (&t)[PTS]) {
+  if (lik == MHX_LIK_POISSON) {
+#pragma unroll
+    for (int j = 0; j < PTS; ++j) {
+      const double a = ys[j] * tlog_rate(v[j]);
+      const double b = a - v[j];
+      t[j] = b + ci[j];
+    }
+  } else if (lik == MHX_LIK_EXPR) {
+#pragma unroll
+    for (int j = 0; j < PTS; ++j) t[j] = Spec::lik_term(f, ys[j], v[j], wi[j]);
+  } else {
+    const bool cut = lik == MHX_LIK_NORMAL_CUTOFF;
+#pragma unroll
+    for (int j = 0; j < PTS; ++j) {
+      const double a = v[j] * wi[j];
+      const double rr = ys[j] - a;
+      const double h = 0.5 * rr;
+      const double q = h * rr;
+      const double e = ci[j] - q;
+      t[j] = cut ? (e > -5000.0 ? e : -5000.0) : e;
+    }
+  }
+}
+// Step s of the running log-sum-exp of the e: max M, and S = sum of exp(e - M).  (if / else, not
+// conditional expressions: from these the compiler lays the walk's steps out as it did when every
+// kernel spelled the recurrence out on its own arrays - k_waic 117 VGPRs against 123, and 2 per
+// cent of its time.)
+__device__ __forceinline__ void lse_push(double& M, double& S, double e, int s) {
+  const bool up = e > M;
+  double a, sn;
+  if (up) a = M - e; else a = e - M;
+  const double ge = gexp(a);
+  if (up) sn = S * ge + 1.0; else sn = S + ge;
+  S = s == 0 ? 1.0 : sn;
+  if (s == 0 || up) M = e;
+}
+// One step of Welford's recurrence for the mean and M2 of the e; qk = 1 / (steps so far, e included).
+__device__ __forceinline__ void welford_push(double& mean, double& m2, double e, double qk) {
+  const double dl = e - mean;
+  mean = mean + dl * qk;
+  m2 = m2 + dl * (e - mean);
+}
+
+// mhx_eval_function and the second half of mhx_get_fit_bands: ONE kernel, so that a band is made
+// of the very bits mhx_eval_function returns.  Wave g serves item g / n_chunks (a parameter
+// vector, or a chain and its selected steps: FitArgs, mhx_types.hpp) and chunk g % n_chunks of
+// the m points: kFitPts x per lane, kept in registers with a running max and min each, which do
+// not depend on the order of the steps.
+struct SelRows {  // an item's rows of FitArgs::theta: the one at `base`, or base + sel[k]
+  const double* theta;
+  const int32_t* sel;
+  int64_t base;
+  __device__ __forceinline__ int64_t slot(int k) const { return base + (sel ? (int64_t)sel[k] : 0); }
+};
 template <class Spec>
 __device__ __forceinline__ void k_fit_body(const ProblemDesc* __restrict__ Pp, FitArgs A) {
-  FitLds& lds = *reinterpret_cast<FitLds*>(mhx_lds_raw);
   lds_tables_begin();
   __syncthreads();  // (the only barrier: waves without work leave behind it)
   const int w = wave_in_group(), l = lane_id();
@@ -4248,7 +4326,6 @@ __device__ __forceinline__ void k_fit_body(const ProblemDesc* __restrict__ Pp, F
   const int64_t i = g / A.n_chunks;
   const int64_t p0 = (g - i * A.n_chunks) * (int64_t)(kWave * kFitPts) + l;
   const FnDesc& f = Pp->fn[A.fn];
-  const int d = Pp->d;
   double x0[kFitPts], x1[kFitPts], mx[kFitPts], mn[kFitPts];
 #pragma unroll
   for (int j = 0; j < kFitPts; ++j) {
@@ -4259,26 +4336,17 @@ __device__ __forceinline__ void k_fit_body(const ProblemDesc* __restrict__ Pp, F
     mx[j] = mn[j] = 0.0;
   }
   const int ns = A.sel ? __builtin_amdgcn_readfirstlane(A.n_sel[i]) : 1;
-  const int32_t* sl = A.sel ? A.sel + i * A.sel_pitch : nullptr;
-  const int64_t base = A.row0 + i * A.rows_per_item;
-  double* th = lds.th[w];
-  double thn = 0.0;
-  if (ns > 0 && l < d) thn = A.theta[(base + (sl ? (int64_t)sl[0] : 0)) * d + l];
+  const SelRows r{A.theta, A.sel ? A.sel + i * A.sel_pitch : nullptr, A.row0 + i * A.rows_per_item};
   bool bad = false;
-  for (int k = 0; k < ns; ++k) {
-    if (l < d) th[l] = thn;
-    __builtin_amdgcn_wave_barrier();
-    if (k + 1 < ns && l < d) thn = A.theta[(base + (int64_t)sl[k + 1]) * d + l];
-    auto pf = [&](int j) -> double { return th[f.idx[j]]; };
-    double v[kFitPts];
-    Spec::template values<kFitPts>(f, pf, lds.scr[w], x0, x1, v);
+  walk_rows<Spec, kFitPts>(f, Pp->d, r, ns, x0, x1,
+                            [&](int k, const double (&v)[kFitPts]) {
 #pragma unroll
     for (int j = 0; j < kFitPts; ++j) {
       bad = bad || !finite_f64(v[j]);
       mx[j] = (k == 0 || v[j] > mx[j]) ? v[j] : mx[j];
       mn[j] = (k == 0 || v[j] < mn[j]) ? v[j] : mn[j];
     }
-  }
+  });
 #pragma unroll
   for (int j = 0; j < kFitPts; ++j) {
     const int64_t p = p0 + (int64_t)j * kWave;
@@ -4296,20 +4364,16 @@ __global__ __launch_bounds__(kThreads) void k_fit(const ProblemDesc* __restrict_
 }
 #endif
 
-// mhx_get_waic (include/mhx.h has the definition, operation by operation): k_fit's shape with the
-// likelihood behind it.  Wave g serves chain g / n_blocks of the launch and block g % n_blocks of
-// its points: kWaicPts points per lane, whose x, ys, w, c and the four accumulators {M, S, mean,
-// M2} stay in registers.  The window's steps are addressed by ring slot, newest first - no
-// selection pass; each step's parameter vector goes through the wave's LDS row with the next
-// step's load in flight, then ONE Spec::values (the bits of mhx_eval_function), the term of the
-// function's likelihood (wave-uniform) and the two accumulations.  Every product and sum below
-// is rounded on its own (the unit is compiled without contraction; no fma is written here).  The
-// block's sums of pw_lppd and pw_p and its count of pw_p > 0.4 go to part_*[chain][block]:
-// k_waic_totals adds them in block order.
+// mhx_get_waic (include/mhx.h has the definition, operation by operation): the walk over a chain's
+// window (addressed by ring slot, newest first - no selection pass) with the likelihood behind it.
+// Wave g serves chain g / n_blocks of the launch and block g % n_blocks of its points: kWaicPts
+// points per lane, whose x, ys, w, c and the four accumulators {M, S, mean, M2} stay in registers.
+// Per step: the term, then its Welford and log-sum-exp pushes.  The block's sums of pw_lppd and
+// pw_p and its count of pw_p > 0.4 go to part_*[chain][block]: k_waic_totals adds them in block
+// order.
 template <class Spec>
 __device__ __forceinline__ void k_waic_body(const ProblemDesc* __restrict__ Pp, ChainState S,
                                             WaicArgs A) {
-  FitLds& lds = *reinterpret_cast<FitLds*>(mhx_lds_raw);
   lds_tables_begin();
   __syncthreads();  // (the only barrier: waves without work leave behind it)
   const int w = wave_in_group(), l = lane_id();
@@ -4319,7 +4383,6 @@ __device__ __forceinline__ void k_waic_body(const ProblemDesc* __restrict__ Pp, 
   const int64_t blk = g - i * A.n_blocks;
   const int64_t p0 = blk * (int64_t)(kWave * kWaicPts) + l;
   const FnDesc& f = Pp->fn[A.fn];
-  const int d = Pp->d;
   const int lik = __builtin_amdgcn_readfirstlane(f.lik);
   double x0[kWaicPts], x1[kWaicPts], ys[kWaicPts], wi[kWaicPts], ci[kWaicPts];
   double aM[kWaicPts], aS[kWaicPts], mean[kWaicPts], m2[kWaicPts];
@@ -4336,54 +4399,20 @@ __device__ __forceinline__ void k_waic_body(const ProblemDesc* __restrict__ Pp, 
   }
   const Ring r = ring_of(S, A.c0 + i);
   const int n = ring_held(r, A.take);
-  double* th = lds.th[w];
-  double thn = 0.0;
-  if (n > 0 && l < d) thn = r.theta[(int64_t)r.slot(0) * d + l];
   bool bad = false;
-  for (int s = 0; s < n; ++s) {
-    if (l < d) th[l] = thn;
-    __builtin_amdgcn_wave_barrier();
-    if (s + 1 < n && l < d) thn = r.theta[(int64_t)r.slot(s + 1) * d + l];
-    auto pf = [&](int j) -> double { return th[f.idx[j]]; };
-    double v[kWaicPts], t[kWaicPts];
-    Spec::template values<kWaicPts>(f, pf, lds.scr[w], x0, x1, v);
-    if (lik == MHX_LIK_POISSON) {
-#pragma unroll
-      for (int j = 0; j < kWaicPts; ++j) {
-        const double a = ys[j] * tlog_rate(v[j]);
-        const double b = a - v[j];
-        t[j] = b + ci[j];
-      }
-    } else if (lik == MHX_LIK_EXPR) {
-#pragma unroll
-      for (int j = 0; j < kWaicPts; ++j) t[j] = Spec::lik_term(f, ys[j], v[j], wi[j]);
-    } else {
-      const bool cut = lik == MHX_LIK_NORMAL_CUTOFF;
-#pragma unroll
-      for (int j = 0; j < kWaicPts; ++j) {
-        const double a = v[j] * wi[j];
-        const double rr = ys[j] - a;
-        const double h = 0.5 * rr;
-        const double q = h * rr;
-        const double e = ci[j] - q;
-        t[j] = cut ? (e > -5000.0 ? e : -5000.0) : e;
-      }
-    }
+  walk_rows<Spec, kWaicPts>(f, Pp->d, r, n, x0, x1,
+                            [&](int s, const double (&v)[kWaicPts]) {
+    double t[kWaicPts];
+    lik_terms<Spec, kWaicPts>(f, lik, ys, v, wi, ci, t);
     const double qk = 1.0 / (double)(s + 1);
 #pragma unroll
     for (int j = 0; j < kWaicPts; ++j) {
       const double e = t[j];
       bad = bad || !finite_f64(v[j]) || !finite_f64(e);
-      const double dl = e - mean[j];
-      mean[j] = mean[j] + dl * qk;
-      m2[j] = m2[j] + dl * (e - mean[j]);
-      const bool up = e > aM[j];
-      const double ge = gexp(up ? aM[j] - e : e - aM[j]);
-      const double sn = up ? aS[j] * ge + 1.0 : aS[j] + ge;
-      aS[j] = s == 0 ? 1.0 : sn;
-      aM[j] = (s == 0 || up) ? e : aM[j];
+      welford_push(mean[j], m2[j], e, qk);
+      lse_push(aM[j], aS[j], e, s);
     }
-  }
+  });
   const double nm1 = (double)(n - 1), nd = (double)n;
   double sl = 0.0, sp = 0.0;
   int nh = 0;
@@ -4466,20 +4495,16 @@ __global__ __launch_bounds__(kThreads) void k_waic_totals(ChainState S, int64_t 
 #endif
 
 // mhx_get_heldout (include/mhx.h has the definition, operation by operation): k_waic_body over data
-// the caller handed in.  The same wave per (chain, block), the same four points a lane, the same
-// walk over the window with the next step's parameter row in flight, ONE Spec::values a step, the
-// same term and the same log-sum-exp - so that with the engine's own data the pair (M, S) and
-// pw_lpd are k_waic's bits.  What differs: ys, w, c and the use flag are read through the pitches of
-// HeldoutArgs (the host prepared them: one instance serves shared and per-chain data), the Welford
-// pair follows the VALUES (k_fitpct_values_body's recurrence), and a point the chain does not use
-// is computed like any other but stores 0.0, adds 0.0 and flags nothing.  Every product and sum is
-// rounded on its own (the unit is compiled without contraction; no fma is written here).  The
-// block's sum of pw_lpd and its count of used points go to part_*[chain][block]: k_heldout_totals
-// adds them in block order.
+// the caller handed in, with the same wave per (chain, block) and the same four points a lane.  By
+// the shared definitions the pair (M, S) and pw_lpd are k_waic's bits with the engine's own data,
+// and the Welford pair, which here follows the VALUES, is k_fitpct_values'.  What differs: ys, w, c
+// and the use flag are read through the pitches of HeldoutArgs (the host prepared them: one
+// instance serves shared and per-chain data), and a point the chain does not use is computed like
+// any other but stores 0.0, adds 0.0 and flags nothing.  The block's sum of pw_lpd and its count of
+// used points go to part_*[chain][block]: k_heldout_totals adds them in block order.
 template <class Spec>
 __device__ __forceinline__ void k_heldout_body(const ProblemDesc* __restrict__ Pp, ChainState S,
                                                HeldoutArgs A) {
-  FitLds& lds = *reinterpret_cast<FitLds*>(mhx_lds_raw);
   lds_tables_begin();
   __syncthreads();  // (the only barrier: waves without work leave behind it)
   const int w = wave_in_group(), l = lane_id();
@@ -4489,7 +4514,6 @@ __device__ __forceinline__ void k_heldout_body(const ProblemDesc* __restrict__ P
   const int64_t blk = g - i * A.n_blocks;
   const int64_t p0 = blk * (int64_t)(kWave * kWaicPts) + l;
   const FnDesc& f = Pp->fn[A.fn];
-  const int d = Pp->d;
   const int lik = __builtin_amdgcn_readfirstlane(f.lik);
   const double* const ysr = A.ys + i * A.y_pitch;
   const double* const wr = A.w + i * A.w_pitch;
@@ -4512,59 +4536,25 @@ __device__ __forceinline__ void k_heldout_body(const ProblemDesc* __restrict__ P
   }
   const Ring r = ring_of(S, A.c0 + i);
   const int n = ring_held(r, A.take);
-  double* th = lds.th[w];
-  double thn = 0.0;
-  if (n > 0 && l < d) thn = r.theta[(int64_t)r.slot(0) * d + l];
   bool bad = false;
-  for (int s = 0; s < n; ++s) {
-    if (l < d) th[l] = thn;
-    __builtin_amdgcn_wave_barrier();
-    if (s + 1 < n && l < d) thn = r.theta[(int64_t)r.slot(s + 1) * d + l];
-    auto pf = [&](int j) -> double { return th[f.idx[j]]; };
-    double v[kWaicPts], t[kWaicPts];
-    Spec::template values<kWaicPts>(f, pf, lds.scr[w], x0, x1, v);
+  walk_rows<Spec, kWaicPts>(f, Pp->d, r, n, x0, x1,
+                            [&, um](int s, const double (&v)[kWaicPts]) {
+    double t[kWaicPts];
     const double qk = 1.0 / (double)(s + 1);
 #pragma unroll
     for (int j = 0; j < kWaicPts; ++j) {  // (the values' moments first: a value then lives to its term only)
       const double u = v[j];
       bad = bad || (((um >> j) & 1u) != 0u && !finite_f64(u));
-      const double dl = u - mean[j];
-      mean[j] = mean[j] + dl * qk;
-      m2[j] = m2[j] + dl * (u - mean[j]);
+      welford_push(mean[j], m2[j], u, qk);
     }
-    if (lik == MHX_LIK_POISSON) {
-#pragma unroll
-      for (int j = 0; j < kWaicPts; ++j) {
-        const double a = ys[j] * tlog_rate(v[j]);
-        const double b = a - v[j];
-        t[j] = b + ci[j];
-      }
-    } else if (lik == MHX_LIK_EXPR) {
-#pragma unroll
-      for (int j = 0; j < kWaicPts; ++j) t[j] = Spec::lik_term(f, ys[j], v[j], wi[j]);
-    } else {
-      const bool cut = lik == MHX_LIK_NORMAL_CUTOFF;
-#pragma unroll
-      for (int j = 0; j < kWaicPts; ++j) {
-        const double a = v[j] * wi[j];
-        const double rr = ys[j] - a;
-        const double h = 0.5 * rr;
-        const double q = h * rr;
-        const double e = ci[j] - q;
-        t[j] = cut ? (e > -5000.0 ? e : -5000.0) : e;
-      }
-    }
+    lik_terms<Spec, kWaicPts>(f, lik, ys, v, wi, ci, t);
 #pragma unroll
     for (int j = 0; j < kWaicPts; ++j) {
       const double e = t[j];
       bad = bad || (((um >> j) & 1u) != 0u && !finite_f64(e));
-      const bool up = e > aM[j];
-      const double ge = gexp(up ? aM[j] - e : e - aM[j]);
-      const double sn = up ? aS[j] * ge + 1.0 : aS[j] + ge;
-      aS[j] = s == 0 ? 1.0 : sn;
-      aM[j] = (s == 0 || up) ? e : aM[j];
+      lse_push(aM[j], aS[j], e, s);
     }
-  }
+  });
   const double nd = (double)n;
   double sl = 0.0;
   int ns = 0;
@@ -5151,18 +5141,14 @@ __global__ __launch_bounds__(kWave) void k_cand_totals(const ProblemDesc* __rest
 }
 #endif
 
-// mhx_get_fit_percentiles, first half (include/mhx.h has the definition): k_waic's walk over the
+// mhx_get_fit_percentiles, first half (include/mhx.h has the definition): the walk over a chain's
 // window with nothing behind the model.  Wave g serves chain g / n_blocks of the launch and block
 // g % n_blocks of its points: kFitPctPts points per lane, whose x and Welford pair {mean, M2} stay
-// in registers.  The window's steps are addressed by ring slot, newest first; each step's
-// parameter vector goes through the wave's LDS row with the next step's load in flight, then ONE
-// Spec::values (the bits of mhx_eval_function), the recurrence, and the values' stores into the
-// portion's stage piece (FitPctArgs has the layout).  Every product and sum is rounded on its own
-// (the unit is compiled without contraction; no fma is written here).
+// in registers.  Per step: the values' Welford push and their stores into the portion's stage
+// piece (FitPctArgs has the layout).
 template <class Spec>
 __device__ __forceinline__ void k_fitpct_values_body(const ProblemDesc* __restrict__ Pp, ChainState S,
                                                      FitPctArgs A) {
-  FitLds& lds = *reinterpret_cast<FitLds*>(mhx_lds_raw);
   lds_tables_begin();
   __syncthreads();  // (the only barrier: waves without work leave behind it)
   const int w = wave_in_group(), l = lane_id();
@@ -5171,7 +5157,6 @@ __device__ __forceinline__ void k_fitpct_values_body(const ProblemDesc* __restri
   const int64_t i = g / A.n_blocks;
   const int64_t p0 = (g - i * A.n_blocks) * (int64_t)(kWave * kFitPctPts) + l;
   const FnDesc& f = Pp->fn[A.fn];
-  const int d = Pp->d;
   double x0[kFitPctPts], x1[kFitPctPts], mean[kFitPctPts], m2[kFitPctPts];
 #pragma unroll
   for (int j = 0; j < kFitPctPts; ++j) {
@@ -5183,30 +5168,20 @@ __device__ __forceinline__ void k_fitpct_values_body(const ProblemDesc* __restri
   }
   const Ring r = ring_of(S, A.c0 + i);
   const int n = ring_held(r, A.take);
-  double* th = lds.th[w];
   double* const out = A.values + i * ((int64_t)A.take * A.m) + p0 * A.vs_point;
-  double thn = 0.0;
-  if (n > 0 && l < d) thn = r.theta[(int64_t)r.slot(0) * d + l];
   bool bad = false;
-  for (int s = 0; s < n; ++s) {
-    if (l < d) th[l] = thn;
-    __builtin_amdgcn_wave_barrier();
-    if (s + 1 < n && l < d) thn = r.theta[(int64_t)r.slot(s + 1) * d + l];
-    auto pf = [&](int j) -> double { return th[f.idx[j]]; };
-    double v[kFitPctPts];
-    Spec::template values<kFitPctPts>(f, pf, lds.scr[w], x0, x1, v);
+  walk_rows<Spec, kFitPctPts>(f, Pp->d, r, n, x0, x1,
+                            [&](int s, const double (&v)[kFitPctPts]) {
     const double qk = 1.0 / (double)(s + 1);
     double* const row = out + (int64_t)s * A.vs_step;
 #pragma unroll
     for (int j = 0; j < kFitPctPts; ++j) {
       const double e = v[j];
       bad = bad || !finite_f64(e);
-      const double dl = e - mean[j];
-      mean[j] = mean[j] + dl * qk;
-      m2[j] = m2[j] + dl * (e - mean[j]);
+      welford_push(mean[j], m2[j], e, qk);
       if (p0 + (int64_t)j * kWave < A.m) row[(int64_t)j * kWave * A.vs_point] = e;
     }
-  }
+  });
   const double nm1 = (double)(n - 1);
 #pragma unroll
   for (int j = 0; j < kFitPctPts; ++j) {
@@ -5361,18 +5336,15 @@ __global__ __launch_bounds__(kPctThreads) void k_fitpct_select(
 }
 #endif
 
-// mhx_get_loo, first half (include/mhx.h has the definition): k_waic's walk over the window with
-// the log-sum-exp pair alone behind the likelihood.  Wave g serves chain g / n_blocks of the launch
-// and block g % n_blocks of its points: kLooValPts points per lane, whose x, ys, w, c and the pair
-// {M, S} stay in registers.  Each step's term goes to the portion's stage piece as
+// mhx_get_loo, first half (include/mhx.h has the definition): the walk over a chain's window
+// with the log-sum-exp pair alone behind the likelihood.  Wave g serves chain g / n_blocks of the
+// launch and block g % n_blocks of its points: kLooValPts points per lane, whose x, ys, w, c and
+// the pair {M, S} stay in registers.  Each step's term goes to the portion's stage piece as
 // k_fitpct_values stores its values (LooArgs has the layout): the stores of a wave are whole lines.
-// The value, the term and the recurrence are k_waic_body's, operation for operation, so pw_lppd is
-// mhx_get_waic's to the bit.  Every product and sum is rounded on its own (the unit is compiled
-// without contraction; no fma is written here).
+// By the shared definitions pw_lppd is mhx_get_waic's to the bit.
 template <class Spec>
 __device__ __forceinline__ void k_loo_values_body(const ProblemDesc* __restrict__ Pp, ChainState S,
                                                   LooArgs A) {
-  FitLds& lds = *reinterpret_cast<FitLds*>(mhx_lds_raw);
   lds_tables_begin();
   __syncthreads();  // (the only barrier: waves without work leave behind it)
   const int w = wave_in_group(), l = lane_id();
@@ -5381,7 +5353,6 @@ __device__ __forceinline__ void k_loo_values_body(const ProblemDesc* __restrict_
   const int64_t i = g / A.n_blocks;
   const int64_t p0 = (g - i * A.n_blocks) * (int64_t)(kWave * kLooValPts) + l;
   const FnDesc& f = Pp->fn[A.fn];
-  const int d = Pp->d;
   const int lik = __builtin_amdgcn_readfirstlane(f.lik);
   double x0[kLooValPts], x1[kLooValPts], ys[kLooValPts], wi[kLooValPts], ci[kLooValPts], aM[kLooValPts], aS[kLooValPts];
 #pragma unroll
@@ -5397,53 +5368,21 @@ __device__ __forceinline__ void k_loo_values_body(const ProblemDesc* __restrict_
   }
   const Ring r = ring_of(S, A.c0 + i);
   const int n = ring_held(r, A.take);
-  double* th = lds.th[w];
   double* const out = A.terms + i * ((int64_t)A.take * A.m) + p0;
-  double thn = 0.0;
-  if (n > 0 && l < d) thn = r.theta[(int64_t)r.slot(0) * d + l];
   bool bad = false;
-  for (int s = 0; s < n; ++s) {
-    if (l < d) th[l] = thn;
-    __builtin_amdgcn_wave_barrier();
-    if (s + 1 < n && l < d) thn = r.theta[(int64_t)r.slot(s + 1) * d + l];
-    auto pf = [&](int j) -> double { return th[f.idx[j]]; };
-    double v[kLooValPts], t[kLooValPts];
-    Spec::template values<kLooValPts>(f, pf, lds.scr[w], x0, x1, v);
-    if (lik == MHX_LIK_POISSON) {
-#pragma unroll
-      for (int j = 0; j < kLooValPts; ++j) {
-        const double a = ys[j] * tlog_rate(v[j]);
-        const double b = a - v[j];
-        t[j] = b + ci[j];
-      }
-    } else if (lik == MHX_LIK_EXPR) {
-#pragma unroll
-      for (int j = 0; j < kLooValPts; ++j) t[j] = Spec::lik_term(f, ys[j], v[j], wi[j]);
-    } else {
-      const bool cut = lik == MHX_LIK_NORMAL_CUTOFF;
-#pragma unroll
-      for (int j = 0; j < kLooValPts; ++j) {
-        const double a = v[j] * wi[j];
-        const double rr = ys[j] - a;
-        const double h = 0.5 * rr;
-        const double q = h * rr;
-        const double e = ci[j] - q;
-        t[j] = cut ? (e > -5000.0 ? e : -5000.0) : e;
-      }
-    }
+  walk_rows<Spec, kLooValPts>(f, Pp->d, r, n, x0, x1,
+                            [&](int s, const double (&v)[kLooValPts]) {
+    double t[kLooValPts];
+    lik_terms<Spec, kLooValPts>(f, lik, ys, v, wi, ci, t);
     double* const row = out + (int64_t)s * A.m;
 #pragma unroll
     for (int j = 0; j < kLooValPts; ++j) {
       const double e = t[j];
       bad = bad || !finite_f64(v[j]) || !finite_f64(e);
-      const bool up = e > aM[j];
-      const double ge = gexp(up ? aM[j] - e : e - aM[j]);
-      const double sn = up ? aS[j] * ge + 1.0 : aS[j] + ge;
-      aS[j] = s == 0 ? 1.0 : sn;
-      aM[j] = (s == 0 || up) ? e : aM[j];
+      lse_push(aM[j], aS[j], e, s);
       if (p0 + (int64_t)j * kWave < A.m) row[j * kWave] = e;
     }
-  }
+  });
   const double nd = (double)n;
 #pragma unroll
   for (int j = 0; j < kLooValPts; ++j) {

@@ -276,8 +276,8 @@ constexpr unsigned fit_lds_bytes(int wpg) {
 // 128 VGPRs (4 waves per SIMD), one above (2 waves per SIMD, whatever the compiler's "3" says).
 // As compiled for gfx950 with 4 points no instance uses scratch; config 2's two-peak kernel takes
 // 117 VGPRs and the polynomials 114: two workgroups a CU, as their k_fit.  The five-peak Poisson,
-// pvoigt2 and lorder instances take 136 to 143 and the generic kernel 185: one workgroup a CU
-// (pvoigt2's and the generic k_fit are there already; Poisson's and lorder's k_fit, at 126 and
+// pvoigt2 and lorder instances take 139 to 145 and the generic kernel 185: one workgroup a CU
+// (pvoigt2's and the generic k_fit are there already; Poisson's and lorder's k_fit, at 123 and
 // 124, still fit two).  With 8 points the arrays alone are 144 VGPRs: EVERY instance, the flagship
 // included, would fall to one workgroup a CU, for the sake of halving a per-step prepare that
 // 256 points share already.  MHX_WAIC_BLOCK must divide kFitChunkPoints, so the choice is among
@@ -317,7 +317,7 @@ struct WaicArgs {
 // value moments take the place of the term moments, and there is no pw_p), and one byte for the use
 // flags (bits of one register): the register budget of kWaicPts above applies.  As compiled for
 // gfx950: config 2's two-peak instance 113 VGPRs and the polynomials 110 and 111 (two workgroups a
-// CU, as their k_waic), five-peak Poisson 143, pvoigt2 141, lorder 136, the generic kernel 185 (one
+// CU, as their k_waic), five-peak Poisson 143, pvoigt2 145, lorder 139, the generic kernel 185 (one
 // workgroup a CU, as their k_waic); no instance uses scratch.  The value moments are taken right
 // behind Spec::values, ahead of the term: with them in the log-sum-exp's loop, where k_waic has
 // its term moments, a value lived across the exponentials and every instance took 20 VGPRs more

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """CPU-side check that the embedded device sources compile under hiprtc for gfx950 (no GPU
-needed): mirrors what mhx_rtc.cpp generates for one expression model and one prior body."""
+needed): mirrors what mhx_rtc.cpp generates for one expression model and one prior body, the
+twins of the five window read-outs (k_fit .. k_heldout) included."""
 import ctypes as C
 import os
 import sys
@@ -23,11 +24,26 @@ struct UserModel0 {
   }
 };
 struct UserSpec {
+  static constexpr bool kDeal = false;
   template <class PF>
   static __device__ __forceinline__ double loglik(const FnDesc& f, PF pf, bool active, GroupLds& lds, double* scratch) {
     switch (f.user_slot) {
       case 0: return GenericSpec::by_lik<UserModel0>(f, pf, active, lds);
       default: return GenericSpec::loglik(f, pf, active, lds, scratch);
+    }
+  }
+  template <int PTS, class PF>
+  static __device__ __forceinline__ void values(const FnDesc& f, PF pf, double* scratch,
+      const double (&x0)[PTS], const double (&x1)[PTS], double (&v)[PTS]) {
+    switch (f.user_slot) {
+      case 0: return model_values<UserModel0, PTS>(f, pf, scratch, x0, x1, v);
+      default: return GenericSpec::values<PTS>(f, pf, scratch, x0, x1, v);
+    }
+  }
+  static __device__ __forceinline__ double lik_term(const FnDesc& f, double y, double model, double error) {
+    switch (f.user_slot) {
+      case 0: return (double)(-0.5 * (y - model) * (y - model) / (error * error));
+      default: return __builtin_nan("");
     }
   }
   static __device__ __forceinline__ double logprior(const FnDesc& f, const double* th, double bounds_total) {
@@ -43,6 +59,16 @@ extern "C" __global__ __launch_bounds__(512) void mhx_user_logpost(const Problem
   k_logpost_body<UserSpec>(P, theta, n, out, parts); }
 extern "C" __global__ __launch_bounds__(512, 4) void mhx_user_adaptive(const ProblemDesc* P, ChainState S, RunDesc R, int64_t max_iters, int plain) {
   k_adaptive_body<UserSpec>(P, S, R, max_iters, plain); }
+extern "C" __global__ __launch_bounds__(512) void mhx_user_fit(const ProblemDesc* P, FitArgs A) {
+  k_fit_body<UserSpec>(P, A); }
+extern "C" __global__ __launch_bounds__(512) void mhx_user_waic(const ProblemDesc* P, ChainState S, WaicArgs A) {
+  k_waic_body<UserSpec>(P, S, A); }
+extern "C" __global__ __launch_bounds__(512) void mhx_user_heldout(const ProblemDesc* P, ChainState S, HeldoutArgs A) {
+  k_heldout_body<UserSpec>(P, S, A); }
+extern "C" __global__ __launch_bounds__(512) void mhx_user_fitpct(const ProblemDesc* P, ChainState S, FitPctArgs A) {
+  k_fitpct_values_body<UserSpec>(P, S, A); }
+extern "C" __global__ __launch_bounds__(512) void mhx_user_loo(const ProblemDesc* P, ChainState S, LooArgs A) {
+  k_loo_values_body<UserSpec>(P, S, A); }
 '''
 
 
@@ -51,14 +77,18 @@ def main():
     hdr_files = [("mhx_kernels.hpp", os.path.join(CSRC, "mhx_kernels.hpp")),
                  ("mhx_device.hpp", os.path.join(CSRC, "mhx_device.hpp")),
                  ("mhx_types.hpp", os.path.join(CSRC, "mhx_types.hpp")),
-                 ("../../include/mhx.h", os.path.join(ROOT, "include", "mhx.h"))]
-    srcs = (C.c_char_p * 4)(*[open(p, "rb").read() for _, p in hdr_files])
-    names = (C.c_char_p * 4)(*[n.encode() for n, _ in hdr_files])
+                 ("../../include/mhx.h", os.path.join(ROOT, "include", "mhx.h")),
+                 ("mhx_exp2_table.inc", os.path.join(CSRC, "mhx_exp2_table.inc")),
+                 ("mhx_log_table.inc", os.path.join(CSRC, "mhx_log_table.inc")),
+                 ("mhx_derived.hpp", os.path.join(CSRC, "mhx_derived.hpp"))]
+    nh = len(hdr_files)
+    srcs = (C.c_char_p * nh)(*[open(p, "rb").read() for _, p in hdr_files])
+    names = (C.c_char_p * nh)(*[n.encode() for n, _ in hdr_files])
     prog = C.c_void_p()
-    rc = rtc.hiprtcCreateProgram(C.byref(prog), SRC.encode(), b"mhx_user.hip", 4, srcs, names)
+    rc = rtc.hiprtcCreateProgram(C.byref(prog), SRC.encode(), b"mhx_user.hip", nh, srcs, names)
     assert rc == 0, rc
-    opts = (C.c_char_p * 4)(b"--offload-arch=gfx950", b"-O3", b"-std=c++17", b"-ffp-contract=off")
-    rc = rtc.hiprtcCompileProgram(prog, 4, opts)
+    opts = [b"--offload-arch=gfx950", b"-O3", b"-std=c++17", b"-ffp-contract=off", b"-DMHX_WPG=8", b"-DMHX_FAMILY=w8"]
+    rc = rtc.hiprtcCompileProgram(prog, len(opts), (C.c_char_p * len(opts))(*opts))
     n = C.c_size_t()
     rtc.hiprtcGetProgramLogSize(prog, C.byref(n))
     log = C.create_string_buffer(n.value + 1)
