@@ -2,7 +2,7 @@
 // walker-with-exp (M:1052-1064) for every step of every chain's window.  Included only by the
 // run-time compiled module mhx_user_derived (mhx_rtc.cpp: generate_derived), never by the
 // stepping programs and never by the ahead-of-time units; the summaries of the values are
-// k_derived_summary's (mhx_kernels.hpp), which needs no expression.
+// k_derived_summary's (mhx_readout_kernels.hpp), which needs no expression.
 #pragma once
 #include "mhx_kernels.hpp"
 

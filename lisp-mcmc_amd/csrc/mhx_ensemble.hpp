@@ -117,7 +117,7 @@ inline void ensemble_take_successors(EnsTarget* t, int n, const uint64_t* least)
     if (t[i].task >= 0) t[i].next = least[t[i].task];
 }
 
-// the double of an order key (order_key of mhx_kernels.hpp, inverted; the NaN key gives a NaN)
+// the double of an order key (order_key of mhx_readout_kernels.hpp, inverted; the NaN key gives a NaN)
 inline double ensemble_key_value(uint64_t k) {
   const uint64_t b = (k >> 63) ? (k ^ ((uint64_t)1 << 63)) : ~k;
   double v;

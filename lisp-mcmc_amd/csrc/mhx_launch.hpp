@@ -63,7 +63,7 @@ struct Family {
 const Family& family_w8();
 const Family& family_w16();
 
-// walker-set-get: summaries of the `n` chains from `c0` on (mhx_kernels.hpp; family-independent,
+// walker-set-get: summaries of the `n` chains from `c0` on (mhx_readout_kernels.hpp; family-independent,
 // compiled once).  Outputs and scratch are indexed by the chain's place in [c0, c0 + n).
 // The LDS a percentile workgroup needs for a window of `take` steps of d parameters, and the
 // column pitch that goes with it; above kPctLdsBudget the kernel reads its columns from memory.

@@ -453,7 +453,9 @@ struct EmbeddedHeader {
   const char* src;
   const char* name;
 };
-// what the stepping programs include (their cache keys hash exactly these, in this order)
+// What the stepping programs include.  Hand-written, because the order matters: a program's cache
+// key hashes exactly these in this order.  (tests/test_device_sources.py holds the list to what
+// the sources include.)
 static const std::vector<EmbeddedHeader> kStepHeaders = {
     {kSrc_mhx_kernels_hpp, "mhx_kernels.hpp"}, {kSrc_mhx_device_hpp, "mhx_device.hpp"},
     {kSrc_mhx_types_hpp, "mhx_types.hpp"},     {kSrc_mhx_h, "../../include/mhx.h"},

@@ -394,6 +394,41 @@ PortionCursor portion_cursor(int64_t items, int64_t points, Carve&& carve) {
   return at;
 }
 
+// The cursor of a call whose values are staged per item, step and point (mhx_get_fit_percentiles,
+// mhx_get_loo).  portion_cursor's fixed chunk would ask 1 GB of one chain at take 1000: here the
+// chunk of points is all of `points` where one item fits the budget with them (fits(m); and they
+// are at most kFitChunkPoints), else the largest whole number of blocks of `block` points, at most
+// kFitChunkPoints, with which one item fits.  chunk == 0: not even one block fits - the caller
+// refuses the call.
+template <class Fits, class Carve>
+PortionCursor block_cursor(int64_t items, int64_t points, int64_t block, Fits&& fits, Carve&& carve) {
+  PortionCursor at;
+  at.items = items;
+  at.points = points;
+  if (points <= kFitChunkPoints && fits(points)) {
+    at.chunk = points;
+  } else {
+    int64_t lo = 0, hi = std::min(points, kFitChunkPoints) / block;  // blocks: lo fits, hi + 1 does not
+    while (lo < hi) {
+      const int64_t mid = (lo + hi + 1) / 2;
+      if (fits(mid * block)) lo = mid; else hi = mid - 1;
+    }
+    at.chunk = lo * block;
+  }
+  at.per_portion = at.chunk > 0 ? portion_of([&](Carver& c, int64_t n) { carve(c, n, at.chunk); }) : 1;
+  return at;
+}
+// the greatest take for which fits(take) holds (0: none does); fits is monotone in take
+template <class Fits>
+int max_take_that_fits(Fits&& fits) {
+  int lo = 0, hi = 1 << 30;
+  while (lo < hi) {
+    const int mid = lo + (hi - lo + 1) / 2;
+    if (fits(mid)) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
 // ---- pointwise percentiles of the fit (mhx_get_fit_percentiles): n chains at m points.  What
 // depends on the chains alone comes first and keeps its place from one chunk of points to the
 // next - status, n_used [n] - then x0, x1 [m], the staged values [n][take][m] (a chain's window
@@ -421,36 +456,15 @@ inline FitPctPieces carve_fitpct(Carver& c, int take, int n_pct, int64_t n_, int
 inline bool fitpct_fits(int take, int n_pct, int64_t m) {
   return one_item_fits([&](Carver& c, int64_t n) { carve_fitpct(c, take, n_pct, n, m); });
 }
-// The cursor of the call.  portion_cursor's fixed chunk would ask 1 GB of one chain at take 1000:
-// here the chunk of points is all of `points` where one chain fits the budget with them (and they
-// are at most kFitChunkPoints), else the largest whole number of blocks, at most kFitChunkPoints,
-// with which one chain fits.  chunk == 0: not even one block fits - the caller refuses the call.
+// The cursor of mhx_get_fit_percentiles: block_cursor over blocks of kFitPctBlock points.
 inline PortionCursor fitpct_cursor(int64_t items, int64_t points, int take, int n_pct) {
-  PortionCursor at;
-  at.items = items;
-  at.points = points;
-  if (points <= kFitChunkPoints && fitpct_fits(take, n_pct, points)) {
-    at.chunk = points;
-  } else {
-    int64_t lo = 0, hi = std::min(points, kFitChunkPoints) / kFitPctBlock;  // blocks: lo fits, hi + 1 does not
-    while (lo < hi) {
-      const int64_t mid = (lo + hi + 1) / 2;
-      if (fitpct_fits(take, n_pct, mid * kFitPctBlock)) lo = mid; else hi = mid - 1;
-    }
-    at.chunk = lo * kFitPctBlock;
-  }
-  at.per_portion = at.chunk > 0 ? portion_of([&](Carver& c, int64_t n) { carve_fitpct(c, take, n_pct, n, at.chunk); }) : 1;
-  return at;
+  return block_cursor(items, points, kFitPctBlock, [&](int64_t m) { return fitpct_fits(take, n_pct, m); },
+                      [&](Carver& c, int64_t n, int64_t m) { carve_fitpct(c, take, n_pct, n, m); });
 }
 // the greatest take at which one chain's smallest chunk of `points` fits (0: none does)
 inline int fitpct_max_take(int64_t points, int n_pct) {
   const int64_t m = std::min(points, kFitPctBlock);
-  int lo = 0, hi = 1 << 30;
-  while (lo < hi) {
-    const int mid = lo + (hi - lo + 1) / 2;
-    if (fitpct_fits(mid, n_pct, m)) lo = mid; else hi = mid - 1;
-  }
-  return lo;
+  return max_take_that_fits([&](int take) { return fitpct_fits(take, n_pct, m); });
 }
 
 // ---- PSIS-LOO (mhx_get_loo): n chains at m points of a function of nb_total blocks.  What depends
@@ -492,39 +506,17 @@ inline LooPieces carve_loo(Carver& c, int64_t nb_total, int take, int P, int wan
 inline bool loo_fits(int64_t nb_total, int take, int P, int want, int64_t m) {
   return one_item_fits([&](Carver& c, int64_t n) { carve_loo(c, nb_total, take, P, want, n, m); });
 }
-// The cursor of the call, as fitpct_cursor: all of `points` where one chain fits the budget with
-// them (and they are at most kFitChunkPoints), else the largest whole number of blocks, at most
-// kFitChunkPoints, with which one chain fits.  chunk == 0: not even one block fits - the caller
-// refuses the call.
+// The cursor of mhx_get_loo: block_cursor over blocks of kLooBlock points.
 inline PortionCursor loo_cursor(int64_t items, int64_t points, int take, int P, int want) {
   const int64_t nb_total = (points + kLooBlock - 1) / kLooBlock;
-  PortionCursor at;
-  at.items = items;
-  at.points = points;
-  if (points <= kFitChunkPoints && loo_fits(nb_total, take, P, want, points)) {
-    at.chunk = points;
-  } else {
-    int64_t lo = 0, hi = std::min(points, kFitChunkPoints) / kLooBlock;  // blocks: lo fits, hi + 1 does not
-    while (lo < hi) {
-      const int64_t mid = (lo + hi + 1) / 2;
-      if (loo_fits(nb_total, take, P, want, mid * kLooBlock)) lo = mid; else hi = mid - 1;
-    }
-    at.chunk = lo * kLooBlock;
-  }
-  at.per_portion =
-      at.chunk > 0 ? portion_of([&](Carver& c, int64_t n) { carve_loo(c, nb_total, take, P, want, n, at.chunk); }) : 1;
-  return at;
+  return block_cursor(items, points, kLooBlock, [&](int64_t m) { return loo_fits(nb_total, take, P, want, m); },
+                      [&](Carver& c, int64_t n, int64_t m) { carve_loo(c, nb_total, take, P, want, n, m); });
 }
 // the greatest take at which one chain's smallest chunk of `points` fits, with the tail of P slots
 // the call asked for (0: none does)
 inline int loo_max_take(int64_t points, int P, int want) {
   const int64_t nb_total = (points + kLooBlock - 1) / kLooBlock, m = std::min(points, kLooBlock);
-  int lo = 0, hi = 1 << 30;
-  while (lo < hi) {
-    const int mid = lo + (hi - lo + 1) / 2;
-    if (loo_fits(nb_total, mid, P, want, m)) lo = mid; else hi = mid - 1;
-  }
-  return lo;
+  return max_take_that_fits([&](int take) { return loo_fits(nb_total, take, P, want, m); });
 }
 
 }  // namespace mhx

@@ -26,7 +26,7 @@ def ratio(p):
 
 
 def order_keys(v):
-    """the order-preserving 64-bit key of every double (csrc/mhx_kernels.hpp, order_key): all bits
+    """the order-preserving 64-bit key of every double (csrc/mhx_readout_kernels.hpp, order_key): all bits
     of a negative flipped, the sign bit of the others set, every NaN the greatest key"""
     v = np.ascontiguousarray(v, dtype=np.float64)
     b = v.view(np.uint64)

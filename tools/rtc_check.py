@@ -6,6 +6,8 @@ import ctypes as C
 import os
 import sys
 
+import embed_src
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "lisp-mcmc_amd", "csrc")
 SRC = r'''
@@ -74,13 +76,7 @@ extern "C" __global__ __launch_bounds__(512) void mhx_user_loo(const ProblemDesc
 
 def main():
     rtc = C.CDLL("/opt/rocm/lib/libhiprtc.so")
-    hdr_files = [("mhx_kernels.hpp", os.path.join(CSRC, "mhx_kernels.hpp")),
-                 ("mhx_device.hpp", os.path.join(CSRC, "mhx_device.hpp")),
-                 ("mhx_types.hpp", os.path.join(CSRC, "mhx_types.hpp")),
-                 ("../../include/mhx.h", os.path.join(ROOT, "include", "mhx.h")),
-                 ("mhx_exp2_table.inc", os.path.join(CSRC, "mhx_exp2_table.inc")),
-                 ("mhx_log_table.inc", os.path.join(CSRC, "mhx_log_table.inc")),
-                 ("mhx_derived.hpp", os.path.join(CSRC, "mhx_derived.hpp"))]
+    hdr_files = embed_src.dev_files()  # (name, path): what libmhx.so embeds
     nh = len(hdr_files)
     srcs = (C.c_char_p * nh)(*[open(p, "rb").read() for _, p in hdr_files])
     names = (C.c_char_p * nh)(*[n.encode() for n, _ in hdr_files])
